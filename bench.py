@@ -1,14 +1,29 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the stable-fluids hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--size 8192] [--iters 80]
+    python bench.py --gpus N --steps K --warmup W [--size 8192] [--iters 80] [--full] [--dump-outputs DIR]
 
 A "step" is ONE poisson_solve (zero fill + `iters` red-black SOR iterations, poisson.cpp:114-125)
 on a `size` x `size` fp32 grid held in HBM -- BASELINE.json's headline metric "cell-iters/sec (SOR
 sweep)", config[2] "8192x8192 fp32, 80 SOR iters/step" at N = 1 and config[3] (same grid, row-slab
-split with RCCL halo exchange) at N > 1, i.e. STRONG scaling.  After the timed region the full
-sim step (advect, divergence, solve, gradient, dye advect: ino:252-287) is timed separately and
-reported as `sim_steps_per_sec` (the metric's "+ steps/sec" half).
+split with RCCL halo exchange) at N > 1, i.e. STRONG scaling.
+
+A plain run does what the headline needs and nothing else: set-up, one untimed solve, a fixed
+probe of PRIMING_PROBE_SOLVES solves and ~80 ms of clock priming, the W warm-up and K timed solves,
+the outputs (--dump-outputs) and the JSON line (`value`, `ms_per_step`, the configuration and the
+roofline figures derived from the timed solves).  Its time outside the W + K solves does not depend
+on --steps or --warmup.  Everything else is
+measured with --full: the full sim step (advect, divergence, solve, gradient, dye advect:
+ino:252-287) timed separately and reported as `sim_steps_per_sec` (the metric's "+ steps/sec" half),
+the per-operator times, the opt-in arithmetic beside the default, the parity checks and the CPU
+baseline below, `value_unprimed` (the W + K region timed once more before the priming), and, for
+N > 1, the in-time schedule's experiment.
+
+--dump-outputs DIR writes the pressure field the LAST timed solve left (what a caller of
+sfl_poisson_solve receives) as DIR/pressure.npy (float32, rows x columns), or, above DUMP_MAX_CELLS
+cells, a fixed seeded sample of it as DIR/pressure_sample.npy (the same cells on every run of the
+same grid).  The inputs are a seeded hash of the cell index: the same arguments give the same
+right-hand side on every run.
 
 Launch.  `python bench.py --gpus N` works as typed: for N > 1 this process touches no GPU, starts
 N child processes (one per GPU; RANK / LOCAL_RANK / WORLD_SIZE in their environment), relays
@@ -19,16 +34,17 @@ coordination (RCCL unique id, barriers, max over ranks) is a small TCP all-gathe
 (esp32-fluid-simulation_amd/rendezvous.py); every halo byte moves through RCCL send/recv issued by
 the C++ library.
 
-Output: ONE JSON line on rank 0 (contract in the task statement), including
+Output: ONE JSON line on rank 0, with --full also
   parity        the pressure field left by the LAST TIMED solve, downloaded and compared bit for
                 bit with the reference CPU loop run on the very same right-hand side (downloaded
                 from the GPU); plus one whole sim step at the two small BASELINE configs (61 x 81 and
                 2048^2), all four fields; the process exits non-zero on a mismatch
+  cpu_baseline  the reference's own CPU loop (oracle/_ref, or the oracle port) on this host,
+                1 thread: the parity solve itself is the timed sample; N = 1 only
+and on every run
   roofline      the bound that binds the temporally blocked kernel (the pass over HBM: bytes really
                 moved, from the committed PMC passes, / launch duration by HIP events), the VALU
                 fraction beside it, and the SURVEY 8d algorithmic-bytes figure (labelled as a ratio)
-  cpu_baseline  the reference's own CPU loop (oracle/_ref, or the oracle port) on this host,
-                1 thread: the parity solve itself is the timed sample; N = 1 only
 """
 import argparse
 import importlib
@@ -84,6 +100,41 @@ def slab_checksums(fields):
         k = (np.arange(w.size, dtype=np.uint64) % np.uint64(65521)) + np.uint64(1)
         out.append([int(w.sum(dtype=np.uint64)), int((w * k).sum(dtype=np.uint64))])
     return out
+
+
+# --dump-outputs: a field of at most this many cells is written whole, a larger one as the same seeded sample of this many
+# cells (fewer: repeated draws are dropped) -- 16 MB of float32 either way
+DUMP_MAX_CELLS = 1 << 22
+DUMP_SEED = 8192
+
+
+def dump_outputs(out_dir, got, row_begin, dim_x, dim_y, rdzv, rank):
+    """Write the pressure of the last timed solve (`got`: this rank's rows from `row_begin` of a dim_x x dim_y field) under
+    `out_dir`: whole, or at the seeded sample of flat indices that depends on the grid alone.  Collective: with several ranks each
+    writes its part next to the result and rank 0 joins the parts in rank order (the ranks share one node's file system, as the
+    parity check's files do; the rendezvous only carries the barrier)."""
+    cells = dim_x * dim_y
+    lo, hi = row_begin * dim_x, row_begin * dim_x + got.size
+    if cells <= DUMP_MAX_CELLS:
+        name, mine = "pressure", got.ravel()
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, cells, DUMP_MAX_CELLS))
+        name, mine = "pressure_sample", got.ravel()[idx[(idx >= lo) & (idx < hi)] - lo]
+    mine = np.ascontiguousarray(mine, dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    arr = mine
+    if rdzv.world > 1:
+        part = os.path.join(out_dir, "." + name + ".rank{}.npy")
+        np.save(part.format(rank), mine)
+        rdzv.barrier()
+        if rank != 0:
+            return
+        arr = np.concatenate([np.load(part.format(r)) for r in range(rdzv.world)])
+        for r in range(rdzv.world):
+            os.unlink(part.format(r))
+    if name == "pressure":
+        arr = arr.reshape(dim_y, dim_x)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def synthetic_color(dim_x, row_begin, row_end, seed=777):
@@ -296,6 +347,9 @@ def pmc_record(grid, fuse, world):
 # untimed sim steps in front of the timed ones: the GPU's clocks, and -- on slabs -- the first 12 solves of a kind, which run on
 # candidate halo depths between events (csrc/sor_executor.cpp choose_halo; the 13th decides, collectively on RCCL ranks)
 SIM_PRIMING_STEPS = 16
+# cold solves a plain run times to size its clock priming (--full times the whole W + K region cold instead): ~50 ms, the load
+# the cold region put in front of the priming at --warmup 5 --steps 20, the committed bench lines' arguments
+PRIMING_PROBE_SOLVES = 25
 SCHEDULES = {0: "none", 1: "in line", 2: "one launch early, behind events", 3: "in time, counted on the device"}
 
 
@@ -311,18 +365,19 @@ def parse_args(argv=None):
     ap.add_argument("--sor-kernel", type=int, default=0)
     ap.add_argument("--sor-fold", action="store_true",
                     help="SFL_OPT_SOR_FOLD = 1 for the TIMED solves: the interior relaxation's one product by -0.25f * omega (opt-in "
-                         "arithmetic, not the reference's bits on sparse fields; the line's `numerics` says so).  Without it the "
-                         "folded arithmetic is still measured once, after everything else, as numerics.value_with_fold")
-    ap.add_argument("--no-fold-leg", action="store_true", help="skip that extra measurement")
+                         "arithmetic, not the reference's bits on sparse fields; the line's `numerics` says so).  Without it, "
+                         "--full still measures the folded arithmetic once, after everything else, as numerics.value_with_fold")
+    ap.add_argument("--no-fold-leg", action="store_true", help="--full: skip that extra measurement")
     ap.add_argument("--sor-rows", type=int, default=0)
     ap.add_argument("--sor-halo", type=int, default=0, help="rows of p exchanged per superstep (0 = auto)")
     ap.add_argument("--lane-cells", type=int, default=0, help="cells per lane of the fused kernel (0 auto, 2)")
-    ap.add_argument("--sim-steps", type=int, default=8, help="full sim steps timed after the main region")
+    ap.add_argument("--sim-steps", type=int, default=None,
+                    help="--full: full sim steps timed after the main region (default 8; a plain run times none)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the reference CPU solve (and with it the parity check)")
-    ap.add_argument("--no-parity", action="store_true", help="N > 1: skip the reference solve on rank 0")
+                    help="--full: skip the reference CPU solve (and with it the parity check)")
+    ap.add_argument("--no-parity", action="store_true", help="--full, N > 1: skip the reference solve on rank 0")
     ap.add_argument("--check-sim-step-parity", action="store_true",
-                    help="N = 1: run the sim-step field check of the multi-GPU path as well (rank 0 replays the steps on a second, "
+                    help="--full, N = 1: run the sim-step field check of the multi-GPU path as well (rank 0 replays the steps on a second, "
                          "whole-domain context; every rank compares checksums of its rows) -- always on for N > 1")
     ap.add_argument("--no-priming", action="store_true",
                     help="skip the ~80 ms of untimed solves that bring the GPU to its sustained clocks")
@@ -352,7 +407,8 @@ def parse_args(argv=None):
                     help="SFL_OPT_EXCHANGE_SCHEDULE = 3: exchanges in time, counted on the device, also where the library would not "
                          "choose them by itself (RCCL ranks whose peers are other processes)")
     ap.add_argument("--no-experiment", action="store_true",
-                    help="multi-GPU runs: skip the extra attempt that times the in-time schedule beside the headline (in_time_experiment)")
+                    help="--full, multi-GPU runs: skip the extra attempt that times the in-time schedule beside the headline "
+                         "(in_time_experiment)")
     ap.add_argument("--share-device", type=int, default=None, metavar="D",
                     help="multi-rank runs on a box with FEWER GPUs than ranks: every rank process uses device D and tells RCCL it "
                          "is a host of its own (NCCL_HOSTID), so the N processes form a real N-rank communicator over RCCL's "
@@ -364,7 +420,25 @@ def parse_args(argv=None):
                          "starts fresh ranks with the next exchange schedule; all attempts together stay under 1500 s)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous plumbing only: the ranks touch no GPU (CPU test)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the sim steps, per-operator times, the folded arithmetic, parity "
+                         "against the reference, the CPU baseline and, for N > 1, the in-time experiment (off: the timed "
+                         "solves and the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the pressure field of the last timed solve under DIR as .npy (float32; a seeded sample of "
+                         f"it above {DUMP_MAX_CELLS} cells)")
+    ap.add_argument("--no-dump-outputs", action="store_true", help=argparse.SUPPRESS)   # the experiment's attempt: not its outputs
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        asked = [o for o, on in (("--sim-steps", bool(args.sim_steps)), ("--check-sim-step-parity", args.check_sim_step_parity)) if on]
+        if asked:
+            print(f"bench.py: {' and '.join(asked)} only take effect with --full; this run times the solves alone", file=sys.stderr)
+        args.sim_steps = 0
+    elif args.sim_steps is None:
+        args.sim_steps = 8
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -375,12 +449,12 @@ def parse_args(argv=None):
 # early, behind events -- ADVICE r05 / VERDICT r05 item 3).  Should that attempt fail, FRESH rank processes try every exchange in
 # line (a process that touched a GPU is never re-executed; a failed attempt's processes are stopped, by PID), and the line says
 # so.  The schedule the library does not pick by itself yet -- exchanges in time, counted on the device: it waits for messages
-# INSIDE kernels and has never run on more than one real GPU -- is timed AFTER a successful headline as a separately labelled
+# INSIDE kernels and has never run on more than one real GPU -- is timed (--full) AFTER a successful headline as a separately labelled
 # experiment (`in_time_experiment`: short, no reference solve, its pressure compared with the headline's by checksum); its
 # failure costs the line nothing.
 PLAN = [("library default", [], "headline"),
         ("in-line", ["--no-overlap"], "fallback"),
-        ("in-time", ["--arrival-in-time", "--no-cpu-baseline", "--sim-steps", "0"], "experiment")]
+        ("in-time", ["--arrival-in-time", "--no-cpu-baseline", "--sim-steps", "0", "--no-dump-outputs"], "experiment")]
 TOTAL_BUDGET_S = 1500.0
 EXPERIMENT_BUDGET_S = 150.0
 
@@ -391,7 +465,7 @@ def attempt_plan(args):
     forced = "in-time" if args.arrival_in_time else "by-event" if args.arrival_by_event else "in-line" if args.no_overlap else None
     if forced:
         return [(forced, [], "headline")]
-    plan = [p for p in PLAN if not (p[2] == "experiment" and args.no_experiment)]
+    plan = [p for p in PLAN if not (p[2] == "experiment" and (args.no_experiment or not args.full))]   # (an experiment: --full)
     if not args.halo_timeout_ms:   # a lost message of the experiment is to end as an error line, not as a stopped process
         plan = [(m, f + ["--halo-timeout-ms", "20000"] if r == "experiment" else f, r) for m, f, r in plan]
     return plan
@@ -796,9 +870,11 @@ def run_rank(args):
         with sfl.stdout_to_stderr():
             s.comm_attach(uid)
 
-    # synthetic inputs, resident in HBM before anything is timed
+    # synthetic inputs, resident in HBM before anything is timed (the dye only feeds the sim steps of --full)
+    full = args.full
     s.upload(capi.FIELD_VELOCITY, synthetic_velocity(size, s.row_begin, s.row_end))
-    s.upload(capi.FIELD_COLOR, synthetic_color(size, s.row_begin, s.row_end))
+    if full:
+        s.upload(capi.FIELD_COLOR, synthetic_color(size, s.row_begin, s.row_end))
     s.calculate_divergence(1.0)     # right-hand side = divergence of the velocity
     s.synchronize()
 
@@ -830,14 +906,25 @@ def run_rank(args):
     # generation, PCIe uploads) the GPU sits at idle clocks and needs ~30 ms of load to reach its
     # sustained rate (tools/solve_sequence_probe.py: 2.7, 2.5, 2.4 ... 1.93 ms per solve over the
     # first 15 solves).  A running simulation lives at the sustained rate, so `value` is measured
-    # after ~80 ms of the same solves; the same W + K region measured BEFORE them is reported as
-    # `value_unprimed`.  The count is agreed across ranks (every rank issues the same exchanges).
+    # after ~80 ms of the same solves, their count sized from the cold time of one solve.  A plain run
+    # takes that time from PRIMING_PROBE_SOLVES solves, a fixed number: its time outside the timed
+    # solves does not grow with --steps.  --full times the whole W + K region cold instead and reports
+    # it as `value_unprimed`.  The count is agreed across ranks (every rank issues the same exchanges).
     priming, unprimed = 0, None
     if not args.no_priming:
         time.sleep(0.05)                 # let the clocks fall back, as after any host-side pause
-        elapsed_cold, _ = timed_region()
-        unprimed = cells * iters * args.steps / elapsed_cold
-        t_one = rdzv.max([elapsed_cold / args.steps])[0]
+        if full:
+            elapsed_cold, _ = timed_region()
+            unprimed = cells * iters * args.steps / elapsed_cold
+            t_one = rdzv.max([elapsed_cold / args.steps])[0]
+        else:
+            s.synchronize()
+            rdzv.barrier()
+            t0 = time.perf_counter()
+            for _ in range(PRIMING_PROBE_SOLVES):
+                s.poisson_solve(1.0, iters, omega)
+            s.synchronize()
+            t_one = rdzv.max([(time.perf_counter() - t0) / PRIMING_PROBE_SOLVES])[0]
         # launch-bound tiny grids do not load the GPU at all: nothing to ramp (and hundreds of queued
         # launches only disturb the host-side launch path that bounds them)
         priming = int(min(400, max(4, 0.08 / t_one))) if t_one >= 0.5e-3 else 0
@@ -852,15 +939,18 @@ def run_rank(args):
     # NOW (with the right-hand side it was solved for); the reference CPU loop runs after all GPU
     # timing is done -- it keeps the host busy for seconds, during which the GPU clocks fall back
     parity, cpu_rec = None, None
-    want_parity = not args.no_cpu_baseline and not (world > 1 and args.no_parity)
+    want_parity = full and not args.no_cpu_baseline and not (world > 1 and args.no_parity)
+    dump = args.dump_outputs if not args.no_dump_outputs else None
     got = None
-    if want_parity or (world > 1 and not emulate):
+    if want_parity or (full and world > 1 and not emulate) or dump:
         got = s.download(capi.FIELD_PRESSURE)
     if want_parity:
         d_own = s.download(capi.FIELD_DIVERGENCE)
+    if dump:    # (an emulated rank's rows are a field of their own)
+        dump_outputs(dump, got, 0 if emulate else s.row_begin, size, (s.row_end - s.row_begin) if emulate else dim_y, rdzv, rank)
     # every rank's rows of the timed solve's pressure as checksums (multi-GPU lines: two attempts of one run -- the headline and the
     # in-time experiment -- are compared through them without a second reference solve)
-    p_sums = rdzv.all_gather(slab_checksums([got])[0] if got is not None else None) if (world > 1 and not emulate) else None
+    p_sums = rdzv.all_gather(slab_checksums([got])[0] if got is not None else None) if (full and world > 1 and not emulate) else None
 
     # ---- full sim step, timed separately (not part of `value`) ---------------------------------
     # A slab reports a back-trace that left its advection halo at synchronize(); every rank still
@@ -951,7 +1041,7 @@ def run_rank(args):
     # ---- the opt-in arithmetic beside the default (numerics.value_with_fold): the same W + K region with SFL_OPT_SOR_FOLD flipped,
     # after everything the line's other numbers come from; one GPU only (RCCL ranks would have to agree on the option collectively)
     other_arith = None
-    if world == 1 and not emulate and not args.no_fold_leg:
+    if full and world == 1 and not emulate and not args.no_fold_leg:
         s.set_option(capi.OPT_SOR_FOLD, 0 if args.sor_fold else 1)
         for _ in range(max(priming, 4)):
             s.poisson_solve(1.0, iters, omega)
@@ -1099,7 +1189,7 @@ def run_rank(args):
         out = {
             "metric": "cell-iters/sec (SOR sweep)", "value": value, "unit": "cell-iters/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "priming_solves": priming,
-            "value_unprimed": unprimed,
+            **({"value_unprimed": unprimed} if full else {}),
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"poisson_solve {size}x{dim_y} fp32, {iters} red-black SOR iters/step, "
@@ -1136,22 +1226,26 @@ def run_rank(args):
             **({"pressure_checksums": p_sums} if p_sums is not None else {}),
             **({"sim_step_parity": step_parity} if step_parity is not None else {}),
             "roofline": roofline,
-            "sim_steps_per_sec": sim_sps,
-            "sim_step_us": (1e6 / sim_sps) if sim_sps else None,
-            "sim_steps_api": "sfl_step_n(n): one call for the timed steps",
-            "sim_steps_per_sec_as_separate_calls": sim_sps_calls,
-            # the kernels of the step outside the solve: bytes from the committed rocprofv3 PMC passes / their own steady-state
-            # duration there, quoted only while the entries' source hash matches the kernels this run uses
-            "sim_step_kernels": step_kernel_records((size, dim_y)) or
-                                ("no PMC entry matches the current kernel sources (profiles/pmc_traffic.json step_entries, "
-                                 "sha16 " + step_kernel_source_hash() + "): re-run profiles/run_step_pmc.sh"),
-            "sim_step_kernels_note": "inside sfl_step advect_velocity + calculate_divergence run as one kernel and "
-                                     "subtract_gradient + advect_color as one, inside sfl_step_n the seam kernel joins the "
-                                     "second of one step to the first of the next; the operators below are timed one by one",
-            "sim_step_per_operator": op_us,
-            **({"sim_steps_note": sim_note} if sim_note else {}),
+            "full": full,
             "device": name,
         }
+        if full:
+            out.update({
+                "sim_steps_per_sec": sim_sps,
+                "sim_step_us": (1e6 / sim_sps) if sim_sps else None,
+                "sim_steps_api": "sfl_step_n(n): one call for the timed steps",
+                "sim_steps_per_sec_as_separate_calls": sim_sps_calls,
+                # the kernels of the step outside the solve: bytes from the committed rocprofv3 PMC passes / their own steady-state
+                # duration there, quoted only while the entries' source hash matches the kernels this run uses
+                "sim_step_kernels": step_kernel_records((size, dim_y)) or
+                                    ("no PMC entry matches the current kernel sources (profiles/pmc_traffic.json step_entries, "
+                                     "sha16 " + step_kernel_source_hash() + "): re-run profiles/run_step_pmc.sh"),
+                "sim_step_kernels_note": "inside sfl_step advect_velocity + calculate_divergence run as one kernel and "
+                                         "subtract_gradient + advect_color as one, inside sfl_step_n the seam kernel joins the "
+                                         "second of one step to the first of the next; the operators below are timed one by one",
+                "sim_step_per_operator": op_us,
+                **({"sim_steps_note": sim_note} if sim_note else {}),
+            })
         if cpu_rec:
             out["cpu_baseline"] = cpu_rec
             out["cpu_baseline"]["host_cores_available"] = os.cpu_count()

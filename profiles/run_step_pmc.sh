@@ -7,7 +7,7 @@ set -u
 OUT=$PWD/gpurun_out/prof_step_${1:-pmc}
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 1 --warmup 0 --no-cpu-baseline --no-fold-leg --sim-steps ${SIM_STEPS:-8}"   # sfl_step_n(n): n - 1 launches of the seam kernel per pass
+ARGS="--steps 1 --warmup 0 --no-cpu-baseline --no-fold-leg --sim-steps ${SIM_STEPS:-8} --full"   # sfl_step_n(n): n - 1 launches of the seam kernel per pass
 # LIB=<path>: a variant build of the library (tools/recipes/build_variant.sh) instead of the product's, through tools/with_lib.py
 RUN="python3 bench.py"; [ -n "${LIB:-}" ] && RUN="python3 tools/with_lib.py $LIB bench.py"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o trace -- $RUN $ARGS > $OUT/stats.log 2>&1

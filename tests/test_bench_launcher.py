@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -56,7 +57,7 @@ def _json_line(stdout):
 
 def test_bench_self_launch_as_typed():
     """`python bench.py --gpus 3` without any launcher: three rank processes, ONE JSON line."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--dry-run"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--dry-run", "--full"],
                        capture_output=True, text=True, timeout=300,
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr
@@ -152,19 +153,19 @@ def test_one_gpu_line_has_no_launcher_fields():
 
 def test_headline_is_the_library_default_and_the_experiment_rides_along():
     """the first multi-GPU line must show what a caller of sfl_poisson_solve gets.  Both keys in ONE line."""
-    r = _bench("--gpus", "2", "--dry-run")
+    r = _bench("--gpus", "2", "--dry-run", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     out = _json_line(r.stdout)
     assert out["exchange_mode"] == "library default" and out["mode"] == "library default" and out["fallback_from"] == []
     assert out["in_time_experiment"] == {"dry_run": True, "mode": "in-time"}
-    r = _bench("--gpus", "2", "--dry-run", "--no-experiment")
+    r = _bench("--gpus", "2", "--dry-run", "--full", "--no-experiment")
     assert r.returncode == 0 and "in_time_experiment" not in _json_line(r.stdout)
 
 
 @pytest.mark.parametrize("broken", ["fail", "hang"])
 def test_a_failing_experiment_costs_the_headline_nothing(broken):
     env = {"SFL_BENCH_TEST_FAIL_MODES": "in-time"} if broken == "fail" else {"SFL_BENCH_TEST_HANG_MODES": "in-time"}
-    r = _bench("--gpus", "2", "--dry-run", "--launch-timeout", "4", **env)
+    r = _bench("--gpus", "2", "--dry-run", "--full", "--launch-timeout", "4", **env)
     assert r.returncode == 0, r.stderr[-2000:]
     out = _json_line(r.stdout)
     assert out["exchange_mode"] == "library default" and out["fallback_from"] == []
@@ -174,7 +175,7 @@ def test_a_failing_experiment_costs_the_headline_nothing(broken):
 def test_self_launcher_falls_back_to_exchanges_in_line():
     """The library's own schedule fails on a rank: fresh ranks are started with every exchange in line, the line says which
     schedule produced it and why the first did not; the experiment still follows the headline it can be compared with."""
-    r = _bench("--gpus", "3", "--dry-run", SFL_BENCH_TEST_FAIL_MODES="library default")
+    r = _bench("--gpus", "3", "--dry-run", "--full", SFL_BENCH_TEST_FAIL_MODES="library default")
     assert r.returncode == 0, r.stderr[-2000:]
     out = _json_line(r.stdout)
     assert out["exchange_mode"] == "in-line" and out["mode"] == "in-line" and out["n_gpus"] == 3
@@ -194,7 +195,7 @@ def test_self_launcher_falls_back_past_a_schedule_that_hangs():
 
 
 def test_self_launcher_reports_every_schedules_reason_when_all_fail():
-    r = _bench("--gpus", "2", "--dry-run", SFL_BENCH_TEST_FAIL_MODES="library default,in-line")
+    r = _bench("--gpus", "2", "--dry-run", "--full", SFL_BENCH_TEST_FAIL_MODES="library default,in-line")
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
     tail = [l for l in r.stderr.splitlines() if "every exchange schedule failed" in l]
@@ -205,12 +206,12 @@ def test_self_launcher_reports_every_schedules_reason_when_all_fail():
 
 
 def test_a_schedule_asked_for_is_the_only_one_tried():
-    r = _bench("--gpus", "2", "--dry-run", "--arrival-by-event", SFL_BENCH_TEST_FAIL_MODES="by-event")
+    r = _bench("--gpus", "2", "--dry-run", "--full", "--arrival-by-event", SFL_BENCH_TEST_FAIL_MODES="by-event")
     assert r.returncode != 0 and "starting fresh ranks" not in r.stderr
-    r = _bench("--gpus", "2", "--dry-run", "--no-overlap", SFL_BENCH_TEST_FAIL_MODES="library default,in-time")
+    r = _bench("--gpus", "2", "--dry-run", "--full", "--no-overlap", SFL_BENCH_TEST_FAIL_MODES="library default,in-time")
     out = _json_line(r.stdout)
     assert r.returncode == 0 and out["exchange_mode"] == "in-line" and "in_time_experiment" not in out
-    r = _bench("--gpus", "2", "--dry-run", "--arrival-in-time")
+    r = _bench("--gpus", "2", "--dry-run", "--full", "--arrival-in-time")
     assert r.returncode == 0 and _json_line(r.stdout)["exchange_mode"] == "in-time"
 
 
@@ -233,7 +234,7 @@ def test_a_variant_library_travels_to_the_rank_processes():
 def _torchrun(port, *argv, **env):
     return subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                           "--dry-run"] + list(argv), capture_output=True, text=True, timeout=600, env=_clean_env(**env))
+                           "--dry-run", "--full"] + list(argv), capture_output=True, text=True, timeout=600, env=_clean_env(**env))
 
 
 @pytest.mark.parametrize("broken", ["fail", "hang"])
@@ -279,3 +280,132 @@ def test_the_multi_gpu_suite_fits_the_drivers_limit():
     assert sum(1 for c in m.REAL_GPU_CASES if c[1] == 16384) == 1
     assert {(c[0], c[1], c[2]) for c in m.REAL_GPU_CASES} >= {(2, 8192, 80), (4, 8192, 80), (8, 8192, 80), (8, 16384, 200)}
     assert len(m.REAL_GPU_CASES_SLOW) >= 5
+
+
+def test_extra_measurements_and_the_experiment_need_full():
+    """A plain run times the headline and nothing else; --steps is the number of timed solves (at least one)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert [p[0] for p in bench.attempt_plan(bench.parse_args(["--gpus", "2"]))] == ["library default", "in-line"]
+    plan = bench.attempt_plan(bench.parse_args(["--gpus", "2", "--full"]))
+    assert [p[0] for p in plan] == ["library default", "in-line", "in-time"] and "--no-dump-outputs" in plan[2][1]
+    assert bench.parse_args(["--steps", "7"]).steps == 7 and not bench.parse_args([]).full
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    r = _bench("--gpus", "2", "--dry-run")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "in_time_experiment" not in _json_line(r.stdout)
+
+
+class _OneOfRanks:
+    """Rendezvous stand-in for one rank of `world`; the test calls the ranks in turn, rank 0 last."""
+
+    def __init__(self, world):
+        self.world = world
+
+    def barrier(self):
+        pass
+
+
+@pytest.mark.parametrize("max_cells", [None, 8])
+def test_dump_outputs_whole_or_seeded_sample_and_the_same_over_slabs(tmp_path, monkeypatch, max_cells):
+    """--dump-outputs: the field as float32 .npy (whole, or the grid's fixed seeded sample), the same bits whether one rank
+    holds the field or two slabs do, and no part files left behind."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    if max_cells:
+        monkeypatch.setattr(bench, "DUMP_MAX_CELLS", max_cells)
+    p = (np.arange(6 * 5, dtype=np.float32) * np.float32(0.5)).reshape(6, 5)
+    bench.dump_outputs(str(tmp_path / "one"), p, 0, 5, 6, _OneOfRanks(1), 0)
+    bench.dump_outputs(str(tmp_path / "again"), p, 0, 5, 6, _OneOfRanks(1), 0)
+    bench.dump_outputs(str(tmp_path / "two"), p[4:], 4, 5, 6, _OneOfRanks(2), 1)      # rank 1: rows 4..5, its part only
+    name = "pressure.npy" if not max_cells else "pressure_sample.npy"
+    assert not (tmp_path / "two" / name).exists()
+    bench.dump_outputs(str(tmp_path / "two"), p[:4], 0, 5, 6, _OneOfRanks(2), 0)
+    assert sorted(os.listdir(tmp_path / "two")) == [name]
+    one, again, two = (np.load(tmp_path / d / name) for d in ("one", "again", "two"))
+    assert one.dtype == np.float32 and np.array_equal(one, again) and np.array_equal(one, two)
+    if max_cells:
+        assert 0 < one.size <= max_cells and np.all(np.diff(one) > 0) and set(one.tolist()) <= set(p.ravel().tolist())
+    else:
+        assert np.array_equal(one, p)
+
+
+class _Clock:
+    """bench.py's `time` in the test below: every solve of the fake library advances it by 2 ms."""
+
+    def __init__(self):
+        self.t, self.solves = 0.0, 0
+
+    def perf_counter(self):
+        return self.t
+
+    monotonic = perf_counter
+
+    def sleep(self, s):
+        self.t += s
+
+
+class _Anything:
+    """Options, fields and no-op calls of the fake library."""
+
+    def __getattr__(self, name):
+        return 0
+
+
+class _FakeSolver:
+    def __init__(self, clock, dim_x, dim_y, device=0, rank=0, nranks=1):
+        self.clock, self.dim_x, self.row_begin, self.row_end = clock, dim_x, 0, dim_y
+
+    def poisson_solve(self, *args):
+        self.clock.t += 0.002
+        self.clock.solves += 1
+
+    def timer_start(self):
+        self.t_event = self.clock.t
+
+    def timer_stop(self):
+        return (self.clock.t - self.t_event) * 1e3
+
+    def last_solve_info(self):
+        return {"launches": 1, "exchanges": 0, "fuse": 2, "halo": 0}
+
+    def get_option(self, option):
+        return -1
+
+    def download(self, field):
+        return np.zeros((self.row_end - self.row_begin, self.dim_x), np.float32)
+
+    def __getattr__(self, name):        # upload, set_option, calculate_divergence, synchronize, close
+        return lambda *args, **kwargs: None
+
+
+def _plain_run(monkeypatch, capsys, steps, warmup):
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    clock, real = _Clock(), importlib.import_module
+    fake = types.SimpleNamespace(Solver=lambda *a, **k: _FakeSolver(clock, *a, **k), device_count=lambda: 1,
+                                 device_info=lambda d: ("fake", 256, 0), capi=_Anything(), SflError=RuntimeError)
+    monkeypatch.setattr(importlib, "import_module", lambda name, *a: fake if name == bench.PKG else real(name, *a))
+    monkeypatch.setattr(bench, "time", clock)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    capsys.readouterr()
+    assert bench.run_rank(bench.parse_args(["--size", "64", "--iters", "2", "--steps", str(steps), "--warmup", str(warmup)])) == 0
+    return clock.solves, _json_line(capsys.readouterr().out)
+
+
+def test_a_plain_run_outside_its_steps_does_not_grow_with_steps(monkeypatch, capsys):
+    """A plain run solves W + K times in its warm-up and timed region and, outside them, a fixed number of times: one untimed
+    solve, the priming probe and ~80 ms of priming -- never a second W + K region; `ms_per_step` is one timed solve."""
+    import bench
+    outside = set()
+    for steps, warmup in ((1, 0), (3, 2), (500, 7)):
+        solves, line = _plain_run(monkeypatch, capsys, steps, warmup)
+        assert line["steps"] == steps and line["warmup"] == warmup and abs(line["ms_per_step"] - 2.0) < 1e-9
+        assert line["priming_solves"] in (39, 40) and "value_unprimed" not in line and line["full"] is False   # 0.08 s / 2 ms
+        outside.add(solves - steps - warmup)
+    assert outside == {1 + bench.PRIMING_PROBE_SOLVES + line["priming_solves"]}

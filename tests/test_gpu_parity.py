@@ -1536,7 +1536,7 @@ def test_bench_checks_the_sim_steps_fields_across_ranks():
     import sys
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "640", "--dim-y", "512", "--iters", "10", "--steps", "2",
-                        "--warmup", "1", "--sim-steps", "3", "--no-priming", "--check-sim-step-parity"],
+                        "--warmup", "1", "--sim-steps", "3", "--no-priming", "--check-sim-step-parity", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -1544,6 +1544,34 @@ def test_bench_checks_the_sim_steps_fields_across_ranks():
     assert sp and sp.get("bit_exact") is True and sp["ranks_differing"] == [], sp
     assert "after 7 sim steps" in sp["what"]
     assert out["parity"]["bit_exact"]
+
+
+def test_plain_bench_times_the_solve_alone_and_dumps_its_pressure(tmp_path, oracle):
+    """bench.py without --full: the timed solves and the line, no sim steps, parity or baseline; --dump-outputs writes the
+    pressure of the last timed solve, which is the reference's for the bench's right-hand side, bit for bit -- also with --full,
+    whose sim steps afterwards leave another pressure on the device (the dump is taken right after the timed solves)."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    from conftest import ROOT
+    n, iters = 384, 12
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", str(n), "--iters", str(iters), "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["full"] is False
+    assert out["parity"] is None and "cpu_baseline" not in out and "sim_steps_per_sec" not in out
+    assert "value_with_fold" not in out["numerics"] and "value_unprimed" not in out
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", str(n), "--iters", str(iters), "--steps", "3",
+                        "--warmup", "1", "--full", "--sim-steps", "2", "--no-cpu-baseline", "--no-fold-leg",
+                        "--dump-outputs", str(tmp_path / "full")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["sim_steps_per_sec"] is not None
+    d = oracle.divergence(bench.synthetic_velocity(n, 0, n), 1.0)
+    want = oracle.poisson_solve(d, 1.0, iters, np.float32(1.96))
+    assert_bit_equal(np.load(tmp_path / "out" / "pressure.npy"), want, "dumped pressure")
+    assert_bit_equal(np.load(tmp_path / "full" / "pressure.npy"), want, "dumped pressure, --full")
 
 
 # ---- round 4: the BASELINE multi-GPU configurations in full on eight virtual ranks -----------------------------

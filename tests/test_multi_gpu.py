@@ -41,7 +41,7 @@ MODES = {"": [], "in-time": ["--arrival-in-time"], "by-event": ["--arrival-by-ev
 
 def _run_bench(nranks, size, iters, halo, mode, steps, extra=(), env_extra=None, experiment=False):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--size", str(size),
-           "--iters", str(iters), "--steps", str(steps), "--warmup", "1", "--sim-steps", "1", "--no-priming"] + MODES[mode] + list(extra)
+           "--iters", str(iters), "--steps", str(steps), "--warmup", "1", "--sim-steps", "1", "--no-priming", "--full"] + MODES[mode] + list(extra)
     if not experiment:
         cmd += ["--no-experiment"]
     if halo:
@@ -140,7 +140,7 @@ def test_a_real_time_out_is_an_error_line_of_the_experiment_and_the_headline_sta
         pytest.skip("needs a GPU")
     _needs_loopback()
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--size", "2048", "--iters", "40", "--steps", "6", "--warmup", "1",
-           "--sim-steps", "1", "--no-priming", "--share-device", "0", "--halo-timeout-ms", "1"]
+           "--sim-steps", "1", "--no-priming", "--share-device", "0", "--halo-timeout-ms", "1", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SFL_BENCH_WORKER")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1800, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -159,7 +159,7 @@ def test_the_drivers_own_command_line_on_a_shared_device():
     _needs_loopback()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29577", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "2048", "--iters", "40", "--steps", "6",
-           "--warmup", "1", "--sim-steps", "1", "--no-priming", "--share-device", "0"]
+           "--warmup", "1", "--sim-steps", "1", "--no-priming", "--share-device", "0", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SFL_BENCH_WORKER")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1800, env=env)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -19,7 +19,7 @@ echo "visible GPUs: $NG" | tee $O/summary.txt
 if [ "$NG" -lt 2 ]; then echo "needs at least 2 GPUs" | tee -a $O/summary.txt; exit 1; fi
 # (0. the same N processes and N-rank communicator on GPU 0 alone, over RCCL's socket transport -- what the one-GPU boxes could show,
 #  profiles/r05_rccl_ranks_on_one_device.txt: if THIS fails here the trouble is not the wire)
-timeout 600 python3 bench.py --gpus 4 --share-device 0 --size 2048 --iters 40 --steps 6 --warmup 1 --sim-steps 1 --no-priming > $O/bench_shared_device_n4.json 2> $O/bench_shared_device_n4.err \
+timeout 600 python3 bench.py --gpus 4 --share-device 0 --size 2048 --iters 40 --steps 6 --warmup 1 --sim-steps 1 --no-priming --full > $O/bench_shared_device_n4.json 2> $O/bench_shared_device_n4.err \
     && echo "4 ranks on device 0 over sockets: ok" | tee -a $O/summary.txt || echo "4 ranks on device 0 over sockets: FAILED (see $O/bench_shared_device_n4.err)" | tee -a $O/summary.txt
 ( time SFL_SLOW_MULTI_GPU=1 python3 -m pytest tests/test_multi_gpu.py -m gpu -x -q ) > $O/pytest_multi_gpu.log 2>&1
 tail -3 $O/pytest_multi_gpu.log | tee -a $O/summary.txt
@@ -29,7 +29,7 @@ for n in 1 2 4 8; do
   # force one schedule (no fallback, no experiment).
   for mode in "" "--arrival-in-time" "--arrival-by-event" "--no-overlap"; do
     tag=n${n}$(echo "$mode" | tr -d ' -')
-    timeout 900 python3 bench.py --gpus $n --steps 10 --warmup 3 $mode > $O/bench_$tag.json 2> $O/bench_$tag.err || tail -3 $O/bench_$tag.err
+    timeout 900 python3 bench.py --gpus $n --steps 10 --warmup 3 --full $mode > $O/bench_$tag.json 2> $O/bench_$tag.err || tail -3 $O/bench_$tag.err
     python3 -c "
 import json; d = json.load(open('$O/bench_$tag.json'))
 print('%-34s %d GPU(s): %.3e cell-iters/s  %.4f ms per solve  %s sim steps/s  parity %s  exchanges per solve %s  halo %s rows  measured exchange %s us  schedule %s  fallback_from %s' % ('${mode:-as the driver runs it}', d['n_gpus'], d['value'], d['ms_per_step'], d['sim_steps_per_sec'], (d.get('parity') or {}).get('bit_exact'), d['config']['halo_exchanges_per_solve'], d['config'].get('halo_rows_per_superstep'), d['config'].get('measured_exchange_latency_us'), d.get('exchange_mode', d['config'].get('exchange_schedule')), [f.get('mode') for f in d.get('fallback_from', [])]) + ('  in-time experiment: %s' % json.dumps(d['in_time_experiment']) if 'in_time_experiment' in d else ''))" | tee -a $O/summary.txt

@@ -12,7 +12,7 @@ EXTRA="$*"
 OUT=gpurun_out/emulate_$TAG.txt; mkdir -p gpurun_out; : > $OUT
 echo "# bench.py --emulate-rank R --of $OF --size $SIZE --iters $ITERS $EXTRA ; $(date -u +%FT%TZ)" | tee -a $OUT
 # the one-GPU solve of the same grid on the same box: what the speed-ups are quoted against
-python bench.py --size $SIZE --iters $ITERS --steps 10 --warmup 3 --no-cpu-baseline --sim-steps 6 > gpurun_out/emulate_$TAG.one.json 2> gpurun_out/emulate_$TAG.err \
+python bench.py --size $SIZE --iters $ITERS --steps 10 --warmup 3 --no-cpu-baseline --sim-steps 6 --full > ${OUT%.txt}.one.json 2> ${OUT%.txt}.err \
   && python - gpurun_out/emulate_$TAG.one.json <<'PY' | tee -a $OUT
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -21,7 +21,7 @@ PY
 for rep in $(seq $REPS); do
   for r in $RANKS; do for w in $WIRES; do for t in $TRANSPORTS; do
     flag=""; [ "$t" = rccl ] && flag="--via-rccl"
-    python bench.py --emulate-rank $r --of $OF --size $SIZE --iters $ITERS --steps 30 --warmup 5 --wire-us $w $flag $EXTRA \
+    python bench.py --emulate-rank $r --of $OF --size $SIZE --iters $ITERS --steps 30 --warmup 5 --wire-us $w --full $flag $EXTRA \
         > gpurun_out/emulate_$TAG.json 2>> gpurun_out/emulate_$TAG.err || { echo "FAILED rank $r $t wire $w" | tee -a $OUT; tail -2 gpurun_out/emulate_$TAG.err; continue; }
     python - gpurun_out/emulate_$TAG.json $rep <<'PY' | tee -a $OUT
 import json, sys

@@ -12,7 +12,7 @@ unset LIB
 : > gpurun_out/r06_strip_steps.txt
 for rep in 1 2 3; do for v in ${STRIPS:-0 16 8 32}; do
   if [ $v = 16 ]; then run="python bench.py"; else run="python tools/with_lib.py build/variants/strip$v/libsfl_hip.so bench.py"; fi
-  $run --steps 3 --warmup 1 --no-cpu-baseline --no-fold-leg --sim-steps 40 2>/dev/null | python -c "
+  $run --steps 3 --warmup 1 --no-cpu-baseline --no-fold-leg --sim-steps 40 --full 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('strip $v rep $rep: %.1f steps/s (step_n)  %.1f (separate calls)' % (d['sim_steps_per_sec'], d['sim_steps_per_sec_as_separate_calls']))" | tee -a gpurun_out/r06_strip_steps.txt
 done; done
 for v in ${STRIPS:-0 16 8 32}; do echo "== strip $v"; cat gpurun_out/r06_strip${v}_rows.txt; done

@@ -14,7 +14,7 @@ for spec in "$@"; do
   case $mode in chain) m="";; in-time) m="--arrival-in-time --halo-timeout-ms 15000";; by-event) m="--arrival-by-event";; in-line) m="--no-overlap";; esac
   h=""; [ "$halo" != 0 ] && h="--sor-halo $halo"
   t0=$(date +%s.%N)
-  NCCL_DEBUG=INFO NCCL_DEBUG_SUBSYS=INIT,NET timeout 900 python bench.py --gpus $n --share-device 0 --size $size --iters $iters --steps 6 --warmup 1 --sim-steps 1 --no-priming $m $h \
+  NCCL_DEBUG=INFO NCCL_DEBUG_SUBSYS=INIT,NET timeout 900 python bench.py --gpus $n --share-device 0 --size $size --iters $iters --steps 6 --warmup 1 --sim-steps 1 --no-priming --full $m $h \
       > gpurun_out/shared_$TAG.json 2> gpurun_out/shared_${TAG}_rccl.log
   rc=$?
   t1=$(date +%s.%N)

@@ -1,7 +1,7 @@
 export TMPDIR=/tmp
 for cfg in "512 20" "1024 20" "2048 40"; do set -- $cfg
   O=gpurun_out/gaps_$1; rm -rf $O; mkdir -p $O
-  rocprofv3 --kernel-trace --output-format csv -d $O -o t -- python3 bench.py --size $1 --iters $2 --steps 1 --warmup 0 --no-cpu-baseline --no-fold-leg --sim-steps 200 > $O/line.json 2> $O/err.log
+  rocprofv3 --kernel-trace --output-format csv -d $O -o t -- python3 bench.py --size $1 --iters $2 --steps 1 --warmup 0 --no-cpu-baseline --no-fold-leg --sim-steps 200 --full > $O/line.json 2> $O/err.log
   python3 - $O $1 <<'PY'
 import csv, glob, json, sys
 o, size = sys.argv[1], sys.argv[2]

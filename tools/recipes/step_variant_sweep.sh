@@ -16,7 +16,7 @@ done
 unset LIB
 for rep in 1 2 3; do for v in "$@"; do
   if [ $v = product ]; then run="python bench.py"; else run="python tools/with_lib.py build/variants/$v/libsfl_hip.so bench.py"; fi
-  $run --steps 3 --warmup 1 --no-cpu-baseline --no-fold-leg --sim-steps 40 2>/dev/null | python -c "
+  $run --steps 3 --warmup 1 --no-cpu-baseline --no-fold-leg --sim-steps 40 --full 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v rep $rep: %.1f steps/s (step_n)  %.1f (separate calls)' % (d['sim_steps_per_sec'], d['sim_steps_per_sec_as_separate_calls']))" >> $OUT
 done; done
 cat $OUT
