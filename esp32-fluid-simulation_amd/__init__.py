@@ -5,7 +5,7 @@ The product is ``lib/libsfl_hip.so`` -- hand-written HIP kernels for gfx950 behi
 only the binding used by the tests and by ``bench.py``:
 
 * :mod:`._capi`   ctypes declarations, 1:1 with include/sfl.h
-* :mod:`.solver`  ``Solver`` (a context) and ``HostPath`` (reference-style operators on host
+* :mod:`.solver`  ``Solver`` (a context), ``BatchSolver`` (many small grids stepped by one launch) and ``HostPath`` (reference-style operators on host
   arrays, executed on the GPU)
 
 Import it with ``importlib.import_module("esp32-fluid-simulation_amd")`` (the directory name is
@@ -14,9 +14,9 @@ call that needs the library fails loudly if it is missing -- there is no CPU fal
 """
 from . import _capi as capi
 from ._capi import LIB_PATH, SflError, build_library
-from .solver import (HostPath, Solver, comm_unique_id, device_count, device_info, plan_poisson,
+from .solver import (BatchSolver, HostPath, Solver, comm_unique_id, device_count, device_info, plan_poisson,
                      slab_rows, sor_pass_plan, stdout_to_stderr)
 
-__all__ = ["capi", "LIB_PATH", "SflError", "build_library", "HostPath", "Solver",
+__all__ = ["capi", "LIB_PATH", "SflError", "build_library", "BatchSolver", "HostPath", "Solver",
            "comm_unique_id", "device_count", "device_info", "plan_poisson", "slab_rows",
            "sor_pass_plan", "stdout_to_stderr"]

@@ -131,6 +131,18 @@ SIGNATURES = {
     "sfl_timer_start": (_i, [_ctx]),
     "sfl_timer_stop": (_i, [_ctx, _pf]),
     "sfl_last_solve_info": (_i, [_ctx, _pi, _pi, _pi]),
+    "sfl_batch_create": (_i, [C.POINTER(_ctx), _i, _i, _i, _i]),
+    "sfl_batch_destroy": (_i, [_ctx]),
+    "sfl_batch_shape": (_i, [_ctx, _pi, _pi, _pi]),
+    "sfl_batch_upload": (_i, [_ctx, _i, _i, _i, C.c_void_p, _sz]),
+    "sfl_batch_download": (_i, [_ctx, _i, _i, _i, C.c_void_p, _sz]),
+    "sfl_batch_field_device_ptr": (_i, [_ctx, _i, C.POINTER(C.c_void_p)]),
+    "sfl_batch_queue_forces": (_i, [_ctx, _pi, _pi, _pf, _i]),
+    "sfl_batch_step_n": (_i, [_ctx, _i, _f, _f, _i, _f]),
+    "sfl_batch_poisson_solve": (_i, [_ctx, _f, _i, _f]),
+    "sfl_batch_setup_sketch_fields": (_i, [_ctx]),
+    "sfl_batch_render_rgb565": (_i, [_ctx, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
+    "sfl_batch_synchronize": (_i, [_ctx]),
 }
 
 

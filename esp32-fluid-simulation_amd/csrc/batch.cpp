@@ -1,0 +1,374 @@
+// batch.cpp -- batches of the C ABI (include/sfl.h group 4, sfl_batch_*): B independent whole-domain simulations of one
+// small grid on one device, stepped by ONE launch of B workgroups (batch_grid.hip).  Argument checks, field I/O, the
+// staging of queued forces into per-member order and the ping-pong of velocity and dye.  Host C++ only; it shares the
+// error plumbing of context.h and nothing else with the context units.
+#include "batch.h"
+
+#include "context.h"
+
+using sfl::host::fail;
+
+struct sfl_batch {
+    int device = 0;
+    int dim_x = 0, dim_y = 0, batch = 0;
+    size_t cells = 0;   // per member
+    hipStream_t stream = nullptr;
+    // fields, member-major; velocity and dye ping-pong between two buffers (ino:255, :286)
+    float *vel = nullptr, *vel_tmp = nullptr;
+    uint32_t *col = nullptr, *col_tmp = nullptr;
+    float *div = nullptr, *p = nullptr;
+    // queued point forces (ino:264-269), in queue order
+    std::vector<int> force_member, force_cells;
+    std::vector<float> force_vel;
+    // staged forces of a step: B + 1 member offsets, then the cells, then the velocities, in ONE device buffer filled
+    // from pinned memory; two host slots used alternately, each rewritten only after its last copy has completed
+    void *d_forces = nullptr;
+    size_t d_forces_bytes = 0;
+    struct Stage {
+        void *host = nullptr;
+        size_t bytes = 0;
+        hipEvent_t copied = nullptr;
+        bool pending = false;
+    } stage[2];
+    int slot = 0;
+    // dye visualiser's device image, kept between frames
+    uint16_t *d_image = nullptr;
+    size_t d_image_bytes = 0;
+};
+
+namespace {
+
+void release(sfl_batch *b)
+{
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    for (void *m : {(void *)b->vel, (void *)b->vel_tmp, (void *)b->col, (void *)b->col_tmp, (void *)b->div, (void *)b->p,
+                    b->d_forces, (void *)b->d_image})
+        if (m) (void)hipFree(m);
+    for (auto &st : b->stage) {
+        if (st.host) (void)hipHostFree(st.host);
+        if (st.copied) (void)hipEventDestroy(st.copied);
+    }
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+}
+
+struct Release {
+    void operator()(sfl_batch *b) const { release(b); }
+};
+
+size_t elem_bytes(int field)
+{
+    switch (field) {
+        case SFL_FIELD_VELOCITY: return 8;
+        case SFL_FIELD_COLOR: return 12;
+        case SFL_FIELD_DIVERGENCE:
+        case SFL_FIELD_PRESSURE: return 4;
+    }
+    return 0;
+}
+
+void *field_base(sfl_batch *b, int field)
+{
+    switch (field) {
+        case SFL_FIELD_VELOCITY: return b->vel;
+        case SFL_FIELD_COLOR: return b->col;
+        case SFL_FIELD_DIVERGENCE: return b->div;
+        case SFL_FIELD_PRESSURE: return b->p;
+    }
+    return nullptr;
+}
+
+int use_device(sfl_batch *b)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    return SFL_OK;
+}
+
+int alloc_field(sfl_batch *b, void **ptr, size_t elem, bool zero)
+{
+    const size_t bytes = (size_t)b->batch * b->cells * elem;
+    HIP_TRY(hipMalloc(ptr, bytes));
+    if (zero) HIP_TRY(hipMemsetAsync(*ptr, 0, bytes, b->stream));
+    return SFL_OK;
+}
+
+// the checks of upload / download: members [first, first + count) of a field, `bytes` of host memory
+int check_range(sfl_batch *b, int field, int first, int count, const void *host, size_t bytes)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    const size_t elem = elem_bytes(field);
+    if (!elem) return fail(SFL_ERR_INVALID, "unknown field id %d", field);
+    if (first < 0 || count < 0 || (int64_t)first + count > b->batch)
+        return fail(SFL_ERR_INVALID, "members [%d, %d + %d) are not inside the batch's [0, %d)", first, first, count, b->batch);
+    const size_t want = (size_t)count * b->cells * elem;
+    if (bytes != want)
+        return fail(SFL_ERR_INVALID, "%d members of field %d are %zu bytes, got %zu", count, field, want, bytes);
+    if (!host && count > 0) return fail(SFL_ERR_INVALID, "host is NULL");
+    return SFL_OK;
+}
+
+// The queued forces in member order -- a stable counting sort, so each member keeps its queue order (the last write
+// to a cell wins, ino:264-269) -- copied to the device behind the launches queued so far.  *offsets = nullptr: none.
+int stage_forces(sfl_batch *b, const int **offsets, const int **cells, const float **vel)
+{
+    *offsets = nullptr;
+    *cells = nullptr;
+    *vel = nullptr;
+    const size_t n = b->force_member.size();
+    if (n == 0) return SFL_OK;
+    const size_t n_off = (size_t)b->batch + 1;
+    const size_t bytes = sizeof(int) * (n_off + 2 * n) + sizeof(float) * 2 * n;
+    sfl_batch::Stage &st = b->stage[b->slot];
+    b->slot ^= 1;
+    if (!st.copied) HIP_TRY(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+    if (st.pending) {
+        HIP_TRY(hipEventSynchronize(st.copied));
+        st.pending = false;
+    }
+    if (bytes > st.bytes) {
+        if (st.host) (void)hipHostFree(st.host);
+        st.host = nullptr;
+        st.bytes = 0;
+        HIP_TRY(hipHostMalloc(&st.host, bytes, hipHostMallocDefault));
+        st.bytes = bytes;
+    }
+    if (bytes > b->d_forces_bytes) {
+        HIP_TRY(hipStreamSynchronize(b->stream));   // an earlier step may still read the old buffer: drain on growth only
+        if (b->d_forces) (void)hipFree(b->d_forces);
+        b->d_forces = nullptr;
+        b->d_forces_bytes = 0;
+        HIP_TRY(hipMalloc(&b->d_forces, bytes));
+        b->d_forces_bytes = bytes;
+    }
+    int *off = static_cast<int *>(st.host);
+    int *hc = off + n_off;
+    float *hv = reinterpret_cast<float *>(hc + 2 * n);
+    std::fill(off, off + n_off, 0);
+    for (size_t k = 0; k < n; ++k) ++off[b->force_member[k] + 1];
+    for (size_t m = 1; m < n_off; ++m) off[m] += off[m - 1];
+    std::vector<int> next(off, off + n_off - 1);
+    for (size_t k = 0; k < n; ++k) {
+        const int at = next[b->force_member[k]]++;
+        hc[2 * at] = b->force_cells[2 * k];
+        hc[2 * at + 1] = b->force_cells[2 * k + 1];
+        hv[2 * at] = b->force_vel[2 * k];
+        hv[2 * at + 1] = b->force_vel[2 * k + 1];
+    }
+    HIP_TRY(hipMemcpyAsync(b->d_forces, st.host, bytes, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipEventRecord(st.copied, b->stream));
+    st.pending = true;
+    b->force_member.clear();
+    b->force_cells.clear();
+    b->force_vel.clear();
+    const int *d_off = static_cast<const int *>(b->d_forces);
+    *offsets = d_off;
+    *cells = d_off + n_off;
+    *vel = reinterpret_cast<const float *>(d_off + n_off + 2 * n);
+    return SFL_OK;
+}
+
+sfl::SorParams sor_params(float dx, float omega)
+{
+    sfl::SorParams prm{};
+    prm.dx = dx;
+    prm.omega = omega;
+    prm.one_minus_omega = 1.0f - omega;  // (1 - omega) in float, poisson.cpp:98,111
+    prm.neg_quarter_omega = -0.25f * omega;
+    prm.fold = 0;                        // (the one-workgroup kernels always multiply twice)
+    return prm;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfl_batch_create(sfl_batch **out, int device, int dim_x, int dim_y, int batch)
+{
+    if (!out) return fail(SFL_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (dim_x < 2 || dim_y < 2) return fail(SFL_ERR_INVALID, "dim_x and dim_y must be >= 2 (got %d x %d)", dim_x, dim_y);
+    if (batch < 1) return fail(SFL_ERR_INVALID, "batch must be >= 1 (got %d)", batch);
+    const int64_t cells = (int64_t)dim_x * dim_y;
+    if (cells > sfl::kSmallGridMaxCells)
+        return fail(SFL_ERR_INVALID, "a batch member holds at most %d cells (one workgroup's LDS): %d x %d has %lld",
+                    sfl::kSmallGridMaxCells, dim_x, dim_y, (long long)cells);
+    if (!sfl::small_grid_fits(dim_x, dim_y))
+        return fail(SFL_ERR_INVALID, "a batch member holds at most %d cells of one colour (dim_y * ceil(dim_x / 2), the "
+                    "cells one workgroup's threads own): %d x %d has %lld", sfl::kSmallGridMaxCells / 2, dim_x, dim_y,
+                    (long long)dim_y * ((dim_x + 1) / 2));
+    if ((int64_t)batch * cells > INT32_MAX)
+        return fail(SFL_ERR_INVALID, "batch x cells must be <= 2^31 - 1 (got %d x %lld)", batch, (long long)cells);
+    int ndev = 0;
+    SFL_TRY(sfl_device_count(&ndev));
+    if (device < 0 || device >= ndev) return fail(SFL_ERR_HIP, "device %d not available (%d visible)", device, ndev);
+
+    std::unique_ptr<sfl_batch, Release> b(new sfl_batch);
+    b->device = device;
+    b->dim_x = dim_x;
+    b->dim_y = dim_y;
+    b->batch = batch;
+    b->cells = (size_t)cells;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->vel, 8, true));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->vel_tmp, 8, false));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->col, 12, true));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->col_tmp, 12, false));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->div, 4, true));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->p, 4, true));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    *out = b.release();
+    return SFL_OK;
+}
+
+int sfl_batch_destroy(sfl_batch *b)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    release(b);
+    return SFL_OK;
+}
+
+int sfl_batch_shape(sfl_batch *b, int *dim_x, int *dim_y, int *batch)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    if (dim_x) *dim_x = b->dim_x;
+    if (dim_y) *dim_y = b->dim_y;
+    if (batch) *batch = b->batch;
+    return SFL_OK;
+}
+
+int sfl_batch_upload(sfl_batch *b, int field, int first, int count, const void *host, size_t bytes)
+{
+    SFL_TRY(check_range(b, field, first, count, host, bytes));
+    if (count == 0) return SFL_OK;
+    SFL_TRY(use_device(b));
+    char *dev = static_cast<char *>(field_base(b, field)) + (size_t)first * b->cells * elem_bytes(field);
+    HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return SFL_OK;
+}
+
+int sfl_batch_download(sfl_batch *b, int field, int first, int count, void *host, size_t bytes)
+{
+    SFL_TRY(check_range(b, field, first, count, host, bytes));
+    if (count == 0) return SFL_OK;
+    SFL_TRY(use_device(b));
+    const char *dev = static_cast<const char *>(field_base(b, field)) + (size_t)first * b->cells * elem_bytes(field);
+    HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return SFL_OK;
+}
+
+int sfl_batch_field_device_ptr(sfl_batch *b, int field, void **dev_ptr)
+{
+    if (!b || !dev_ptr) return fail(SFL_ERR_INVALID, "NULL argument");
+    if (!elem_bytes(field)) return fail(SFL_ERR_INVALID, "unknown field id %d", field);
+    *dev_ptr = field_base(b, field);
+    return SFL_OK;
+}
+
+int sfl_batch_queue_forces(sfl_batch *b, const int *members, const int *cells_ij, const float *vel_xy, int n)
+{
+    if (!b || n < 0 || (n > 0 && (!members || !cells_ij || !vel_xy))) return fail(SFL_ERR_INVALID, "bad arguments");
+    for (int k = 0; k < n; ++k)   // all or nothing
+        if (members[k] < 0 || members[k] >= b->batch)
+            return fail(SFL_ERR_INVALID, "force %d names member %d, outside the batch's [0, %d): nothing queued", k,
+                        members[k], b->batch);
+    b->force_member.insert(b->force_member.end(), members, members + n);
+    b->force_cells.insert(b->force_cells.end(), cells_ij, cells_ij + 2 * (size_t)n);
+    b->force_vel.insert(b->force_vel.end(), vel_xy, vel_xy + 2 * (size_t)n);
+    return SFL_OK;
+}
+
+int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float omega)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
+    if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
+    if (n == 0) return SFL_OK;
+    SFL_TRY(use_device(b));
+    sfl::BatchStep a{};
+    a.step.div = b->div;
+    a.step.p = b->p;
+    a.step.dim_x = b->dim_x;
+    a.step.dim_y = b->dim_y;
+    a.step.iters = iters;
+    a.step.dt = dt;
+    a.step.two_dx_inv = 1.0f / (2.0f * dx);  // finitediff.cpp:36, :78-79
+    a.step.prm = sor_params(dx, omega);
+    for (int k = 0; k < n; ++k) {
+        // queued forces go into the first step (the queue is empty after it)
+        SFL_TRY(stage_forces(b, &a.force_offsets, &a.step.force_cells, &a.step.force_vel));
+        a.step.v_in = b->vel;
+        a.step.v_out = b->vel_tmp;
+        a.step.col_in = b->col;
+        a.step.col_out = b->col_tmp;
+        HIP_TRY(sfl::launch_batch_step(b->stream, a, b->batch));
+        std::swap(b->vel, b->vel_tmp);  // ino:255
+        std::swap(b->col, b->col_tmp);  // ino:286
+    }
+    return SFL_OK;
+}
+
+int sfl_batch_poisson_solve(sfl_batch *b, float dx, int iters, float omega)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
+    SFL_TRY(use_device(b));
+    HIP_TRY(sfl::launch_batch_solve(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch, iters, sor_params(dx, omega)));
+    return SFL_OK;
+}
+
+// Member 0 as sfl_setup_sketch_fields makes it, then copied to the others by doubling: 1 -> 2 -> 4 ... members, a
+// copy per doubling instead of a setup per member.
+int sfl_batch_setup_sketch_fields(sfl_batch *b)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    SFL_TRY(use_device(b));
+    HIP_TRY(sfl::launch_setup_sketch_fields(b->stream, b->vel, b->col, b->dim_x, b->dim_y));
+    for (size_t have = 1; have < (size_t)b->batch; have *= 2) {
+        const size_t more = std::min(have, (size_t)b->batch - have) * b->cells;
+        HIP_TRY(hipMemcpyAsync(b->vel + 2 * have * b->cells, b->vel, more * 8, hipMemcpyDeviceToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->col + 3 * have * b->cells, b->col, more * 12, hipMemcpyDeviceToDevice, b->stream));
+    }
+    return SFL_OK;
+}
+
+int sfl_batch_render_rgb565(sfl_batch *b, int member, int scaling, int byteswap, uint16_t *host_image, size_t bytes)
+{
+    if (!b || !host_image) return fail(SFL_ERR_INVALID, "NULL argument");
+    if (member < 0 || member >= b->batch)
+        return fail(SFL_ERR_INVALID, "member %d outside the batch's [0, %d)", member, b->batch);
+    if (scaling < 1 || scaling > 64) return fail(SFL_ERR_INVALID, "scaling must be 1..64 (got %d)", scaling);
+    const size_t w = (size_t)scaling * (b->dim_y - 1), h = (size_t)scaling * (b->dim_x - 1);
+    if (bytes != w * h * 2) return fail(SFL_ERR_INVALID, "image is %zu x %zu uint16 = %zu bytes, got %zu", h, w, w * h * 2, bytes);
+    SFL_TRY(use_device(b));
+    if (bytes > b->d_image_bytes) {  // the frame buffer stays with the batch between frames
+        if (b->d_image) {
+            HIP_TRY(hipStreamSynchronize(b->stream));
+            (void)hipFree(b->d_image);
+            b->d_image = nullptr;
+            b->d_image_bytes = 0;
+        }
+        void *img = nullptr;
+        HIP_TRY(hipMalloc(&img, bytes));
+        b->d_image = static_cast<uint16_t *>(img);
+        b->d_image_bytes = bytes;
+    }
+    HIP_TRY(sfl::launch_render_rgb565(b->stream, b->d_image, b->col + 3 * (size_t)member * b->cells, b->dim_x, b->dim_y,
+                                      scaling, byteswap != 0));
+    HIP_TRY(hipMemcpyAsync(host_image, b->d_image, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));  // the caller reads host_image on return
+    return SFL_OK;
+}
+
+int sfl_batch_synchronize(sfl_batch *b)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    SFL_TRY(use_device(b));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return SFL_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,23 @@
+// batch.h -- launch interface of the batched one-workgroup kernels (batch_grid.hip; internal, the public boundary is
+// include/sfl.h sfl_batch_*).  A batch is B independent whole-domain grids of one shape that passes small_grid_fits,
+// stored member-major: member m of a field starts at element m * dim_x * dim_y.  Workgroup m steps / solves member m;
+// members never communicate.  Every launcher is asynchronous on the given stream and returns the hipError_t of the launch.
+#pragma once
+#include "kernels.h"
+
+namespace sfl {
+
+// One step (ino:252-287) of every member.  `step` describes member 0: its arrays (the kernel adds each member's offset,
+// computed in 64-bit), the shape and the parameters, which every member shares.  Forces: force_offsets == nullptr = none;
+// else B + 1 ints, and member m applies records [force_offsets[m], force_offsets[m + 1]) of step.force_cells /
+// step.force_vel in that order (step.n_forces is ignored).
+struct BatchStep {
+    SmallStep step;
+    const int *force_offsets;
+};
+hipError_t launch_batch_step(hipStream_t s, const BatchStep &a, int batch);
+// poisson_solve (poisson.cpp:114-125) of every member: p = iters red-black SOR iterations from zero on rhs d.
+hipError_t launch_batch_solve(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch, int iters,
+                              SorParams prm);
+
+}  // namespace sfl

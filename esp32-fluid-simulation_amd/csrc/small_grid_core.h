@@ -1,0 +1,130 @@
+// small_grid_core.h -- the device code of the one-workgroup kernels, shared by small_grid.hip (one grid per launch) and
+// batch_grid.hip (one grid per workgroup, many grids per launch): the whole step or the whole pressure solve of a grid of
+// at most kSmallGridMaxCells cells with its velocity, divergence and pressure in the workgroup's LDS.
+//
+// Numerics contract: -ffp-contract=off, every operation individually rounded in the
+// reference's order.  Reference citations are file:line under /root/reference/ESP32-fluid-simulation/.
+// Offsets inside one grid are 32-bit ints (at most 6144 cells); a caller that places grids side by side
+// passes each grid's base pointers, computed in 64-bit.
+#pragma once
+#include "advect_math.h"
+#include "kernels.h"
+
+namespace sfl {
+namespace small_core {
+
+using namespace advect_math;
+
+// cells of one colour a thread may own (registers): a grid qualifies when its rows x ceil(dim_x / 2) positions of
+// one colour fit (small_grid_fits; only widths of 3 .. 7 cells with thousands of rows do not)
+template <int kThreads>
+constexpr int cells_per_colour() { return kSmallGridMaxCells / 2 / kThreads; }
+
+struct Lds {
+    float2 *v;   // advected (then projected) velocity
+    float *d;    // divergence
+    float *p;    // pressure
+};
+
+__device__ __forceinline__ Lds carve(char *base, int cells)
+{
+    Lds l;
+    l.v = reinterpret_cast<float2 *>(base);
+    l.d = reinterpret_cast<float *>(base + (size_t)cells * 8);
+    l.p = l.d + cells;
+    return l;
+}
+
+// iters x two colour passes of poisson.cpp:14-112 on p (zero-filled here, :117-119) in LDS.
+// A thread owns the same cells in every pass: their pressure, dx * d, -1/n and the boundary facts stay in
+// registers; LDS holds p for the neighbours.  A pass is branch-free: all neighbour reads of the thread's cells go
+// out together, and both reference formulas are evaluated as (((z + W) + E) + S) + N -- an absent neighbour
+// contributes -0.0f, the additive identity, z = -0.0f inside and +0.0f on the perimeter (the fused kernel's
+// formulation, sor_stream_core.h): interior ((W + E) + S) + N  (pois_sor_fast, :107-109), perimeter the running
+// sum from 0 over the neighbours present (pois_gs_safe, :67-89).
+template <int kThreads>
+__device__ __forceinline__ void sor_in_lds(float *p, const float *d, int dim_x, int dim_y, int iters, SorParams prm)
+{
+    constexpr int kCellsPerColour = cells_per_colour<kThreads>();
+    const int cells = dim_x * dim_y, half = (dim_x + 1) / 2;
+    const int i_max = dim_x - 1, j_max = dim_y - 1;
+    for (int c = threadIdx.x; c < cells; c += kThreads) p[c] = 0.0f;
+    __syncthreads();   // (also: d is complete)
+    const int per_colour = dim_y * half;                              // positions of one colour, row-major
+    const int kmax = (per_colour + kThreads - 1) / kThreads;          // block-uniform, <= kCellsPerColour
+    int cm[2][kCellsPerColour];      // cell index | neighbour mask << 16 (bit 0 W, 1 E, 2 S, 3 N present; bit 4: cell exists)
+    float own[2][kCellsPerColour], rhs[2][kCellsPerColour], kf[2][kCellsPerColour], z[2][kCellsPerColour];
+#pragma unroll
+    for (int colour = 0; colour < 2; ++colour)
+#pragma unroll
+        for (int k = 0; k < kCellsPerColour; ++k) {
+            const int q = threadIdx.x + k * kThreads;
+            const int gj = q / half, ii = q - gj * half;
+            const int i = 2 * ii + ((gj + colour) & 1);
+            const bool have = k < kmax && gj < dim_y && i < dim_x;
+            const int c = have ? gj * dim_x + i : 0;
+            const int m = (i > 0 ? 1 : 0) | (i < i_max ? 2 : 0) | (gj > 0 ? 4 : 0) | (gj < j_max ? 8 : 0);
+            const int present = __builtin_popcount(m);
+            cm[colour][k] = have ? (c | ((m | 16) << 16)) : 0;
+            own[colour][k] = 0.0f;
+            rhs[colour][k] = have ? prm.dx * d[c] : 0.0f;   // dx * d, :108 / :88 (the same product every pass)
+            kf[colour][k] = (present == 2) ? (float)(-1.0 / 2.0) : (present == 3) ? (float)(-1.0 / 3.0) : -0.25f;  // :67
+            z[colour][k] = (present == 4) ? -0.0f : 0.0f;
+        }
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int colour = 0; colour < 2; ++colour) {  // colour 0 = even (i + j) first, poisson.cpp:22,57-60
+            float w[kCellsPerColour], e[kCellsPerColour], s[kCellsPerColour], n[kCellsPerColour];
+#pragma unroll
+            for (int k = 0; k < kCellsPerColour; ++k) {
+                if (k >= kmax) break;
+                const int c = cm[colour][k] & 0xffff, m = cm[colour][k] >> 16;
+                w[k] = (m & 1) ? p[c - 1] : -0.0f;
+                e[k] = (m & 2) ? p[c + 1] : -0.0f;
+                s[k] = (m & 4) ? p[c - dim_x] : -0.0f;
+                n[k] = (m & 8) ? p[c + dim_x] : -0.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < kCellsPerColour; ++k) {
+                if (k >= kmax) break;
+                const float sum = (((z[colour][k] + w[k]) + e[k]) + s[k]) + n[k];
+                const float p_gs = kf[colour][k] * (rhs[colour][k] - sum);
+                const float fresh = prm.one_minus_omega * own[colour][k] + prm.omega * p_gs;  // :98, :111
+                own[colour][k] = fresh;
+                if (cm[colour][k] >> 20) p[cm[colour][k] & 0xffff] = fresh;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- poisson_solve (poisson.cpp:114-125) alone: d_in -> p_out of ONE grid ------------------------
+template <int kThreads>
+__device__ __forceinline__ void solve_in_lds(char *lds_raw, float *p_out, const float *d_in,
+                                             int dim_x, int dim_y, int iters, SorParams prm)
+{
+    const int cells = dim_x * dim_y;
+    const Lds l = carve(lds_raw, cells);
+    for (int c = threadIdx.x; c < cells; c += kThreads) l.d[c] = d_in[c];
+    sor_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, iters, prm);   // (its first barrier also covers the copy of d)
+    for (int c = threadIdx.x; c < cells; c += kThreads) p_out[c] = l.p[c];
+}
+
+// (the step itself: small_step_body.inc)
+
+}  // namespace small_core
+
+// more than 64 KB of dynamic LDS has to be granted once per kernel and device (host side of the launchers)
+inline hipError_t allow_small_grid_lds(const void *kernel, bool *granted)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    if (granted[dev]) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSmallGridMaxCells * 16);
+    if (e == hipSuccess) granted[dev] = true;
+    return e;
+}
+
+}  // namespace sfl

@@ -1,8 +1,9 @@
 """numpy-level front-end over the C ABI.
 
-Two classes:
+Three classes:
 
 * :class:`Solver` -- one context (= one GPU's row slab, fields resident in HBM); thin, explicit.
+* :class:`BatchSolver` -- a batch: many independent small grids of one shape, stepped by one launch.
 * :class:`HostPath` -- the reference's operator interface on host arrays (same names, argument
   meaning and result layout as the oracle's ``CpuPath``), each call going through the
   ``sfl_host_*`` drop-ins or a temporary :class:`Solver`.  This is what the parity tests drive.
@@ -250,6 +251,103 @@ class Solver:
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         capi.check(self._lib.sfl_last_solve_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"launches": a.value, "exchanges": b.value, "fuse": c.value, "halo": self.get_option(capi.OPT_LAST_HALO)}
+
+
+class BatchSolver:
+    """A batch (sfl_batch_*): `batch` independent whole-domain simulations of one dim_x * dim_y grid on one device,
+    every member stepped by the same launch.  Member m holds, bit for bit, what a :class:`Solver` of the same shape
+    holds after the same calls made with member m's data and forces.  Arrays of members are shaped
+    ``(count, dim_y, dim_x[, k])``."""
+
+    def __init__(self, dim_x: int, dim_y: int, batch: int, device: int = 0):
+        self._h = C.c_void_p()
+        self._lib = capi.lib()
+        capi.check(self._lib.sfl_batch_create(C.byref(self._h), device, dim_x, dim_y, batch))
+        self.dim_x, self.dim_y, self.batch, self.device = dim_x, dim_y, batch, device
+
+    def close(self):
+        if self._h:
+            self._lib.sfl_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def shape(self):
+        """(dim_x, dim_y, batch) as the library reports it."""
+        x, y, b = C.c_int(), C.c_int(), C.c_int()
+        capi.check(self._lib.sfl_batch_shape(self._h, C.byref(x), C.byref(y), C.byref(b)))
+        return x.value, y.value, b.value
+
+    def _shape(self, field, count):
+        _, nc = _FIELD_SPEC[field]
+        return (count, self.dim_y, self.dim_x, nc) if nc > 1 else (count, self.dim_y, self.dim_x)
+
+    def upload(self, field: int, a: np.ndarray, first: int = 0):
+        """Members [first, first + len(a)) of a field (synchronous)."""
+        dt, _ = _FIELD_SPEC[field]
+        a = np.ascontiguousarray(a, dtype=dt)
+        if a.shape[1:] != self._shape(field, 0)[1:]:
+            raise ValueError(f"field {field}: shape {a.shape}, a batch member wants {self._shape(field, 0)[1:]}")
+        capi.check(self._lib.sfl_batch_upload(self._h, field, first, a.shape[0], a.ctypes.data, a.nbytes))
+
+    def download(self, field: int, first: int = 0, count=None) -> np.ndarray:
+        """Members [first, first + count) of a field (synchronous; count None = to the end of the batch)."""
+        dt, _ = _FIELD_SPEC[field]
+        count = self.batch - first if count is None else count
+        a = np.empty(self._shape(field, max(count, 0)), dt)
+        capi.check(self._lib.sfl_batch_download(self._h, field, first, count, a.ctypes.data, a.nbytes))
+        return a
+
+    def device_ptr(self, field: int) -> int:
+        """Member 0 of the field's current buffer (valid until the next step)."""
+        p = C.c_void_p()
+        capi.check(self._lib.sfl_batch_field_device_ptr(self._h, field, C.byref(p)))
+        return p.value
+
+    def queue_forces(self, members, cells_ij, vel_xy):
+        """Point forces of the next step: record k sets member members[k]'s velocity at cell cells_ij[k] to vel_xy[k]."""
+        members = np.ascontiguousarray(members, np.int32).reshape(-1)
+        cells = np.ascontiguousarray(cells_ij, np.int32).reshape(-1, 2)
+        vel = np.ascontiguousarray(vel_xy, np.float32).reshape(-1, 2)
+        if not len(members) == len(cells) == len(vel):
+            raise ValueError("members, cells_ij and vel_xy need one entry per force")
+        capi.check(self._lib.sfl_batch_queue_forces(
+            self._h, members.ctypes.data_as(C.POINTER(C.c_int)), cells.ctypes.data_as(C.POINTER(C.c_int)),
+            vel.ctypes.data_as(C.POINTER(C.c_float)), len(members)))
+
+    def step_n(self, n, dt, dx=1.0, iters=10, omega=1.96):
+        capi.check(self._lib.sfl_batch_step_n(self._h, n, dt, dx, iters, omega))
+
+    def step(self, dt, dx=1.0, iters=10, omega=1.96):
+        self.step_n(1, dt, dx, iters, omega)
+
+    def poisson_solve(self, dx=1.0, iters=10, omega=1.96):
+        capi.check(self._lib.sfl_batch_poisson_solve(self._h, dx, iters, omega))
+
+    def setup_sketch_fields(self):
+        """Every member: velocity = 0, dye = the sketch's blurred three-sector pattern (setup(), ino:196-241)."""
+        capi.check(self._lib.sfl_batch_setup_sketch_fields(self._h))
+
+    def render_rgb565(self, member: int, scaling: int = 4, byteswap: bool = True) -> np.ndarray:
+        """One member's dye -> RGB565 image, uint16[scaling*(dim_x-1), scaling*(dim_y-1)] (ino:116-176)."""
+        img = np.empty((scaling * (self.dim_x - 1), scaling * (self.dim_y - 1)), np.uint16)
+        capi.check(self._lib.sfl_batch_render_rgb565(self._h, member, scaling, int(byteswap),
+                                                     img.ctypes.data_as(C.POINTER(C.c_uint16)), img.nbytes))
+        return img
+
+    def synchronize(self):
+        capi.check(self._lib.sfl_batch_synchronize(self._h))
 
 
 def _fp(a):

@@ -16,12 +16,14 @@
  * uint32 raw values (Vector3<UQ32>, vector.h:63-122 + uq32.h:8-16, 12 B);
  * pressure / divergence = float32.
  *
- * Three groups of entry points:
+ * Four groups of entry points:
  *   1. host-pointer drop-ins  sfl_host_*      the reference signatures + status; upload,
  *                                             run the HIP kernels, download (parity / porting aid)
  *   2. solver contexts        sfl_create ...  device-resident fields for one GPU's row slab of
  *                                             the domain, operators, RCCL halo exchange
  *   3. utilities              version, errors, device query, slab partition arithmetic
+ *   4. batches                sfl_batch_*     many independent small grids of one shape on one
+ *                                             device, stepped by one launch
  *
  * There is NO CPU fallback anywhere behind this header: without a usable GPU every
  * compute entry point fails with SFL_ERR_HIP.
@@ -175,6 +177,7 @@ extern "C" {
                                      either way (tests/test_gpu_parity.py test_quiescent_*)                        */
 
 typedef struct sfl_context sfl_context;
+typedef struct sfl_batch sfl_batch;
 
 /* =====================================================================================
  * 3. utilities
@@ -426,6 +429,48 @@ SFL_API int sfl_timer_stop(sfl_context *ctx, float *elapsed_ms);
 /* Launch statistics of the last sfl_poisson_solve on this context: kernel launches, halo
  * exchanges, half-sweeps fused per launch.  Any out pointer may be NULL.                    */
 SFL_API int sfl_last_solve_info(sfl_context *ctx, int *launches, int *exchanges, int *fuse);
+
+/* =====================================================================================
+ * 4. batches: B independent whole-domain simulations of one dim_x * dim_y grid on one
+ *    device (ensembles, parameter studies).  One launch steps every member, one workgroup
+ *    per member with its fields in LDS.  After any sequence of batch calls member m holds,
+ *    bit for bit, what a whole-domain context of the same shape holds after the same calls
+ *    made with member m's data and member m's forces.
+ * ===================================================================================== */
+
+/* Limits: the shapes the one-workgroup path of a context takes (SFL_OPT_SMALL_GRID): dim_x, dim_y >= 2, at most
+ * 6144 cells and at most 3072 cells of one colour (dim_y * ceil(dim_x / 2)); batch >= 1 and batch * dim_x * dim_y
+ * <= 2^31 - 1.  Violations return SFL_ERR_INVALID before any GPU is touched; a failed allocation returns
+ * SFL_ERR_NOMEM.  Every field is zero after create.                                               */
+SFL_API int sfl_batch_create(sfl_batch **out, int device, int dim_x, int dim_y, int batch);
+SFL_API int sfl_batch_destroy(sfl_batch *b);
+/* Any out pointer may be NULL. */
+SFL_API int sfl_batch_shape(sfl_batch *b, int *dim_x, int *dim_y, int *batch);
+/* --- field I/O of members [first, first + count), synchronous.  Fields are the SFL_FIELD_* of a context with their
+ *     element types, stored member-major: member m starts at element m * dim_x * dim_y and is laid out as a context's
+ *     field.  bytes must be exactly count * dim_x * dim_y * element size.                          */
+SFL_API int sfl_batch_upload(sfl_batch *b, int field, int first, int count, const void *host, size_t bytes);
+SFL_API int sfl_batch_download(sfl_batch *b, int field, int first, int count, void *host, size_t bytes);
+/* Device pointer of member 0 of the field's CURRENT buffer.  Velocity and colour ping-pong between two buffers as on a
+ * context: the pointer is valid until the next step.                                             */
+SFL_API int sfl_batch_field_device_ptr(sfl_batch *b, int field, void **dev_ptr);
+/* Queue n point forces: record k sets velocity[member members[k], cell (cells_ij[2k], cells_ij[2k+1])] =
+ * (vel_xy[2k], vel_xy[2k+1]) in the next step, between the velocity advection and the divergence (ino:264-269), in
+ * queue order within each member (the last write wins).  Cells outside the domain are skipped; a member outside
+ * [0, batch) fails the call with SFL_ERR_INVALID and queues nothing.                                */
+SFL_API int sfl_batch_queue_forces(sfl_batch *b, const int *members, const int *cells_ij, const float *vel_xy, int n);
+/* n sim steps of every member, as sfl_step_n (queued forces go into the first step; n == 0 does nothing).  dt, dx,
+ * iters and omega are the same for every member.  Asynchronous on the batch's stream.              */
+SFL_API int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float omega);
+/* pressure <- poisson_solve(divergence, dx, iters, omega) of every member.  Asynchronous.          */
+SFL_API int sfl_batch_poisson_solve(sfl_batch *b, float dx, int iters, float omega);
+/* sfl_setup_sketch_fields for every member (the saturating definition included).  Asynchronous.    */
+SFL_API int sfl_batch_setup_sketch_fields(sfl_batch *b);
+/* sfl_render_rgb565 of one member's dye.  Synchronous.                                            */
+SFL_API int sfl_batch_render_rgb565(sfl_batch *b, int member, int scaling, int byteswap, uint16_t *host_image,
+                                    size_t bytes);
+/* A batch is used from one thread at a time, as a context is.                                    */
+SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Throughput of batches (sfl_batch_*): B independent members of one small grid stepped by one launch per step.
+
+    python tools/batch_throughput.py --size 61 81 --iters 20 [--batches 1 64 256 1024 4096] [--steps K] [--warmup W] [--check]
+
+Every member starts from the sketch's fields (setup_sketch_fields) with a drag of its own in the first warm-up step, so
+that no two members hold the same numbers.  Per B: W warm-up steps, then step_n(K) timed with a host clock around a
+synchronize.  One JSON line per B with
+  * member-steps/s and microseconds per batch step (one launch that steps every member);
+  * the bytes model: 48 B per cell and member-step (velocity in + out 16, dye in + out 24, divergence 4, pressure 4), as
+    GB/s and as a fraction of the MI355X's 8 TB/s;
+  * the ratio to ONE context's sfl_step_n rate, measured in this process on the same grid, iterations and step count;
+  * the ratio to the unmodified reference on one host core: its step at this size as committed in
+    profiles/r06_bench_c1_61x81.json (cited, not re-measured; 61 x 81 at 20 iterations only).
+--check: after the timed run, members {0, 1, B/2, B - 1} against single contexts given the same start, drag and
+steps -- velocity, divergence, pressure and dye bit for bit."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sfl = importlib.import_module("esp32-fluid-simulation_amd")
+
+DT, DX, OMEGA = np.float32(1 / 30.0), 1.0, np.float32(1.96)
+BYTES_PER_CELL_STEP = 48
+HBM_BYTES_PER_S = 8e12
+REFERENCE_PROFILE = os.path.join(ROOT, "profiles", "r06_bench_c1_61x81.json")
+
+
+def reference_step_ms(dim_x, dim_y, iters):
+    """The reference's step on one host core at this size, from the committed C1 bench line (None if not measured)."""
+    with open(REFERENCE_PROFILE) as f:
+        line = json.load(f)
+    for entry in line["cpu_baseline"]["sim_step_per_operator"]:
+        if tuple(entry["grid"]) == (dim_x, dim_y) and entry["iters"] == iters:
+            return entry["ms"]["step"]
+    return None
+
+
+def drag_of(member, dim_x, dim_y):
+    """A drag of this member's own: (cell, velocity)."""
+    return (member % dim_x, (member // dim_x) % dim_y), (10.0 + member % 7, -5.0 + member % 11)
+
+
+def time_context(dim_x, dim_y, iters, warmup, steps):
+    with sfl.Solver(dim_x, dim_y) as s:
+        s.setup_sketch_fields()
+        s.step_n(warmup, DT, DX, iters, OMEGA)
+        s.synchronize()
+        t0 = time.perf_counter()
+        s.step_n(steps, DT, DX, iters, OMEGA)
+        s.synchronize()
+        return steps / (time.perf_counter() - t0)
+
+
+def check_members(b, members, dim_x, dim_y, iters, total_steps):
+    bad = []
+    with sfl.Solver(dim_x, dim_y) as s:
+        for m in members:
+            s.setup_sketch_fields()
+            cell, vel = drag_of(m, dim_x, dim_y)
+            s.queue_forces(np.array([cell], np.int32), np.array([vel], np.float32))
+            s.step_n(total_steps, DT, DX, iters, OMEGA)
+            s.synchronize()
+            for field in (sfl.capi.FIELD_VELOCITY, sfl.capi.FIELD_DIVERGENCE, sfl.capi.FIELD_PRESSURE, sfl.capi.FIELD_COLOR):
+                got = b.download(field, m, 1)[0]
+                want = s.download(field)
+                if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
+                    bad.append((m, field))
+    return bad
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--size", type=int, nargs=2, default=[61, 81], metavar=("DIM_X", "DIM_Y"))
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 64, 256, 1024, 4096])
+    ap.add_argument("--steps", type=int, default=200, help="timed steps per batch (K)")
+    ap.add_argument("--warmup", type=int, default=20, help="untimed steps before them (W)")
+    ap.add_argument("--check", action="store_true", help="compare members with single contexts after the timed run")
+    ap.add_argument("--label", default="", help="free text carried into every line (e.g. the build variant)")
+    a = ap.parse_args()
+    dim_x, dim_y = a.size
+    cells = dim_x * dim_y
+    context_rate = time_context(dim_x, dim_y, a.iters, a.warmup, a.steps)
+    ref_ms = reference_step_ms(dim_x, dim_y, a.iters)
+    ok = True
+    for batch in a.batches:
+        with sfl.BatchSolver(dim_x, dim_y, batch) as b:
+            b.setup_sketch_fields()
+            drags = [drag_of(m, dim_x, dim_y) for m in range(batch)]
+            b.queue_forces(np.arange(batch, dtype=np.int32), [d[0] for d in drags], [d[1] for d in drags])
+            b.step_n(a.warmup, DT, DX, a.iters, OMEGA)
+            b.synchronize()
+            t0 = time.perf_counter()
+            b.step_n(a.steps, DT, DX, a.iters, OMEGA)
+            b.synchronize()
+            seconds = time.perf_counter() - t0
+            rate = batch * a.steps / seconds
+            gbs = BYTES_PER_CELL_STEP * cells * rate / 1e9
+            line = {
+                "grid": [dim_x, dim_y], "iters": a.iters, "batch": batch, "steps": a.steps, "warmup": a.warmup,
+                "member_steps_per_s": rate, "us_per_batch_step": seconds / a.steps * 1e6,
+                "bytes_model_per_member_step": BYTES_PER_CELL_STEP * cells, "gb_per_s": gbs,
+                "frac_of_8tb_s": gbs * 1e9 / HBM_BYTES_PER_S,
+                "context_steps_per_s": context_rate, "x_one_context": rate / context_rate,
+                "x_reference_core": rate * ref_ms / 1e3 if ref_ms else None,
+                "reference_step_ms": ref_ms, "reference_source": "profiles/r06_bench_c1_61x81.json cpu_baseline" if ref_ms else None,
+            }
+            if a.label:
+                line["label"] = a.label
+            if a.check:
+                members = sorted({0, min(1, batch - 1), batch // 2, batch - 1})
+                bad = check_members(b, members, dim_x, dim_y, a.iters, a.warmup + a.steps)
+                line["check_members"] = members
+                line["check_bit_exact"] = not bad
+                ok = ok and not bad
+            print(json.dumps(line), flush=True)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
