@@ -364,83 +364,35 @@ static void invalidate_exchange_measurement(sfl_context *c)
     t.active = false;
 }
 
+static const OptionRow *find_option(int option)
+{
+    for (const OptionRow &o : kOptions)
+        if (o.id == option) return &o;
+    return nullptr;
+}
+
 static int set_option_one(sfl_context *c, int option, int value)
 {
-    switch (option) {
-        case SFL_OPT_SOR_KERNEL:
-            if (value < 0 || value > 2) return fail(SFL_ERR_INVALID, "SOR kernel must be 0, 1 or 2");
-            c->opt_sor_kernel = value;
-            return SFL_OK;
-        case SFL_OPT_SOR_FUSE:
-            if (value != 0 && (value < 2 || value > SFL_MAX_FUSE || (value & 1)))
-                return fail(SFL_ERR_INVALID, "fuse must be 0 (auto) or even, 2..%d (got %d)", SFL_MAX_FUSE, value);
-            c->opt_sor_fuse = value;
-            return SFL_OK;
-        case SFL_OPT_ADVECT_HALO:
-            if (value < 0 || value > kAdvectGhostRows)
-                return fail(SFL_ERR_INVALID, "advect halo must be 0 (auto) or 1..%d rows", kAdvectGhostRows);
-            c->opt_advect_halo = value;
-            return SFL_OK;
-        case SFL_OPT_SOR_ROWS:
-            if (value < 0) return fail(SFL_ERR_INVALID, "rows per chunk must be >= 0");
-            if (value != c->opt_sor_rows) invalidate_exchange_measurement(c);   // (the timed solves the halo depth was chosen from ran on other tiles)
-            c->opt_sor_rows = value;
-            return SFL_OK;
-        case SFL_OPT_TRANSPORT:
-            return fail(SFL_ERR_INVALID, "SFL_OPT_TRANSPORT is read-only: use sfl_comm_attach / sfl_group_link");
-        case SFL_OPT_LAST_EARLY_ROWS:
-        case SFL_OPT_MEASURED_WIRE_US:
-        case SFL_OPT_LAST_HALO:
-            return fail(SFL_ERR_INVALID, "this option is read-only");
-        case SFL_OPT_FUSE_PROJECTION:
-            c->opt_fuse_projection = value ? 1 : 0;
-            return SFL_OK;
-        case SFL_OPT_EXCHANGE_SCHEDULE: {   // 0 automatic, 1 in line, 2 one launch early behind events, 3 in time
-            if (value < 0 || value > 3) return fail(SFL_ERR_INVALID, "exchange schedule must be 0 (auto), 1 (in line), 2 (behind events) or 3 (in time)");
-            const int overlap = value == 1 ? 0 : 1, arrival = value == 2 ? 0 : value == 3 ? 1 : -1;
-            if (overlap != c->opt_sor_overlap || arrival != c->opt_sor_arrival) invalidate_exchange_measurement(c);   // (measured with the other protocol)
-            c->opt_sor_overlap = overlap;
-            c->opt_sor_arrival = arrival;
-            return SFL_OK;
-        }
-        case SFL_OPT_FUSE_DIVERGENCE:
-            c->opt_fuse_divergence = value ? 1 : 0;
-            return SFL_OK;
-        case SFL_OPT_SMALL_GRID:
-            c->opt_small_grid = value ? 1 : 0;
-            return SFL_OK;
-        case SFL_OPT_ADVECT_KERNEL:
-            if (value < 0 || value > 2) return fail(SFL_ERR_INVALID, "advection kernel must be 0, 1 or 2");
-            c->opt_advect_kernel = value;
-            return SFL_OK;
-        case SFL_OPT_EMULATE_WIRE_US:
-            if (value < 0 || value > 10000) return fail(SFL_ERR_INVALID, "emulated wire delay must be 0..10000 us");
-            c->opt_emulate_wire_us = value;
-            invalidate_exchange_measurement(c);   // what an exchange costs is measured again before the next solve
-            return SFL_OK;
-        case SFL_OPT_HALO_TIMEOUT_MS:
-            if (value < 0) return fail(SFL_ERR_INVALID, "halo timeout must be >= 0 ms (0 = the transport's default)");
-            c->opt_halo_timeout_ms = value;
-            return SFL_OK;
-        case SFL_OPT_STEP_SEAMS:
-            c->opt_step_seams = value ? 1 : 0;
-            return SFL_OK;
-        case SFL_OPT_SOR_FOLD:
-            c->opt_sor_fold = value ? 1 : 0;
-            return SFL_OK;
-        case SFL_OPT_SOR_HALO:
-            if (value != 0 && (value < 2 || value > kGhostRows))
-                return fail(SFL_ERR_INVALID, "SOR halo must be 0 (auto) or 2..%d rows", kGhostRows);
-            c->opt_sor_halo = value;
-            return SFL_OK;
-        case SFL_OPT_SOR_LANE_CELLS:
-            if (value != 0 && value != 2)
-                return fail(SFL_ERR_INVALID, "cells per lane must be 0 (auto) or 2 (the packed 4-cell "
-                            "flavour of round 1 is gone: never faster)");
-            c->opt_sor_lane_cells = value;
-            return SFL_OK;
+    const OptionRow *o = find_option(option);
+    if (!o) return fail(SFL_ERR_INVALID, "unknown option %d", option);
+    const bool in_range = value >= o->lo && value <= o->hi;
+    const bool ok = o->check == kRange ? in_range
+                  : o->check == kZeroOrRange ? value == 0 || in_range
+                  : o->check == kZeroOrEven ? value == 0 || (in_range && !(value & 1))
+                  : o->check == kBool;
+    if (!ok) return fail(SFL_ERR_INVALID, o->error, o->hi, value);
+    if (option == SFL_OPT_EXCHANGE_SCHEDULE) {   // 0 automatic, 1 in line, 2 one launch early behind events, 3 in time
+        const int overlap = value == 1 ? 0 : 1, arrival = value == 2 ? 0 : value == 3 ? 1 : -1;
+        if (overlap != c->opt.sor_overlap || arrival != c->opt.sor_arrival) invalidate_exchange_measurement(c);   // (measured with the other protocol)
+        c->opt.sor_overlap = overlap;
+        c->opt.sor_arrival = arrival;
+        return SFL_OK;
     }
-    return fail(SFL_ERR_INVALID, "unknown option %d", option);
+    if (o->check == kBool) value = value ? 1 : 0;
+    int &stored = c->opt.*o->field;
+    if ((o->flags & kForgetOnSet) || ((o->flags & kForgetOnChange) && value != stored)) invalidate_exchange_measurement(c);
+    stored = value;
+    return SFL_OK;
 }
 
 // Options of a linked group are GROUP-wide: the slabs execute one program in lock step, and a
@@ -461,37 +413,30 @@ int sfl_set_option(sfl_context *ctx, int option, int value)
 int sfl_get_option(sfl_context *c, int option, int *value)
 {
     if (!c || !value) return fail(SFL_ERR_INVALID, "NULL argument");
-    switch (option) {
-        case SFL_OPT_SOR_KERNEL: *value = c->opt_sor_kernel; return SFL_OK;
-        case SFL_OPT_SOR_FOLD: *value = c->opt_sor_fold; return SFL_OK;
-        case SFL_OPT_SOR_FUSE: *value = c->opt_sor_fuse; return SFL_OK;
-        case SFL_OPT_ADVECT_HALO: *value = c->opt_advect_halo; return SFL_OK;
-        case SFL_OPT_SOR_ROWS: *value = c->opt_sor_rows; return SFL_OK;
-        case SFL_OPT_TRANSPORT: *value = c->transport ? c->transport->kind() : 0; return SFL_OK;
-        case SFL_OPT_HALO_TIMEOUT_MS: *value = c->opt_halo_timeout_ms; return SFL_OK;
-        case SFL_OPT_LAST_HALO: *value = c->last_halo; return SFL_OK;
+    const OptionRow *o = find_option(option);
+    if (!o) return fail(SFL_ERR_INVALID, "unknown option %d", option);
+    if (o->field) {
+        *value = c->opt.*o->field;
+        return SFL_OK;
+    }
+    switch (option) {   // computed, or read from the solver's state
+        case SFL_OPT_TRANSPORT: *value = c->transport ? c->transport->kind() : 0; break;
+        case SFL_OPT_LAST_HALO: *value = c->last_halo; break;
+        case SFL_OPT_LAST_EARLY_ROWS: *value = c->last_early_kept; break;
         case SFL_OPT_MEASURED_WIRE_US:   // (a query only: measuring is a COLLECTIVE of the ranks and belongs to the next solve, resolve_schedule)
             *value = c->transport && c->nranks > 1 ? c->exchange_latency_us : -1;
-            return SFL_OK;
+            break;
         case SFL_OPT_EXCHANGE_SCHEDULE: {   // what the next solve will do: needs the streams' verdict (transport.cpp)
-            if (!c->transport || c->nranks < 2 || c->opt_sor_kernel == 1) { *value = 0; return SFL_OK; }
+            *value = 0;
+            if (!c->transport || c->nranks < 2 || c->opt.sor_kernel == 1) break;
             bool side_by_side = false;
             SFL_TRY(streams_run_concurrently(c, &side_by_side));
-            const int asked = c->opt_sor_arrival >= 0 ? c->opt_sor_arrival : (c->transport->arrival_by_default() ? 1 : 0);
-            *value = !c->opt_sor_overlap ? 1 : (asked && side_by_side ? 3 : 2);
-            return SFL_OK;
+            const int asked = c->opt.sor_arrival >= 0 ? c->opt.sor_arrival : (c->transport->arrival_by_default() ? 1 : 0);
+            *value = !c->opt.sor_overlap ? 1 : (asked && side_by_side ? 3 : 2);
+            break;
         }
-        case SFL_OPT_SOR_LANE_CELLS: *value = c->opt_sor_lane_cells; return SFL_OK;
-        case SFL_OPT_SOR_HALO: *value = c->opt_sor_halo; return SFL_OK;
-        case SFL_OPT_FUSE_PROJECTION: *value = c->opt_fuse_projection; return SFL_OK;
-        case SFL_OPT_ADVECT_KERNEL: *value = c->opt_advect_kernel; return SFL_OK;
-        case SFL_OPT_FUSE_DIVERGENCE: *value = c->opt_fuse_divergence; return SFL_OK;
-        case SFL_OPT_SMALL_GRID: *value = c->opt_small_grid; return SFL_OK;
-        case SFL_OPT_EMULATE_WIRE_US: *value = c->opt_emulate_wire_us; return SFL_OK;
-        case SFL_OPT_STEP_SEAMS: *value = c->opt_step_seams; return SFL_OK;
-        case SFL_OPT_LAST_EARLY_ROWS: *value = c->last_early_kept; return SFL_OK;
     }
-    return fail(SFL_ERR_INVALID, "unknown option %d", option);
+    return SFL_OK;
 }
 
 int sfl_slab_of(sfl_context *c, int *row_begin, int *row_end, int *rank, int *nranks)
@@ -568,7 +513,7 @@ int sfl_synchronize(sfl_context *ctx)
             if (words[0]) {
                 HIP_TRY(hipMemset(c->halo_flag, 0, sizeof(int)));
                 rc = fail(SFL_ERR_HALO, "slab %d/%d: a back-trace left the %d-row advect halo; raise "
-                          "SFL_OPT_ADVECT_HALO", c->rank, c->nranks, c->opt_advect_halo);
+                          "SFL_OPT_ADVECT_HALO", c->rank, c->nranks, c->opt.advect_halo);
             }
             if (words[2]) {
                 HIP_TRY(hipMemset(c->halo_flag + 2, 0, sizeof(int)));

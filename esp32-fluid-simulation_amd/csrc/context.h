@@ -14,6 +14,7 @@
 // SFL_ERR_HIP when no device is usable.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -106,6 +107,68 @@ struct HaloTuner {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
+};
+
+// What sfl_set_option stores, with the defaults.  A solve reads these as plain members; everything else the library knows
+// about an option is its row of kOptions below.
+struct Options {
+    int sor_kernel = 0, sor_fuse = 0, advect_halo = 0, sor_rows = 0, sor_lane_cells = 0, sor_halo = 0, fuse_projection = 1,
+        advect_kernel = 0, fuse_divergence = 1, small_grid = 1, emulate_wire_us = 0, step_seams = 1, halo_timeout_ms = 0, sor_fold = 0;
+    // the two halves of SFL_OPT_EXCHANGE_SCHEDULE: sor_overlap 0 = in line (1); sor_arrival -1 = automatic (the transport's choice,
+    // Transport::arrival_by_default), 0 = behind events (2), 1 = in time (3)
+    int sor_overlap = 1, sor_arrival = -1;
+};
+
+// One row per option number sfl_set_option / sfl_get_option accept.  How a set is checked:
+enum OptionCheck {
+    kRange,        // lo <= value <= hi
+    kZeroOrRange,  // 0, or lo <= value <= hi
+    kZeroOrEven,   // 0, or even and lo <= value <= hi
+    kBool,         // any value, stored as 0 / 1
+    kReadOnly,     // never
+};
+enum : unsigned {
+    kForgetOnChange = 1,  // a CHANGED value forgets the measured exchange and the halo depths chosen from it (context.cpp)
+    kForgetOnSet = 2,     // ... every set does
+    kGroupWide = 4,       // sfl_group_link copies slab 0's value to the other members
+    kHostReset = 8,       // the host drop-ins put a cached context back to the default (host_dropin.cpp)
+};
+struct OptionRow {
+    int id;                // SFL_OPT_*
+    int Options::*field;   // where the value lives; null: computed, or not one int (context.cpp handles those by hand)
+    OptionCheck check;
+    int lo, hi;
+    const char *error;     // of a refused set: a printf format that is given (hi, value)
+    unsigned flags;
+    int block_word;        // RCCL ranks must agree on the value: its word of the option block (transport.cpp); 0: not compared
+};
+// Flags that look like omissions, and are (first item; closing them changes behaviour and the ABI version, so not
+// here): linking a group leaves SFL_OPT_EMULATE_WIRE_US (12) and SFL_OPT_STEP_SEAMS (14) as each slab had them, and RCCL ranks
+// never compare SFL_OPT_SOR_ROWS (3), SOR_LANE_CELLS (5), EMULATE_WIRE_US (12), STEP_SEAMS (14) and HALO_TIMEOUT_MS (18).
+constexpr OptionRow kOptions[] = {
+    {SFL_OPT_SOR_KERNEL, &Options::sor_kernel, kRange, 0, 2, "SOR kernel must be 0, 1 or 2", kGroupWide | kHostReset, 4},
+    {SFL_OPT_SOR_FUSE, &Options::sor_fuse, kZeroOrEven, 2, SFL_MAX_FUSE, "fuse must be 0 (auto) or even, 2..%d (got %d)", kGroupWide | kHostReset, 5},
+    {SFL_OPT_ADVECT_HALO, &Options::advect_halo, kRange, 0, kAdvectGhostRows, "advect halo must be 0 (auto) or 1..%d rows", kGroupWide, 8},
+    // (a change: the timed solves the halo depth was chosen from ran on other tiles)
+    {SFL_OPT_SOR_ROWS, &Options::sor_rows, kRange, 0, INT_MAX, "rows per chunk must be >= 0", kForgetOnChange | kGroupWide | kHostReset, 0},
+    {SFL_OPT_TRANSPORT, nullptr, kReadOnly, 0, 0, "SFL_OPT_TRANSPORT is read-only: use sfl_comm_attach / sfl_group_link", 0, 0},
+    {SFL_OPT_SOR_LANE_CELLS, &Options::sor_lane_cells, kZeroOrRange, 2, 2,
+     "cells per lane must be 0 (auto) or 2 (the packed 4-cell flavour of round 1 is gone: never faster)", kGroupWide | kHostReset, 0},
+    {SFL_OPT_SOR_HALO, &Options::sor_halo, kZeroOrRange, 2, kGhostRows, "SOR halo must be 0 (auto) or 2..%d rows", kGroupWide, 6},
+    {SFL_OPT_FUSE_PROJECTION, &Options::fuse_projection, kBool, 0, 1, nullptr, kGroupWide, 9},
+    {SFL_OPT_ADVECT_KERNEL, &Options::advect_kernel, kRange, 0, 2, "advection kernel must be 0, 1 or 2", kGroupWide | kHostReset, 10},
+    {SFL_OPT_FUSE_DIVERGENCE, &Options::fuse_divergence, kBool, 0, 1, nullptr, kGroupWide, 11},
+    {SFL_OPT_SMALL_GRID, &Options::small_grid, kBool, 0, 1, nullptr, kGroupWide, 12},
+    // (every set: what an exchange costs is measured again before the next solve)
+    {SFL_OPT_EMULATE_WIRE_US, &Options::emulate_wire_us, kRange, 0, 10000, "emulated wire delay must be 0..10000 us", kForgetOnSet, 0},
+    {SFL_OPT_STEP_SEAMS, &Options::step_seams, kBool, 0, 1, nullptr, 0, 0},
+    {SFL_OPT_LAST_EARLY_ROWS, nullptr, kReadOnly, 0, 0, "this option is read-only", 0, 0},
+    {SFL_OPT_HALO_TIMEOUT_MS, &Options::halo_timeout_ms, kRange, 0, INT_MAX, "halo timeout must be >= 0 ms (0 = the transport's default)", kGroupWide, 0},
+    // one number over the two stored halves: set, get, the group's copy and the option block (words 7 and 13) name them by hand
+    {SFL_OPT_EXCHANGE_SCHEDULE, nullptr, kRange, 0, 3, "exchange schedule must be 0 (auto), 1 (in line), 2 (behind events) or 3 (in time)", kGroupWide, 0},
+    {SFL_OPT_MEASURED_WIRE_US, nullptr, kReadOnly, 0, 0, "this option is read-only", 0, 0},
+    {SFL_OPT_LAST_HALO, nullptr, kReadOnly, 0, 0, "this option is read-only", 0, 0},
+    {SFL_OPT_SOR_FOLD, &Options::sor_fold, kBool, 0, 1, nullptr, kGroupWide | kHostReset, 14},
 };
 
 }  // namespace host
@@ -203,12 +266,7 @@ struct sfl_context {
     uint64_t known_epoch = 0, vel_epoch = 1;   // vel_epoch counts the writes to the velocity field
     float known_dt = 0.0f;
 
-    // the two halves of SFL_OPT_EXCHANGE_SCHEDULE: opt_sor_overlap 0 = in line (1); opt_sor_arrival -1 = automatic (the transport's choice,
-    // Transport::arrival_by_default), 0 = behind events (2), 1 = in time (3)
-    int opt_sor_kernel = 0, opt_sor_fuse = 0, opt_advect_halo = 0, opt_sor_rows = 0,
-        opt_sor_lane_cells = 0, opt_sor_halo = 0, opt_fuse_projection = 1, opt_sor_overlap = 1,
-        opt_advect_kernel = 0, opt_fuse_divergence = 1, opt_small_grid = 1, opt_emulate_wire_us = 0, opt_sor_arrival = -1,
-        opt_step_seams = 1, opt_halo_timeout_ms = 0, opt_sor_fold = 0;
+    sfl::host::Options opt;   // what sfl_set_option stores (kOptions above: one row per option)
 
     // how halo rows reach the neighbouring slabs (transport.h); null on a whole-domain context and on a slab that has
     // not been attached / linked yet.  `group` = the same object when it is an in-process group of virtual ranks.

@@ -47,13 +47,9 @@ struct HostCtx {
         if (k && k->device == dev && k->dim_x == dim_x && k->gdim_y == dim_y) {
             c = k;
             cached = true;
-            sfl_context fresh;  // option defaults
-            c->opt_sor_kernel = fresh.opt_sor_kernel;
-            c->opt_sor_fold = fresh.opt_sor_fold;
-            c->opt_sor_fuse = fresh.opt_sor_fuse;
-            c->opt_sor_rows = fresh.opt_sor_rows;
-            c->opt_sor_lane_cells = fresh.opt_sor_lane_cells;
-            c->opt_advect_kernel = fresh.opt_advect_kernel;
+            const Options fresh;  // option defaults
+            for (const OptionRow &o : kOptions)
+                if (o.flags & kHostReset) c->opt.*o.field = fresh.*o.field;
             return SFL_OK;
         }
         if (k) {
@@ -111,7 +107,7 @@ int sfl_host_advect_vec2f(float *next_p, const float *p, const float *vel, int d
         src = c->host_scratch;
     }
     hipError_t e = sfl::launch_advect_vec2f(c->stream, c->vel_tmp, src, c->vel, c->geom, 0, dim_y, 0,
-                                            dim_y, dt, no_slip != 0, nullptr, nullptr, c->opt_advect_kernel);
+                                            dim_y, dt, no_slip != 0, nullptr, nullptr, c->opt.advect_kernel);
     int rc = e == hipSuccess ? download_raw(c, c->vel_tmp, next_p, 8)
                              : fail(SFL_ERR_HIP, "advect launch failed: %s", hipGetErrorString(e));
     return t.done(rc);

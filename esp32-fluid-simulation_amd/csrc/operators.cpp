@@ -66,8 +66,8 @@ static int plan_advect(sfl_context *ctx, const std::vector<sfl_context *> &peers
 {
     *plan = AdvectPlan{};
     if (ctx->nranks == 1) return SFL_OK;
-    if (ctx->opt_advect_halo > 0) {
-        plan->halo = ctx->opt_advect_halo;
+    if (ctx->opt.advect_halo > 0) {
+        plan->halo = ctx->opt.advect_halo;
         return SFL_OK;
     }
     int reach = 0;
@@ -101,17 +101,17 @@ int advect_velocity_planned(sfl_context *ctx, const std::vector<sfl_context *> &
         if (plan.gather)
             HIP_TRY(sfl::launch_advect_vec2f(c->stream, c->vel_tmp, static_cast<const float *>(c->gather_buf),
                                              c->vel, c->geom, c->g0, c->g1, 0, c->gdim_y, dt, no_slip != 0,
-                                             nullptr, &whole, c->opt_advect_kernel));
+                                             nullptr, &whole, c->opt.advect_kernel));
         else if (interior_done > 0)   // both bands in one launch
             HIP_TRY(sfl::launch_advect_vec2f(c->stream, c->vel_tmp, c->vel, c->vel, c->geom, clip_lo(c, c->g0 - extend),
                                              c->g0 + interior_done, clip_lo(c, c->g0 - plan.halo),
                                              clip_hi(c, c->g1 + plan.halo), dt, no_slip != 0, advect_flag(c, plan), nullptr,
-                                             c->opt_advect_kernel, c->g1 - interior_done, clip_hi(c, c->g1 + extend)));
+                                             c->opt.advect_kernel, c->g1 - interior_done, clip_hi(c, c->g1 + extend)));
         else
             HIP_TRY(sfl::launch_advect_vec2f(c->stream, c->vel_tmp, c->vel, c->vel, c->geom,
                                              clip_lo(c, c->g0 - extend), clip_hi(c, c->g1 + extend),
                                              clip_lo(c, c->g0 - plan.halo), clip_hi(c, c->g1 + plan.halo), dt,
-                                             no_slip != 0, advect_flag(c, plan), nullptr, c->opt_advect_kernel));
+                                             no_slip != 0, advect_flag(c, plan), nullptr, c->opt.advect_kernel));
         std::swap(c->vel, c->vel_tmp);  // ino:255
         ++c->vel_epoch;
         c->v_ghost_valid = plan.gather ? 0 : extend;
@@ -141,11 +141,11 @@ int advect_color_planned(sfl_context *ctx, const std::vector<sfl_context *> &pee
         if (plan.gather)
             HIP_TRY(sfl::launch_advect_vec3uq32(c->stream, c->col_tmp, static_cast<const uint32_t *>(c->gather_buf),
                                                 c->vel, c->geom, c->g0, c->g1, 0, c->gdim_y, dt, no_slip != 0,
-                                                nullptr, &whole, c->opt_advect_kernel));
+                                                nullptr, &whole, c->opt.advect_kernel));
         else
             HIP_TRY(sfl::launch_advect_vec3uq32(c->stream, c->col_tmp, c->col, c->vel, c->geom, c->g0, c->g1,
                                                 clip_lo(c, c->g0 - plan.halo), clip_hi(c, c->g1 + plan.halo), dt,
-                                                no_slip != 0, advect_flag(c, plan), nullptr, c->opt_advect_kernel));
+                                                no_slip != 0, advect_flag(c, plan), nullptr, c->opt.advect_kernel));
         std::swap(c->col, c->col_tmp);  // ino:286
     }
     return SFL_OK;
@@ -250,7 +250,7 @@ int project_and_advect_color(sfl_context *ctx, float dt, float dx, int halo, boo
         HIP_TRY(sfl::launch_project_advect_vec3uq32(
             c->stream, c->col_tmp, c->col, c->vel, c->p, c->geom, c->g0, c->g1, clip_lo(c, c->g0 - h),
             clip_hi(c, c->g1 + h), dt, false, c->nranks > 1 ? (report ? c->d_report + 2 : c->halo_flag) : nullptr,
-            two_dx_inv, c->opt_advect_kernel, c->nranks > 1 && report ? &c->reach_in_report : nullptr));
+            two_dx_inv, c->opt.advect_kernel, c->nranks > 1 && report ? &c->reach_in_report : nullptr));
         std::swap(c->col, c->col_tmp);  // ino:286
         ++c->vel_epoch;                 // the projection rewrote the velocity
         c->v_ghost_valid = 0;
@@ -262,9 +262,9 @@ int project_and_advect_color(sfl_context *ctx, float dt, float dx, int halo, boo
 // forces, ino:264-269) and every neighbour of every cell is on this GPU (whole-domain context)
 bool can_fuse_divergence(const sfl_context *c)
 {
-    if (!c->opt_fuse_divergence || c->nranks != 1 || c->transport || !c->force_cells.empty()) return false;
+    if (!c->opt.fuse_divergence || c->nranks != 1 || c->transport || !c->force_cells.empty()) return false;
     const int64_t cells = (int64_t)c->dim_x * c->gdim_y;
-    return c->opt_advect_kernel == 2 || (c->opt_advect_kernel == 0 && cells >= sfl::kAdvectTiledMinCells);
+    return c->opt.advect_kernel == 2 || (c->opt.advect_kernel == 0 && cells >= sfl::kAdvectTiledMinCells);
 }
 
 int advect_velocity_and_divergence(sfl_context *c, float dt, float dx)
@@ -357,7 +357,7 @@ int sfl_calculate_divergence(sfl_context *ctx, float dx)
     for (sfl_context *c : peers) {
         SFL_TRY(use_device(c));
         HIP_TRY(sfl::launch_divergence(c->stream, c->div, c->vel, c->geom, c->g0, c->g1, two_dx_inv,
-                                       c->opt_advect_kernel));
+                                       c->opt.advect_kernel));
     }
     return SFL_OK;
 }
@@ -385,7 +385,7 @@ int sfl_subtract_gradient(sfl_context *ctx, float dx)
     for (sfl_context *c : peers) {
         SFL_TRY(use_device(c));
         HIP_TRY(sfl::launch_subtract_gradient(c->stream, c->vel, c->p, c->geom, c->g0, c->g1,
-                                              two_dx_inv, c->opt_advect_kernel));
+                                              two_dx_inv, c->opt.advect_kernel));
         ++c->vel_epoch;
         c->v_ghost_valid = 0;
     }

@@ -234,7 +234,7 @@ static int slab_step_auto(sfl_context *ctx, float dt, float dx, int iters, float
         HIP_TRY(hipMemsetAsync(c->d_report, 0, kReachWords * sizeof(int), c->stream));
     }
     for (sfl_context *c : peers) c->report_zeroed = false;
-    if (ctx->opt_fuse_projection) {
+    if (ctx->opt.fuse_projection) {
         SFL_TRY(project_and_advect_color(ctx, dt, dx, guess, true, true));  // ino:276 + ino:281-287, one pass over v
     } else {
         SFL_TRY(sfl_subtract_gradient(ctx, dx));                            // ino:276
@@ -265,7 +265,7 @@ static int advect_interior_early(sfl_context *ctx, float dt)
     for (sfl_context *c : peers) {
         SFL_TRY(use_device(c));
         HIP_TRY(sfl::launch_advect_vec2f(c->stream, c->vel_tmp, c->vel, c->vel, c->geom, c->g0 + limit, c->g1 - limit, c->g0,
-                                         c->g1, dt, true, nullptr, nullptr, c->opt_advect_kernel));
+                                         c->g1, dt, true, nullptr, nullptr, c->opt.advect_kernel));
         c->early_rows = limit;
         c->early_epoch = c->vel_epoch;
         c->early_dt = dt;
@@ -301,12 +301,12 @@ extern "C" {
 int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
 {
     if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
-    if (ctx->nranks > 1 && ctx->opt_advect_halo == 0 && ctx->color_unsettled && ctx->unsettled_dt == dt && ctx->force_cells.empty())
+    if (ctx->nranks > 1 && ctx->opt.advect_halo == 0 && ctx->color_unsettled && ctx->unsettled_dt == dt && ctx->force_cells.empty())
         SFL_TRY(advect_interior_early(ctx, dt));
     SFL_TRY(settle_color(ctx, true));
     SFL_TRY(check_wait_error(ctx));
     if (small_grid(ctx)) return small_grid_step(ctx, dt, dx, iters, omega);
-    if (ctx->nranks > 1 && ctx->opt_advect_halo == 0) return slab_step_auto(ctx, dt, dx, iters, omega);
+    if (ctx->nranks > 1 && ctx->opt.advect_halo == 0) return slab_step_auto(ctx, dt, dx, iters, omega);
     if (can_fuse_divergence(ctx)) {
         SFL_TRY(advect_velocity_and_divergence(ctx, dt, dx));  // ino:252-256 + ino:274
     } else {
@@ -315,8 +315,8 @@ int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
         SFL_TRY(sfl_calculate_divergence(ctx, dx));            // ino:274
     }
     SFL_TRY(sfl_poisson_solve(ctx, dx, iters, omega));     // ino:275
-    if (ctx->opt_fuse_projection) {
-        SFL_TRY(project_and_advect_color(ctx, dt, dx, ctx->opt_advect_halo, false));  // ino:276 + ino:281-287, one pass over v
+    if (ctx->opt.fuse_projection) {
+        SFL_TRY(project_and_advect_color(ctx, dt, dx, ctx->opt.advect_halo, false));  // ino:276 + ino:281-287, one pass over v
     } else {
         SFL_TRY(sfl_subtract_gradient(ctx, dx));           // ino:276
         SFL_TRY(sfl_advect_color(ctx, dt, 0));             // ino:281-287
@@ -335,9 +335,9 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
     SFL_TRY(settle_color(ctx, true));
     SFL_TRY(check_wait_error(ctx));
     const int64_t cells = (int64_t)ctx->dim_x * ctx->gdim_y;
-    const bool tiled = ctx->opt_advect_kernel == 2 || (ctx->opt_advect_kernel == 0 && cells >= sfl::kAdvectTiledMinCells);
-    const bool seams = n > 1 && ctx->opt_step_seams && ctx->nranks == 1 && !ctx->transport && !small_grid(ctx) && tiled &&
-                       ctx->opt_fuse_projection && ctx->opt_fuse_divergence;
+    const bool tiled = ctx->opt.advect_kernel == 2 || (ctx->opt.advect_kernel == 0 && cells >= sfl::kAdvectTiledMinCells);
+    const bool seams = n > 1 && ctx->opt.step_seams && ctx->nranks == 1 && !ctx->transport && !small_grid(ctx) && tiled &&
+                       ctx->opt.fuse_projection && ctx->opt.fuse_divergence;
     if (!seams) {
         for (int k = 0; k < n; ++k) SFL_TRY(sfl_step(ctx, dt, dx, iters, omega));
         return SFL_OK;
@@ -355,7 +355,7 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
         if (k + 1 < n)
             SFL_TRY(step_seam(ctx, dt, dx));                                                      // ino:276, :281-287 | :252-256, :274
         else
-            SFL_TRY(project_and_advect_color(ctx, dt, dx, ctx->opt_advect_halo, false));          // ino:276 + ino:281-287
+            SFL_TRY(project_and_advect_color(ctx, dt, dx, ctx->opt.advect_halo, false));          // ino:276 + ino:281-287
     }
     return SFL_OK;
 }

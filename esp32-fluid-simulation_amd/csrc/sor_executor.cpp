@@ -25,7 +25,7 @@ sfl::SorParams sor_params(const sfl_context *c, float dx, float omega)
     prm.omega = omega;
     prm.one_minus_omega = 1.0f - omega;  // (1 - omega) in float, poisson.cpp:98,111
     prm.neg_quarter_omega = -0.25f * omega;
-    prm.fold = c->opt_sor_fold && quarter_omega_is_exact(omega) ? 1 : 0;
+    prm.fold = c->opt.sor_fold && quarter_omega_is_exact(omega) ? 1 : 0;
     return prm;
 }
 
@@ -40,7 +40,7 @@ sfl::SorParams sor_params(const sfl_context *c, float dx, float omega)
 // re-streams.  Every rank of a group sees the same thinnest slab, so all ranks resolve the same value.
 int effective_fuse(const sfl_context *c)
 {
-    int f = c->opt_sor_fuse;
+    int f = c->opt.sor_fuse;
     if (f == 0) {
         const int64_t cells = (int64_t)min_owned_rows(c) * c->dim_x;
         f = cells >= 12000000 ? 16 : cells >= 3000000 ? 10 : 8;
@@ -50,15 +50,15 @@ int effective_fuse(const sfl_context *c)
     return f & ~1;
 }
 
-int effective_kernel(const sfl_context *c) { return c->opt_sor_kernel == 1 ? 1 : 2; }
+int effective_kernel(const sfl_context *c) { return c->opt.sor_kernel == 1 ? 1 : 2; }
 
 // One workgroup, fields in LDS (small_grid.hip): whole-domain contexts of at most kSmallGridMaxCells cells whose
 // kernel options are all automatic (an explicit kernel / fuse / tile choice is honoured as given).
 bool small_grid(const sfl_context *c)
 {
-    return c->opt_small_grid && c->nranks == 1 && !c->transport &&
-           sfl::small_grid_fits(c->dim_x, c->gdim_y) && c->opt_sor_kernel == 0 &&
-           c->opt_sor_fuse == 0 && c->opt_sor_rows == 0 && c->opt_sor_lane_cells == 0 && c->opt_advect_kernel == 0;
+    return c->opt.small_grid && c->nranks == 1 && !c->transport &&
+           sfl::small_grid_fits(c->dim_x, c->gdim_y) && c->opt.sor_kernel == 0 &&
+           c->opt.sor_fuse == 0 && c->opt.sor_rows == 0 && c->opt.sor_lane_cells == 0 && c->opt.advect_kernel == 0;
 }
 
 
@@ -136,7 +136,7 @@ static int modelled_best_halo(const sfl_context *c, int fuse, int iters, bool in
 // legacy depth (plans queried from outside, the model's own plans).
 int effective_halo(const sfl_context *c, int fuse, int iters, bool in_time)
 {
-    if (c->opt_sor_halo) return clamp_halo(c, fuse, c->opt_sor_halo);
+    if (c->opt.sor_halo) return clamp_halo(c, fuse, c->opt.sor_halo);
     const HaloTuner &t = c->group ? c->group->halo_tuner : c->halo_tuner;
     const HaloTuner::Kind kind{iters, fuse, c->solve_tail, in_time ? 1 : 0};
     for (const HaloTuner::Decided &d : t.decided)
@@ -154,7 +154,7 @@ static int choose_halo(sfl_context *ctx, int fuse, int iters, bool in_time, int 
 {
     *timed_solve = -1;
     HaloTuner &t = ctx->group ? ctx->group->halo_tuner : ctx->halo_tuner;
-    if (ctx->opt_sor_halo || !ctx->transport || ctx->nranks < 2 || iters < 1 || ctx->exchange_latency_us < 0) {
+    if (ctx->opt.sor_halo || !ctx->transport || ctx->nranks < 2 || iters < 1 || ctx->exchange_latency_us < 0) {
         t.active = false;
         return effective_halo(ctx, fuse, iters, in_time);
     }
@@ -227,8 +227,8 @@ static int choose_halo(sfl_context *ctx, int fuse, int iters, bool in_time, int 
 // seen to run side by side (resolve_schedule: a launch that waits inside the kernel must not sit in front of its message).
 bool in_time_exchanges(const sfl_context *c)
 {
-    if (!c->transport || !c->opt_sor_overlap || c->nranks < 2 || c->opt_sor_kernel == 1) return false;
-    const int asked = c->opt_sor_arrival >= 0 ? c->opt_sor_arrival : (c->transport->arrival_by_default() ? 1 : 0);
+    if (!c->transport || !c->opt.sor_overlap || c->nranks < 2 || c->opt.sor_kernel == 1) return false;
+    const int asked = c->opt.sor_arrival >= 0 ? c->opt.sor_arrival : (c->transport->arrival_by_default() ? 1 : 0);
     const int side_by_side = c->group ? c->group->streams_concurrent : c->streams_concurrent;
     return asked && side_by_side == 1;
 }
@@ -243,14 +243,14 @@ int resolve_schedule(sfl_context *ctx)
     // what an exchange costs (the automatic halo depth is chosen from it): RCCL ranks measured it, collectively, at
     // attach; ranks that share this host thread do it here, once, when no halo depth was asked for; and everybody again
     // after an option changed the protocol it was measured with
-    if (ctx->exchange_latency_us < 0 && ctx->opt_sor_halo == 0 && ctx->opt_sor_kernel != 1)
+    if (ctx->exchange_latency_us < 0 && ctx->opt.sor_halo == 0 && ctx->opt.sor_kernel != 1)
         SFL_TRY(measure_exchange(ctx));   // (RCCL ranks get here together: each of them changed the option that invalidated it)
     return SFL_OK;
 }
 
 int halo_timeout_us(const sfl_context *c)
 {
-    if (c->opt_halo_timeout_ms > 0) return c->opt_halo_timeout_ms > 2000000 ? 2000000000 : c->opt_halo_timeout_ms * 1000;
+    if (c->opt.halo_timeout_ms > 0) return c->opt.halo_timeout_ms > 2000000 ? 2000000000 : c->opt.halo_timeout_ms * 1000;
     return c->transport ? c->transport->default_timeout_us() : 2000000;
 }
 
@@ -273,7 +273,7 @@ int launch_sor_rows(sfl_context *c, const sfl_plan_step &st, const sfl::SorParam
     const int sweep = c->local_cells() >= kAlternateSweepCells ? c->last_launches : 0;
     HIP_TRY(sfl::launch_sor_fused(on ? on : c->stream, out, st.from_zero ? nullptr : in, c->div, c->geom,
                                   sfl::SorRows{g_begin, g_end, g2_begin, g2_end}, st.nsweeps, st.first_colour,
-                                  prm, c->opt_sor_rows, sweep, wait, senders));
+                                  prm, c->opt.sor_rows, sweep, wait, senders));
     return SFL_OK;
 }
 
@@ -481,7 +481,7 @@ int run_poisson(sfl_context *ctx, float dx, int iters, float omega)
         }
         return SFL_OK;
     }
-    if (kernel == 2 && ctx->nranks > 1 && ctx->opt_sor_overlap && ctx->transport) {
+    if (kernel == 2 && ctx->nranks > 1 && ctx->opt.sor_overlap && ctx->transport) {
         SFL_TRY(run_poisson_overlapped(ctx, peers, progs, prm));
     } else {
         for (size_t i = 0; i < progs[0].size(); ++i) {

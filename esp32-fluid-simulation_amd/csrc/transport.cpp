@@ -60,7 +60,7 @@ public:
         SFL_TRY(use_device(c));
         hipStream_t st = on ? on : c->stream;
         const size_t bytes = band_bytes(c, b);
-        if (self) HIP_TRY(launch_spin_us(st, c->opt_emulate_wire_us));   // (a rank talking to itself has no wire: SFL_OPT_EMULATE_WIRE_US adds one)
+        if (self) HIP_TRY(launch_spin_us(st, c->opt.emulate_wire_us));   // (a rank talking to itself has no wire: SFL_OPT_EMULATE_WIRE_US adds one)
         NCCL_TRY(ncclGroupStart());
         if (c->rank > 0) {
             NCCL_TRY(ncclSend(row_ptr(c, b.field, c->g0 + b.skip), bytes, ncclChar, peer(c->rank - 1), comm, st));
@@ -118,7 +118,7 @@ public:
         const bool lo = c->rank > 0, hi = c->rank < c->nranks - 1;
         void *dst_a = lo ? row_ptr(c, b.field, c->g0 - b.skip - b.rows) : nullptr, *dst_b = hi ? row_ptr(c, b.field, c->g1 + b.skip) : nullptr;
         const void *src_a = lo ? row_ptr(c, b.field, c->g0 + b.skip) : nullptr, *src_b = hi ? row_ptr(c, b.field, c->g1 - b.skip - b.rows) : nullptr;
-        HIP_TRY(launch_spin_us(st, c->opt_emulate_wire_us));   // the wire a self-copy does not have (0: none)
+        HIP_TRY(launch_spin_us(st, c->opt.emulate_wire_us));   // the wire a self-copy does not have (0: none)
         HIP_TRY(launch_copy_bands(st, dst_a, src_a, dst_b, src_b, band_bytes(c, b)));
         return SFL_OK;
     }
@@ -478,14 +478,23 @@ int sfl_comm_unique_id(void *id_out, size_t id_bytes)
 
 // Everything that must be identical on all ranks of a communicator for their programs to match: the domain,
 // the group size and every option a plan or an exchange depends on.
+// Words 0 .. 3 are the header, the flagged rows of kOptions name theirs, 7 and 13 are the two halves of the exchange schedule.
 constexpr int kOptionBlockInts = 16;
+constexpr unsigned option_block_words()
+{
+    unsigned words = 0xf | 1u << 7 | 1u << 13 | 1u << (kOptionBlockInts - 1);
+    for (const OptionRow &o : kOptions)
+        if (o.block_word) words = words & 1u << o.block_word ? 0 : words | 1u << o.block_word;   // (a word named twice: 0)
+    return words;
+}
+static_assert(option_block_words() == (1u << kOptionBlockInts) - 1, "kOptions' block words and the fixed ones must fill the option block exactly");
 static void option_block(const sfl_context *c, int *b)
 {
-    const int v[kOptionBlockInts] = {SFL_ABI_VERSION, c->dim_x, c->gdim_y, c->nranks, c->opt_sor_kernel, c->opt_sor_fuse,
-                                     c->opt_sor_halo, c->opt_sor_overlap, c->opt_advect_halo, c->opt_fuse_projection,
-                                     c->opt_advect_kernel, c->opt_fuse_divergence, c->opt_small_grid, c->opt_sor_arrival,
-                                     c->opt_sor_fold, c->streams_concurrent};   // (streams_concurrent LAST: sfl_comm_check_options)
-    memcpy(b, v, sizeof v);
+    b[0] = SFL_ABI_VERSION; b[1] = c->dim_x; b[2] = c->gdim_y; b[3] = c->nranks;
+    for (const OptionRow &o : kOptions)
+        if (o.block_word) b[o.block_word] = c->opt.*o.field;
+    b[7] = c->opt.sor_overlap; b[13] = c->opt.sor_arrival;
+    b[kOptionBlockInts - 1] = c->streams_concurrent;   // (streams_concurrent LAST: sfl_comm_check_options)
 }
 
 int sfl_comm_check_options(sfl_context *c)
@@ -640,21 +649,10 @@ int sfl_group_link(sfl_context **ctxs, int n)
     HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&g->xstream, hipStreamNonBlocking));
     for (int r = 1; r < n; ++r) {  // group-wide options: slab 0's values
-        sfl_context *c = ctxs[r], *z = ctxs[0];
-        c->opt_sor_kernel = z->opt_sor_kernel;
-        c->opt_sor_fuse = z->opt_sor_fuse;
-        c->opt_advect_halo = z->opt_advect_halo;
-        c->opt_sor_rows = z->opt_sor_rows;
-        c->opt_sor_lane_cells = z->opt_sor_lane_cells;
-        c->opt_sor_halo = z->opt_sor_halo;
-        c->opt_fuse_projection = z->opt_fuse_projection;
-        c->opt_sor_overlap = z->opt_sor_overlap;
-        c->opt_advect_kernel = z->opt_advect_kernel;
-        c->opt_fuse_divergence = z->opt_fuse_divergence;
-        c->opt_small_grid = z->opt_small_grid;
-        c->opt_sor_arrival = z->opt_sor_arrival;
-        c->opt_halo_timeout_ms = z->opt_halo_timeout_ms;
-        c->opt_sor_fold = z->opt_sor_fold;
+        for (const OptionRow &o : kOptions)
+            if ((o.flags & kGroupWide) && o.field) ctxs[r]->opt.*o.field = ctxs[0]->opt.*o.field;
+        ctxs[r]->opt.sor_overlap = ctxs[0]->opt.sor_overlap;   // SFL_OPT_EXCHANGE_SCHEDULE: its two halves
+        ctxs[r]->opt.sor_arrival = ctxs[0]->opt.sor_arrival;
     }
     for (int r = 0; r < n; ++r) {  // one stream orders the whole group
         sfl_context *c = ctxs[r];

@@ -60,3 +60,15 @@ def test_host_side_runs_through_under_asan_over_the_fake_runtime():
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-6000:])
     assert "0 failed checks, 0 allocations left" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-6000:]
+
+
+def test_every_option_number_sets_reads_and_links_as_the_header_says():
+    """`host_tsan_driver options`, single-threaded over the same fake runtime: for every option number the default, the accepted
+    values at both ends of each range, the first refused value beyond them with its message, read-back, the read-only and the
+    unknown numbers (the retired 8, 13, 15, 16 among them), and after sfl_group_link which options follow slab 0 -- from a table
+    of expectations written in the driver, not from the library's own option table (csrc/context.h kOptions)."""
+    subprocess.run(["make", "-C", CPP, "tsan_host"], check=True, stdout=subprocess.DEVNULL)
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0:exitcode=66")
+    r = subprocess.run([os.path.join(CPP, "host_tsan_driver"), "options"], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-6000:])
+    assert "15 options, 0 failed checks, 0 allocations left" in r.stdout and "ThreadSanitizer" not in r.stderr, r.stderr[-6000:]
