@@ -9,6 +9,8 @@
 // gfx950 -- profiles/r02_experiments_without_gain.txt -- it was never faster and is gone.)
 //
 // Compiled with -ffp-contract=off (bit-exactness contract, see stencil_kernels.hip).
+// tools/sor_clock_probe.hip includes this file as text and puts a measuring kernel of its own around relax_tile, tile_of_wave
+// and plan_launch; nothing here knows about it.
 #include <cstdio>
 #include <cstdlib>
 
@@ -30,34 +32,7 @@ constexpr size_t kNtStoreCells = SFL_NT_STORE_CELLS;  // local cells from which 
 constexpr int kFlipTiles = 1;                // alternate the stream direction of vertically adjacent tiles
 constexpr int kThreads = 64 * kWavesPerBlock;
 
-#ifdef SFL_SOR_TRACE
-// Diagnostic builds only (tools/sor_clock_probe.hip; never defined for the product library): every wave
-// records when it started and ended on the shader clock (s_memtime) AND on the constant 100 MHz
-// real-time clock (s_memrealtime), plus where it ran -- 6 words per tile.
-__device__ unsigned long long *g_sor_trace;
-struct WaveTrace {
-    unsigned long long t0, w0;
-    unsigned hwid, xcc;
-    __device__ __forceinline__ void begin()
-    {
-        t0 = __builtin_readcyclecounter();
-        w0 = __builtin_amdgcn_s_memrealtime();
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    }
-    __device__ __forceinline__ void end(int tile, int kind) const
-    {
-        const unsigned long long t1 = __builtin_readcyclecounter(), w1 = __builtin_amdgcn_s_memrealtime();
-        if ((threadIdx.x & 63) == 0 && g_sor_trace) {
-            unsigned long long *o = g_sor_trace + 6 * (size_t)tile;
-            o[0] = t0; o[1] = t1; o[2] = w0; o[3] = w1; o[4] = hwid; o[5] = ((unsigned long long)kind << 32) | xcc;
-        }
-    }
-};
-#endif
-
 #include "sor_lane.h"
-
 
 // Occupancy the register allocator must keep: a launch lasts as long as one wave's chain of iterations, and
 // that chain is served best with >= 3 waves on the SIMD (NS >= 12: 168 VGPRs) / 4 (NS <= 10: 128).
@@ -66,31 +41,13 @@ struct WaveTrace {
 #ifndef SFL_MIN_WAVES_DEEP
 #define SFL_MIN_WAVES_DEEP 3
 #endif
-#ifndef SFL_PROBE_NO_EDGE
-#define SFL_PROBE_NO_EDGE 0  // diagnostic builds only: every tile takes the interior path (wrong results at the walls)
-#endif
-#ifndef SFL_SOR_TRACE
-// The SFL_PROBE_* switches compute WRONG results; they exist for
-// tools/sor_clock_probe.hip, which includes this file with SFL_SOR_TRACE defined.  A product library never sees them set:
-// `make EXTRA_FLAGS=-DSFL_PROBE_NO_LOAD=1` stops here.
-#ifdef SFL_PROBE_COOP
-#error "SFL_PROBE_COOP is a timing mock (wrong results): only with SFL_SOR_TRACE (tools/sor_clock_probe.hip)"
-#endif
-static_assert(SFL_PROBE_NO_LDS == 0 && SFL_PROBE_NO_LOAD == 0 && SFL_PROBE_SHIFT == 0 && SFL_PROBE_NO_EDGE == 0 &&
-                  SFL_PROBE_P_LOAD_AUX == 0 && SFL_PROBE_P_STORE_AUX == 0 && SFL_PROBE_NO_STORE == 0,
-              "SFL_PROBE_* switches give wrong results: diagnostic builds only (define SFL_SOR_TRACE, tools/sor_clock_probe.hip)");
-#endif
 constexpr int min_waves_per_simd(int ns) { return ns == 14 ? 2 : ns >= 12 ? SFL_MIN_WAVES_DEEP : 4; }
 
 // One tile: its NS passes over output rows rect.[r0, r1) of strip rect.strip, from p_in (ZERO_IN: from zero) to p_out.
 // Returns the path taken (0 interior bottom-up, 1 boundary, 2 interior top-down).
 template <class B, int NS, bool DX1, bool ZERO_IN>
 __device__ __forceinline__ int relax_tile(float *p_out, const float *p_in, const float *d, const Slab &g, const sor::Tiling &t,
-                                          const sor::TileRect &rect, const SorParams &prm, bool sender, float *ring_base, int lane
-#ifdef SFL_PROBE_COOP
-                                          , float *coop_mem, int wave
-#endif
-                                          )
+                                          const sor::TileRect &rect, const SorParams &prm, bool sender, float *ring_base, int lane)
 {
     const int x0 = sor::strip_x0(t, rect.strip);
     const int r0 = rect.r0, r1 = rect.r1;
@@ -114,26 +71,9 @@ __device__ __forceinline__ int relax_tile(float *p_out, const float *p_in, const
         bk.prio_on = sender ? 2 : t.rotate;   // senders first: the message is waiting for them
         bk.start_turns();
         bk.setup(ring_base, lane, x0, t.halo_cols);
-#if defined(SFL_PROBE_COOP) && SFL_PROBE_COOP == 3
-        {
-            float *pair = coop_mem + (wave >> 1) * (8 * 128 + 16);
-            bk.vp_ring = pair + lane * 2;
-            bk.vp_mine = reinterpret_cast<int *>(pair + 8 * 128) + (wave & 1);
-            bk.vp_other = reinterpret_cast<int *>(pair + 8 * 128) + 1 - (wave & 1);
-            bk.vp_rows = 0;
-            bk.vp_producer = (wave & 1) == 0;
-        }
-#endif
-#ifdef SFL_PROBE_COOP
-        bk.coop_is_pub = lane == 1 || lane == 62;
-        bk.coop_is_ghost = lane == 0 || lane == 63;
-        bk.coop_pub = coop_mem + wave * 2 + (lane == 62);
-        // lane 0 picks up what the wave on its left published from lane 62, lane 63 what the wave on its right did from lane 1
-        bk.coop_get = coop_mem + ((wave + (lane == 0 ? kWavesPerBlock - 1 : 1)) % kWavesPerBlock) * 2 + (lane == 0);
-#endif
         return bk;
     };
-    if (!SFL_PROBE_NO_EDGE && sor::tile_touches_boundary(t, rect, g.gdim_y)) {  // wave-uniform
+    if (sor::tile_touches_boundary(t, rect, g.gdim_y)) {  // wave-uniform
         B bk = backend();
         sor::Consts<B> c{bk.splat(prm.dx), bk.splat(prm.omega), bk.splat(prm.one_minus_omega), bk.splat(prm.neg_quarter_omega)};
         const auto eca = bk.edge_cell(lane, x0, 0);
@@ -156,45 +96,37 @@ __device__ __forceinline__ int relax_tile(float *p_out, const float *p_in, const
     return 0;
 }
 
-template <class B, int NS, bool DX1, bool ZERO_IN>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(min_waves_per_simd(NS))))
-sor_fused_kernel(float *p_out, const float *p_in, const float *d, Slab g, sor::Tiling t1,
-                 sor::Tiling t2, SorParams prm, HaloWait hw, int rot_c, int rot_e, int free_blocks)
+// The launch's tile number of a wave (wave-uniform), in the XCD-aware block order: the dispatcher deals consecutive blocks
+// round-robin to the 8 XCDs (each with a private L2); give every XCD a CONTIGUOUS range of tiles instead, so that
+// horizontally / vertically adjacent tiles -- which re-read each other's halo columns and
+// rows -- hit in the same L2.  Speed only: any placement computes the same result.
+// The blocks that hold tiles which wait for a halo message inside the launch keep the dispatcher's own rotation over the
+// XCDs and come LAST (sor::tile_rect has the reason); the contiguous ranges are dealt over the blocks in front.
+__device__ __forceinline__ int tile_of_wave(int wave, int free_blocks)
 {
-    __shared__ __attribute__((aligned(16))) float ring_mem[kWavesPerBlock][B::kRingFloats];
-#if defined(SFL_PROBE_COOP) && SFL_PROBE_COOP == 3
-    __shared__ float coop_mem[2 * (8 * 128 + 16)];   // per pair of waves: an 8-row ring of 64 x 2 words + the two row counts
-    for (int k = threadIdx.x; k < 2 * (8 * 128 + 16); k += kThreads) coop_mem[k] = 0.0f;
-    __syncthreads();
-#elif defined(SFL_PROBE_COOP)
-    __shared__ float coop_mem[2 * NS * 8];   // [row parity][value][wave x {left edge, right edge}]
-#endif
-
-    // everything derived from the wave index is wave-uniform: tell the compiler (SGPRs)
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    // XCD-aware block order: the dispatcher deals consecutive blocks round-robin to the 8 XCDs
-    // (each with a private L2); give every XCD a CONTIGUOUS range of tiles instead, so that
-    // horizontally / vertically adjacent tiles -- which re-read each other's halo columns and
-    // rows -- hit in the same L2.  Speed only: any placement computes the same result.
-    // The blocks that hold tiles which wait for a halo message inside the launch keep the dispatcher's own rotation over the
-    // XCDs and come LAST (sor::tile_rect has the reason); the contiguous ranges are dealt over the blocks in front.
     int block = blockIdx.x;
     if (block < free_blocks) {
         const int per = free_blocks >> 3, rem = free_blocks & 7;
         const int xcd = block & 7, idx = block >> 3;
         block = xcd * per + min(xcd, rem) + idx;  // bijective on [0, free_blocks) for every count
     }
+    return block * kWavesPerBlock + wave;
+}
+
+template <class B, int NS, bool DX1, bool ZERO_IN>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(min_waves_per_simd(NS))))
+sor_fused_kernel(float *p_out, const float *p_in, const float *d, Slab g, sor::Tiling t1,
+                 sor::Tiling t2, SorParams prm, HaloWait hw, int rot_c, int rot_e, int free_blocks)
+{
+    __shared__ __attribute__((aligned(16))) float ring_mem[kWavesPerBlock][B::kRingFloats];
+
+    // everything derived from the wave index is wave-uniform: tell the compiler (SGPRs)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
     // a launch covers up to two row ranges (the two cut-adjacent bands of a slab in one launch):
     // the tiles of the second tiling follow those of the first
-    int tile = block * kWavesPerBlock + wave;
+    int tile = tile_of_wave(wave, free_blocks);
     if (tile >= t1.n_tiles + t2.n_tiles) return;
-#ifdef SFL_SOR_TRACE
-    WaveTrace trace;
-    trace.begin();
-    const int trace_tile = tile;
-    int trace_kind = 0;
-#endif
     const bool second = tile >= t1.n_tiles;  // wave-uniform
     const sor::Tiling t = second ? t2 : t1;
     if (second) tile -= t1.n_tiles;
@@ -233,16 +165,7 @@ sor_fused_kernel(float *p_out, const float *p_in, const float *d, Slab g, sor::T
     // a SENDER tile (kernels.h HaloWait::done): its output rows are part of the next halo message
     const bool sender = hw.done != nullptr && (r0 < hw.send_lo_end || r1 > hw.send_hi_begin);   // wave-uniform
 
-#ifdef SFL_PROBE_COOP
-    const int kind = relax_tile<B, NS, DX1, ZERO_IN>(p_out, p_in, d, g, t, rect, prm, sender, ring_mem[wave], lane, coop_mem, wave);
-#else
-    const int kind = relax_tile<B, NS, DX1, ZERO_IN>(p_out, p_in, d, g, t, rect, prm, sender, ring_mem[wave], lane);
-#endif
-#ifdef SFL_SOR_TRACE
-    trace_kind = kind;
-#else
-    (void)kind;
-#endif
+    relax_tile<B, NS, DX1, ZERO_IN>(p_out, p_in, d, g, t, rect, prm, sender, ring_mem[wave], lane);
     if (sender) {
         // This wave's rows must be in memory before it counts itself: the copy / send kernel that picks them up runs on any
         // XCD, or on another GPU.  Written-through stores (B::kStoreAux == 16) only have to be waited for -- every storing
@@ -255,10 +178,6 @@ sor_fused_kernel(float *p_out, const float *p_in, const float *d, Slab g, sor::T
         }
         if (lane == 0) __hip_atomic_fetch_add(hw.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-#ifdef SFL_SOR_TRACE
-    __builtin_amdgcn_s_waitcnt(0);  // the wave's stores have left
-    trace.end(trace_tile, trace_kind);
-#endif
 }
 
 // Resident waves of one instantiation on the whole device (occupancy query, cached).
@@ -327,10 +246,20 @@ int auto_rows_per_chunk(const Slab &g, int g_begin, int g_end, int ns, int waves
     return best_rows;
 }
 
+// What the launcher decides before it launches: the tilings of the (up to two) row ranges, the grid, the dispatch order
+// and how many of the tiles are senders.  Host code only.
+struct LaunchPlan {
+    sor::Tiling t1, t2;
+    HaloWait hw;
+    int blocks;                       // 0: nothing to do
+    int rot_c, rot_e, free_blocks;    // dispatch order (sor::tile_rect, tile_of_wave)
+    int senders;                      // tiles that will add to *hw.done
+};
+
 template <class B, int NS, bool DX1, bool ZERO_IN>
-hipError_t launch_variant(hipStream_t s, float *p_out, const float *p_in, const float *d, Slab g,
-                          SorRows rows, SorParams prm, int rows_per_chunk, int sweep, const HaloWait *wait, int *senders)
+LaunchPlan plan_launch(Slab g, SorRows rows, int rows_per_chunk, int sweep, const HaloWait *wait)
 {
+    LaunchPlan pl{};
     auto tiling = [&](int g_begin, int g_end) {
         if (g_end <= g_begin) {
             sor::Tiling none{};
@@ -350,22 +279,25 @@ hipError_t launch_variant(hipStream_t s, float *p_out, const float *p_in, const 
         // 18.16 -> 17.7 ms per solve; with every tile resident the same cut costs 0.5 - 2 %: profiles/r05_fold_quarter_omega.txt)
         return t.n_tiles > resident ? with_edge_cost(sor::kEdgeRowCostQueued16) : t;
     };
-    sor::Tiling t1 = tiling(rows.g_begin, rows.g_end), t2 = tiling(rows.g2_begin, rows.g2_end);
+    sor::Tiling &t1 = pl.t1, &t2 = pl.t2;
+    t1 = tiling(rows.g_begin, rows.g_end);
+    t2 = tiling(rows.g2_begin, rows.g2_end);
     const int tiles = t1.n_tiles + t2.n_tiles;
-    if (tiles == 0) return hipSuccess;
+    if (tiles == 0) return pl;
     // rotating issue priority (WaveCommon::next_turn) only when every tile is resident from the start AND the SIMDs
     // hold three waves: with two, the second wave fills the first one's gaps anyway (8192 x 1024, NS = 10: 24.6 us per
     // launch with and without), and a thin slab's launches run next to the halo exchange's kernels, which should
     // not have to compete with raised priorities
     t1.rotate = t2.rotate = SFL_PRIO_FORCE >= 0 ? SFL_PRIO_FORCE
                                           : tiles <= resident_waves<B, NS, DX1, ZERO_IN>() && 2 * tiles > 5 * device_simds();
-    const int blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    HaloWait hw = wait ? *wait : HaloWait{nullptr, nullptr, 0, 0, 0, nullptr, 0, 0, 0, 0};
+    pl.blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+    HaloWait &hw = pl.hw;
+    hw = wait ? *wait : HaloWait{nullptr, nullptr, 0, 0, 0, nullptr, 0, 0, 0, 0};
     if (hw.timeout_us <= 0) hw.timeout_us = kHaloWaitDefaultTimeoutUs;
     // dispatch order (sor::tile_rect): nothing special unless tiles of this launch will wait inside it -- then the chunks that do
     // not wait first (the same test as the kernel's, on the chunks of an inner strip and of a boundary strip), and only their
     // blocks in the XCD-contiguous deal
-    int rot_c = 0, rot_e = 0, free_blocks = blocks;
+    pl.free_blocks = pl.blocks;
     if (hw.flag != nullptr && t2.n_tiles == 0) {
         const int line_rows = (g.dim_x & 63) ? 1 + 63 / g.dim_x : 0;
         const int reach = NS + sor::ring_rows(NS) + line_rows;
@@ -379,21 +311,28 @@ hipError_t launch_variant(hipStream_t s, float *p_out, const float *p_in, const 
             }
         };
         int fc = 0, fe = 0;
-        if (t1.n_inner > 0) free_range(1, t1.n_chunks, &rot_c, &fc);
-        free_range(0, t1.n_chunks_edge, &rot_e, &fe);
-        free_blocks = fc * t1.n_inner / kWavesPerBlock;
+        if (t1.n_inner > 0) free_range(1, t1.n_chunks, &pl.rot_c, &fc);
+        free_range(0, t1.n_chunks_edge, &pl.rot_e, &fe);
+        pl.free_blocks = fc * t1.n_inner / kWavesPerBlock;
     }
-    if (senders) {   // the same test as the kernel's, on the same tilings
-        int n = 0;
-        if (hw.done)
-            for (const sor::Tiling *t : {&t1, &t2})
-                for (int k = 0; k < t->n_tiles; ++k) {
-                    const sor::TileRect r = sor::tile_rect(*t, k);
-                    n += r.r0 < hw.send_lo_end || r.r1 > hw.send_hi_begin;
-                }
-        *senders = n;
-    }
-    sor_fused_kernel<B, NS, DX1, ZERO_IN><<<blocks, kThreads, 0, s>>>(p_out, p_in, d, g, t1, t2, prm, hw, rot_c, rot_e, free_blocks);
+    if (hw.done)   // the same test as the kernel's, on the same tilings
+        for (const sor::Tiling *t : {&t1, &t2})
+            for (int k = 0; k < t->n_tiles; ++k) {
+                const sor::TileRect r = sor::tile_rect(*t, k);
+                pl.senders += r.r0 < hw.send_lo_end || r.r1 > hw.send_hi_begin;
+            }
+    return pl;
+}
+
+template <class B, int NS, bool DX1, bool ZERO_IN>
+hipError_t launch_variant(hipStream_t s, float *p_out, const float *p_in, const float *d, Slab g,
+                          SorRows rows, SorParams prm, int rows_per_chunk, int sweep, const HaloWait *wait, int *senders)
+{
+    const LaunchPlan pl = plan_launch<B, NS, DX1, ZERO_IN>(g, rows, rows_per_chunk, sweep, wait);
+    if (pl.blocks == 0) return hipSuccess;
+    if (senders) *senders = pl.senders;
+    sor_fused_kernel<B, NS, DX1, ZERO_IN><<<pl.blocks, kThreads, 0, s>>>(p_out, p_in, d, g, pl.t1, pl.t2, prm, pl.hw, pl.rot_c, pl.rot_e,
+                                                                        pl.free_blocks);
     return hipGetLastError();
 }
 

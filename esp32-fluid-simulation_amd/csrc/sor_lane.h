@@ -7,8 +7,6 @@
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef int v2i __attribute__((ext_vector_type(2)));
 
-// DPP full-wave shifts (GFX9 wave_shr:1 / wave_shl:1).  Lane 0 / lane 63 receive 0, which only
-// ever feeds cells of the tile's invalid rim.
 #ifndef SFL_PRIO_LEVELS
 #define SFL_PRIO_LEVELS 4  // priority levels the waves of a SIMD rotate through (1 = leave the priority alone)
 #endif
@@ -18,36 +16,16 @@ typedef int v2i __attribute__((ext_vector_type(2)));
 #ifndef SFL_PRIO_ROWS
 #define SFL_PRIO_ROWS 2    // rows (pipeline iterations) a wave spends on one level; must divide 6
 #endif
-#ifndef SFL_PROBE_NO_LDS
-#define SFL_PROBE_NO_LDS 0   // diagnostic builds only: no rhs ring traffic (wrong results)
-#endif
-#ifndef SFL_PROBE_NO_LOAD
-#define SFL_PROBE_NO_LOAD 0  // diagnostic builds only: no global loads (wrong results)
-#endif
-#ifndef SFL_PROBE_P_LOAD_AUX
-#define SFL_PROBE_P_LOAD_AUX 0   // diagnostic builds only: cache-policy bits of the p loads (16 = sc1: agent scope, bypasses L1)
-#endif
-#ifndef SFL_PROBE_P_STORE_AUX
-#define SFL_PROBE_P_STORE_AUX 0  // diagnostic builds only: ... of the p stores (16 = sc1: written through the XCD's L2)
-#endif
-#ifndef SFL_PROBE_NO_STORE
-#define SFL_PROBE_NO_STORE 0  // diagnostic builds only: the finished rows are not stored (what would a last launch
-                              // of a solve cost whose pressure nobody reads from memory? profiles/r06_pressure_never_stored.txt)
-#endif
-#ifndef SFL_PROBE_SHIFT
-#define SFL_PROBE_SHIFT 0  // diagnostic builds only (tools/sor_clock_probe.hip): 1 = no lane shift at all, 2 = row_shr / row_shl
-#endif
+
+// DPP full-wave shifts (GFX9 wave_shr:1 / wave_shl:1).  Lane 0 / lane 63 receive 0, which only
+// ever feeds cells of the tile's invalid rim.
 __device__ __forceinline__ float lane_below(float x)  // value of lane - 1
 {
-    if (SFL_PROBE_SHIFT == 1) return x;
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), SFL_PROBE_SHIFT == 2 ? 0x111 : 0x138, 0xf, 0xf, false));
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x138, 0xf, 0xf, false));
 }
 __device__ __forceinline__ float lane_above(float x)  // value of lane + 1
 {
-    if (SFL_PROBE_SHIFT == 1) return x;
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), SFL_PROBE_SHIFT == 2 ? 0x101 : 0x130, 0xf, 0xf, false));
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x130, 0xf, 0xf, false));
 }
 
 // State shared by both flavours.  Loads are UNCONDITIONAL and branch-free: the row index is
@@ -209,10 +187,6 @@ struct Lane2 : WaveCommon {
     }
     __device__ __forceinline__ void load_row(int r, V &pa, V &pb, V &da, V &db) const
     {
-        if (SFL_PROBE_NO_LOAD) {
-            asm volatile("" : "+v"(pa), "+v"(pb), "+v"(da), "+v"(db));
-            return;
-        }
         const int soff = load_row_bytes(r);
         if (VEC) {
             const v2f f = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rs_d, off_a, soff, 0));
@@ -224,7 +198,7 @@ struct Lane2 : WaveCommon {
         }
         if (!ZERO_IN) {
             if (VEC) {
-                const v2f q = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rs_p, off_a, soff, SFL_PROBE_P_LOAD_AUX));
+                const v2f q = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rs_p, off_a, soff, 0));
                 pa = q.x;
                 pb = q.y;
             } else {
@@ -236,42 +210,29 @@ struct Lane2 : WaveCommon {
 
     __device__ __forceinline__ void store_row(int r, V a, V b) const
     {
-        if (SFL_PROBE_NO_STORE) {   // (the values stay "used": the relaxations are not optimised away)
-            asm volatile("" ::"v"(a), "v"(b));
-            return;
-        }
         const int soff = row_bytes(r);
         if (VEC) {
             if (a_out) {
                 v2f o;
                 o.x = a;
                 o.y = b;
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2i, o), rs_out, off_out, soff, SFL_PROBE_P_STORE_AUX ? SFL_PROBE_P_STORE_AUX : ST);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2i, o), rs_out, off_out, soff, ST);
             }
         } else {
             if (a_out) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, a), rs_out, off_out, soff, 0);
             if (b_out) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, b), rs_out, off_out + 4, soff, 0);
         }
     }
-#ifdef SFL_PROBE_COOP
-#include "sor_probe_mocks.inc"
-#endif
 
     // ring: [RING slots][2 planes][64 lanes]; slot and plane are compile-time constants at
     // every call site, so each access is one DS instruction with an immediate offset
     __device__ __forceinline__ void ring_store(int slot, int plane, V x) const
     {
-        if (SFL_PROBE_NO_LDS) return;
         ring[(slot * 2 + plane) * 64] = x;
     }
     __device__ __forceinline__ void pin() const { __builtin_amdgcn_sched_barrier(0); }
     __device__ __forceinline__ V ring_load(int slot, int plane) const
     {
-        if (SFL_PROBE_NO_LDS) {
-            V r = __builtin_bit_cast(float, off_out);
-            asm volatile("" : "+v"(r));
-            return r;
-        }
         return ring[(slot * 2 + plane) * 64];
     }
 };

@@ -165,11 +165,6 @@ SFL_HD void iterate(B &bk, Pipe<B, NS> &pp, const Consts<B> &c, const EdgeCell<B
 
     // the waves that share a SIMD take turns at the top issue priority (Lane2::next_turn; a no-op in the emulator)
     if (U % B::kTurnRows == 0) bk.next_turn();
-#ifdef SFL_PROBE_COOP
-    // TIMING MOCK (diagnostic builds only, wrong results): what sharing column halos between the waves of a block
-    // would add to every row -- see Lane2::coop_mock
-    bk.template coop_mock<NS, U>(pp);
-#endif
 
     // ---- row y enters: hand it to version 0, park its d in the ring, refill the slot ----
     {

@@ -1,11 +1,14 @@
 """CPU suite: guards of the build and of the source layout.
 
-* The diagnostic switches of the fused SOR kernel (SFL_PROBE_*: ablations and timing mocks that compute WRONG results) are legal
-  only in the trace harness tools/sor_clock_probe.hip; a product build that carries one -- `make EXTRA_FLAGS=-DSFL_PROBE_NO_LOAD=1`
-  -- must stop in the compiler.
+* csrc/ holds the product only.  Ablations and timing mocks compute WRONG results (SFL_PROBE_*, SEAM_MOCK_NO_P): no such flag
+  changes one token of what the compiler sees of the product, none of their names occurs under csrc/, and csrc/ includes nothing
+  from tools/.
+* The trace harness tools/sor_clock_probe.hip (which brings its own backend and kernel, tools/probe/) compiles, plain and with each
+  of its switches.
 * No translation unit or header under csrc/ grows past 900 lines again (round 4's sfl_api.cpp had reached 2710)."""
 import glob
 import os
+import re
 import subprocess
 
 import pytest
@@ -14,17 +17,56 @@ from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "esp32-fluid-simulation_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
+PRODUCT_DEFINES = ["-DSFL_NS_GROUP=2", "-DSFL_DX_PART=0", "-DSFL_FOLD_PART=0"]
+PROBE_TOKENS = ["SFL_PROBE", "SFL_SOR_TRACE", "SEAM_MOCK", "SFL_ALLOW_TIMING_MOCKS", "coop_mock", "coop_mem", "WaveTrace", "g_sor_trace"]
+
+
+def _preprocessed(source, flags):
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "--cuda-device-only", "-std=c++17", "-ffp-contract=off", "-E", "-P", *PRODUCT_DEFINES,
+                        *flags, os.path.join(CSRC, source), "-o", "-"], capture_output=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-1500:]
+    assert len(r.stdout) > 10000
+    return r.stdout
 
 
 @pytest.mark.parametrize("flag", ["-DSFL_PROBE_NO_LOAD=1", "-DSFL_PROBE_SHIFT=1", "-DSFL_PROBE_COOP=3", "-DSFL_PROBE_NO_STORE=1", "-DSEAM_MOCK_NO_P=1"])
-def test_a_product_build_refuses_the_diagnostic_switches(flag):
+def test_no_diagnostic_switch_changes_the_product_source(flag):
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc")
     source = "advect_tiled.hip" if "SEAM" in flag else "sor_fused.hip"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fsyntax-only", "-DSFL_NS_GROUP=2",
-                        "-DSFL_DX_PART=0", "-DSFL_FOLD_PART=0", flag, os.path.join(CSRC, source)], capture_output=True, text=True, timeout=600)
-    assert r.returncode != 0
-    assert "diagnostic builds only" in r.stderr or "only with SFL_SOR_TRACE" in r.stderr, r.stderr[-1500:]
+    assert _preprocessed(source, [flag]) == _preprocessed(source, [])
+
+
+def test_csrc_holds_no_probe_code():
+    files = [f for f in glob.glob(os.path.join(CSRC, "**", "*"), recursive=True) if os.path.isfile(f)]
+    assert len(files) > 20
+    assert not [f for f in files if os.path.basename(f) == "sor_probe_mocks.inc"]
+    for f in files:
+        text = open(f, errors="replace").read()
+        assert not [t for t in PROBE_TOKENS if t in text], f
+        assert not [inc for inc in re.findall(r'#\s*include\s*"([^"]+)"', text) if "tools/" in inc.replace("\\", "/")], f
+
+
+# every remaining switch of tools/probe/sor_probe.h is set in at least one run (the two load / store switches of a pair exclude
+# each other: NO_LOAD hides what P_LOAD_AUX changes)
+PROBE_BUILDS = [
+    [],
+    ["-DSFL_PROBE_NO_LOAD=1", "-DSFL_PROBE_NO_STORE=1", "-DSFL_PROBE_SHIFT=1", "-DSFL_PROBE_NO_LDS=1"],
+    ["-DSFL_PROBE_P_LOAD_AUX=16", "-DSFL_PROBE_P_STORE_AUX=16", "-DSFL_PROBE_SHIFT=2", "-DSFL_PROBE_NO_EDGE=1"],
+]
+
+
+@pytest.mark.parametrize("flags", PROBE_BUILDS, ids=lambda f: "+".join(x[12:] for x in f) or "plain")
+def test_the_probe_compiles(flags):
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc")
+    header = open(os.path.join(ROOT, "tools", "probe", "sor_probe.h")).read()
+    switches = set(re.findall(r"#ifndef (SFL_PROBE_\w+)", header))
+    assert switches and switches == {x[2:].split("=")[0] for build in PROBE_BUILDS for x in build}
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fsyntax-only",
+                        "-DSFL_NS_GROUP=5", "-DPROBE_NS=16", *flags, os.path.join(ROOT, "tools", "sor_clock_probe.hip")],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
 
 
 def test_no_source_file_outgrows_900_lines():

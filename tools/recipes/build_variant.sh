@@ -7,8 +7,11 @@
 #            run with  python tools/with_lib.py build/variants/<name>/libsfl_hip.so bench.py ...  or LIB=<path> in bench_sweep.sh
 #   probe <name> <NS> "<extra flags>"
 #         -> build/probes/sor_clock_probe_<name>: tools/sor_clock_probe.hip (the fused kernel with per-wave clocks; the
-#            SFL_PROBE_* ablations and timing mocks are legal only here) at fuse depth NS
-# e.g.  bash tools/recipes/build_variant.sh probe ns10_vpipe 10 "-DSFL_PROBE_COOP=3"
+#            SFL_PROBE_* ablations exist only there, tools/probe/sor_probe.h lists them) at fuse depth NS
+# The timing mocks -DSFL_PROBE_COOP=1 / 2 / 3 (probe) and -DSEAM_MOCK_NO_P=1 -DSFL_ALLOW_TIMING_MOCKS (lib, advect_tiled.hip) lived
+# inside the product kernels' sources; their experiments are closed (profiles/r04_cooperative_tiles_mock.txt, r05_share_tiling.txt,
+# r06_pressure_never_stored.txt) and they were last buildable at commit 5a86197.
+# e.g.  bash tools/recipes/build_variant.sh probe ns10_noload 10 "-DSFL_PROBE_NO_LOAD=1"
 #       bash tools/recipes/build_variant.sh lib seam_early "-DSEAM_DYE_LOADS=1" advect_tiled.hip
 set -eu
 cd "$(dirname "$0")/../.."

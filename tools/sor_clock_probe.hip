@@ -2,8 +2,10 @@
 // for the whole launch?  ("what binds the kernel": a clock64()-only reading said 1.22 GHz,
 // GRBM_GUI_ACTIVE / wall said 2.1 GHz.)
 //
-// The kernel source is compiled here with SFL_SOR_TRACE: every wave records s_memtime (shader clock)
-// and s_memrealtime (constant 100 MHz) at its start and end, plus HW_ID / XCC_ID.  From one launch:
+// The product's source is included as text and run by a kernel of the probe's own (tools/probe/sor_probe.h: the same
+// mapping of blocks and waves to tiles, the product's relax_tile, the geometry the product's launcher decides): every wave
+// records s_memtime (shader clock) and s_memrealtime (constant 100 MHz) at its start and end, plus HW_ID / XCC_ID.
+// The SFL_PROBE_* ablations (wrong results; listed in sor_probe.h) exist only here.  From one launch:
 //   * shader clock of each wave = d(s_memtime) / d(s_memrealtime) x 100 MHz  -- no assumption about
 //     how long the wave lived;
 //   * when each wave started and ended relative to the first wave of the launch: residency rounds,
@@ -12,10 +14,10 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -DSFL_NS_GROUP=5 -DPROBE_NS=16 \
 //       tools/sor_clock_probe.hip -o tools/sor_clock_probe_ns16
 // Run:  sor_clock_probe_ns16 <dim_x> <dim_y> [launches] [rows_per_chunk] [csv path] [loop seconds]
-#define SFL_SOR_TRACE 1
 #define SFL_DX_PART 0
 #define SFL_FOLD_PART 0
 #include "../esp32-fluid-simulation_amd/csrc/sor_fused.hip"
+#include "probe/sor_probe.h"
 
 #include <algorithm>
 #include <chrono>
@@ -27,9 +29,6 @@
 #ifndef PROBE_NS
 #define PROBE_NS 16
 #endif
-#define PASTE2(a, b, c) a##b##c
-#define PASTE(a, b, c) PASTE2(a, b, c)
-#define PROBE_LAUNCH PASTE(launch_sor_fused_ns, PROBE_NS, _p0_f0)
 
 #define CK(x)                                                                             \
     do {                                                                                  \
@@ -85,8 +84,9 @@ int main(int argc, char **argv)
     sfl::SorParams prm{1.0f, 1.96f, 1.0f - 1.96f, -0.25f * 1.96f};
     const int alternate = getenv("PROBE_ALTERNATE") ? atoi(getenv("PROBE_ALTERNATE")) : 0;
     int n_launch = 0;
+    sfl::LaunchPlan plan{};   // of the last launch
     auto launch = [&](float *out, const float *in) {
-        return sfl::PROBE_LAUNCH(st, out, in, d, g, rows, prm, rpc, alternate ? n_launch++ : 0, nullptr, nullptr);
+        return sfl::probe_launch<PROBE_NS>(st, out, in, d, g, rows, prm, rpc, alternate ? n_launch++ : 0, &plan);
     };
 
     if (loop_s > 0) {  // a steady load for clock polling from outside (rocm-smi / amd-smi)
@@ -180,12 +180,8 @@ int main(int argc, char **argv)
         for (double x : life_us) sum += x;
         printf("mean waves alive over the span: %.1f (of %zu)\n", sum / ((double)(wlast - wbase) * 0.01), n);
     }
-    {   // the slowest waves and what they were streaming (the tiling the launcher chose, recomputed here)
-        using B = sfl::Lane2<PROBE_NS, true, false, false>;
-        const int waves = sfl::resident_waves<B, PROBE_NS, true, false>();
-        const int use_rpc = rpc > 0 ? rpc : sfl::auto_rows_per_chunk<B>(g, 0, dim_y, PROBE_NS, waves, sfl::device_simds(), sfl::sor::kEdgeRowCost16);
-        const sfl::sor::Tiling t = sfl::sor::make_tiling(PROBE_NS, B::kTileCols, B::kColAlign, dim_x, dim_y, 0, dim_y, use_rpc,
-                                                         sfl::sor::kEdgeRowCost16, 1);
+    {   // the slowest waves and what they were streaming (the tiling the product's launcher chose)
+        const sfl::sor::Tiling t = plan.t1;
         printf("tiling: rows per tile %d (boundary strips %d, first / last chunk %d / %d), %d strips (%d inner), %d tiles\n",
                t.rows_per_chunk, t.rows_edge, t.rows_first, t.rows_last, t.n_strips, t.n_inner, t.n_tiles);
         std::vector<std::pair<double, size_t>> order;
