@@ -41,6 +41,11 @@ class Drag(C.Structure):
     _fields_ = [("coord_x", C.c_uint16), ("coord_y", C.c_uint16), ("vel_x", C.c_float), ("vel_y", C.c_float)]
 
 
+class MemberParams(C.Structure):
+    """sfl_member_params: the parameters of ONE batch member (sfl_batch_*_each), 16 bytes."""
+    _fields_ = [("dt", C.c_float), ("dx", C.c_float), ("omega", C.c_float), ("iters", C.c_int32)]
+
+
 class SflError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"sfl error {code}: {message}")
@@ -140,6 +145,9 @@ SIGNATURES = {
     "sfl_batch_queue_forces": (_i, [_ctx, _pi, _pi, _pf, _i]),
     "sfl_batch_step_n": (_i, [_ctx, _i, _f, _f, _i, _f]),
     "sfl_batch_poisson_solve": (_i, [_ctx, _f, _i, _f]),
+    "sfl_batch_step_n_each": (_i, [_ctx, _i, C.POINTER(MemberParams)]),
+    "sfl_batch_poisson_solve_each": (_i, [_ctx, C.POINTER(MemberParams)]),
+    "sfl_batch_residual": (_i, [_ctx, _i, _i, _pf, _sz]),
     "sfl_batch_setup_sketch_fields": (_i, [_ctx]),
     "sfl_batch_render_rgb565": (_i, [_ctx, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),

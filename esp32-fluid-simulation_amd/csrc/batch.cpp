@@ -1,7 +1,7 @@
 // batch.cpp -- batches of the C ABI (include/sfl.h group 4, sfl_batch_*): B independent whole-domain simulations of one
 // small grid on one device, stepped by ONE launch of B workgroups (batch_grid.hip).  Argument checks, field I/O, the
-// staging of queued forces into per-member order and the ping-pong of velocity and dye.  Host C++ only; it shares the
-// error plumbing of context.h and nothing else with the context units.
+// staging of queued forces into per-member order, of per-member parameters into device records, and the ping-pong of
+// velocity and dye.  Host C++ only; it shares the error plumbing of context.h and nothing else with the context units.
 #include "batch.h"
 
 #include "context.h"
@@ -31,6 +31,13 @@ struct sfl_batch {
         bool pending = false;
     } stage[2];
     int slot = 0;
+    // per-member parameters (sfl_batch_*_each): `batch` device records, filled from pinned memory by the same two-slot rule,
+    // and one float per member for the update norm the *_each kernels leave (valid: see sfl_batch_residual)
+    sfl::BatchMember *d_members = nullptr;
+    Stage member_stage[2];
+    int member_slot = 0;
+    float *d_report = nullptr;
+    bool report_valid = false;
     // dye visualiser's device image, kept between frames
     uint16_t *d_image = nullptr;
     size_t d_image_bytes = 0;
@@ -43,12 +50,13 @@ void release(sfl_batch *b)
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (void *m : {(void *)b->vel, (void *)b->vel_tmp, (void *)b->col, (void *)b->col_tmp, (void *)b->div, (void *)b->p,
-                    b->d_forces, (void *)b->d_image})
+                    b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_image})
         if (m) (void)hipFree(m);
-    for (auto &st : b->stage) {
-        if (st.host) (void)hipHostFree(st.host);
-        if (st.copied) (void)hipEventDestroy(st.copied);
-    }
+    for (sfl_batch::Stage *pair : {b->stage, b->member_stage})
+        for (int k = 0; k < 2; ++k) {
+            if (pair[k].host) (void)hipHostFree(pair[k].host);
+            if (pair[k].copied) (void)hipEventDestroy(pair[k].copied);
+        }
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -179,6 +187,62 @@ sfl::SorParams sor_params(float dx, float omega)
     return prm;
 }
 
+// 1 / (2 dx) as the divergence and the gradient use it (finitediff.cpp:36, :78-79)
+float two_dx_inv(float dx) { return 1.0f / (2.0f * dx); }
+
+// the checks of the *_each calls on their records: nothing is launched or dequeued before they pass
+int check_members(sfl_batch *b, const sfl_member_params *params)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    if (!params) return fail(SFL_ERR_INVALID, "params is NULL");
+    for (int m = 0; m < b->batch; ++m)
+        if (params[m].iters < 0)
+            return fail(SFL_ERR_INVALID, "member %d: iters must be >= 0 (got %d)", m, (int)params[m].iters);
+    return SFL_OK;
+}
+
+// The members' records, with the host-derived constants formed as the uniform path forms them, copied to the device
+// behind the launches queued so far.  Launch order: when the iteration counts differ, the members with the most go first
+// (a stable sort, so the order is a function of the parameters alone) -- workgroups start roughly in that order and a
+// long member that starts last would set the launch's end alone; results do not depend on it.  The device array has its
+// final size from the first call on and is written in stream order, so nothing ever drains the stream; a pinned slot is
+// rewritten only after its last copy has completed.
+int stage_members(sfl_batch *b, const sfl_member_params *params)
+{
+    const size_t bytes = sizeof(sfl::BatchMember) * (size_t)b->batch;
+    sfl_batch::Stage &st = b->member_stage[b->member_slot];
+    b->member_slot ^= 1;
+    if (!st.copied) HIP_TRY(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+    if (st.pending) {
+        HIP_TRY(hipEventSynchronize(st.copied));
+        st.pending = false;
+    }
+    if (!st.host) {
+        HIP_TRY(hipHostMalloc(&st.host, bytes, hipHostMallocDefault));
+        st.bytes = bytes;
+    }
+    if (!b->d_members) HIP_TRY(hipMalloc((void **)&b->d_members, bytes));
+    if (!b->d_report) HIP_TRY(hipMalloc((void **)&b->d_report, sizeof(float) * (size_t)b->batch));
+    std::vector<int> order((size_t)b->batch);
+    for (int m = 0; m < b->batch; ++m) order[m] = m;
+    const auto differs = [&](const sfl_member_params &q) { return q.iters != params[0].iters; };
+    if (std::any_of(params, params + b->batch, differs))
+        std::stable_sort(order.begin(), order.end(), [&](int l, int r) { return params[l].iters > params[r].iters; });
+    sfl::BatchMember *rec = static_cast<sfl::BatchMember *>(st.host);
+    for (int k = 0; k < b->batch; ++k) {
+        const sfl_member_params &q = params[order[k]];
+        rec[k].dt = q.dt;
+        rec[k].two_dx_inv = two_dx_inv(q.dx);
+        rec[k].prm = sor_params(q.dx, q.omega);
+        rec[k].iters = q.iters;
+        rec[k].member = order[k];
+    }
+    HIP_TRY(hipMemcpyAsync(b->d_members, st.host, bytes, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipEventRecord(st.copied, b->stream));
+    st.pending = true;
+    return SFL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -243,6 +307,7 @@ int sfl_batch_upload(sfl_batch *b, int field, int first, int count, const void *
     SFL_TRY(check_range(b, field, first, count, host, bytes));
     if (count == 0) return SFL_OK;
     SFL_TRY(use_device(b));
+    if (field == SFL_FIELD_DIVERGENCE || field == SFL_FIELD_PRESSURE) b->report_valid = false;
     char *dev = static_cast<char *>(field_base(b, field)) + (size_t)first * b->cells * elem_bytes(field);
     HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -288,6 +353,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     if (n == 0) return SFL_OK;
     SFL_TRY(use_device(b));
+    b->report_valid = false;   // (the uniform kernels leave no update norm)
     sfl::BatchStep a{};
     a.step.div = b->div;
     a.step.p = b->p;
@@ -295,7 +361,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     a.step.dim_y = b->dim_y;
     a.step.iters = iters;
     a.step.dt = dt;
-    a.step.two_dx_inv = 1.0f / (2.0f * dx);  // finitediff.cpp:36, :78-79
+    a.step.two_dx_inv = two_dx_inv(dx);
     a.step.prm = sor_params(dx, omega);
     for (int k = 0; k < n; ++k) {
         // queued forces go into the first step (the queue is empty after it)
@@ -316,7 +382,65 @@ int sfl_batch_poisson_solve(sfl_batch *b, float dx, int iters, float omega)
     if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     SFL_TRY(use_device(b));
+    b->report_valid = false;
     HIP_TRY(sfl::launch_batch_solve(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch, iters, sor_params(dx, omega)));
+    return SFL_OK;
+}
+
+int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
+{
+    SFL_TRY(check_members(b, params));
+    if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
+    if (n == 0) return SFL_OK;
+    SFL_TRY(use_device(b));
+    SFL_TRY(stage_members(b, params));
+    b->report_valid = false;   // until every launch below is queued
+    sfl::BatchStep a{};   // (dt, two_dx_inv, iters and prm come from the members' records)
+    a.step.div = b->div;
+    a.step.p = b->p;
+    a.step.dim_x = b->dim_x;
+    a.step.dim_y = b->dim_y;
+    for (int k = 0; k < n; ++k) {
+        // queued forces go into the first step (the queue is empty after it)
+        SFL_TRY(stage_forces(b, &a.force_offsets, &a.step.force_cells, &a.step.force_vel));
+        a.step.v_in = b->vel;
+        a.step.v_out = b->vel_tmp;
+        a.step.col_in = b->col;
+        a.step.col_out = b->col_tmp;
+        HIP_TRY(sfl::launch_batch_step_each(b->stream, a, b->batch, b->d_members, b->d_report));
+        std::swap(b->vel, b->vel_tmp);  // ino:255
+        std::swap(b->col, b->col_tmp);  // ino:286
+    }
+    b->report_valid = true;   // of the last step's solve: the divergence and pressure a download hands out now
+    return SFL_OK;
+}
+
+int sfl_batch_poisson_solve_each(sfl_batch *b, const sfl_member_params *params)
+{
+    SFL_TRY(check_members(b, params));
+    SFL_TRY(use_device(b));
+    SFL_TRY(stage_members(b, params));
+    b->report_valid = false;
+    HIP_TRY(sfl::launch_batch_solve_each(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch, b->d_members, b->d_report));
+    b->report_valid = true;
+    return SFL_OK;
+}
+
+int sfl_batch_residual(sfl_batch *b, int first, int count, float *host, size_t bytes)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    if (first < 0 || count < 0 || (int64_t)first + count > b->batch)
+        return fail(SFL_ERR_INVALID, "members [%d, %d + %d) are not inside the batch's [0, %d)", first, first, count, b->batch);
+    if (bytes != (size_t)count * sizeof(float))
+        return fail(SFL_ERR_INVALID, "the update norm of %d members is %zu bytes, got %zu", count, (size_t)count * sizeof(float), bytes);
+    if (!host && count > 0) return fail(SFL_ERR_INVALID, "host is NULL");
+    if (!b->report_valid)
+        return fail(SFL_ERR_STATE, "no update norm to report: the last call that wrote the divergence or the pressure was not "
+                    "sfl_batch_step_n_each or sfl_batch_poisson_solve_each; call one of them first");
+    if (count == 0) return SFL_OK;
+    SFL_TRY(use_device(b));
+    HIP_TRY(hipMemcpyAsync(host, b->d_report + first, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
     return SFL_OK;
 }
 

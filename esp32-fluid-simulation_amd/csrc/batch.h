@@ -20,4 +20,22 @@ hipError_t launch_batch_step(hipStream_t s, const BatchStep &a, int batch);
 hipError_t launch_batch_solve(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch, int iters,
                               SorParams prm);
 
+
+// ---- per-member parameters ----------------------------------------------------------------------------------------
+// What the two kernels above take once for all members, for ONE member, with the host-derived constants already formed
+// (batch.cpp: by the expressions of the uniform path), and which member that is.  36 bytes; workgroup k of a launch
+// runs record k of a device array that holds every member exactly once, in any order (batch.cpp: most iterations first).
+struct BatchMember {
+    float dt, two_dx_inv;
+    SorParams prm;
+    int iters;
+    int member;
+};
+// launch_batch_step / launch_batch_solve with the dt, two_dx_inv, iters and prm of member m = members[k].member taken
+// from members[k] (those of `step` are ignored), and report[m] = member m's update norm (include/sfl.h sfl_batch_residual): max over all cells of
+// |p_gs - p| on the pressure the call leaves, a NaN if any term is one.  members and report: device arrays of `batch`.
+hipError_t launch_batch_step_each(hipStream_t s, const BatchStep &a, int batch, const BatchMember *members, float *report);
+hipError_t launch_batch_solve_each(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
+                                   const BatchMember *members, float *report);
+
 }  // namespace sfl

@@ -17,6 +17,17 @@
 // scratch, two members per CU -- 1.27x the member-steps/s of the same kernel at 70 VGPRs and one member per CU, whose
 // instructions are small_step_kernel's; 512 threads ran slower with either budget.
 //
+// Per-member parameters (batch_step_each_kernel, batch_solve_each_kernel): the same bodies with dt, dx, iters and omega
+// read from record blockIdx.x of a BatchMember array -- a workgroup-uniform address, so the values arrive by scalar loads,
+// the iteration loop and its barriers stay scalar-controlled and the register budget above is not touched; members with
+// different iteration counts simply leave at different times.  The record names its member: workgroups are handed out
+// roughly in blockIdx order, and the host lists the members with the most iterations first, so that no long member
+// starts last and sets the launch's end alone (1.46x at B = 1024 with iters spread over 5 .. 80, profiles/batch_params.txt).
+// Results do not depend on that order.  These kernels end with the member's update norm
+// (update_norm_in_lds): max |p_gs - p| over the final pressure, evaluated from the p and d still in LDS, one float per
+// member.  They are kernels of their own, not a template parameter of the two above: the uniform kernels keep their
+// instructions.
+//
 // Numerics contract: -ffp-contract=off, every operation individually rounded in the
 // reference's order.  Reference citations are file:line under /root/reference/ESP32-fluid-simulation/.
 #include "batch.h"
@@ -78,6 +89,96 @@ batch_solve_kernel(float *__restrict__ p_out, const float *__restrict__ d_in, in
     solve_in_lds<kThreads>(lds_raw, p_out + base, d_in + base, dim_x, dim_y, iters, prm);
 }
 
+// ---- the update norm of one member: max over all cells of |p_gs(c) - p(c)| on the pressure as it stands ------------
+// p_gs is the value a plain Gauss-Seidel update would put into the cell, in the algebra of sor_in_lds: (((z + W) + E)
+// + S) + N with -0.0f for an absent neighbour, z = -0.0f inside and +0.0f on the perimeter, k = -1/2, -1/3, -1/4
+// (poisson.cpp:67-89, :107-109).  Nothing is updated: both colours are read from the same p.  The maximum is taken over
+// the bit patterns of |p_gs - p| as unsigned integers, which orders finite values and +inf as floats do and lets any NaN
+// win: a diverged member reports a NaN, never a finite number.  A maximum does not depend on the order of reduction.
+// p and d are only read, so no barrier is needed in front as long as the caller's last writes to them are behind one;
+// `worst` is LDS of its own (static, 4 B), touched by nothing else.  One plain store by thread 0.
+template <int kT>
+__device__ __forceinline__ void update_norm_in_lds(const float *p, const float *d, int dim_x, int dim_y, float dx, float *out)
+{
+    __shared__ unsigned worst;
+    if (threadIdx.x == 0) worst = 0u;
+    const int cells = dim_x * dim_y, i_max = dim_x - 1, j_max = dim_y - 1;
+    unsigned m = 0u;
+    // (gj, i) of the thread's cells by stepping, one division per thread instead of one per cell: the pass costs about
+    // what the divisions cost (profiles/batch_params.txt)
+    const int step_j = kT / dim_x, step_i = kT - step_j * dim_x;   // workgroup-uniform
+    int gj = (int)threadIdx.x / dim_x, i = (int)threadIdx.x - gj * dim_x;
+    for (int c = threadIdx.x; c < cells; c += kT, gj += step_j, i += step_i) {
+        if (i >= dim_x) {
+            i -= dim_x;
+            ++gj;
+        }
+        const int present = (i > 0) + (i < i_max) + (gj > 0) + (gj < j_max);
+        const float w = (i > 0) ? p[c - 1] : -0.0f;
+        const float e = (i < i_max) ? p[c + 1] : -0.0f;
+        const float s = (gj > 0) ? p[c - dim_x] : -0.0f;
+        const float n = (gj < j_max) ? p[c + dim_x] : -0.0f;
+        const float z = (present == 4) ? -0.0f : 0.0f;
+        const float kf = (present == 2) ? (float)(-1.0 / 2.0) : (present == 3) ? (float)(-1.0 / 3.0) : -0.25f;
+        const float sum = (((z + w) + e) + s) + n;
+        const float p_gs = kf * (dx * d[c] - sum);
+        const unsigned bits = __float_as_uint(p_gs - p[c]) & 0x7fffffffu;   // |p_gs - p|
+        m = bits > m ? bits : m;
+    }
+    for (int o = 32; o > 0; o >>= 1) {   // the wave's maximum
+        const unsigned t = __shfl_xor(m, o);
+        m = t > m ? t : m;
+    }
+    __syncthreads();   // worst = 0 is visible
+    if ((threadIdx.x & 63) == 0) atomicMax(&worst, m);
+    __syncthreads();
+    if (threadIdx.x == 0) *out = __uint_as_float(worst);
+}
+
+// ---- one whole step of member blockIdx.x with that member's parameters, then its update norm ------------------
+__global__ void SFL_BATCH_BOUNDS
+batch_step_each_kernel(BatchStep b, const BatchMember *__restrict__ members, float *__restrict__ report)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    const BatchMember q = members[blockIdx.x];   // workgroup-uniform: scalar loads
+    const size_t member = (size_t)q.member;      // (the host hands out long members first)
+    const size_t base = member * (size_t)b.step.dim_x * (size_t)b.step.dim_y;   // 64-bit: cells before this member
+    SmallStep a = b.step;
+    a.dt = q.dt;
+    a.two_dx_inv = q.two_dx_inv;
+    a.iters = q.iters;
+    a.prm = q.prm;
+    a.v_in += 2 * base;
+    a.v_out += 2 * base;
+    a.col_in += 3 * base;
+    a.col_out += 3 * base;
+    a.div += base;
+    a.p += base;
+    a.n_forces = 0;
+    if (b.force_offsets) {   // this member's records, in queue order
+        const int f0 = b.force_offsets[member], f1 = b.force_offsets[member + 1];
+        a.force_cells += 2 * (size_t)f0;
+        a.force_vel += 2 * (size_t)f0;
+        a.n_forces = f1 - f0;
+    }
+#include "small_step_body.inc"
+    // (the body's last loop only reads l.p and l.v; l.p and l.d are final since the solve's last barrier)
+    update_norm_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, a.prm.dx, report + member);
+}
+
+// ---- poisson_solve of member blockIdx.x with that member's dx, iters and omega, then its update norm ----------
+__global__ void SFL_BATCH_BOUNDS
+batch_solve_each_kernel(float *__restrict__ p_out, const float *__restrict__ d_in, int dim_x, int dim_y,
+                        const BatchMember *__restrict__ members, float *__restrict__ report)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    const BatchMember q = members[blockIdx.x];
+    const size_t base = (size_t)q.member * (size_t)dim_x * (size_t)dim_y;
+    solve_in_lds<kThreads>(lds_raw, p_out + base, d_in + base, dim_x, dim_y, q.iters, q.prm);
+    const Lds l = carve(lds_raw, dim_x * dim_y);
+    update_norm_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, q.prm.dx, report + q.member);
+}
+
 }  // namespace
 
 hipError_t launch_batch_step(hipStream_t s, const BatchStep &a, int batch)
@@ -98,6 +199,27 @@ hipError_t launch_batch_solve(hipStream_t s, float *p, const float *d, int dim_x
     hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(batch_solve_kernel), granted);
     if (e != hipSuccess) return e;
     batch_solve_kernel<<<batch, kThreads, lds, s>>>(p, d, dim_x, dim_y, iters, prm);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_step_each(hipStream_t s, const BatchStep &a, int batch, const BatchMember *members, float *report)
+{
+    static bool granted[64];
+    const size_t lds = (size_t)a.step.dim_x * a.step.dim_y * 16;
+    hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(batch_step_each_kernel), granted);
+    if (e != hipSuccess) return e;
+    batch_step_each_kernel<<<batch, kThreads, lds, s>>>(a, members, report);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_solve_each(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
+                                   const BatchMember *members, float *report)
+{
+    static bool granted[64];
+    const size_t lds = (size_t)dim_x * dim_y * 16;
+    hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(batch_solve_each_kernel), granted);
+    if (e != hipSuccess) return e;
+    batch_solve_each_kernel<<<batch, kThreads, lds, s>>>(p, d, dim_x, dim_y, members, report);
     return hipGetLastError();
 }
 

@@ -27,6 +27,22 @@ _FIELD_SPEC = {
 }
 
 
+MEMBER_PARAMS_DTYPE = np.dtype([("dt", "<f4"), ("dx", "<f4"), ("omega", "<f4"), ("iters", "<i4")])   # sfl_member_params
+
+
+def member_params(batch: int, dt, dx=1.0, iters=10, omega=1.96) -> np.ndarray:
+    """The per-member records of ``BatchSolver.step_n_each`` / ``poisson_solve_each``: every argument a scalar (every
+    member gets it) or a sequence of length `batch` (member m gets element m), as a C-contiguous structured array of
+    `batch` records laid out as sfl_member_params.  Pure numpy: no GPU, no library."""
+    out = np.empty(batch, MEMBER_PARAMS_DTYPE)
+    for name, value in (("dt", dt), ("dx", dx), ("omega", omega), ("iters", iters)):
+        a = np.asarray(value)
+        if a.ndim > 1 or (a.ndim == 1 and len(a) != batch):
+            raise ValueError(f"{name}: a scalar or a sequence of {batch} values (one per member), got shape {a.shape}")
+        out[name] = a
+    return out
+
+
 def device_count() -> int:
     n = C.c_int(0)
     rc = capi.lib().sfl_device_count(C.byref(n))
@@ -334,6 +350,40 @@ class BatchSolver:
 
     def poisson_solve(self, dx=1.0, iters=10, omega=1.96):
         capi.check(self._lib.sfl_batch_poisson_solve(self._h, dx, iters, omega))
+
+    def _member_params(self, first, *rest):
+        """`first` a ready-made member_params array, or the arguments of member_params after `batch`."""
+        if isinstance(first, np.ndarray) and first.dtype.names:
+            if first.dtype != MEMBER_PARAMS_DTYPE or first.shape != (self.batch,):
+                raise ValueError(f"member parameters: want {self.batch} records of {MEMBER_PARAMS_DTYPE}, got "
+                                 f"{first.shape} of {first.dtype}")
+            prm = np.ascontiguousarray(first)
+        else:
+            prm = member_params(self.batch, first, *rest)
+        return prm, prm.ctypes.data_as(C.POINTER(capi.MemberParams))
+
+    def step_n_each(self, n, dt, dx=1.0, iters=10, omega=1.96):
+        """step_n with parameters of each member's own: every argument a scalar or a sequence of `batch` values, or
+        `dt` a ready-made :func:`member_params` array (the others are then ignored).  Leaves ``residual()``."""
+        prm, ptr = self._member_params(dt, dx, iters, omega)
+        capi.check(self._lib.sfl_batch_step_n_each(self._h, n, ptr))
+
+    def poisson_solve_each(self, dx=1.0, iters=10, omega=1.96):
+        """poisson_solve with each member's own dx, iters and omega (scalars or sequences of `batch` values), or `dx` a
+        ready-made :func:`member_params` array (its dt is ignored).  Leaves ``residual()``."""
+        if not (isinstance(dx, np.ndarray) and dx.dtype.names):
+            dx = member_params(self.batch, 0.0, dx, iters, omega)
+        prm, ptr = self._member_params(dx)
+        capi.check(self._lib.sfl_batch_poisson_solve_each(self._h, ptr))
+
+    def residual(self, first: int = 0, count=None) -> np.ndarray:
+        """The update norm of members [first, first + count) as the last ``*_each`` call left it, float32[count]:
+        max |p_gs - p| over the member's cells on its final pressure, a NaN for a member that diverged to one
+        (include/sfl.h sfl_batch_residual).  Synchronous; SflError with ERR_STATE when no ``*_each`` call wrote it."""
+        count = self.batch - first if count is None else count
+        a = np.empty(max(count, 0), np.float32)
+        capi.check(self._lib.sfl_batch_residual(self._h, first, count, _fp(a), a.nbytes))
+        return a
 
     def setup_sketch_fields(self):
         """Every member: velocity = 0, dye = the sketch's blurred three-sector pattern (setup(), ino:196-241)."""

@@ -460,10 +460,43 @@ SFL_API int sfl_batch_field_device_ptr(sfl_batch *b, int field, void **dev_ptr);
  * [0, batch) fails the call with SFL_ERR_INVALID and queues nothing.                                */
 SFL_API int sfl_batch_queue_forces(sfl_batch *b, const int *members, const int *cells_ij, const float *vel_xy, int n);
 /* n sim steps of every member, as sfl_step_n (queued forces go into the first step; n == 0 does nothing).  dt, dx,
- * iters and omega are the same for every member.  Asynchronous on the batch's stream.              */
+ * iters and omega are the same for every member (sfl_batch_step_n_each: one set per member).  Asynchronous on the
+ * batch's stream.                                                                                 */
 SFL_API int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float omega);
 /* pressure <- poisson_solve(divergence, dx, iters, omega) of every member.  Asynchronous.          */
 SFL_API int sfl_batch_poisson_solve(sfl_batch *b, float dx, int iters, float omega);
+
+/* --- per-member parameters and the update norm (parameter studies: one member per parameter point) ---------------- */
+/* parameters of ONE member: what sfl_batch_step_n takes once for all of them */
+typedef struct sfl_member_params {
+    float dt, dx, omega;
+    int32_t iters;
+} sfl_member_params;                       /* 16 bytes */
+/* n sim steps; member m runs every one of them with params[m] (an array of `batch` records, HOST memory, read before
+ * the call returns).  Otherwise exactly sfl_batch_step_n: queued forces go into the first step, n == 0 does nothing
+ * (beyond checking its arguments), asynchronous.  Member m ends up, bit for bit, where a context of the same shape
+ * ends up after sfl_step_n(ctx, n, params[m].dt, params[m].dx, params[m].iters, params[m].omega) with member m's data
+ * and forces.  b or params NULL, n < 0 or any params[m].iters < 0 return SFL_ERR_INVALID (the message names the first
+ * such member) before anything is launched or the force queue is touched; the floats are not checked, as
+ * sfl_batch_step_n checks none.  Members with different iters finish at different times (the library starts those with
+ * the most first, whatever their place in the batch); nothing else differs.                          */
+SFL_API int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params);
+/* pressure <- poisson_solve(divergence, params[m].dx, params[m].iters, params[m].omega) of every member (dt is
+ * ignored).  Asynchronous.                                                                          */
+SFL_API int sfl_batch_poisson_solve_each(sfl_batch *b, const sfl_member_params *params);
+/* The update norm of members [first, first + count) as the last *_each call left it: one float per member.
+ * Synchronous.  bytes must be count * 4.
+ *   The update norm of a member with pressure p, divergence d and its own dx is  max over all cells c of
+ * |g(c) - p(c)|, where g(c) = k(c) * (dx * d(c) - sum(c)) is the value a plain Gauss-Seidel update would put into the
+ * cell (poisson.cpp's p_gs): sum(c) = the neighbours that exist, added in the order W, E, S (row j - 1), N (row j + 1),
+ * k = -1/2, -1/3, -1/4 for 2, 3, 4 neighbours; float32, every operation rounded on its own.  It is evaluated on the
+ * FINAL pressure of the call (after sfl_batch_step_n_each(n): of the last step's solve, i.e. of the divergence and
+ * pressure sfl_batch_download hands out afterwards), both colours, no cell updated in between -- the distance of p
+ * from the fixed point of its iteration, in units of p.  If any |g - p| is a NaN the report is a NaN: a diverged member
+ * never reports a finite number.  The value does not depend on how the device reduces it: reproducible bit for bit.
+ *   Every *_each call (n > 0) writes the report of every member.  sfl_batch_step_n (n > 0), sfl_batch_poisson_solve and
+ * an sfl_batch_upload of the divergence or the pressure make it stale, and a fresh batch has none: SFL_ERR_STATE.  */
+SFL_API int sfl_batch_residual(sfl_batch *b, int first, int count, float *host, size_t bytes);
 /* sfl_setup_sketch_fields for every member (the saturating definition included).  Asynchronous.    */
 SFL_API int sfl_batch_setup_sketch_fields(sfl_batch *b);
 /* sfl_render_rgb565 of one member's dye.  Synchronous.                                            */

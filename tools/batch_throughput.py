@@ -2,6 +2,7 @@
 """Throughput of batches (sfl_batch_*): B independent members of one small grid stepped by one launch per step.
 
     python tools/batch_throughput.py --size 61 81 --iters 20 [--batches 1 64 256 1024 4096] [--steps K] [--warmup W] [--check]
+                                     [--each uniform | spread | spread-sorted]
 
 Every member starts from the sketch's fields (setup_sketch_fields) with a drag of its own in the first warm-up step, so
 that no two members hold the same numbers.  Per B: W warm-up steps, then step_n(K) timed with a host clock around a
@@ -12,8 +13,13 @@ synchronize.  One JSON line per B with
   * the ratio to ONE context's sfl_step_n rate, measured in this process on the same grid, iterations and step count;
   * the ratio to the unmodified reference on one host core: its step at this size as committed in
     profiles/r06_bench_c1_61x81.json (cited, not re-measured; 61 x 81 at 20 iterations only).
---check: after the timed run, members {0, 1, B/2, B - 1} against single contexts given the same start, drag and
-steps -- velocity, divergence, pressure and dye bit for bit."""
+--each: step through step_n_each (parameters of each member's own, and the update norm at the end of every step) instead
+of step_n.  uniform = every member at --iters; spread = each member's iters drawn from 5 .. 80 with a fixed seed (dt, dx
+and omega as always), in that natural order; spread-sorted = the same multiset of iters, members sorted by iters
+descending (does the order in which workgroups are handed out matter?).  Every line carries sum_iters, the SOR iterations
+of one batch step over all members, so that a line can be set against a uniform run of the same total work.
+--check: after the timed run, members {0, 1, B/2, B - 1} against single contexts given the same start, drag, steps and
+that member's parameters -- velocity, divergence, pressure and dye bit for bit."""
 import argparse
 import importlib
 import json
@@ -28,6 +34,7 @@ sys.path.insert(0, ROOT)
 sfl = importlib.import_module("esp32-fluid-simulation_amd")
 
 DT, DX, OMEGA = np.float32(1 / 30.0), 1.0, np.float32(1.96)
+SPREAD_ITERS, SPREAD_SEED = (5, 80), 20261016   # --each spread: iters uniform on [5, 80]
 BYTES_PER_CELL_STEP = 48
 HBM_BYTES_PER_S = 8e12
 REFERENCE_PROFILE = os.path.join(ROOT, "profiles", "r06_bench_c1_61x81.json")
@@ -59,14 +66,23 @@ def time_context(dim_x, dim_y, iters, warmup, steps):
         return steps / (time.perf_counter() - t0)
 
 
+def member_iters(each, batch, iters):
+    """iters of every member: --iters for all (step_n and --each uniform), or the seeded spread, natural or sorted."""
+    if each in (None, "uniform"):
+        return np.full(batch, iters, np.int32)
+    drawn = np.random.default_rng(SPREAD_SEED).integers(SPREAD_ITERS[0], SPREAD_ITERS[1] + 1, batch).astype(np.int32)
+    return np.sort(drawn)[::-1].copy() if each == "spread-sorted" else drawn
+
+
 def check_members(b, members, dim_x, dim_y, iters, total_steps):
+    """iters: one value per member of the batch."""
     bad = []
     with sfl.Solver(dim_x, dim_y) as s:
         for m in members:
             s.setup_sketch_fields()
             cell, vel = drag_of(m, dim_x, dim_y)
             s.queue_forces(np.array([cell], np.int32), np.array([vel], np.float32))
-            s.step_n(total_steps, DT, DX, iters, OMEGA)
+            s.step_n(total_steps, DT, DX, int(iters[m]), OMEGA)
             s.synchronize()
             for field in (sfl.capi.FIELD_VELOCITY, sfl.capi.FIELD_DIVERGENCE, sfl.capi.FIELD_PRESSURE, sfl.capi.FIELD_COLOR):
                 got = b.download(field, m, 1)[0]
@@ -84,6 +100,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200, help="timed steps per batch (K)")
     ap.add_argument("--warmup", type=int, default=20, help="untimed steps before them (W)")
     ap.add_argument("--check", action="store_true", help="compare members with single contexts after the timed run")
+    ap.add_argument("--each", choices=["uniform", "spread", "spread-sorted"], default=None,
+                    help="step through step_n_each with these per-member iters (default: step_n)")
     ap.add_argument("--label", default="", help="free text carried into every line (e.g. the build variant)")
     a = ap.parse_args()
     dim_x, dim_y = a.size
@@ -96,30 +114,41 @@ def main():
             b.setup_sketch_fields()
             drags = [drag_of(m, dim_x, dim_y) for m in range(batch)]
             b.queue_forces(np.arange(batch, dtype=np.int32), [d[0] for d in drags], [d[1] for d in drags])
-            b.step_n(a.warmup, DT, DX, a.iters, OMEGA)
+            iters = member_iters(a.each, batch, a.iters)
+            if a.each:
+                prm = sfl.member_params(batch, DT, DX, iters, OMEGA)
+                step_n = lambda n: b.step_n_each(n, prm)
+            else:
+                step_n = lambda n: b.step_n(n, DT, DX, a.iters, OMEGA)
+            step_n(a.warmup)
             b.synchronize()
             t0 = time.perf_counter()
-            b.step_n(a.steps, DT, DX, a.iters, OMEGA)
+            step_n(a.steps)
             b.synchronize()
             seconds = time.perf_counter() - t0
             rate = batch * a.steps / seconds
             gbs = BYTES_PER_CELL_STEP * cells * rate / 1e9
             line = {
-                "grid": [dim_x, dim_y], "iters": a.iters, "batch": batch, "steps": a.steps, "warmup": a.warmup,
+                "grid": [dim_x, dim_y], "iters": a.iters if a.each in (None, "uniform") else "%d..%d" % SPREAD_ITERS,
+                "call": "step_n_each" if a.each else "step_n", "each": a.each, "sum_iters": int(iters.sum()),
+                "mean_iters": float(iters.mean()), "batch": batch, "steps": a.steps, "warmup": a.warmup,
                 "member_steps_per_s": rate, "us_per_batch_step": seconds / a.steps * 1e6,
                 "bytes_model_per_member_step": BYTES_PER_CELL_STEP * cells, "gb_per_s": gbs,
                 "frac_of_8tb_s": gbs * 1e9 / HBM_BYTES_PER_S,
-                "context_steps_per_s": context_rate, "x_one_context": rate / context_rate,
-                "x_reference_core": rate * ref_ms / 1e3 if ref_ms else None,
+                # (one context at --iters: no yardstick for a batch whose members differ)
+                "context_steps_per_s": context_rate, "x_one_context": rate / context_rate if len(set(iters)) == 1 else None,
+                "x_reference_core": rate * ref_ms / 1e3 if ref_ms and len(set(iters)) == 1 else None,
                 "reference_step_ms": ref_ms, "reference_source": "profiles/r06_bench_c1_61x81.json cpu_baseline" if ref_ms else None,
             }
             if a.label:
                 line["label"] = a.label
             if a.check:
                 members = sorted({0, min(1, batch - 1), batch // 2, batch - 1})
-                bad = check_members(b, members, dim_x, dim_y, a.iters, a.warmup + a.steps)
+                bad = check_members(b, members, dim_x, dim_y, iters, a.warmup + a.steps)
                 line["check_members"] = members
                 line["check_bit_exact"] = not bad
+                if a.each:   # the update norm of the last step, as the batch reports it
+                    line["residual_of_checked_members"] = [float(r) for r in b.residual()[members]]
                 ok = ok and not bad
             print(json.dumps(line), flush=True)
     return 0 if ok else 1
