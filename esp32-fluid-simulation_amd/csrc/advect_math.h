@@ -1,11 +1,14 @@
-// advect_math.h -- per-point arithmetic of the semi-Lagrangian advection shared by the one-thread-per-
-// cell kernels (stencil_kernels.hip) and the LDS-staged tile kernels (advect_tiled.hip).
+// advect_math.h -- per-cell arithmetic of the sim step outside the pressure solve (semi-Lagrangian advection,
+// divergence, v - grad p), each stencil written ONCE and shared by the one-thread-per-cell kernels
+// (stencil_kernels.hip), the LDS-staged tile kernels (advect_tiled.hip, advect_seam.h) and the one-workgroup
+// step (small_step_body.inc).
 //
 // Numerics contract: compiled with -ffp-contract=off; every product and sum is
 // individually rounded in the order the reference evaluates it.  Reference citations are file:line
 // under /root/reference/ESP32-fluid-simulation/.
 #pragma once
 #include "kernels.h"
+#include <type_traits>
 
 namespace sfl {
 namespace advect_math {
@@ -75,6 +78,105 @@ __device__ __forceinline__ bool rows_available(const SrcPos &s, int valid_begin,
     return s.cj >= valid_begin && last < valid_end;
 }
 
+// the four texels of an in-domain sample mixed (advect.h:40-43): pIJ = texel (ci + I - 1, cj + J - 1)
+__device__ __forceinline__ float mix4(const SrcPos &s, float p11, float p12, float p21, float p22)
+{
+    return mix1(s.di, mix1(s.dj, p11, p12), mix1(s.dj, p21, p22));
+}
+__device__ __forceinline__ float2 mix4(const SrcPos &s, float2 p11, float2 p12, float2 p21, float2 p22)
+{
+    float2 r;
+    r.x = mix4(s, p11.x, p12.x, p21.x, p22.x);
+    r.y = mix4(s, p11.y, p12.y, p21.y, p22.y);
+    return r;
+}
+
+// sample() of a float2 field (advect.h:37-72); texel(a, b) is the field at cell (s.ci + a, s.cj + b), a and b
+// 0 or 1, of a domain of dim_x x gdim_y cells
+template <bool NO_SLIP, class T>
+__device__ __forceinline__ float2 sample_vec2f(const SrcPos &s, float si, float sj, int dim_x, int gdim_y,
+                                               T texel)
+{
+    float2 r;
+    if (!s.x_oob && !s.y_oob) {
+        const float2 p11 = texel(0, 0), p12 = texel(0, 1), p21 = texel(1, 0), p22 = texel(1, 1);
+        r = mix4(s, p11, p12, p21, p22);
+    } else {
+        if (s.x_oob && s.y_oob) {
+            r = texel(0, 0);
+        } else if (s.x_oob) {
+            const float2 a = texel(0, 0), b = texel(0, 1);
+            r.x = mix1(s.dj, a.x, b.x);
+            r.y = mix1(s.dj, a.y, b.y);
+        } else {
+            const float2 a = texel(0, 0), b = texel(1, 0);
+            r.x = mix1(s.di, a.x, b.x);
+            r.y = mix1(s.di, a.y, b.y);
+        }
+        if (NO_SLIP) {
+            const float f = wall_discount(s, si, sj, dim_x, gdim_y);
+            r.x = r.x * f;
+            r.y = r.y * f;
+        }
+    }
+    return r;
+}
+
+// the same of a field's array in memory; gs = geometry of that array
+template <bool NO_SLIP>
+__device__ __forceinline__ float2 sample_global_vec2f(const float2 *p, const Slab &gs, const SrcPos &s, float si,
+                                                      float sj)
+{
+    const size_t t = lcell(gs, s.ci, s.cj);
+    return sample_vec2f<NO_SLIP>(s, si, sj, gs.dim_x, gs.gdim_y,
+                                 [&](int a, int b) { return p[t + b * gs.dim_x + a]; });
+}
+
+// calculate_divergence for one cell (finitediff.cpp:9-31), before the factor 1 / (2 dx); q points at the cell,
+// in an LDS window or an array in memory, rows `stride` apart
+__device__ __forceinline__ float divergence_sum(const float2 *q, int stride, int i, int gj, int i_max, int j_max)
+{
+    float s;
+    if (i > 0 && i < i_max && gj > 0 && gj < j_max) {  // div_expr_fast, :29
+        const float hx = -q[-1].x + q[1].x;
+        const float hy = -q[-stride].y + q[stride].y;
+        s = hx + hy;
+    } else {  // div_expr_safe, :15-20: ghost velocity = -own
+        const float2 own = q[0];
+        s = 0.0f;
+        s += (i > 0) ? -q[-1].x : own.x;
+        s += (i < i_max) ? q[1].x : -own.x;
+        s += (gj > 0) ? -q[-stride].y : own.y;
+        s += (gj < j_max) ? q[stride].y : -own.y;
+    }
+    return s;
+}
+
+// subtract_gradient for one cell (finitediff.cpp:41-73): v - grad p, a missing neighbour's pressure is the
+// cell's own; pressure_at(a, b) is the pressure of cell (a, b)
+template <class P>
+__device__ __forceinline__ float2 project_cell(float2 u, int i, int gj, int i_max, int j_max, float two_dx_inv,
+                                               P pressure_at)
+{
+    const float pc = pressure_at(i, gj);
+    const float pw = (i > 0) ? pressure_at(i - 1, gj) : pc;
+    const float pe = (i < i_max) ? pressure_at(i + 1, gj) : pc;
+    const float ps = (gj > 0) ? pressure_at(i, gj - 1) : pc;
+    const float pn = (gj < j_max) ? pressure_at(i, gj + 1) : pc;
+    const float gx = (pe - pw) * two_dx_inv;
+    const float gy = (pn - ps) * two_dx_inv;
+    u.x = u.x - gx;
+    u.y = u.y - gy;
+    return u;
+}
+// the same with q pointing at the cell's pressure, rows `stride` apart (the offsets fold to constants)
+__device__ __forceinline__ float2 project_cell(float2 u, const float *q, int stride, int i, int gj, int i_max,
+                                               int j_max, float two_dx_inv)
+{
+    return project_cell(u, i, gj, i_max, j_max, two_dx_inv,
+                        [=](int a, int b) { return q[(b - gj) * stride + (a - i)]; });
+}
+
 struct uq3 {
     uint32_t x, y, z;
 };
@@ -84,42 +186,23 @@ __device__ __forceinline__ uq3 load_uq3(const uint32_t *p, size_t cell)
     const uint32_t *q = p + 3 * cell;
     return {q[0], q[1], q[2]};
 }
+__device__ __forceinline__ void store_uq3(uint32_t *p, size_t cell, const uq3 &r)
+{
+    uint32_t *q = p + 3 * cell;
+    q[0] = r.x;
+    q[1] = r.y;
+    q[2] = r.z;
+}
 
 __device__ __forceinline__ uint32_t uq_mix(float t, uint32_t a, uint32_t b)
 {
     return uq_narrow(mix1(t, uq_widen(a), uq_widen(b)));
 }
-
-// sample() of a float2 field from its array in memory (advect.h:37-72); gs = geometry of that array
-template <bool NO_SLIP>
-__device__ __forceinline__ float2 sample_global_vec2f(const float2 *p, const Slab &gs, const SrcPos &s, float si,
-                                                      float sj)
+// one dye channel of an in-domain sample: widen, mix, narrow once
+__device__ __forceinline__ uint32_t uq_mix4(const SrcPos &s, uint32_t p11, uint32_t p12, uint32_t p21,
+                                            uint32_t p22)
 {
-    const size_t t = lcell(gs, s.ci, s.cj);
-    float2 r;
-    if (!s.x_oob && !s.y_oob) {
-        const float2 p11 = p[t], p12 = p[t + gs.dim_x], p21 = p[t + 1], p22 = p[t + gs.dim_x + 1];
-        r.x = mix1(s.di, mix1(s.dj, p11.x, p12.x), mix1(s.dj, p21.x, p22.x));
-        r.y = mix1(s.di, mix1(s.dj, p11.y, p12.y), mix1(s.dj, p21.y, p22.y));
-    } else {
-        if (s.x_oob && s.y_oob) {
-            r = p[t];
-        } else if (s.x_oob) {
-            const float2 a = p[t], b = p[t + gs.dim_x];
-            r.x = mix1(s.dj, a.x, b.x);
-            r.y = mix1(s.dj, a.y, b.y);
-        } else {
-            const float2 a = p[t], b = p[t + 1];
-            r.x = mix1(s.di, a.x, b.x);
-            r.y = mix1(s.di, a.y, b.y);
-        }
-        if (NO_SLIP) {
-            const float f = wall_discount(s, si, sj, gs.dim_x, gs.gdim_y);
-            r.x = r.x * f;
-            r.y = r.y * f;
-        }
-    }
-    return r;
+    return uq_narrow(mix4(s, uq_widen(p11), uq_widen(p12), uq_widen(p21), uq_widen(p22)));
 }
 
 // sample() of a Vector3<UQ32> field from its array in memory (advect.h:37-72 + uq32.h)
@@ -132,12 +215,8 @@ __device__ __forceinline__ uq3 sample_global_uq3(const uint32_t *p, const Slab &
     if (!s.x_oob && !s.y_oob) {
         const uq3 p11 = load_uq3(p, t), p12 = load_uq3(p, t + gs.dim_x);
         const uq3 p21 = load_uq3(p, t + 1), p22 = load_uq3(p, t + gs.dim_x + 1);
-        r.x = uq_narrow(mix1(s.di, mix1(s.dj, uq_widen(p11.x), uq_widen(p12.x)),
-                             mix1(s.dj, uq_widen(p21.x), uq_widen(p22.x))));
-        r.y = uq_narrow(mix1(s.di, mix1(s.dj, uq_widen(p11.y), uq_widen(p12.y)),
-                             mix1(s.dj, uq_widen(p21.y), uq_widen(p22.y))));
-        r.z = uq_narrow(mix1(s.di, mix1(s.dj, uq_widen(p11.z), uq_widen(p12.z)),
-                             mix1(s.dj, uq_widen(p21.z), uq_widen(p22.z))));
+        r = {uq_mix4(s, p11.x, p12.x, p21.x, p22.x), uq_mix4(s, p11.y, p12.y, p21.y, p22.y),
+             uq_mix4(s, p11.z, p12.z, p21.z, p22.z)};
     } else {
         // "T p_edge" narrows once (advect.h:45-54); returned raw when !no_slip (:57-59)
         if (s.x_oob && s.y_oob) {
@@ -157,6 +236,14 @@ __device__ __forceinline__ uq3 sample_global_uq3(const uint32_t *p, const Slab &
         }
     }
     return r;
+}
+
+// a runtime bool as a template argument of a launch: go(std::true_type{}) or go(std::false_type{})
+template <class F>
+inline void with_bool(bool b, F go)
+{
+    if (b) go(std::true_type{});
+    else go(std::false_type{});
 }
 
 }  // namespace advect_math

@@ -106,21 +106,76 @@ __device__ __forceinline__ bool in_window(const Window &w, const SrcPos &s)
     return !s.x_oob && !s.y_oob && s.ci >= w.lx0 && s.ci + 1 < w.lx1 && s.cj >= w.ly0 && s.cj + 1 < w.ly1;
 }
 
+// ---- staging a window -----------------------------------------------------------------------------
+// A window of SX x SY elements travels from memory to LDS in two phases, THREADS threads taking elements t, t + THREADS, ...:
+// stage_loads fills registers (at(cell) reads the array; what is not part of the loaded window is T{}, zeros), stage_writes
+// empties them into LDS.  Two calls, so that a kernel can have every load of the block -- several windows, its own
+// cells -- in flight before the first LDS write.
+constexpr int staged(int elements, int threads) { return (elements + threads - 1) / threads; }   // registers per thread
+
+template <int SX, int SY, int THREADS, class T, class F>
+__device__ __forceinline__ void stage_loads(T (&got)[staged(SX * SY, THREADS)], const Window &w, const Slab &gs, F at)
+{
+#pragma unroll
+    for (int k = 0; k < staged(SX * SY, THREADS); ++k) {
+        const int e = threadIdx.x + k * THREADS;
+        got[k] = window_has<SX>(w, e) ? at(window_cell<SX>(w, gs, e)) : T{};
+    }
+}
+template <int SX, int SY, int THREADS, class T>
+__device__ __forceinline__ void stage_writes(T *lds, const T (&got)[staged(SX * SY, THREADS)])
+{
+#pragma unroll
+    for (int k = 0; k < staged(SX * SY, THREADS); ++k) {
+        const int e = threadIdx.x + k * THREADS;
+        if (e < SX * SY) lds[e] = got[k];
+    }
+}
+// dye: the three channels go to three planes of SX x SY words
+template <int SX, int SY, int THREADS>
+__device__ __forceinline__ void stage_writes(uint32_t *lds, const uq3 (&got)[staged(SX * SY, THREADS)])
+{
+#pragma unroll
+    for (int k = 0; k < staged(SX * SY, THREADS); ++k) {
+        const int e = threadIdx.x + k * THREADS;
+        if (e < SX * SY) {
+            lds[e] = got[k].x;
+            lds[SX * SY + e] = got[k].y;
+            lds[2 * SX * SY + e] = got[k].z;
+        }
+    }
+}
+
 // sample() of a float2 field whose window sits in LDS (SX elements per row); the rare back-trace that
-// leaves the window or the domain reads memory instead -- the same arithmetic either way
-template <bool NO_SLIP, int SX>
-__device__ __forceinline__ float2 sample_window_vec2f(const float2 *tile, const Window &w, const float2 *p,
-                                                      const Slab &gs, const SrcPos &s, float si, float sj)
+// leaves the window or the domain takes fallback() instead -- the same arithmetic on texels from memory
+template <int SX, class F>
+__device__ __forceinline__ float2 sample_window_vec2f(const float2 *tile, const Window &w, const SrcPos &s, F fallback)
 {
     if (in_window(w, s)) {
         const float2 *q = tile + (s.cj - w.sy0) * SX + (s.ci - w.sx0);
         const float2 p11 = q[0], p21 = q[1], p12 = q[SX], p22 = q[SX + 1];
-        float2 r;
-        r.x = mix1(s.di, mix1(s.dj, p11.x, p12.x), mix1(s.dj, p21.x, p22.x));
-        r.y = mix1(s.di, mix1(s.dj, p11.y, p12.y), mix1(s.dj, p21.y, p22.y));
-        return r;
+        return mix4(s, p11, p12, p21, p22);
     }
-    return sample_global_vec2f<NO_SLIP>(p, gs, s, si, sj);
+    return fallback();
+}
+
+// sample() of a dye field whose window sits in LDS as three planes of SX x SY words, likewise
+template <bool NO_SLIP, int SX, int SY>
+__device__ __forceinline__ uq3 sample_window_uq3(const uint32_t *tile, const Window &w, const uint32_t *p, const Slab &gs,
+                                                 const SrcPos &s, float si, float sj)
+{
+    if (in_window(w, s)) {
+        const uint32_t *q = tile + (s.cj - w.sy0) * SX + (s.ci - w.sx0);
+        uint32_t out[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t *qk = q + k * SX * SY;
+            const uint32_t p11 = qk[0], p21 = qk[1], p12 = qk[SX], p22 = qk[SX + 1];
+            out[k] = uq_mix4(s, p11, p12, p21, p22);
+        }
+        return {out[0], out[1], out[2]};
+    }
+    return sample_global_uq3<NO_SLIP>(p, gs, s, si, sj);
 }
 
 // ---- advect<Vector2<float>, float>  (advect.h:24-85) -------------------------------------------
@@ -134,7 +189,6 @@ advect_vec2f_tiled_kernel(float2 *__restrict__ next_p, const float2 *p, const fl
                           int *halo_flag, int ny1, int g2_begin, int g2_end)
 {
     constexpr int kWaves = THREADS / 64, kRows = kTY / kWaves;
-    constexpr int kLoads = (kSX * kSY + THREADS - 1) / THREADS;
     __shared__ float2 tile[kSY * kSX];
     int tx, ty;
     if (!tile_of_block(tg, tx, ty)) return;
@@ -151,12 +205,8 @@ advect_vec2f_tiled_kernel(float2 *__restrict__ next_p, const float2 *p, const fl
     const bool column = i < g.dim_x;
     float2 own[kRows];
     {   // every load of the block in flight before the first LDS write
-        float2 got[kLoads];
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            got[k] = window_has<kSX>(w, e) ? p[window_cell<kSX>(w, gs, e)] : float2{0.0f, 0.0f};
-        }
+        float2 got[staged(kSX * kSY, THREADS)];
+        stage_loads<kSX, kSY, THREADS>(got, w, gs, [&](size_t c) { return p[c]; });
         if (!SELF) {
 #pragma unroll
             for (int r = 0; r < kRows; ++r) {
@@ -164,11 +214,7 @@ advect_vec2f_tiled_kernel(float2 *__restrict__ next_p, const float2 *p, const fl
                 own[r] = (column && gj < g_end) ? vel[lcell(g, i, gj)] : float2{0.0f, 0.0f};
             }
         }
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            if (e < kSX * kSY) tile[e] = got[k];
-        }
+        stage_writes<kSX, kSY, THREADS>(tile, got);
     }
     __syncthreads();
 
@@ -185,7 +231,8 @@ advect_vec2f_tiled_kernel(float2 *__restrict__ next_p, const float2 *p, const fl
             if (halo_flag) atomicOr(halo_flag, 1);
             continue;
         }
-        next_p[lcell(g, i, gj)] = sample_window_vec2f<NO_SLIP, kSX>(tile, w, p, gs, s, si, sj);
+        next_p[lcell(g, i, gj)] =
+            sample_window_vec2f<kSX>(tile, w, s, [&] { return sample_global_vec2f<NO_SLIP>(p, gs, s, si, sj); });
     }
 }
 
@@ -198,13 +245,55 @@ constexpr int kDX = kTX + 2 * kRD, kDY = kTY + 2 * kRD;   // window
 constexpr int kVX = kTX + 2, kVY = kTY + 2;               // advected cells kept in LDS
 constexpr int kRing = 2 * kVX + 2 * kTY;                  // cells around the tile
 
+// the cell of the ring that thread t advects: bottom row, top row, left column, right column of the (kTX + 2) x (kTY + 2)
+// block of cells around the tile at (x0, y0); inside = it is a cell of the domain (and t < kRing)
+struct RingCell {
+    int i, gj;
+    bool inside;
+};
+__device__ __forceinline__ RingCell ring_cell(int t, int x0, int y0, const Slab &g)
+{
+    int ri = -1, rj = -1;
+    if (t < kVX) { ri = x0 - 1 + t; rj = y0 - 1; }
+    else if (t < 2 * kVX) { ri = x0 - 1 + (t - kVX); rj = y0 + kTY; }
+    else if (t < 2 * kVX + kTY) { ri = x0 - 1; rj = y0 + (t - 2 * kVX); }
+    else if (t < kRing) { ri = x0 + kTX; rj = y0 + (t - 2 * kVX - kTY); }
+    return {ri, rj, ri >= 0 && ri < g.dim_x && rj >= 0 && rj < g.gdim_y};
+}
+
+// The advected cells of the tile (mine: row wave + kWaves * r, column lane) and of the ring (around) are parked in LDS as
+// kVY x kVX cells from adv[0] on and differenced there: calculate_divergence (ino:274, finitediff.cpp:9-39) of a velocity
+// field that is never read back from memory.  The caller's barrier stands in front: nobody reads what adv held before.
+template <int THREADS>
+__device__ __forceinline__ void divergence_of_parked(float *__restrict__ div, float2 *adv, const float2 (&mine)[kTY * 64 / THREADS],
+                                                     const RingCell &rc, float2 around, const Slab &g, int x0, int y0,
+                                                     float two_dx_inv)
+{
+    constexpr int kWaves = THREADS / 64, kRows = kTY / kWaves;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = x0 + lane;
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) adv[(wave + kWaves * r + 1) * kVX + lane + 1] = mine[r];
+    if (rc.inside) adv[(rc.gj - (y0 - 1)) * kVX + (rc.i - (x0 - 1))] = around;
+    __syncthreads();
+
+    if (i >= g.dim_x) return;
+    const int i_max = g.dim_x - 1, j_max = g.gdim_y - 1;
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+        const int row = wave + kWaves * r, gj = y0 + row;
+        if (gj >= g.gdim_y) break;
+        const float2 *q = adv + (row + 1) * kVX + lane + 1;
+        div[lcell(g, i, gj)] = divergence_sum(q, kVX, i, gj, i_max, j_max) * two_dx_inv;
+    }
+}
+
 template <bool NO_SLIP, int THREADS>
 __global__ void __launch_bounds__(THREADS)
 advect_divergence_tiled_kernel(float2 *__restrict__ next_v, float *__restrict__ div, const float2 *v, Slab g,
                                TileGrid tg, float dt, float two_dx_inv)
 {
     constexpr int kWaves = THREADS / 64, kRows = kTY / kWaves;
-    constexpr int kLoads = (kDX * kDY + THREADS - 1) / THREADS;
     static_assert(kRing <= THREADS, "one ring cell per thread");
     static_assert(kVX * kVY <= kDX * kDY, "the advected cells reuse the window's LDS");
     __shared__ float2 lds[kDY * kDX];   // the window, then (from element 0) the kVY x kVX advected cells
@@ -213,17 +302,9 @@ advect_divergence_tiled_kernel(float2 *__restrict__ next_v, float *__restrict__ 
     const int x0 = tx * kTX, y0 = ty * kTY;
     const Window w = window_of<kRD>(x0, y0, g, 0, g.gdim_y);
     {
-        float2 got[kLoads];
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            got[k] = window_has<kDX>(w, e) ? v[window_cell<kDX>(w, g, e)] : float2{0.0f, 0.0f};
-        }
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            if (e < kDX * kDY) lds[e] = got[k];
-        }
+        float2 got[staged(kDX * kDY, THREADS)];
+        stage_loads<kDX, kDY, THREADS>(got, w, g, [&](size_t c) { return v[c]; });
+        stage_writes<kDX, kDY, THREADS>(lds, got);
     }
     __syncthreads();
 
@@ -232,7 +313,7 @@ advect_divergence_tiled_kernel(float2 *__restrict__ next_v, float *__restrict__ 
         const float si = (float)i - u.x * dt;
         const float sj = (float)gj - u.y * dt;
         const SrcPos s = classify(si, sj, g.dim_x, g.gdim_y);
-        return sample_window_vec2f<NO_SLIP, kDX>(lds, w, v, g, s, si, sj);
+        return sample_window_vec2f<kDX>(lds, w, s, [&] { return sample_global_vec2f<NO_SLIP>(v, g, s, si, sj); });
     };
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = x0 + lane;
@@ -247,44 +328,11 @@ advect_divergence_tiled_kernel(float2 *__restrict__ next_v, float *__restrict__ 
             next_v[lcell(g, i, gj)] = mine[r];
         }
     }
-    // ring: bottom row, top row, left column, right column of the (kTX + 2) x (kTY + 2) block of cells
-    const int t = threadIdx.x;
-    int ri = -1, rj = -1;
-    if (t < kVX) { ri = x0 - 1 + t; rj = y0 - 1; }
-    else if (t < 2 * kVX) { ri = x0 - 1 + (t - kVX); rj = y0 + kTY; }
-    else if (t < 2 * kVX + kTY) { ri = x0 - 1; rj = y0 + (t - 2 * kVX); }
-    else if (t < kRing) { ri = x0 + kTX; rj = y0 + (t - 2 * kVX - kTY); }
-    const bool ring = ri >= 0 && ri < g.dim_x && rj >= 0 && rj < g.gdim_y;
+    const RingCell rc = ring_cell(threadIdx.x, x0, y0, g);
     float2 around = float2{0.0f, 0.0f};
-    if (ring) around = advected(ri, rj);
+    if (rc.inside) around = advected(rc.i, rc.gj);
     __syncthreads();   // everybody is done with the window
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) lds[(wave + kWaves * r + 1) * kVX + lane + 1] = mine[r];
-    if (ring) lds[(rj - (y0 - 1)) * kVX + (ri - (x0 - 1))] = around;
-    __syncthreads();
-
-    if (!column) return;
-    const int i_max = g.dim_x - 1, j_max = g.gdim_y - 1;
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) {
-        const int row = wave + kWaves * r, gj = y0 + row;
-        if (gj >= g.gdim_y) break;
-        const float2 *q = lds + (row + 1) * kVX + lane + 1;
-        float s;
-        if (i > 0 && i < i_max && gj > 0 && gj < j_max) {  // div_expr_fast, finitediff.cpp:29
-            const float hx = -q[-1].x + q[1].x;
-            const float hy = -q[-kVX].y + q[kVX].y;
-            s = hx + hy;
-        } else {  // div_expr_safe, :15-20: ghost velocity = -own
-            const float2 own = q[0];
-            s = 0.0f;
-            s += (i > 0) ? -q[-1].x : own.x;
-            s += (i < i_max) ? q[1].x : -own.x;
-            s += (gj > 0) ? -q[-kVX].y : own.y;
-            s += (gj < j_max) ? q[kVX].y : -own.y;
-        }
-        div[lcell(g, i, gj)] = s * two_dx_inv;
-    }
+    divergence_of_parked<THREADS>(div, lds, mine, rc, around, g, x0, y0, two_dx_inv);
 }
 
 // ---- calculate_divergence (finitediff.cpp:9-39) and subtract_gradient (finitediff.cpp:41-82) as tiles ----------
@@ -298,24 +346,15 @@ divergence_tiled_kernel(float *__restrict__ div, const float2 *__restrict__ v, S
                         int g_end, float two_dx_inv)
 {
     constexpr int kWaves = THREADS / 64, kRows = kTY / kWaves;
-    constexpr int kLoads = (kFX * kFY + THREADS - 1) / THREADS;
     __shared__ float2 win[kFY * kFX];
     int tx, ty;
     if (!tile_of_block(tg, tx, ty)) return;
     const int x0 = tx * kTX, y0 = g_begin + ty * kTY;
     const Window w = window_of<1>(x0, y0, g, g.grow0, g.grow0 + g.lrows);
     {
-        float2 got[kLoads];
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            got[k] = window_has<kFX>(w, e) ? v[window_cell<kFX>(w, g, e)] : float2{0.0f, 0.0f};
-        }
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            if (e < kFX * kFY) win[e] = got[k];
-        }
+        float2 got[staged(kFX * kFY, THREADS)];
+        stage_loads<kFX, kFY, THREADS>(got, w, g, [&](size_t c) { return v[c]; });
+        stage_writes<kFX, kFY, THREADS>(win, got);
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -327,20 +366,7 @@ divergence_tiled_kernel(float *__restrict__ div, const float2 *__restrict__ v, S
         const int gj = y0 + wave + kWaves * r;
         if (gj >= g_end) break;
         const float2 *q = win + (gj - w.sy0) * kFX + (i - w.sx0);
-        float s;
-        if (i > 0 && i < i_max && gj > 0 && gj < j_max) {  // div_expr_fast, :29
-            const float hx = -q[-1].x + q[1].x;
-            const float hy = -q[-kFX].y + q[kFX].y;
-            s = hx + hy;
-        } else {  // div_expr_safe, :15-20: ghost velocity = -own
-            const float2 own = q[0];
-            s = 0.0f;
-            s += (i > 0) ? -q[-1].x : own.x;
-            s += (i < i_max) ? q[1].x : -own.x;
-            s += (gj > 0) ? -q[-kFX].y : own.y;
-            s += (gj < j_max) ? q[kFX].y : -own.y;
-        }
-        div[lcell(g, i, gj)] = s * two_dx_inv;
+        div[lcell(g, i, gj)] = divergence_sum(q, kFX, i, gj, i_max, j_max) * two_dx_inv;
     }
 }
 
@@ -350,7 +376,6 @@ gradient_tiled_kernel(float2 *v, const float *__restrict__ p, Slab g, TileGrid t
                       float two_dx_inv)
 {
     constexpr int kWaves = THREADS / 64, kRows = kTY / kWaves;
-    constexpr int kLoads = (kFX * kFY + THREADS - 1) / THREADS;
     __shared__ float win[kFY * kFX];
     int tx, ty;
     if (!tile_of_block(tg, tx, ty)) return;
@@ -361,22 +386,14 @@ gradient_tiled_kernel(float2 *v, const float *__restrict__ p, Slab g, TileGrid t
     const bool column = i < g.dim_x;
     float2 own[kRows];
     {
-        float got[kLoads];
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            got[k] = window_has<kFX>(w, e) ? p[window_cell<kFX>(w, g, e)] : 0.0f;
-        }
+        float got[staged(kFX * kFY, THREADS)];
+        stage_loads<kFX, kFY, THREADS>(got, w, g, [&](size_t c) { return p[c]; });
 #pragma unroll
         for (int r = 0; r < kRows; ++r) {
             const int gj = y0 + wave + kWaves * r;
             own[r] = (column && gj < g_end) ? v[lcell(g, i, gj)] : float2{0.0f, 0.0f};
         }
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            if (e < kFX * kFY) win[e] = got[k];
-        }
+        stage_writes<kFX, kFY, THREADS>(win, got);
     }
     __syncthreads();
     if (!column) return;
@@ -386,17 +403,7 @@ gradient_tiled_kernel(float2 *v, const float *__restrict__ p, Slab g, TileGrid t
         const int gj = y0 + wave + kWaves * r;
         if (gj >= g_end) break;
         const float *q = win + (gj - w.sy0) * kFX + (i - w.sx0);
-        const float pc = q[0];
-        const float pw = (i > 0) ? q[-1] : pc;      // finitediff.cpp:47-69: a missing neighbour is the cell itself
-        const float pe = (i < i_max) ? q[1] : pc;
-        const float ps = (gj > 0) ? q[-kFX] : pc;
-        const float pn = (gj < j_max) ? q[kFX] : pc;
-        const float gx = (pe - pw) * two_dx_inv;
-        const float gy = (pn - ps) * two_dx_inv;
-        float2 u = own[r];
-        u.x = u.x - gx;
-        u.y = u.y - gy;
-        v[lcell(g, i, gj)] = u;
+        v[lcell(g, i, gj)] = project_cell(own[r], q, kFX, i, gj, i_max, j_max, two_dx_inv);
     }
 }
 
@@ -416,9 +423,7 @@ advect_vec3uq32_tiled_kernel(uint32_t *__restrict__ next_p, const uint32_t *p, f
                              int *halo_flag, const float *__restrict__ pressure, float two_dx_inv)
 {
     constexpr int kWaves = THREADS / 64, kRows = kTY / kWaves;
-    constexpr int kPlane = kSY * kSX;
-    constexpr int kLoads = (kPlane + THREADS - 1) / THREADS;
-    __shared__ uint32_t tile[3 * kPlane];
+    __shared__ uint32_t tile[3 * kSY * kSX];
     int tx, ty;
     if (!tile_of_block(tg, tx, ty)) return;
     const int x0 = tx * kTX, y0 = g_begin + ty * kTY;
@@ -429,12 +434,8 @@ advect_vec3uq32_tiled_kernel(uint32_t *__restrict__ next_p, const uint32_t *p, f
     const int i_max = g.dim_x - 1, j_max = g.gdim_y - 1;
     float2 own[kRows];
     {
-        uq3 got[kLoads];
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            got[k] = window_has<kSX>(w, e) ? load_uq3(p, window_cell<kSX>(w, gs, e)) : uq3{0u, 0u, 0u};
-        }
+        uq3 got[staged(kSX * kSY, THREADS)];
+        stage_loads<kSX, kSY, THREADS>(got, w, gs, [&](size_t c) { return load_uq3(p, c); });
 #pragma unroll
         for (int r = 0; r < kRows; ++r) {
             const int gj = y0 + wave + kWaves * r;
@@ -443,29 +444,13 @@ advect_vec3uq32_tiled_kernel(uint32_t *__restrict__ next_p, const uint32_t *p, f
                 const size_t c = lcell(g, i, gj);
                 float2 u = vel[c];
                 if (FUSE_GRAD) {
-                    const float pc = pressure[c];
-                    const float pw = (i > 0) ? pressure[c - 1] : pc;
-                    const float pe = (i < i_max) ? pressure[c + 1] : pc;
-                    const float ps = (gj > 0) ? pressure[c - g.dim_x] : pc;
-                    const float pn = (gj < j_max) ? pressure[c + g.dim_x] : pc;
-                    const float gx = (pe - pw) * two_dx_inv;
-                    const float gy = (pn - ps) * two_dx_inv;
-                    u.x = u.x - gx;
-                    u.y = u.y - gy;
+                    u = project_cell(u, pressure + c, g.dim_x, i, gj, i_max, j_max, two_dx_inv);
                     vel[c] = u;
                 }
                 own[r] = u;
             }
         }
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) {
-            const int e = threadIdx.x + k * THREADS;
-            if (e < kPlane) {
-                tile[e] = got[k].x;
-                tile[kPlane + e] = got[k].y;
-                tile[2 * kPlane + e] = got[k].z;
-            }
-        }
+        stage_writes<kSX, kSY, THREADS>(tile, got);
     }
     __syncthreads();
 
@@ -499,25 +484,7 @@ advect_vec3uq32_tiled_kernel(uint32_t *__restrict__ next_p, const uint32_t *p, f
             if (halo_flag) atomicOr(halo_flag, 1);
             continue;
         }
-        uq3 res;
-        if (in_window(w, s)) {
-            const uint32_t *q = tile + (s.cj - w.sy0) * kSX + (s.ci - w.sx0);
-            uint32_t out[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const uint32_t *qk = q + k * kPlane;
-                const float p11 = uq_widen(qk[0]), p21 = uq_widen(qk[1]);
-                const float p12 = uq_widen(qk[kSX]), p22 = uq_widen(qk[kSX + 1]);
-                out[k] = uq_narrow(mix1(s.di, mix1(s.dj, p11, p12), mix1(s.dj, p21, p22)));
-            }
-            res = {out[0], out[1], out[2]};
-        } else {
-            res = sample_global_uq3<NO_SLIP>(p, gs, s, si, sj);
-        }
-        uint32_t *o = next_p + 3 * lcell(g, i, gj);
-        o[0] = res.x;
-        o[1] = res.y;
-        o[2] = res.z;
+        store_uq3(next_p, lcell(g, i, gj), sample_window_uq3<NO_SLIP, kSX, kSY>(tile, w, p, gs, s, si, sj));
     }
     if (REACH) {   // every lane of the block is here again: one look at each word per BLOCK (word [3] is positive in every wave:
                    // an atomic per wave on it took 330 us, a look per wave still 50), an atomic only where there is something to add
@@ -574,15 +541,12 @@ hipError_t launch_advect_vec2f_tiled(hipStream_t s, float *next_p, const float *
     auto *pi = reinterpret_cast<const float2 *>(p);
     auto *vi = reinterpret_cast<const float2 *>(vel);
     const bool self = p == vel && !src;
-#define SFL_GO(NS_, SELF_)                                                                 \
-    advect_vec2f_tiled_kernel<NS_, SELF_, kThreadsVec2><<<grid, block, 0, s>>>(            \
-        o, pi, vi, g, gs, tg, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, ny1, g2_begin, g2_end)
-    if (no_slip) {
-        if (self) { SFL_GO(true, true); } else { SFL_GO(true, false); }
-    } else {
-        if (self) { SFL_GO(false, true); } else { SFL_GO(false, false); }
-    }
-#undef SFL_GO
+    with_bool(no_slip, [&](auto ns) {
+        with_bool(self, [&](auto sf) {
+            advect_vec2f_tiled_kernel<decltype(ns)::value, decltype(sf)::value, kThreadsVec2><<<grid, block, 0, s>>>(
+                o, pi, vi, g, gs, tg, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, ny1, g2_begin, g2_end);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -598,23 +562,18 @@ hipError_t launch_advect_vec3uq32_tiled(hipStream_t s, uint32_t *next_p, const u
     auto *vi = reinterpret_cast<float2 *>(vel);
     if (reach) {   // (see the kernel: halo_flag = word [2] of a reach report, the projection fused in)
         if (!pressure || !halo_flag || src) return hipErrorInvalidValue;
-        if (no_slip)
-            advect_vec3uq32_tiled_kernel<true, true, kThreadsDye, true><<<grid, block, 0, s>>>(
+        with_bool(no_slip, [&](auto ns) {
+            advect_vec3uq32_tiled_kernel<decltype(ns)::value, true, kThreadsDye, true><<<grid, block, 0, s>>>(
                 next_p, p, vi, g, gs, tg, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, pressure, two_dx_inv);
-        else
-            advect_vec3uq32_tiled_kernel<false, true, kThreadsDye, true><<<grid, block, 0, s>>>(
-                next_p, p, vi, g, gs, tg, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, pressure, two_dx_inv);
+        });
         return hipGetLastError();
     }
-#define SFL_GO(NS_, FG_)                                                                                    \
-    advect_vec3uq32_tiled_kernel<NS_, FG_, kThreadsDye><<<grid, block, 0, s>>>(                             \
-        next_p, p, vi, g, gs, tg, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, pressure, two_dx_inv)
-    if (no_slip) {
-        if (pressure) { SFL_GO(true, true); } else { SFL_GO(true, false); }
-    } else {
-        if (pressure) { SFL_GO(false, true); } else { SFL_GO(false, false); }
-    }
-#undef SFL_GO
+    with_bool(no_slip, [&](auto ns) {
+        with_bool(pressure != nullptr, [&](auto fg) {
+            advect_vec3uq32_tiled_kernel<decltype(ns)::value, decltype(fg)::value, kThreadsDye><<<grid, block, 0, s>>>(
+                next_p, p, vi, g, gs, tg, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, pressure, two_dx_inv);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -625,10 +584,9 @@ hipError_t launch_advect_divergence_tiled(hipStream_t s, float *next_v, float *d
     const dim3 grid(tg.per_xcd * kXcds), block(512);
     auto *o = reinterpret_cast<float2 *>(next_v);
     auto *vi = reinterpret_cast<const float2 *>(v);
-    if (no_slip)
-        advect_divergence_tiled_kernel<true, 512><<<grid, block, 0, s>>>(o, div, vi, g, tg, dt, two_dx_inv);
-    else
-        advect_divergence_tiled_kernel<false, 512><<<grid, block, 0, s>>>(o, div, vi, g, tg, dt, two_dx_inv);
+    with_bool(no_slip, [&](auto ns) {
+        advect_divergence_tiled_kernel<decltype(ns)::value, 512><<<grid, block, 0, s>>>(o, div, vi, g, tg, dt, two_dx_inv);
+    });
     return hipGetLastError();
 }
 

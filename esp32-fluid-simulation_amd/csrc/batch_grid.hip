@@ -55,12 +55,9 @@ constexpr int kThreads = SFL_BATCH_THREADS;
 // accepts exactly the shapes small_grid_fits accepts
 static_assert(cells_per_colour<kThreads>() * kThreads == kSmallGridMaxCells / 2, "SFL_BATCH_THREADS must divide 3072");
 
-// ---- one whole step of member blockIdx.x, ino:252-287 ---------------------------------------------
-__global__ void SFL_BATCH_BOUNDS
-batch_step_kernel(BatchStep b)
+// the step of one member: every pointer at that member's first cell, its force records
+__device__ __forceinline__ SmallStep member_step(const BatchStep &b, size_t member)
 {
-    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-    const size_t member = blockIdx.x;
     const size_t base = member * (size_t)b.step.dim_x * (size_t)b.step.dim_y;   // 64-bit: cells before this member
     SmallStep a = b.step;
     a.v_in += 2 * base;
@@ -76,6 +73,15 @@ batch_step_kernel(BatchStep b)
         a.force_vel += 2 * (size_t)f0;
         a.n_forces = f1 - f0;
     }
+    return a;
+}
+
+// ---- one whole step of member blockIdx.x, ino:252-287 ---------------------------------------------
+__global__ void SFL_BATCH_BOUNDS
+batch_step_kernel(BatchStep b)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    const SmallStep a = member_step(b, blockIdx.x);
 #include "small_step_body.inc"
 }
 
@@ -142,25 +148,11 @@ batch_step_each_kernel(BatchStep b, const BatchMember *__restrict__ members, flo
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     const BatchMember q = members[blockIdx.x];   // workgroup-uniform: scalar loads
     const size_t member = (size_t)q.member;      // (the host hands out long members first)
-    const size_t base = member * (size_t)b.step.dim_x * (size_t)b.step.dim_y;   // 64-bit: cells before this member
-    SmallStep a = b.step;
+    SmallStep a = member_step(b, member);
     a.dt = q.dt;
     a.two_dx_inv = q.two_dx_inv;
     a.iters = q.iters;
     a.prm = q.prm;
-    a.v_in += 2 * base;
-    a.v_out += 2 * base;
-    a.col_in += 3 * base;
-    a.col_out += 3 * base;
-    a.div += base;
-    a.p += base;
-    a.n_forces = 0;
-    if (b.force_offsets) {   // this member's records, in queue order
-        const int f0 = b.force_offsets[member], f1 = b.force_offsets[member + 1];
-        a.force_cells += 2 * (size_t)f0;
-        a.force_vel += 2 * (size_t)f0;
-        a.n_forces = f1 - f0;
-    }
 #include "small_step_body.inc"
     // (the body's last loop only reads l.p and l.v; l.p and l.d are final since the solve's last barrier)
     update_norm_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, a.prm.dx, report + member);
@@ -179,48 +171,40 @@ batch_solve_each_kernel(float *__restrict__ p_out, const float *__restrict__ d_i
     update_norm_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, q.prm.dx, report + q.member);
 }
 
+// every launch of this file: one workgroup per member, 16 B of LDS per cell, which a kernel is granted once per device
+template <auto KERNEL, class... A>
+hipError_t launch_members(hipStream_t s, int dim_x, int dim_y, int batch, A... args)
+{
+    static bool granted[64];
+    const size_t lds = (size_t)dim_x * dim_y * 16;
+    hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(KERNEL), granted);
+    if (e != hipSuccess) return e;
+    KERNEL<<<batch, kThreads, lds, s>>>(args...);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_batch_step(hipStream_t s, const BatchStep &a, int batch)
 {
-    static bool granted[64];
-    const size_t lds = (size_t)a.step.dim_x * a.step.dim_y * 16;
-    hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(batch_step_kernel), granted);
-    if (e != hipSuccess) return e;
-    batch_step_kernel<<<batch, kThreads, lds, s>>>(a);
-    return hipGetLastError();
+    return launch_members<batch_step_kernel>(s, a.step.dim_x, a.step.dim_y, batch, a);
 }
 
 hipError_t launch_batch_solve(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch, int iters,
                               SorParams prm)
 {
-    static bool granted[64];
-    const size_t lds = (size_t)dim_x * dim_y * 16;
-    hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(batch_solve_kernel), granted);
-    if (e != hipSuccess) return e;
-    batch_solve_kernel<<<batch, kThreads, lds, s>>>(p, d, dim_x, dim_y, iters, prm);
-    return hipGetLastError();
+    return launch_members<batch_solve_kernel>(s, dim_x, dim_y, batch, p, d, dim_x, dim_y, iters, prm);
 }
 
 hipError_t launch_batch_step_each(hipStream_t s, const BatchStep &a, int batch, const BatchMember *members, float *report)
 {
-    static bool granted[64];
-    const size_t lds = (size_t)a.step.dim_x * a.step.dim_y * 16;
-    hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(batch_step_each_kernel), granted);
-    if (e != hipSuccess) return e;
-    batch_step_each_kernel<<<batch, kThreads, lds, s>>>(a, members, report);
-    return hipGetLastError();
+    return launch_members<batch_step_each_kernel>(s, a.step.dim_x, a.step.dim_y, batch, a, members, report);
 }
 
 hipError_t launch_batch_solve_each(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
                                    const BatchMember *members, float *report)
 {
-    static bool granted[64];
-    const size_t lds = (size_t)dim_x * dim_y * 16;
-    hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(batch_solve_each_kernel), granted);
-    if (e != hipSuccess) return e;
-    batch_solve_each_kernel<<<batch, kThreads, lds, s>>>(p, d, dim_x, dim_y, members, report);
-    return hipGetLastError();
+    return launch_members<batch_solve_each_kernel>(s, dim_x, dim_y, batch, p, d, dim_x, dim_y, members, report);
 }
 
 }  // namespace sfl

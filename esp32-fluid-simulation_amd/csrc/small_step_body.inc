@@ -35,21 +35,7 @@
     const int i_max = dim_x - 1, j_max = dim_y - 1;
     for (int c = threadIdx.x; c < cells; c += kThreads) {
         const int gj = c / dim_x, i = c - gj * dim_x;
-        const float2 *q = l.v + c;
-        float s;
-        if (i > 0 && i < i_max && gj > 0 && gj < j_max) {  // div_expr_fast, :29
-            const float hx = -q[-1].x + q[1].x;
-            const float hy = -q[-dim_x].y + q[dim_x].y;
-            s = hx + hy;
-        } else {  // div_expr_safe, :15-20: ghost velocity = -own
-            const float2 own = q[0];
-            s = 0.0f;
-            s += (i > 0) ? -q[-1].x : own.x;
-            s += (i < i_max) ? q[1].x : -own.x;
-            s += (gj > 0) ? -q[-dim_x].y : own.y;
-            s += (gj < j_max) ? q[dim_x].y : -own.y;
-        }
-        const float dv = s * a.two_dx_inv;
+        const float dv = divergence_sum(l.v + c, dim_x, i, gj, i_max, j_max) * a.two_dx_inv;
         l.d[c] = dv;
         a.div[c] = dv;
     }
@@ -61,23 +47,11 @@
     for (int c = threadIdx.x; c < cells; c += kThreads) {
         const int gj = c / dim_x, i = c - gj * dim_x;
         const float pc = l.p[c];
-        const float pw = (i > 0) ? l.p[c - 1] : pc;
-        const float pe = (i < i_max) ? l.p[c + 1] : pc;
-        const float ps = (gj > 0) ? l.p[c - dim_x] : pc;
-        const float pn = (gj < j_max) ? l.p[c + dim_x] : pc;
-        const float gx = (pe - pw) * a.two_dx_inv;
-        const float gy = (pn - ps) * a.two_dx_inv;
-        float2 u = l.v[c];
-        u.x = u.x - gx;
-        u.y = u.y - gy;
+        const float2 u = project_cell(l.v[c], l.p + c, dim_x, i, gj, i_max, j_max, a.two_dx_inv);
         v_out[c] = u;
         a.p[c] = pc;
         const float si = (float)i - u.x * a.dt;
         const float sj = (float)gj - u.y * a.dt;
         const SrcPos s = classify(si, sj, dim_x, dim_y);
-        const uq3 r = sample_global_uq3<false>(col_in, g, s, si, sj);
-        uint32_t *o = a.col_out + 3 * (size_t)c;
-        o[0] = r.x;
-        o[1] = r.y;
-        o[2] = r.z;
+        store_uq3(a.col_out, (size_t)c, sample_global_uq3<false>(col_in, g, s, si, sj));
     }

@@ -64,15 +64,7 @@ advect_vec3uq32_kernel(uint32_t *__restrict__ next_p, const uint32_t *p, float2 
     float2 u = vel[c];
     if (FUSE_GRAD) {
         const int i_max = g.dim_x - 1, j_max = g.gdim_y - 1;
-        const float pc = pressure[c];
-        const float pw = (i > 0) ? pressure[c - 1] : pc;
-        const float pe = (i < i_max) ? pressure[c + 1] : pc;
-        const float ps = (gj > 0) ? pressure[c - g.dim_x] : pc;
-        const float pn = (gj < j_max) ? pressure[c + g.dim_x] : pc;
-        const float gx = (pe - pw) * two_dx_inv;
-        const float gy = (pn - ps) * two_dx_inv;
-        u.x = u.x - gx;
-        u.y = u.y - gy;
+        u = project_cell(u, pressure + c, g.dim_x, i, gj, i_max, j_max, two_dx_inv);
         vel[c] = u;
     }
     const float si = (float)i - u.x * dt;
@@ -82,11 +74,7 @@ advect_vec3uq32_kernel(uint32_t *__restrict__ next_p, const uint32_t *p, float2 
         if (halo_flag) atomicOr(halo_flag, 1);
         return;
     }
-    const uq3 r = sample_global_uq3<NO_SLIP>(p, gs, s, si, sj);
-    uint32_t *o = next_p + 3 * c;
-    o[0] = r.x;
-    o[1] = r.y;
-    o[2] = r.z;
+    store_uq3(next_p, c, sample_global_uq3<NO_SLIP>(p, gs, s, si, sj));
 }
 
 // ---- how far do the back-traces of a slab reach beyond its owned rows? ------------------------
@@ -125,20 +113,7 @@ divergence_kernel(float *__restrict__ div, const float2 *__restrict__ v, Slab g,
     if (i >= g.dim_x) return;
     const int i_max = g.dim_x - 1, j_max = g.gdim_y - 1;
     const size_t c = lcell(g, i, gj);
-    float s;
-    if (i > 0 && i < i_max && gj > 0 && gj < j_max) {  // div_expr_fast, :29
-        const float hx = -v[c - 1].x + v[c + 1].x;
-        const float hy = -v[c - g.dim_x].y + v[c + g.dim_x].y;
-        s = hx + hy;
-    } else {  // div_expr_safe, :15-20: ghost velocity = -own
-        const float2 own = v[c];
-        s = 0.0f;
-        s += (i > 0) ? -v[c - 1].x : own.x;
-        s += (i < i_max) ? v[c + 1].x : -own.x;
-        s += (gj > 0) ? -v[c - g.dim_x].y : own.y;
-        s += (gj < j_max) ? v[c + g.dim_x].y : -own.y;
-    }
-    div[c] = s * two_dx_inv;
+    div[c] = divergence_sum(v + c, g.dim_x, i, gj, i_max, j_max) * two_dx_inv;
 }
 
 // ---- subtract_gradient (finitediff.cpp:41-82), in place on v ------------------------------
@@ -151,17 +126,7 @@ subtract_gradient_kernel(float2 *v, const float *__restrict__ p, Slab g, int g_b
     if (i >= g.dim_x) return;
     const int i_max = g.dim_x - 1, j_max = g.gdim_y - 1;
     const size_t c = lcell(g, i, gj);
-    const float pc = p[c];
-    const float pw = (i > 0) ? p[c - 1] : pc;
-    const float pe = (i < i_max) ? p[c + 1] : pc;
-    const float ps = (gj > 0) ? p[c - g.dim_x] : pc;
-    const float pn = (gj < j_max) ? p[c + g.dim_x] : pc;
-    const float gx = (pe - pw) * two_dx_inv;
-    const float gy = (pn - ps) * two_dx_inv;
-    float2 u = v[c];
-    u.x = u.x - gx;
-    u.y = u.y - gy;
-    v[c] = u;
+    v[c] = project_cell(v[c], p + c, g.dim_x, i, gj, i_max, j_max, two_dx_inv);
 }
 
 // ---- baseline SOR colour pass (poisson.cpp:14-112), in place --------------------------------
@@ -339,12 +304,10 @@ hipError_t launch_advect_vec2f(hipStream_t s, float *next_p, const float *p, con
     auto *o = reinterpret_cast<float2 *>(next_p);
     auto *pi = reinterpret_cast<const float2 *>(p);
     auto *vi = reinterpret_cast<const float2 *>(vel);
-    if (no_slip)
-        advect_vec2f_kernel<true><<<agrid, ablock, 0, s>>>(o, pi, vi, g, gs, g_begin, g_end, valid_begin,
-                                                          valid_end, dt, halo_flag);
-    else
-        advect_vec2f_kernel<false><<<agrid, ablock, 0, s>>>(o, pi, vi, g, gs, g_begin, g_end, valid_begin,
-                                                           valid_end, dt, halo_flag);
+    with_bool(no_slip, [&](auto ns) {
+        advect_vec2f_kernel<decltype(ns)::value><<<agrid, ablock, 0, s>>>(o, pi, vi, g, gs, g_begin, g_end, valid_begin,
+                                                                          valid_end, dt, halo_flag);
+    });
     return hipGetLastError();
 }
 
@@ -360,12 +323,10 @@ hipError_t launch_advect_vec3uq32(hipStream_t s, uint32_t *next_p, const uint32_
     const Slab gs = src ? *src : g;
     SFL_ADV_GRID(g.dim_x, g_end - g_begin);
     auto *vi = reinterpret_cast<float2 *>(const_cast<float *>(vel));  // read-only without FUSE_GRAD
-    if (no_slip)
-        advect_vec3uq32_kernel<true, false><<<agrid, ablock, 0, s>>>(
+    with_bool(no_slip, [&](auto ns) {
+        advect_vec3uq32_kernel<decltype(ns)::value, false><<<agrid, ablock, 0, s>>>(
             next_p, p, vi, g, gs, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, nullptr, 0.0f);
-    else
-        advect_vec3uq32_kernel<false, false><<<agrid, ablock, 0, s>>>(
-            next_p, p, vi, g, gs, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, nullptr, 0.0f);
+    });
     return hipGetLastError();
 }
 
@@ -384,12 +345,10 @@ hipError_t launch_project_advect_vec3uq32(hipStream_t s, uint32_t *next_p, const
     }
     SFL_ADV_GRID(g.dim_x, g_end - g_begin);
     auto *vi = reinterpret_cast<float2 *>(vel);
-    if (no_slip)
-        advect_vec3uq32_kernel<true, true><<<agrid, ablock, 0, s>>>(
+    with_bool(no_slip, [&](auto ns) {
+        advect_vec3uq32_kernel<decltype(ns)::value, true><<<agrid, ablock, 0, s>>>(
             next_p, p, vi, g, g, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, pressure, two_dx_inv);
-    else
-        advect_vec3uq32_kernel<false, true><<<agrid, ablock, 0, s>>>(
-            next_p, p, vi, g, g, g_begin, g_end, valid_begin, valid_end, dt, halo_flag, pressure, two_dx_inv);
+    });
     return hipGetLastError();
 }
 

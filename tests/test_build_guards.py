@@ -5,7 +5,8 @@
   from tools/.
 * The trace harness tools/sor_clock_probe.hip (which brings its own backend and kernel, tools/probe/) compiles, plain and with each
   of its switches.
-* No translation unit or header under csrc/ grows past 900 lines again (round 4's sfl_api.cpp had reached 2710)."""
+* No translation unit or header under csrc/ grows past 900 lines again (round 4's sfl_api.cpp had reached 2710).
+* The stencils of the sim step are written once (advect_math.h); the kernels call them."""
 import glob
 import os
 import re
@@ -72,3 +73,32 @@ def test_the_probe_compiles(flags):
 def test_no_source_file_outgrows_900_lines():
     long = {os.path.basename(f): sum(1 for _ in open(f)) for f in glob.glob(os.path.join(CSRC, "*")) if os.path.isfile(f)}
     assert long and max(long.values()) <= 900, {k: v for k, v in long.items() if v > 900}
+
+
+def test_each_step_stencil_is_written_once():
+    """Divergence, v - grad p and the four-texel mix carry the numerics contract (operation order, the -0.0f rules, where a UQ32
+    narrows): one copy each, in advect_math.h, so that a change cannot reach some kernels and miss others."""
+    text = {os.path.basename(f): open(f, errors="replace").read() for f in glob.glob(os.path.join(CSRC, "*")) if os.path.isfile(f)}
+    assert len(text) > 20
+
+    def where(pattern):
+        return {name: len(re.findall(pattern, body)) for name, body in text.items() if re.search(pattern, body)}
+
+    assert where(r"\(pe - pw\)") == {"advect_math.h": 1}                      # the gradient difference
+    assert where(r"\? *-\w+(\[[^\]]*\])*\.x *: *\w+\.x") == {"advect_math.h": 1}  # div_expr_safe: (i > 0) ? -west.x : own.x
+    assert where(r": *-own\.x") == {"advect_math.h": 1}                       # ... and its ghost on the other side
+    # the nested mix of four texels: the one of advect_math.h (mix4) and advect_generic.hip's per-channel one
+    assert where(r"mix1\(s\.di, *mix1\(s\.dj,") == {"advect_math.h": 1, "advect_generic.hip": 1}
+    # a closed experiment's switch (DESIGN.md 4.2): nowhere but in the records of its measurements
+    closed = "SEAM_DYE_" + "LOADS"
+    kept = (os.path.join(ROOT, "profiles") + os.sep, os.path.join(ROOT, "DESIGN.md"), os.path.join(ROOT, "build") + os.sep,
+            os.path.join(ROOT, ".git") + os.sep)
+    hits = []
+    for folder, _, names in os.walk(ROOT):
+        for name in names:
+            f = os.path.join(folder, name)
+            if f.startswith(kept) or not name.endswith((".h", ".hip", ".inc", ".cpp", ".c", ".py", ".sh", ".md", ".txt", ".json", "Makefile")):
+                continue
+            if closed in open(f, errors="replace").read():
+                hits.append(os.path.relpath(f, ROOT))
+    assert not hits, hits

@@ -12,7 +12,7 @@
 # inside the product kernels' sources; their experiments are closed (profiles/r04_cooperative_tiles_mock.txt, r05_share_tiling.txt,
 # r06_pressure_never_stored.txt) and they were last buildable at commit 5a86197.
 # e.g.  bash tools/recipes/build_variant.sh probe ns10_noload 10 "-DSFL_PROBE_NO_LOAD=1"
-#       bash tools/recipes/build_variant.sh lib seam_early "-DSEAM_DYE_LOADS=1" advect_tiled.hip
+#       bash tools/recipes/build_variant.sh lib strip16 "-DSFL_STRIP_TILES=16" advect_tiled.hip
 set -eu
 cd "$(dirname "$0")/../.."
 F="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC -fvisibility=hidden -Wno-unused-parameter"
