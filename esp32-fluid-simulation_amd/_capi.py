@@ -46,6 +46,11 @@ class MemberParams(C.Structure):
     _fields_ = [("dt", C.c_float), ("dx", C.c_float), ("omega", C.c_float), ("iters", C.c_int32)]
 
 
+class MemberStop(C.Structure):
+    """sfl_member_stop: when ONE batch member's pressure solve stops (sfl_batch_*_until), 8 bytes."""
+    _fields_ = [("tol", C.c_float), ("every", C.c_int32)]
+
+
 class SflError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"sfl error {code}: {message}")
@@ -148,6 +153,9 @@ SIGNATURES = {
     "sfl_batch_step_n_each": (_i, [_ctx, _i, C.POINTER(MemberParams)]),
     "sfl_batch_poisson_solve_each": (_i, [_ctx, C.POINTER(MemberParams)]),
     "sfl_batch_residual": (_i, [_ctx, _i, _i, _pf, _sz]),
+    "sfl_batch_step_n_until": (_i, [_ctx, _i, C.POINTER(MemberParams), C.POINTER(MemberStop)]),
+    "sfl_batch_poisson_solve_until": (_i, [_ctx, C.POINTER(MemberParams), C.POINTER(MemberStop)]),
+    "sfl_batch_iterations": (_i, [_ctx, _i, _i, C.POINTER(C.c_int32), _sz]),
     "sfl_batch_setup_sketch_fields": (_i, [_ctx]),
     "sfl_batch_render_rgb565": (_i, [_ctx, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),

@@ -6,6 +6,8 @@
 
 #include "context.h"
 
+#include <cmath>
+
 using sfl::host::fail;
 
 struct sfl_batch {
@@ -38,6 +40,11 @@ struct sfl_batch {
     int member_slot = 0;
     float *d_report = nullptr;
     bool report_valid = false;
+    // stopping rules (sfl_batch_*_until): the members' sfl_member_stop behind their records, in the same device array and
+    // in launch order, and two ints per member for the iterations the *_until kernels ran (valid: see sfl_batch_iterations)
+    sfl::BatchStop *d_stops = nullptr;
+    int *d_counts = nullptr;
+    bool counts_valid = false;
     // dye visualiser's device image, kept between frames
     uint16_t *d_image = nullptr;
     size_t d_image_bytes = 0;
@@ -50,7 +57,7 @@ void release(sfl_batch *b)
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (void *m : {(void *)b->vel, (void *)b->vel_tmp, (void *)b->col, (void *)b->col_tmp, (void *)b->div, (void *)b->p,
-                    b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_image})
+                    b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_counts, (void *)b->d_image})
         if (m) (void)hipFree(m);
     for (sfl_batch::Stage *pair : {b->stage, b->member_stage})
         for (int k = 0; k < 2; ++k) {
@@ -201,15 +208,35 @@ int check_members(sfl_batch *b, const sfl_member_params *params)
     return SFL_OK;
 }
 
+// ... and of the *_until calls on both kinds of record: the first member with anything wrong is the one named
+int check_members(sfl_batch *b, const sfl_member_params *params, const sfl_member_stop *stops)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    if (!params) return fail(SFL_ERR_INVALID, "params is NULL");
+    if (!stops) return fail(SFL_ERR_INVALID, "stops is NULL");
+    for (int m = 0; m < b->batch; ++m) {
+        if (params[m].iters < 0)
+            return fail(SFL_ERR_INVALID, "member %d: iters (the cap) must be >= 0 (got %d)", m, (int)params[m].iters);
+        if (stops[m].every < 1)
+            return fail(SFL_ERR_INVALID, "member %d: every must be >= 1 (got %d)", m, (int)stops[m].every);
+        if (std::isnan(stops[m].tol))
+            return fail(SFL_ERR_INVALID, "member %d: tol is a NaN (a negative tol never stops a member, +inf stops it at once)", m);
+    }
+    return SFL_OK;
+}
+
 // The members' records, with the host-derived constants formed as the uniform path forms them, copied to the device
 // behind the launches queued so far.  Launch order: when the iteration counts differ, the members with the most go first
 // (a stable sort, so the order is a function of the parameters alone) -- workgroups start roughly in that order and a
 // long member that starts last would set the launch's end alone; results do not depend on it.  The device array has its
 // final size from the first call on and is written in stream order, so nothing ever drains the stream; a pinned slot is
-// rewritten only after its last copy has completed.
-int stage_members(sfl_batch *b, const sfl_member_params *params)
+// rewritten only after its last copy has completed.  With `stops` (the *_until calls) the members' stopping rules travel
+// behind the records -- same order, same copy, the tail of the same device array (d_stops).
+int stage_members(sfl_batch *b, const sfl_member_params *params, const sfl_member_stop *stops = nullptr)
 {
-    const size_t bytes = sizeof(sfl::BatchMember) * (size_t)b->batch;
+    const size_t rec_bytes = sizeof(sfl::BatchMember) * (size_t)b->batch;
+    const size_t all_bytes = rec_bytes + sizeof(sfl::BatchStop) * (size_t)b->batch;
+    const size_t bytes = stops ? all_bytes : rec_bytes;
     sfl_batch::Stage &st = b->member_stage[b->member_slot];
     b->member_slot ^= 1;
     if (!st.copied) HIP_TRY(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
@@ -218,11 +245,15 @@ int stage_members(sfl_batch *b, const sfl_member_params *params)
         st.pending = false;
     }
     if (!st.host) {
-        HIP_TRY(hipHostMalloc(&st.host, bytes, hipHostMallocDefault));
-        st.bytes = bytes;
+        HIP_TRY(hipHostMalloc(&st.host, all_bytes, hipHostMallocDefault));
+        st.bytes = all_bytes;
     }
-    if (!b->d_members) HIP_TRY(hipMalloc((void **)&b->d_members, bytes));
+    if (!b->d_members) {
+        HIP_TRY(hipMalloc((void **)&b->d_members, all_bytes));
+        b->d_stops = reinterpret_cast<sfl::BatchStop *>(b->d_members + b->batch);
+    }
     if (!b->d_report) HIP_TRY(hipMalloc((void **)&b->d_report, sizeof(float) * (size_t)b->batch));
+    if (!b->d_counts) HIP_TRY(hipMalloc((void **)&b->d_counts, sizeof(int) * 2 * (size_t)b->batch));
     std::vector<int> order((size_t)b->batch);
     for (int m = 0; m < b->batch; ++m) order[m] = m;
     const auto differs = [&](const sfl_member_params &q) { return q.iters != params[0].iters; };
@@ -236,6 +267,10 @@ int stage_members(sfl_batch *b, const sfl_member_params *params)
         rec[k].prm = sor_params(q.dx, q.omega);
         rec[k].iters = q.iters;
         rec[k].member = order[k];
+    }
+    if (stops) {
+        sfl::BatchStop *stop = reinterpret_cast<sfl::BatchStop *>(rec + b->batch);
+        for (int k = 0; k < b->batch; ++k) stop[k] = sfl::BatchStop{stops[order[k]].tol, stops[order[k]].every};
     }
     HIP_TRY(hipMemcpyAsync(b->d_members, st.host, bytes, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipEventRecord(st.copied, b->stream));
@@ -307,7 +342,7 @@ int sfl_batch_upload(sfl_batch *b, int field, int first, int count, const void *
     SFL_TRY(check_range(b, field, first, count, host, bytes));
     if (count == 0) return SFL_OK;
     SFL_TRY(use_device(b));
-    if (field == SFL_FIELD_DIVERGENCE || field == SFL_FIELD_PRESSURE) b->report_valid = false;
+    if (field == SFL_FIELD_DIVERGENCE || field == SFL_FIELD_PRESSURE) b->report_valid = b->counts_valid = false;
     char *dev = static_cast<char *>(field_base(b, field)) + (size_t)first * b->cells * elem_bytes(field);
     HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -353,7 +388,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     if (n == 0) return SFL_OK;
     SFL_TRY(use_device(b));
-    b->report_valid = false;   // (the uniform kernels leave no update norm)
+    b->report_valid = b->counts_valid = false;   // (the uniform kernels leave no update norm)
     sfl::BatchStep a{};
     a.step.div = b->div;
     a.step.p = b->p;
@@ -382,7 +417,7 @@ int sfl_batch_poisson_solve(sfl_batch *b, float dx, int iters, float omega)
     if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     SFL_TRY(use_device(b));
-    b->report_valid = false;
+    b->report_valid = b->counts_valid = false;
     HIP_TRY(sfl::launch_batch_solve(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch, iters, sor_params(dx, omega)));
     return SFL_OK;
 }
@@ -394,7 +429,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
     if (n == 0) return SFL_OK;
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
-    b->report_valid = false;   // until every launch below is queued
+    b->report_valid = b->counts_valid = false;   // until every launch below is queued; no iterations to report afterwards
     sfl::BatchStep a{};   // (dt, two_dx_inv, iters and prm come from the members' records)
     a.step.div = b->div;
     a.step.p = b->p;
@@ -420,9 +455,50 @@ int sfl_batch_poisson_solve_each(sfl_batch *b, const sfl_member_params *params)
     SFL_TRY(check_members(b, params));
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
-    b->report_valid = false;
+    b->report_valid = b->counts_valid = false;
     HIP_TRY(sfl::launch_batch_solve_each(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch, b->d_members, b->d_report));
     b->report_valid = true;
+    return SFL_OK;
+}
+
+int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params, const sfl_member_stop *stops)
+{
+    SFL_TRY(check_members(b, params, stops));
+    if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
+    if (n == 0) return SFL_OK;
+    SFL_TRY(use_device(b));
+    SFL_TRY(stage_members(b, params, stops));
+    b->report_valid = b->counts_valid = false;   // until every launch below is queued
+    sfl::BatchStep a{};   // (dt, two_dx_inv, iters and prm come from the members' records)
+    a.step.div = b->div;
+    a.step.p = b->p;
+    a.step.dim_x = b->dim_x;
+    a.step.dim_y = b->dim_y;
+    for (int k = 0; k < n; ++k) {
+        // queued forces go into the first step (the queue is empty after it)
+        SFL_TRY(stage_forces(b, &a.force_offsets, &a.step.force_cells, &a.step.force_vel));
+        a.step.v_in = b->vel;
+        a.step.v_out = b->vel_tmp;
+        a.step.col_in = b->col;
+        a.step.col_out = b->col_tmp;
+        // (the first step starts every member's sum of iterations, the later ones add to it)
+        HIP_TRY(sfl::launch_batch_step_until(b->stream, a, b->batch, b->d_members, b->d_stops, b->d_report, b->d_counts, k > 0));
+        std::swap(b->vel, b->vel_tmp);  // ino:255
+        std::swap(b->col, b->col_tmp);  // ino:286
+    }
+    b->report_valid = b->counts_valid = true;   // of the last step's solve; the sum over all n
+    return SFL_OK;
+}
+
+int sfl_batch_poisson_solve_until(sfl_batch *b, const sfl_member_params *params, const sfl_member_stop *stops)
+{
+    SFL_TRY(check_members(b, params, stops));
+    SFL_TRY(use_device(b));
+    SFL_TRY(stage_members(b, params, stops));
+    b->report_valid = b->counts_valid = false;
+    HIP_TRY(sfl::launch_batch_solve_until(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch, b->d_members, b->d_stops,
+                                          b->d_report, b->d_counts));
+    b->report_valid = b->counts_valid = true;
     return SFL_OK;
 }
 
@@ -436,10 +512,29 @@ int sfl_batch_residual(sfl_batch *b, int first, int count, float *host, size_t b
     if (!host && count > 0) return fail(SFL_ERR_INVALID, "host is NULL");
     if (!b->report_valid)
         return fail(SFL_ERR_STATE, "no update norm to report: the last call that wrote the divergence or the pressure was not "
-                    "sfl_batch_step_n_each or sfl_batch_poisson_solve_each; call one of them first");
+                    "sfl_batch_step_n_each or sfl_batch_poisson_solve_each (or their _until forms); call one of them first");
     if (count == 0) return SFL_OK;
     SFL_TRY(use_device(b));
     HIP_TRY(hipMemcpyAsync(host, b->d_report + first, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return SFL_OK;
+}
+
+int sfl_batch_iterations(sfl_batch *b, int first, int count, int32_t *host, size_t bytes)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    if (first < 0 || count < 0 || (int64_t)first + count > b->batch)
+        return fail(SFL_ERR_INVALID, "members [%d, %d + %d) are not inside the batch's [0, %d)", first, first, count, b->batch);
+    if (bytes != (size_t)count * 2 * sizeof(int32_t))
+        return fail(SFL_ERR_INVALID, "the iterations of %d members are %zu bytes, got %zu", count,
+                    (size_t)count * 2 * sizeof(int32_t), bytes);
+    if (!host && count > 0) return fail(SFL_ERR_INVALID, "host is NULL");
+    if (!b->counts_valid)
+        return fail(SFL_ERR_STATE, "no iterations to report: the last call that wrote the divergence or the pressure was not "
+                    "sfl_batch_step_n_until or sfl_batch_poisson_solve_until; call one of them first");
+    if (count == 0) return SFL_OK;
+    SFL_TRY(use_device(b));
+    HIP_TRY(hipMemcpyAsync(host, b->d_counts + 2 * (size_t)first, bytes, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return SFL_OK;
 }

@@ -38,4 +38,20 @@ hipError_t launch_batch_step_each(hipStream_t s, const BatchStep &a, int batch, 
 hipError_t launch_batch_solve_each(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
                                    const BatchMember *members, float *report);
 
+// ---- per-member parameters, the solve stopped at a tolerance ------------------------------------------------------
+// sfl_member_stop of the member that members[k] names: stops[k] goes with members[k] (a device array of its own, so that
+// BatchMember and the *_each kernels that read it stay as they are).  members[k].iters is the cap.
+struct BatchStop {
+    float tol;
+    int every;
+};
+// launch_batch_step_each / launch_batch_solve_each with every solve run by the rule of include/sfl.h (sfl_member_stop):
+// report[m] = the update norm of the pressure member m is left with, counts[2 m] = the iterations its solve ran,
+// counts[2 m + 1] = that count again (solve; step with add == false) or added to what is there (step with add == true:
+// the later steps of one call).  stops, report, counts: device arrays of `batch`, `batch` and 2 * `batch`.
+hipError_t launch_batch_step_until(hipStream_t s, const BatchStep &a, int batch, const BatchMember *members,
+                                   const BatchStop *stops, float *report, int *counts, bool add);
+hipError_t launch_batch_solve_until(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
+                                    const BatchMember *members, const BatchStop *stops, float *report, int *counts);
+
 }  // namespace sfl

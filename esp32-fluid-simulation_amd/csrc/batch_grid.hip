@@ -28,6 +28,13 @@
 // member.  They are kernels of their own, not a template parameter of the two above: the uniform kernels keep their
 // instructions.
 //
+// Stopping at a tolerance (batch_step_until_kernel, batch_solve_until_kernel): the *_each kernels with sor_until_in_lds
+// (small_grid_core.h) for their solve -- a check of the update norm in front of every `every`-th iteration, formed from
+// the registers of the solve, and the member leaves the loop at the first one that finds the norm <= tol (or a NaN).
+// tol and every arrive like the record, by scalar loads of BatchStop blockIdx.x, and the verdict of a check is made
+// wave-uniform, so the loop stays scalar-controlled.  The last check is the report; the iterations run go out beside it.
+// Kernels of their own again: the six kernels that existed keep their instructions (profiles/batch_until.txt).
+//
 // Numerics contract: -ffp-contract=off, every operation individually rounded in the
 // reference's order.  Reference citations are file:line under /root/reference/ESP32-fluid-simulation/.
 #include "batch.h"
@@ -171,6 +178,55 @@ batch_solve_each_kernel(float *__restrict__ p_out, const float *__restrict__ d_i
     update_norm_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, q.prm.dx, report + q.member);
 }
 
+// ---- the *_until kernels: the *_each kernels with the solve stopped at a tolerance (sor_until_in_lds) ---------------
+// stops[k] belongs to members[k].  What a member leaves besides its fields: report[m] = the update norm of its final
+// pressure (the solve's own last check: no walk afterwards) and counts[2 m], counts[2 m + 1] = the iterations of this
+// solve and their sum over the launches of one call (`add` = 0 in the call's first launch).  Plain stores by thread 0.
+__device__ __forceinline__ void leave_until(const UntilResult &r, size_t member, float *report, int *counts, int add)
+{
+    if (threadIdx.x == 0) {
+        report[member] = __uint_as_float(r.norm_bits);
+        counts[2 * member] = r.iters;
+        counts[2 * member + 1] = add ? counts[2 * member + 1] + r.iters : r.iters;
+    }
+}
+
+__global__ void SFL_BATCH_BOUNDS
+batch_step_until_kernel(BatchStep b, const BatchMember *__restrict__ members, const BatchStop *__restrict__ stops,
+                        float *__restrict__ report, int *__restrict__ counts, int add)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    const BatchMember q = members[blockIdx.x];   // workgroup-uniform: scalar loads
+    const BatchStop stop = stops[blockIdx.x];
+    const size_t member = (size_t)q.member;
+    SmallStep a = member_step(b, member);
+    a.dt = q.dt;
+    a.two_dx_inv = q.two_dx_inv;
+    a.iters = q.iters;
+    a.prm = q.prm;
+#define SFL_STEP_SOLVE const UntilResult r = sor_until_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, a.iters, a.prm, stop.tol, stop.every)
+#include "small_step_body.inc"
+#undef SFL_STEP_SOLVE
+    leave_until(r, member, report, counts, add);
+}
+
+__global__ void SFL_BATCH_BOUNDS
+batch_solve_until_kernel(float *__restrict__ p_out, const float *__restrict__ d_in, int dim_x, int dim_y,
+                         const BatchMember *__restrict__ members, const BatchStop *__restrict__ stops,
+                         float *__restrict__ report, int *__restrict__ counts)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    const BatchMember q = members[blockIdx.x];
+    const BatchStop stop = stops[blockIdx.x];
+    const size_t base = (size_t)q.member * (size_t)dim_x * (size_t)dim_y;
+    const int cells = dim_x * dim_y;
+    const Lds l = carve(lds_raw, cells);
+    for (int c = threadIdx.x; c < cells; c += kThreads) l.d[c] = d_in[base + c];
+    const UntilResult r = sor_until_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, q.iters, q.prm, stop.tol, stop.every);
+    for (int c = threadIdx.x; c < cells; c += kThreads) p_out[base + c] = l.p[c];
+    leave_until(r, (size_t)q.member, report, counts, 0);
+}
+
 // every launch of this file: one workgroup per member, 16 B of LDS per cell, which a kernel is granted once per device
 template <auto KERNEL, class... A>
 hipError_t launch_members(hipStream_t s, int dim_x, int dim_y, int batch, A... args)
@@ -205,6 +261,20 @@ hipError_t launch_batch_solve_each(hipStream_t s, float *p, const float *d, int 
                                    const BatchMember *members, float *report)
 {
     return launch_members<batch_solve_each_kernel>(s, dim_x, dim_y, batch, p, d, dim_x, dim_y, members, report);
+}
+
+hipError_t launch_batch_step_until(hipStream_t s, const BatchStep &a, int batch, const BatchMember *members,
+                                   const BatchStop *stops, float *report, int *counts, bool add)
+{
+    return launch_members<batch_step_until_kernel>(s, a.step.dim_x, a.step.dim_y, batch, a, members, stops, report, counts,
+                                                   add ? 1 : 0);
+}
+
+hipError_t launch_batch_solve_until(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
+                                    const BatchMember *members, const BatchStop *stops, float *report, int *counts)
+{
+    return launch_members<batch_solve_until_kernel>(s, dim_x, dim_y, batch, p, d, dim_x, dim_y, members, stops, report,
+                                                    counts);
 }
 
 }  // namespace sfl

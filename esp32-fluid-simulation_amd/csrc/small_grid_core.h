@@ -98,6 +98,150 @@ __device__ __forceinline__ void sor_in_lds(float *p, const float *d, int dim_x, 
     }
 }
 
+// ---- sor_in_lds that stops at a tolerance (include/sfl.h sfl_member_stop) -------------------------------------------
+// The registers of sor_in_lds as a record, its set-up and its iteration as functions, for sor_until_in_lds below.  The
+// same ownership of cells, the same pass and the same expressions, written a second time: sor_in_lds itself keeps its
+// text, because built from these pieces it compiles to other instructions (the arithmetic is the same either way), and
+// the kernels that exist keep theirs.
+template <int kThreads>
+struct SorCells {
+    static constexpr int kCellsPerColour = cells_per_colour<kThreads>();
+    int kmax;                        // cells of one colour this workgroup's threads own at most: block-uniform, <= kCellsPerColour
+    int cm[2][kCellsPerColour];      // cell index | neighbour mask << 16 (bit 0 W, 1 E, 2 S, 3 N present; bit 4: cell exists)
+    float own[2][kCellsPerColour], rhs[2][kCellsPerColour], kf[2][kCellsPerColour], z[2][kCellsPerColour];
+};
+
+// the thread's cells of both colours on p = 0; d is complete in LDS (behind a barrier)
+template <int kThreads>
+__device__ __forceinline__ void sor_cells_init(SorCells<kThreads> &t, const float *d, int dim_x, int dim_y, float dx)
+{
+    constexpr int kCellsPerColour = SorCells<kThreads>::kCellsPerColour;
+    const int half = (dim_x + 1) / 2;
+    const int i_max = dim_x - 1, j_max = dim_y - 1;
+    const int per_colour = dim_y * half;                              // positions of one colour, row-major
+    t.kmax = (per_colour + kThreads - 1) / kThreads;
+#pragma unroll
+    for (int colour = 0; colour < 2; ++colour)
+#pragma unroll
+        for (int k = 0; k < kCellsPerColour; ++k) {
+            const int q = threadIdx.x + k * kThreads;
+            const int gj = q / half, ii = q - gj * half;
+            const int i = 2 * ii + ((gj + colour) & 1);
+            const bool have = k < t.kmax && gj < dim_y && i < dim_x;
+            const int c = have ? gj * dim_x + i : 0;
+            const int m = (i > 0 ? 1 : 0) | (i < i_max ? 2 : 0) | (gj > 0 ? 4 : 0) | (gj < j_max ? 8 : 0);
+            const int present = __builtin_popcount(m);
+            t.cm[colour][k] = have ? (c | ((m | 16) << 16)) : 0;
+            t.own[colour][k] = 0.0f;
+            t.rhs[colour][k] = have ? dx * d[c] : 0.0f;   // dx * d, :108 / :88 (the same product every pass)
+            t.kf[colour][k] = (present == 2) ? (float)(-1.0 / 2.0) : (present == 3) ? (float)(-1.0 / 3.0) : -0.25f;  // :67
+            t.z[colour][k] = (present == 4) ? -0.0f : 0.0f;
+        }
+}
+
+// one iteration: the two colour passes, each behind its barrier
+template <int kThreads>
+__device__ __forceinline__ void sor_iteration(SorCells<kThreads> &t, float *p, int dim_x, const SorParams &prm)
+{
+    constexpr int kCellsPerColour = SorCells<kThreads>::kCellsPerColour;
+#pragma unroll
+    for (int colour = 0; colour < 2; ++colour) {  // colour 0 = even (i + j) first, poisson.cpp:22,57-60
+        float w[kCellsPerColour], e[kCellsPerColour], s[kCellsPerColour], n[kCellsPerColour];
+#pragma unroll
+        for (int k = 0; k < kCellsPerColour; ++k) {
+            if (k >= t.kmax) break;
+            const int c = t.cm[colour][k] & 0xffff, m = t.cm[colour][k] >> 16;
+            w[k] = (m & 1) ? p[c - 1] : -0.0f;
+            e[k] = (m & 2) ? p[c + 1] : -0.0f;
+            s[k] = (m & 4) ? p[c - dim_x] : -0.0f;
+            n[k] = (m & 8) ? p[c + dim_x] : -0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < kCellsPerColour; ++k) {
+            if (k >= t.kmax) break;
+            const float sum = (((t.z[colour][k] + w[k]) + e[k]) + s[k]) + n[k];
+            const float p_gs = t.kf[colour][k] * (t.rhs[colour][k] - sum);
+            const float fresh = prm.one_minus_omega * t.own[colour][k] + prm.omega * p_gs;  // :98, :111
+            t.own[colour][k] = fresh;
+            if (t.cm[colour][k] >> 20) p[t.cm[colour][k] & 0xffff] = fresh;
+        }
+        __syncthreads();
+    }
+}
+
+// What a solve by the rule leaves: the iterations run and the update norm of the pressure they left, as bits.  Both are
+// the same in every thread and wave-uniform by construction (SGPRs).
+struct UntilResult {
+    int iters;
+    unsigned norm_bits;
+};
+
+// sor_in_lds -- the same cells, the same iteration -- with a check in front of iteration k = 0, every, 2 * every, ...
+// < cap and once more at the iteration the solve ends with: the update norm u_k of the pressure as it stands, formed
+// FROM THE REGISTERS OF THE SOLVE: p_gs = kf * (rhs - ((((z + W) + E) + S) + N)) with the neighbours of both colours
+// read from LDS (nothing is updated in between), |p_gs - own| as unsigned bits -- own is the bit pattern the thread
+// stored into p[c], rhs the product dx * d[c] of batch_grid.hip's update_norm_in_lds: term for term that walk's
+// arithmetic, without its reads of d and its index derivation.  One cell at a time, not a colour's cells together as a
+// pass reads them: what a check keeps in flight comes on top of everything the iteration loop keeps in registers, and
+// the budget is 64 (profiles/batch_until.txt has the forms tried).  The maximum: wave by __shfl_xor, then one LDS
+// atomicMax per wave (a maximum over bit patterns does not depend on the order; any NaN wins).
+// The solve stops at the first checkpoint with u_k <= tol or u_k a NaN, given tol >= 0 (a negative tol stops nothing,
+// a NaN included: the member runs to its cap as under sor_in_lds), else at k = cap.  The verdict is read back by
+// every thread behind a barrier and made wave-uniform by readfirstlane, so the loop, its branches and its barriers stay
+// scalar-controlled.  Two LDS words used alternately: check n accumulates into word n & 1 while thread 0 clears the other
+// one, which every thread has finished reading at check n - 1 before it passed the barriers of the iteration in
+// between -- no third barrier.  The last check is the report: no walk afterwards.
+template <int kThreads>
+__device__ __forceinline__ UntilResult sor_until_in_lds(float *p, const float *d, int dim_x, int dim_y, int cap,
+                                                        SorParams prm, float tol, int every)
+{
+    constexpr int kCellsPerColour = SorCells<kThreads>::kCellsPerColour;
+    __shared__ unsigned worst[2];
+    const int cells = dim_x * dim_y;
+    for (int c = threadIdx.x; c < cells; c += kThreads) p[c] = 0.0f;
+    if (threadIdx.x == 0) worst[0] = 0u;
+    __syncthreads();   // (also: d is complete)
+    SorCells<kThreads> t;
+    sor_cells_init(t, d, dim_x, dim_y, prm.dx);
+    UntilResult r{0, 0u};
+    int next_check = 0, word = 0;
+    for (;;) {
+        if (r.iters == next_check || r.iters >= cap) {   // scalar: a checkpoint, or the end
+            unsigned mx = 0u;
+#pragma unroll
+            for (int colour = 0; colour < 2; ++colour)
+#pragma unroll
+                for (int k = 0; k < kCellsPerColour; ++k) {
+                    if (k >= t.kmax) break;
+                    const int c = t.cm[colour][k] & 0xffff, m = t.cm[colour][k] >> 16;
+                    const float w = (m & 1) ? p[c - 1] : -0.0f;
+                    const float e = (m & 2) ? p[c + 1] : -0.0f;
+                    const float s = (m & 4) ? p[c - dim_x] : -0.0f;
+                    const float n = (m & 8) ? p[c + dim_x] : -0.0f;
+                    const float sum = (((t.z[colour][k] + w) + e) + s) + n;
+                    const float p_gs = t.kf[colour][k] * (t.rhs[colour][k] - sum);
+                    const unsigned bits = __float_as_uint(p_gs - t.own[colour][k]) & 0x7fffffffu;   // |p_gs - p|
+                    if (m >> 4) mx = bits > mx ? bits : mx;   // (a position without a cell has no say)
+                }
+            for (int o = 32; o > 0; o >>= 1) {   // the wave's maximum
+                const unsigned u = __shfl_xor(mx, o);
+                mx = u > mx ? u : mx;
+            }
+            if ((threadIdx.x & 63) == 0) atomicMax(&worst[word], mx);
+            if (threadIdx.x == 0) worst[word ^ 1] = 0u;   // for the next check (see above)
+            __syncthreads();
+            r.norm_bits = __builtin_amdgcn_readfirstlane(worst[word]);
+            word ^= 1;
+            const float u = __uint_as_float(r.norm_bits);
+            if (r.iters >= cap || (tol >= 0.0f && !(u > tol))) break;   // !(u > tol): u <= tol, or u is a NaN
+            next_check += every;
+        }
+        sor_iteration(t, p, dim_x, prm);
+        ++r.iters;
+    }
+    return r;
+}
+
 // ---- poisson_solve (poisson.cpp:114-125) alone: d_in -> p_out of ONE grid ------------------------
 template <int kThreads>
 __device__ __forceinline__ void solve_in_lds(char *lds_raw, float *p_out, const float *d_in,

@@ -39,8 +39,13 @@
         l.d[c] = dv;
         a.div[c] = dv;
     }
-    // poisson_solve: ino:275 (the barrier inside also orders the divergence writes above)
+    // poisson_solve: ino:275 (the barrier inside also orders the divergence writes above).  A kernel whose solve is
+    // another one names it in SFL_STEP_SOLVE before it includes this text (batch_grid.hip: the solve to a tolerance)
+#ifdef SFL_STEP_SOLVE
+    SFL_STEP_SOLVE;
+#else
     sor_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, a.iters, a.prm);
+#endif
     // subtract_gradient (ino:276, finitediff.cpp:41-82), then the dye back-trace with the projected velocity of
     // the cell itself (ino:281-287, advect.h:81) -- per cell, no barrier needed in between
     const uint32_t *col_in = a.col_in;

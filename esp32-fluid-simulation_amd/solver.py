@@ -43,6 +43,21 @@ def member_params(batch: int, dt, dx=1.0, iters=10, omega=1.96) -> np.ndarray:
     return out
 
 
+MEMBER_STOP_DTYPE = np.dtype([("tol", "<f4"), ("every", "<i4")])   # sfl_member_stop
+
+
+def member_stops(batch: int, tol, every=4) -> np.ndarray:
+    """The per-member stopping records of ``BatchSolver.step_n_until`` / ``poisson_solve_until``: `tol` and `every` each a
+    scalar or a sequence of length `batch`, as a C-contiguous structured array laid out as sfl_member_stop.  Pure numpy."""
+    out = np.empty(batch, MEMBER_STOP_DTYPE)
+    for name, value in (("tol", tol), ("every", every)):
+        a = np.asarray(value)
+        if a.ndim > 1 or (a.ndim == 1 and len(a) != batch):
+            raise ValueError(f"{name}: a scalar or a sequence of {batch} values (one per member), got shape {a.shape}")
+        out[name] = a
+    return out
+
+
 def device_count() -> int:
     n = C.c_int(0)
     rc = capi.lib().sfl_device_count(C.byref(n))
@@ -376,8 +391,50 @@ class BatchSolver:
         prm, ptr = self._member_params(dx)
         capi.check(self._lib.sfl_batch_poisson_solve_each(self._h, ptr))
 
+    def _member_stops(self, tol, every):
+        """`tol` a ready-made member_stops array, or the arguments of member_stops after `batch`."""
+        if tol is None:
+            raise ValueError("tol: a scalar, a sequence of one value per member or a member_stops array is required")
+        if isinstance(tol, np.ndarray) and tol.dtype.names:
+            if tol.dtype != MEMBER_STOP_DTYPE or tol.shape != (self.batch,):
+                raise ValueError(f"member stops: want {self.batch} records of {MEMBER_STOP_DTYPE}, got {tol.shape} of "
+                                 f"{tol.dtype}")
+            stops = np.ascontiguousarray(tol)
+        else:
+            stops = member_stops(self.batch, tol, every)
+        return stops, stops.ctypes.data_as(C.POINTER(capi.MemberStop))
+
+    def step_n_until(self, n, dt, dx=1.0, max_iters=10, omega=1.96, tol=None, every=4):
+        """step_n_each with every step's pressure solve stopped by each member's own rule (include/sfl.h
+        sfl_member_stop): in front of every `every`-th iteration the update norm is checked, and the solve ends at the
+        first check that finds it <= `tol` (or a NaN), at `max_iters` at the latest.  Arguments: scalars or sequences of
+        `batch` values; `dt` may be a ready-made :func:`member_params` array (its iters is the cap; dx, max_iters and omega
+        are then ignored) and `tol` (required) a ready-made :func:`member_stops` array (every is then ignored).  Leaves ``residual()`` and
+        ``iterations()``."""
+        prm, ptr = self._member_params(dt, dx, max_iters, omega)
+        stops, sptr = self._member_stops(tol, every)
+        capi.check(self._lib.sfl_batch_step_n_until(self._h, n, ptr, sptr))
+
+    def poisson_solve_until(self, dx=1.0, max_iters=10, omega=1.96, tol=None, every=4):
+        """poisson_solve_each stopped by each member's own rule (see :meth:`step_n_until`); `dx` may be a ready-made
+        :func:`member_params` array (its dt is ignored), `tol` a ready-made :func:`member_stops` array."""
+        if not (isinstance(dx, np.ndarray) and dx.dtype.names):
+            dx = member_params(self.batch, 0.0, dx, max_iters, omega)
+        prm, ptr = self._member_params(dx)
+        stops, sptr = self._member_stops(tol, every)
+        capi.check(self._lib.sfl_batch_poisson_solve_until(self._h, ptr, sptr))
+
+    def iterations(self, first: int = 0, count=None) -> np.ndarray:
+        """The iterations of members [first, first + count) as the last ``*_until`` call left them, int32[count, 2]: those
+        of the member's last solve, and their sum over the steps of that call.  Synchronous; SflError with ERR_STATE
+        when the last call that wrote the pressure was not an ``*_until`` call."""
+        count = self.batch - first if count is None else count
+        a = np.empty((max(count, 0), 2), np.int32)
+        capi.check(self._lib.sfl_batch_iterations(self._h, first, count, a.ctypes.data_as(C.POINTER(C.c_int32)), a.nbytes))
+        return a
+
     def residual(self, first: int = 0, count=None) -> np.ndarray:
-        """The update norm of members [first, first + count) as the last ``*_each`` call left it, float32[count]:
+        """The update norm of members [first, first + count) as the last ``*_each`` or ``*_until`` call left it, float32[count]:
         max |p_gs - p| over the member's cells on its final pressure, a NaN for a member that diverged to one
         (include/sfl.h sfl_batch_residual).  Synchronous; SflError with ERR_STATE when no ``*_each`` call wrote it."""
         count = self.batch - first if count is None else count

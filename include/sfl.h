@@ -484,7 +484,7 @@ SFL_API int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *
 /* pressure <- poisson_solve(divergence, params[m].dx, params[m].iters, params[m].omega) of every member (dt is
  * ignored).  Asynchronous.                                                                          */
 SFL_API int sfl_batch_poisson_solve_each(sfl_batch *b, const sfl_member_params *params);
-/* The update norm of members [first, first + count) as the last *_each call left it: one float per member.
+/* The update norm of members [first, first + count) as the last *_each or *_until call left it: one float per member.
  * Synchronous.  bytes must be count * 4.
  *   The update norm of a member with pressure p, divergence d and its own dx is  max over all cells c of
  * |g(c) - p(c)|, where g(c) = k(c) * (dx * d(c) - sum(c)) is the value a plain Gauss-Seidel update would put into the
@@ -494,9 +494,39 @@ SFL_API int sfl_batch_poisson_solve_each(sfl_batch *b, const sfl_member_params *
  * pressure sfl_batch_download hands out afterwards), both colours, no cell updated in between -- the distance of p
  * from the fixed point of its iteration, in units of p.  If any |g - p| is a NaN the report is a NaN: a diverged member
  * never reports a finite number.  The value does not depend on how the device reduces it: reproducible bit for bit.
- *   Every *_each call (n > 0) writes the report of every member.  sfl_batch_step_n (n > 0), sfl_batch_poisson_solve and
+ *   Every *_each and *_until call (n > 0) writes the report of every member.  sfl_batch_step_n (n > 0), sfl_batch_poisson_solve and
  * an sfl_batch_upload of the divergence or the pressure make it stale, and a fresh batch has none: SFL_ERR_STATE.  */
 SFL_API int sfl_batch_residual(sfl_batch *b, int first, int count, float *host, size_t bytes);
+/* --- the same, each member's pressure solve stopped at a tolerance ("how many iterations does this omega need?") --- */
+/* when ONE member's solve stops: the second record of a member in the *_until calls */
+typedef struct sfl_member_stop {
+    float tol;                             /* stop at the first check with update norm <= tol; < 0: never */
+    int32_t every;                         /* a check in front of every `every`-th iteration, >= 1 */
+} sfl_member_stop;                         /* 8 bytes */
+/* The rule.  Member m has params[m] = {dt, dx, omega, iters} and stops[m] = {tol, every}; iters is now the CAP K.  Let
+ * u_k be the update norm of the member's pressure after k iterations of its solve -- sfl_batch_residual's definition
+ * below, word for word: both colours, nothing updated in between -- with u_0 taken on p = 0.  The solve stops at the
+ * smallest k in {0, every, 2 * every, ...} with k < K for which u_k <= tol (IEEE float comparison) or u_k is a NaN (a
+ * diverged member ends at the first check that sees the NaN); otherwise at k = K.  The pressure left is that of exactly
+ * k iterations: bit for bit poisson_solve(divergence, dx, k, omega) of the reference, which has no such test of its
+ * own.  The update norm reported (sfl_batch_residual) is u_k of that final pressure, the iteration count reported
+ * (sfl_batch_iterations) is k.
+ *   A negative tol never stops a member, not even at a NaN: the call is then the *_each call, bit for bit, report
+ * included, and every count is the cap.  tol = +inf stops at k = 0: p = 0.  every < 1, a NaN tol or iters < 0 return
+ * SFL_ERR_INVALID (the message names the first such member) before anything is launched or the force queue is
+ * touched, as b, params or stops NULL and n < 0 do.  Members are started by cap, the largest first.          */
+/* sfl_batch_step_n_each with the solve of every step run by the rule (queued forces go into the first step; n == 0
+ * launches nothing and leaves the reports as they were).  Asynchronous; params and stops are arrays of `batch` records
+ * in HOST memory, read before the call returns.                                                       */
+SFL_API int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params, const sfl_member_stop *stops);
+/* pressure of every member <- its solve by the rule on its divergence (dt is ignored).  Asynchronous.  */
+SFL_API int sfl_batch_poisson_solve_until(sfl_batch *b, const sfl_member_params *params, const sfl_member_stop *stops);
+/* The iterations of members [first, first + count) as the last *_until call left them, two ints per member: those of
+ * the member's last solve (the one sfl_batch_residual reports on), then their sum over the n steps of that call (after
+ * sfl_batch_poisson_solve_until: the same number twice).  Synchronous.  bytes must be count * 8.  Valid only after an
+ * *_until call (n > 0): whatever makes sfl_batch_residual stale makes this stale, and so does an *_each call --
+ * SFL_ERR_STATE, and the message says to call sfl_batch_step_n_until or sfl_batch_poisson_solve_until.    */
+SFL_API int sfl_batch_iterations(sfl_batch *b, int first, int count, int32_t *host, size_t bytes);
 /* sfl_setup_sketch_fields for every member (the saturating definition included).  Asynchronous.    */
 SFL_API int sfl_batch_setup_sketch_fields(sfl_batch *b);
 /* sfl_render_rgb565 of one member's dye.  Synchronous.                                            */

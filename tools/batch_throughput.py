@@ -2,7 +2,7 @@
 """Throughput of batches (sfl_batch_*): B independent members of one small grid stepped by one launch per step.
 
     python tools/batch_throughput.py --size 61 81 --iters 20 [--batches 1 64 256 1024 4096] [--steps K] [--warmup W] [--check]
-                                     [--each uniform | spread | spread-sorted]
+                                     [--each uniform | spread | spread-sorted] [--until TOL [--every C] [--omega-mix]]
 
 Every member starts from the sketch's fields (setup_sketch_fields) with a drag of its own in the first warm-up step, so
 that no two members hold the same numbers.  Per B: W warm-up steps, then step_n(K) timed with a host clock around a
@@ -18,6 +18,12 @@ of step_n.  uniform = every member at --iters; spread = each member's iters draw
 and omega as always), in that natural order; spread-sorted = the same multiset of iters, members sorted by iters
 descending (does the order in which workgroups are handed out matter?).  Every line carries sum_iters, the SOR iterations
 of one batch step over all members, so that a line can be set against a uniform run of the same total work.
+--until TOL: step through step_n_until -- the members' iters (--iters, or --each's) become caps, and every member's solve
+stops at the first check, made in front of every C-th iteration (--every, default 4), whose update norm is <= TOL.  TOL =
+-1 stops nothing: the arithmetic of step_n_each with the checks still made, which prices a check.  --omega-mix gives each
+member an omega drawn from 1.0 .. 1.99 with a fixed seed instead of 1.96 (a parameter study whose members need different
+numbers of iterations).  Such a line carries iters_run_last_step and iters_run_timed: the iterations the members
+really ran in the last step and over the K timed steps, against sum_iters (one step at the caps).
 --check: after the timed run, members {0, 1, B/2, B - 1} against single contexts given the same start, drag, steps and
 that member's parameters -- velocity, divergence, pressure and dye bit for bit."""
 import argparse
@@ -35,6 +41,7 @@ sfl = importlib.import_module("esp32-fluid-simulation_amd")
 
 DT, DX, OMEGA = np.float32(1 / 30.0), 1.0, np.float32(1.96)
 SPREAD_ITERS, SPREAD_SEED = (5, 80), 20261016   # --each spread: iters uniform on [5, 80]
+MIX_OMEGAS = (1.0, 1.5, 1.8, 1.9, 1.96, 1.99)   # --omega-mix: drawn with SPREAD_SEED + 1
 BYTES_PER_CELL_STEP = 48
 HBM_BYTES_PER_S = 8e12
 REFERENCE_PROFILE = os.path.join(ROOT, "profiles", "r06_bench_c1_61x81.json")
@@ -102,8 +109,16 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare members with single contexts after the timed run")
     ap.add_argument("--each", choices=["uniform", "spread", "spread-sorted"], default=None,
                     help="step through step_n_each with these per-member iters (default: step_n)")
+    ap.add_argument("--until", type=float, default=None, metavar="TOL",
+                    help="step through step_n_until: iters are caps, a solve stops at update norm <= TOL (-1: never)")
+    ap.add_argument("--every", type=int, default=4, help="with --until: a check in front of every C-th iteration")
+    ap.add_argument("--omega-mix", action="store_true", help="with --until: each member's omega drawn from 1.0 .. 1.99")
     ap.add_argument("--label", default="", help="free text carried into every line (e.g. the build variant)")
     a = ap.parse_args()
+    if a.until is None and a.omega_mix:
+        ap.error("--omega-mix needs --until")
+    if a.until is not None and a.check:
+        ap.error("--check compares with contexts at fixed iterations: not with --until")
     dim_x, dim_y = a.size
     cells = dim_x * dim_y
     context_rate = time_context(dim_x, dim_y, a.iters, a.warmup, a.steps)
@@ -115,7 +130,14 @@ def main():
             drags = [drag_of(m, dim_x, dim_y) for m in range(batch)]
             b.queue_forces(np.arange(batch, dtype=np.int32), [d[0] for d in drags], [d[1] for d in drags])
             iters = member_iters(a.each, batch, a.iters)
-            if a.each:
+            if a.until is not None:
+                omega = OMEGA
+                if a.omega_mix:
+                    omega = np.random.default_rng(SPREAD_SEED + 1).choice(np.array(MIX_OMEGAS, np.float32), batch)
+                prm = sfl.member_params(batch, DT, DX, iters, omega)
+                stops = sfl.member_stops(batch, a.until, a.every)
+                step_n = lambda n: b.step_n_until(n, prm, tol=stops)
+            elif a.each:
                 prm = sfl.member_params(batch, DT, DX, iters, OMEGA)
                 step_n = lambda n: b.step_n_each(n, prm)
             else:
@@ -130,7 +152,7 @@ def main():
             gbs = BYTES_PER_CELL_STEP * cells * rate / 1e9
             line = {
                 "grid": [dim_x, dim_y], "iters": a.iters if a.each in (None, "uniform") else "%d..%d" % SPREAD_ITERS,
-                "call": "step_n_each" if a.each else "step_n", "each": a.each, "sum_iters": int(iters.sum()),
+                "call": "step_n_until" if a.until is not None else "step_n_each" if a.each else "step_n", "each": a.each, "sum_iters": int(iters.sum()),
                 "mean_iters": float(iters.mean()), "batch": batch, "steps": a.steps, "warmup": a.warmup,
                 "member_steps_per_s": rate, "us_per_batch_step": seconds / a.steps * 1e6,
                 "bytes_model_per_member_step": BYTES_PER_CELL_STEP * cells, "gb_per_s": gbs,
@@ -140,6 +162,12 @@ def main():
                 "x_reference_core": rate * ref_ms / 1e3 if ref_ms and len(set(iters)) == 1 else None,
                 "reference_step_ms": ref_ms, "reference_source": "profiles/r06_bench_c1_61x81.json cpu_baseline" if ref_ms else None,
             }
+            if a.until is not None:
+                ran = b.iterations().astype(np.int64)
+                line.update({"until": a.until, "every": a.every, "omega_mix": a.omega_mix,
+                             "iters_run_last_step": int(ran[:, 0].sum()), "iters_run_timed": int(ran[:, 1].sum())})
+                for key in ("x_one_context", "x_reference_core"):   # (one context at --iters is no yardstick for it)
+                    line[key] = None
             if a.label:
                 line["label"] = a.label
             if a.check:
