@@ -131,6 +131,9 @@ SIGNATURES = {
     "sfl_calculate_divergence": (_i, [_ctx, _f]),
     "sfl_poisson_solve": (_i, [_ctx, _f, _i, _f]),
     "sfl_subtract_gradient": (_i, [_ctx, _f]),
+    "sfl_residual": (_i, [_ctx, _f, _pf]),
+    "sfl_poisson_continue": (_i, [_ctx, _f, _i, _f]),
+    "sfl_poisson_solve_until": (_i, [_ctx, _f, _i, _f, _f, _i, C.POINTER(C.c_int32), _pf]),
     "sfl_step": (_i, [_ctx, _f, _f, _i, _f]),
     "sfl_step_n": (_i, [_ctx, _i, _f, _f, _i, _f]),
     "sfl_queue_forces": (_i, [_ctx, _pi, _pf, _i]),

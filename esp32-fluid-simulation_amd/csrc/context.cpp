@@ -292,12 +292,16 @@ int sfl_create_slab(sfl_context **out, int device, int dim_x, int dim_y, int ran
     HIP_TRY(hipEventCreate(&c->ev_start));
     HIP_TRY(hipEventCreate(&c->ev_stop));
     void *flag = nullptr;
-    HIP_TRY(hipMalloc(&flag, (4 + kCollectiveWords) * sizeof(int)));
-    HIP_TRY(hipMemset(flag, 0, (4 + kCollectiveWords) * sizeof(int)));
+    HIP_TRY(hipMalloc(&flag, (4 + kCollectiveWords + kNormWords) * sizeof(int)));
+    HIP_TRY(hipMemset(flag, 0, (4 + kCollectiveWords + kNormWords) * sizeof(int)));
     c->halo_flag = static_cast<int *>(flag);
     c->d_arrival = c->halo_flag + 1;
     c->d_done = c->halo_flag + 3;
     c->d_collective = c->halo_flag + 4;
+    c->d_norm = reinterpret_cast<unsigned *>(c->halo_flag + 4 + kCollectiveWords);
+    void *pinned = nullptr;
+    HIP_TRY(hipHostMalloc(&pinned, kNormWords * sizeof(unsigned), hipHostMallocDefault));
+    c->h_norm = static_cast<unsigned *>(pinned);
     *out = c.release();
     return SFL_OK;
 }
@@ -342,6 +346,7 @@ int sfl_destroy(sfl_context *c)
     }
     if (c->d_report) (void)hipFree(c->d_report);
     if (c->h_report) (void)hipHostFree(c->h_report);
+    if (c->h_norm) (void)hipHostFree(c->h_norm);
     if (c->ev_report) (void)hipEventDestroy(c->ev_report);
     if (c->ev_color_halo) (void)hipEventDestroy(c->ev_color_halo);
     if (c->ev_vel_final) (void)hipEventDestroy(c->ev_vel_final);

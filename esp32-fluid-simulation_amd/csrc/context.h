@@ -6,6 +6,7 @@
 //                     protocol around them, communicator attach / option check
 //   sor_executor.cpp  poisson_solve: walks slab_plan.h programs (in line, early exchanges behind events, exchanges in
 //                     time counted on the device)
+//   solve_until.cpp   the update norm of a context, a continued solve, a solve stopped at a tolerance
 //   operators.cpp     advection, divergence, projection, forces, setup / render
 //   slab_step.cpp     sfl_step / sfl_step_n, the automatic advection halo of a slab's step
 //   host_dropin.cpp   the host-pointer drop-ins (sfl_host_*) and their per-thread context
@@ -80,6 +81,7 @@ class Group;
 // count, fuse depth, tail and schedule -- runs on one of them between two events (every depth gives the same bits), and the
 // fastest is kept for that kind from then on (another depth has to beat the legacy one by 1.5 %).
 constexpr int kCollectiveWords = 8;   // sfl_context::d_collective
+constexpr int kNormWords = 2;         // sfl_context::d_norm / h_norm
 
 struct HaloTuner {
     struct Kind {
@@ -207,6 +209,9 @@ struct sfl_context {
                                    //     with the context, so that no rank can drop out of a collective over a failed allocation
     int *d_done = nullptr;         // [3] sender tiles finished so far (kernels.h HaloWait::done): what the exchange stream waits
     int done_target = 0;           //     for before a halo message leaves; done_target = the count the launches queued so far reach
+    unsigned *d_norm = nullptr;    // [4 + kCollectiveWords, + kNormWords) what a norm launch or the small-grid until kernel leaves: the bits
+                                   //     of an update norm, then an iteration count (sfl_residual, sfl_poisson_solve_until)
+    unsigned *h_norm = nullptr;    // ... and their pinned host copy: allocated with the context, nothing is allocated per call
     bool wait_error_seen = false;  // word [2] was found raised (download, a step's report): every call fails until sfl_synchronize
                                    // has reported and cleared it
 
@@ -319,7 +324,9 @@ int download_raw(sfl_context *c, const void *dev, void *host, size_t elem_bytes)
 int check_wait_error(sfl_context *c);
 
 // ---- sor_executor.cpp ----
-int run_poisson(sfl_context *ctx, float dx, int iters, float omega);
+// warm: `iters` MORE iterations on the pressure the context holds instead of a solve from zero (whole-domain contexts
+// on the general kernels)
+int run_poisson(sfl_context *ctx, float dx, int iters, float omega, bool warm = false);
 SorParams sor_params(const sfl_context *c, float dx, float omega);
 // one workgroup, fields in LDS (small_grid.hip): may this context take that path?
 bool small_grid(const sfl_context *c);

@@ -242,6 +242,25 @@ __device__ __forceinline__ UntilResult sor_until_in_lds(float *p, const float *d
     return r;
 }
 
+// ---- `iters` MORE iterations on the pressure p holds (include/sfl.h sfl_poisson_continue) -------------------------------
+// sor_in_lds without its zero fill: the same ownership of cells, the same iteration (sor_iteration), the thread's
+// registers started from the pressure in LDS instead of zero -- own is the bit pattern p[c] holds, which is what the
+// iterations before left there.  p and d are complete in LDS behind a barrier of the caller's; a cell is read here and
+// written later by its owner alone.
+template <int kThreads>
+__device__ __forceinline__ void sor_warm_in_lds(float *p, const float *d, int dim_x, int dim_y, int iters, SorParams prm)
+{
+    constexpr int kCellsPerColour = SorCells<kThreads>::kCellsPerColour;
+    SorCells<kThreads> t;
+    sor_cells_init(t, d, dim_x, dim_y, prm.dx);
+#pragma unroll
+    for (int colour = 0; colour < 2; ++colour)
+#pragma unroll
+        for (int k = 0; k < kCellsPerColour; ++k)
+            if (t.cm[colour][k] >> 20) t.own[colour][k] = p[t.cm[colour][k] & 0xffff];
+    for (int it = 0; it < iters; ++it) sor_iteration(t, p, dim_x, prm);
+}
+
 // ---- poisson_solve (poisson.cpp:114-125) alone: d_in -> p_out of ONE grid ------------------------
 template <int kThreads>
 __device__ __forceinline__ void solve_in_lds(char *lds_raw, float *p_out, const float *d_in,

@@ -438,9 +438,15 @@ int run_poisson_overlapped(sfl_context *ctx, const std::vector<sfl_context *> &p
     return rc;
 }
 
-int run_poisson(sfl_context *ctx, float dx, int iters, float omega)
+// warm (whole-domain contexts on the general kernels; solve_until.cpp: sfl_poisson_continue, the segments of run_poisson_until): the program of a solve of `iters`
+// iterations with its FIRST launch reading the pressure the context holds instead of taking it as zero, and without the
+// baseline kernel's zero fill.  Everything else is the same walk, so the result does not depend on the fuse depth either.
+int run_poisson(sfl_context *ctx, float dx, int iters, float omega, bool warm)
 {
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
+    if (warm && ctx->nranks > 1)   // (a slab's plan sends no halo for its first superstep: p is zero there)
+        return fail(SFL_ERR_STATE, "a solve continues from the pressure it holds on whole-domain contexts only (slab %d/%d)",
+                    ctx->rank, ctx->nranks);
 
     std::vector<sfl_context *> peers = peers_of(ctx);
     SFL_TRY(resolve_schedule(ctx));
@@ -466,9 +472,21 @@ int run_poisson(sfl_context *ctx, float dx, int iters, float omega)
         c->p_ghost_valid = 0;
         c->last_fuse = kernel == 1 ? 1 : fuse;
     }
+    if (warm)
+        for (std::vector<sfl_plan_step> &prog : progs) {
+            if (!prog.empty() && prog.front().kind == SFL_STEP_ZERO) prog.erase(prog.begin());
+            for (sfl_plan_step &st : prog)
+                if (st.kind == SFL_STEP_SOR) {
+                    st.from_zero = 0;
+                    break;
+                }
+        }
     const sfl::SorParams prm = sor_params(ctx, dx, omega);
+    if (warm && iters == 0) return SFL_OK;   // the pressure stays as it is
     if (small_grid(ctx)) {  // one workgroup, p and d in LDS, every iteration in one launch
         SFL_TRY(use_device(ctx));
+        if (warm)   // (solve_until.cpp launches the one-workgroup kernel that starts from a pressure itself)
+            return fail(SFL_ERR_STATE, "the warm walk is the general kernels': a small grid continues in its own launch");
         HIP_TRY(sfl::launch_small_solve(ctx->stream, ctx->p, ctx->div, ctx->dim_x, ctx->gdim_y, iters, prm));
         ctx->last_launches = 1;
         ctx->last_fuse = 2 * iters;

@@ -232,6 +232,34 @@ class Solver:
     def poisson_solve(self, dx=1.0, iters=10, omega=1.96):
         capi.check(self._lib.sfl_poisson_solve(self._h, dx, iters, omega))
 
+    def residual(self, dx=1.0) -> np.float32:
+        """The update norm of the pressure and divergence the context holds right now: max |p_gs - p| over all cells, a
+        NaN when any cell's is one (include/sfl.h sfl_residual; the definition of BatchSolver.residual).  One pass over
+        p and d; synchronous.  Whole-domain contexts only."""
+        u = C.c_float()
+        capi.check(self._lib.sfl_residual(self._h, dx, C.byref(u)))
+        return np.float32(u.value)
+
+    def poisson_continue(self, dx=1.0, iters=10, omega=1.96):
+        """`iters` more red-black iterations on the pressure the context holds (sfl_poisson_continue): after
+        poisson_solve(dx, a, omega) it leaves poisson_solve(dx, a + iters, omega), bit for bit; after an upload of the
+        pressure it iterates from that field.  Whole-domain contexts only."""
+        capi.check(self._lib.sfl_poisson_continue(self._h, dx, iters, omega))
+
+    def poisson_solve_until(self, dx=1.0, max_iters=10, omega=1.96, tol=None, every=8):
+        """poisson_solve stopped at a tolerance (sfl_poisson_solve_until, the rule of BatchSolver.poisson_solve_until): in
+        front of every `every`-th iteration the update norm is checked, and the solve ends at the first check that finds
+        it <= `tol` (or a NaN), at `max_iters` at the latest; a negative `tol` never stops.  A check is one pass over p
+        and d and a round trip to the host -- at 8192 x 8192 what about six iterations cost -- so choose `every` with
+        that in mind (include/sfl.h has the measurements).  Returns (iterations,
+        residual): the iterations run and the update norm of the pressure they left.  Synchronous.  Whole-domain
+        contexts only."""
+        if tol is None:
+            raise ValueError("tol: a tolerance is required (a negative one never stops the solve)")
+        k, u = C.c_int32(), C.c_float()
+        capi.check(self._lib.sfl_poisson_solve_until(self._h, dx, max_iters, omega, tol, every, C.byref(k), C.byref(u)))
+        return k.value, np.float32(u.value)
+
     def subtract_gradient(self, dx=1.0):
         capi.check(self._lib.sfl_subtract_gradient(self._h, dx))
 

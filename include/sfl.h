@@ -374,6 +374,40 @@ SFL_API int sfl_calculate_divergence(sfl_context *ctx, float dx);
 SFL_API int sfl_poisson_solve(sfl_context *ctx, float dx, int iters, float omega);
 /* velocity <- subtract_gradient(velocity, pressure, dx)     ino:276     */
 SFL_API int sfl_subtract_gradient(sfl_context *ctx, float dx);
+/* --- how far the pressure is from converged, and solves that go on from it ("how many iterations does this omega
+ *     need?" on a context of any size).  WHOLE-DOMAIN contexts only: a slab gets SFL_ERR_STATE.  The definitions are
+ *     the batches' (group 4: sfl_batch_residual, sfl_member_stop), word for word.                                    */
+/* Update norm of the context's CURRENT pressure and divergence: *norm = max over all cells c of |p_gs(c) - p(c)|,
+ * where p_gs(c) = k(c) * (dx * d(c) - sum(c)) is the value a plain Gauss-Seidel update would put into the cell: sum(c) =
+ * the neighbours that exist, added in the order W, E, S (row j - 1), N (row j + 1), k = -1/2, -1/3, -1/4 for 2, 3, 4
+ * neighbours; float32, every operation rounded on its own; both colours read from the same p, nothing is updated.  If
+ * any |p_gs - p| is a NaN the result is a NaN.  The value does not depend on how the device reduces it: reproducible
+ * bit for bit.  Cost: ONE streaming pass over p and d (8 bytes per cell) and one round trip to the host: on an MI355X
+ * 0.13 ms at 8192 x 8192, the time of about six iterations of the solve there (profiles/context_until.txt).  ctx or
+ * norm NULL return SFL_ERR_INVALID.  Synchronous.                                                                     */
+SFL_API int sfl_residual(sfl_context *ctx, float dx, float *norm);
+/* `iters` MORE red-black iterations starting from the pressure the context holds, not from zero.  After
+ * sfl_poisson_solve(dx, a, omega), sfl_poisson_continue(dx, b, omega) leaves, bit for bit, poisson_solve(divergence, dx,
+ * a + b, omega); after an sfl_upload of the pressure it iterates from that field.  iters == 0 does nothing; iters < 0
+ * returns SFL_ERR_INVALID.  Asynchronous.                                                                            */
+SFL_API int sfl_poisson_continue(sfl_context *ctx, float dx, int iters, float omega);
+/* pressure <- the solve from zero stopped by the rule of sfl_member_stop.  `iters` is the cap K.  With u_k the update
+ * norm (sfl_residual) of the pressure after k iterations, u_0 taken on p = 0, the solve stops at the smallest k in {0,
+ * every, 2 * every, ...} with k < K for which u_k <= tol (IEEE float comparison) or u_k is a NaN, else at K.  The
+ * pressure left is, bit for bit, poisson_solve(divergence, dx, k, omega).  *iterations = k, *norm = u_k of that pressure
+ * (always evaluated, also at the cap); either out pointer may be NULL.  tol = +inf stops at k = 0: p = 0.  tol < 0 never
+ * stops and makes no checks: the call is sfl_poisson_solve plus one final norm.  iters < 0, every < 1 or a NaN tol
+ * return SFL_ERR_INVALID before any GPU work.  sfl_last_solve_info afterwards counts the solve's launches, not the checks'.
+ *   Choosing `every`: a check costs one pass over p and d and one round trip to the host.  Measured on an MI355X
+ * (profiles/context_until.txt): 0.13 ms at 8192 x 8192, where an iteration of the fused solve takes 0.023 ms -- a check
+ * costs what about six iterations cost (the norm kernel alone: 0.58 of a 16-pass launch); at 2048 x 2048 0.03 ms,
+ * nearly nine iterations.  Over a solve of 80 iterations the checks add 81 % at every = 8, 45 % at 16 and 24 % at 40.
+ * A large `every` costs at most every - 1 iterations past the first k that would have passed, a small one costs a
+ * check per `every` iterations: choose every >= 16 for production (32 .. 40 keeps the checks near a fifth of the
+ * solve's time), small values for studies of the convergence itself.  Grids of at most 6144 cells run the whole rule inside
+ * one launch, where a check is cheap (profiles/batch_until.txt).  Synchronous.                                        */
+SFL_API int sfl_poisson_solve_until(sfl_context *ctx, float dx, int iters, float omega, float tol, int every,
+                                    int32_t *iterations, float *norm);
 /* next_p <- advect(p, velocity, dt, no_slip) for a field of the CALLER's, resident on the context's device
  * (advect.h:74-85; element = `channels` x `kind` as for sfl_host_advect_channels): further quantities carried by
  * the flow -- a temperature, a second dye -- without a round trip through the host.  Whole-domain contexts only;
@@ -426,7 +460,7 @@ SFL_API int sfl_synchronize(sfl_context *ctx);
  * until the stop event has completed).                                                     */
 SFL_API int sfl_timer_start(sfl_context *ctx);
 SFL_API int sfl_timer_stop(sfl_context *ctx, float *elapsed_ms);
-/* Launch statistics of the last sfl_poisson_solve on this context: kernel launches, halo
+/* Launch statistics of the last sfl_poisson_solve (sfl_poisson_continue, sfl_poisson_solve_until) on this context: kernel launches, halo
  * exchanges, half-sweeps fused per launch.  Any out pointer may be NULL.                    */
 SFL_API int sfl_last_solve_info(sfl_context *ctx, int *launches, int *exchanges, int *fuse);
 
