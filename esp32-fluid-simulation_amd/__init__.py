@@ -15,8 +15,9 @@ call that needs the library fails loudly if it is missing -- there is no CPU fal
 from . import _capi as capi
 from ._capi import LIB_PATH, SflError, build_library
 from .solver import (BatchSolver, HostPath, Solver, comm_unique_id, device_count, device_info, plan_poisson,
-                     member_params, member_stops, slab_rows, sor_pass_plan, stdout_to_stderr)
+                     member_params, member_stops, slab_rows, sor_pass_plan, stdout_to_stderr, FLOW_STATS_DTYPE,
+                     FLOW_STATS_STRIP_COLS, FLOW_STATS_CHUNK_ROWS)
 
 __all__ = ["capi", "LIB_PATH", "SflError", "build_library", "BatchSolver", "HostPath", "Solver",
            "comm_unique_id", "device_count", "device_info", "member_params", "member_stops", "plan_poisson", "slab_rows",
-           "sor_pass_plan", "stdout_to_stderr"]
+           "sor_pass_plan", "stdout_to_stderr", "FLOW_STATS_DTYPE", "FLOW_STATS_STRIP_COLS", "FLOW_STATS_CHUNK_ROWS"]

@@ -28,6 +28,7 @@ OPT_LAST_HALO = 21
 OPT_SOR_FOLD = 22
 CHANNEL_F32, CHANNEL_UQ32 = 0, 1
 STEP_EXCHANGE, STEP_SOR, STEP_ZERO = 1, 2, 3
+STATS_VELOCITY, STATS_DYE = 1, 2
 UNIQUE_ID_BYTES = 128
 
 
@@ -49,6 +50,12 @@ class MemberParams(C.Structure):
 class MemberStop(C.Structure):
     """sfl_member_stop: when ONE batch member's pressure solve stops (sfl_batch_*_until), 8 bytes."""
     _fields_ = [("tol", C.c_float), ("every", C.c_int32)]
+
+
+class FlowStats(C.Structure):
+    """struct sfl_flow_stats: what sfl_flow_stats and sfl_batch_flow_stats[_each] report, 40 bytes."""
+    _fields_ = [("max_abs_vx", C.c_float), ("max_abs_vy", C.c_float), ("max_abs_div", C.c_float), ("what", C.c_uint32),
+                ("dye_sum", C.c_uint64 * 3)]
 
 
 class SflError(RuntimeError):
@@ -134,6 +141,7 @@ SIGNATURES = {
     "sfl_residual": (_i, [_ctx, _f, _pf]),
     "sfl_poisson_continue": (_i, [_ctx, _f, _i, _f]),
     "sfl_poisson_solve_until": (_i, [_ctx, _f, _i, _f, _f, _i, C.POINTER(C.c_int32), _pf]),
+    "sfl_flow_stats": (_i, [_ctx, _i, _f, C.POINTER(FlowStats)]),
     "sfl_step": (_i, [_ctx, _f, _f, _i, _f]),
     "sfl_step_n": (_i, [_ctx, _i, _f, _f, _i, _f]),
     "sfl_queue_forces": (_i, [_ctx, _pi, _pf, _i]),
@@ -159,6 +167,8 @@ SIGNATURES = {
     "sfl_batch_step_n_until": (_i, [_ctx, _i, C.POINTER(MemberParams), C.POINTER(MemberStop)]),
     "sfl_batch_poisson_solve_until": (_i, [_ctx, C.POINTER(MemberParams), C.POINTER(MemberStop)]),
     "sfl_batch_iterations": (_i, [_ctx, _i, _i, C.POINTER(C.c_int32), _sz]),
+    "sfl_batch_flow_stats": (_i, [_ctx, _i, _f, _i, _i, C.POINTER(FlowStats), _sz]),
+    "sfl_batch_flow_stats_each": (_i, [_ctx, _i, C.POINTER(MemberParams), _i, _i, C.POINTER(FlowStats), _sz]),
     "sfl_batch_setup_sketch_fields": (_i, [_ctx]),
     "sfl_batch_render_rgb565": (_i, [_ctx, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),

@@ -5,6 +5,7 @@
 #include "batch.h"
 
 #include "context.h"
+#include "stats_kernels.h"
 
 #include <cmath>
 
@@ -45,6 +46,9 @@ struct sfl_batch {
     sfl::BatchStop *d_stops = nullptr;
     int *d_counts = nullptr;
     bool counts_valid = false;
+    // flow statistics (sfl_batch_flow_stats[_each]): one record per member that the two passes leave, behind them one
+    // 1 / (2 dx) per member; the same in pinned memory.  Allocated at the first call, nothing per call
+    sfl::FlowStatsRecord *d_stats = nullptr, *h_stats = nullptr;
     // dye visualiser's device image, kept between frames
     uint16_t *d_image = nullptr;
     size_t d_image_bytes = 0;
@@ -57,8 +61,10 @@ void release(sfl_batch *b)
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (void *m : {(void *)b->vel, (void *)b->vel_tmp, (void *)b->col, (void *)b->col_tmp, (void *)b->div, (void *)b->p,
-                    b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_counts, (void *)b->d_image})
+                    b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_counts, (void *)b->d_image,
+                    (void *)b->d_stats})
         if (m) (void)hipFree(m);
+    if (b->h_stats) (void)hipHostFree(b->h_stats);
     for (sfl_batch::Stage *pair : {b->stage, b->member_stage})
         for (int k = 0; k < 2; ++k) {
             if (pair[k].host) (void)hipHostFree(pair[k].host);
@@ -275,6 +281,40 @@ int stage_members(sfl_batch *b, const sfl_member_params *params, const sfl_membe
     HIP_TRY(hipMemcpyAsync(b->d_members, st.host, bytes, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipEventRecord(st.copied, b->stream));
     st.pending = true;
+    return SFL_OK;
+}
+
+// sfl_batch_flow_stats and its _each form: dx for every member, or params[m].dx (each).  The checks that need no batch come
+// first, so that each of them answers with its own message on a box without a GPU too.
+int flow_stats(sfl_batch *b, int what, float dx, bool each, const sfl_member_params *params, int first, int count,
+               struct sfl_flow_stats *host, size_t bytes)
+{
+    if (what == 0 || (what & ~(SFL_STATS_VELOCITY | SFL_STATS_DYE)))
+        return fail(SFL_ERR_INVALID, "what must be SFL_STATS_VELOCITY (1), SFL_STATS_DYE (2) or both (got %d)", what);
+    if (count < 0 || bytes != (size_t)count * sizeof(struct sfl_flow_stats))
+        return fail(SFL_ERR_INVALID, "the flow statistics of %d members are %zu bytes, got %zu", count,
+                    (size_t)std::max(count, 0) * sizeof(struct sfl_flow_stats), bytes);
+    if (!b || !host || (each && !params)) return fail(SFL_ERR_INVALID, "NULL argument");
+    if (first < 0 || (int64_t)first + count > b->batch)
+        return fail(SFL_ERR_INVALID, "members [%d, %d + %d) are not inside the batch's [0, %d)", first, first, count, b->batch);
+    if (count == 0) return SFL_OK;
+    SFL_TRY(use_device(b));
+    const size_t rec_bytes = sizeof(sfl::FlowStatsRecord) * (size_t)b->batch, all_bytes = rec_bytes + sizeof(float) * (size_t)b->batch;
+    if (!b->d_stats) HIP_TRY(hipMalloc((void **)&b->d_stats, all_bytes));
+    if (!b->h_stats) HIP_TRY(hipHostMalloc((void **)&b->h_stats, all_bytes, hipHostMallocDefault));
+    // (the call is synchronous: the pinned block is never in flight when the next call writes it)
+    const float *d_scale = nullptr;
+    if (each && (what & SFL_STATS_VELOCITY)) {
+        float *scale = reinterpret_cast<float *>(b->h_stats + b->batch);
+        for (int m = 0; m < b->batch; ++m) scale[m] = two_dx_inv(params[m].dx);
+        HIP_TRY(hipMemcpyAsync(b->d_stats + b->batch, scale, sizeof(float) * (size_t)b->batch, hipMemcpyHostToDevice, b->stream));
+        d_scale = reinterpret_cast<const float *>(b->d_stats + b->batch);
+    }
+    HIP_TRY(sfl::launch_flow_stats(b->stream, b->d_stats, what, b->vel, b->col, b->dim_x, b->dim_y, b->batch, two_dx_inv(dx), d_scale));
+    HIP_TRY(hipMemcpyAsync(b->h_stats + first, b->d_stats + first, (size_t)count * sizeof(struct sfl_flow_stats), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    memcpy(host, b->h_stats + first, (size_t)count * sizeof(struct sfl_flow_stats));
+    for (int k = 0; k < count; ++k) host[k].what = (uint32_t)what;
     return SFL_OK;
 }
 
@@ -537,6 +577,17 @@ int sfl_batch_iterations(sfl_batch *b, int first, int count, int32_t *host, size
     HIP_TRY(hipMemcpyAsync(host, b->d_counts + 2 * (size_t)first, bytes, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return SFL_OK;
+}
+
+int sfl_batch_flow_stats(sfl_batch *b, int what, float dx, int first, int count, struct sfl_flow_stats *host, size_t bytes)
+{
+    return flow_stats(b, what, dx, false, nullptr, first, count, host, bytes);
+}
+
+int sfl_batch_flow_stats_each(sfl_batch *b, int what, const sfl_member_params *params, int first, int count,
+                              struct sfl_flow_stats *host, size_t bytes)
+{
+    return flow_stats(b, what, 1.0f, true, params, first, count, host, bytes);
 }
 
 // Member 0 as sfl_setup_sketch_fields makes it, then copied to the others by doubling: 1 -> 2 -> 4 ... members, a

@@ -347,6 +347,8 @@ int sfl_destroy(sfl_context *c)
     if (c->d_report) (void)hipFree(c->d_report);
     if (c->h_report) (void)hipHostFree(c->h_report);
     if (c->h_norm) (void)hipHostFree(c->h_norm);
+    if (c->d_stats) (void)hipFree(c->d_stats);
+    if (c->h_stats) (void)hipHostFree(c->h_stats);
     if (c->ev_report) (void)hipEventDestroy(c->ev_report);
     if (c->ev_color_halo) (void)hipEventDestroy(c->ev_color_halo);
     if (c->ev_vel_final) (void)hipEventDestroy(c->ev_vel_final);

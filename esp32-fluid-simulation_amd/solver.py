@@ -58,6 +58,22 @@ def member_stops(batch: int, tol, every=4) -> np.ndarray:
     return out
 
 
+# struct sfl_flow_stats: what Solver.flow_stats returns (one record) and BatchSolver.flow_stats (one per member)
+FLOW_STATS_DTYPE = np.dtype([("max_abs_vx", "<f4"), ("max_abs_vy", "<f4"), ("max_abs_div", "<f4"), ("what", "<u4"),
+                             ("dye_sum", "<u8", (3,))])
+# The tiles of the velocity pass of flow_stats (csrc/stats_kernels.h kStatsStripCols, kStatsChunkRows): a wave owns a strip
+# of 128 columns and a chunk of 8 rows (16 or 32 on grids that fill the chip several times over).  Stated for the tests,
+# which put extreme values on both sides of the boundaries; no result depends on them.
+FLOW_STATS_STRIP_COLS, FLOW_STATS_CHUNK_ROWS = 128, 8
+
+
+def _stats_what(velocity, dye) -> int:
+    what = (capi.STATS_VELOCITY if velocity else 0) | (capi.STATS_DYE if dye else 0)
+    if not what:
+        raise ValueError("flow_stats: ask for the velocity, the dye or both")
+    return what
+
+
 def device_count() -> int:
     n = C.c_int(0)
     rc = capi.lib().sfl_device_count(C.byref(n))
@@ -262,6 +278,17 @@ class Solver:
 
     def subtract_gradient(self, dx=1.0):
         capi.check(self._lib.sfl_subtract_gradient(self._h, dx))
+
+    def flow_stats(self, dx=1.0, velocity=True, dye=True):
+        """What the flow the context holds looks like, without a download (sfl_flow_stats): one record of
+        FLOW_STATS_DTYPE.  With `velocity`: max_abs_vx, max_abs_vy = max |v.x|, max |v.y| -- times dt the longest
+        back-trace of the next advection, bit for bit -- and max_abs_div = max |calculate_divergence(v, dx)|, the figure
+        of merit of the projection; a NaN anywhere makes the figure a NaN.  With `dye`: dye_sum = the exact uint64 sum
+        of every channel's raw values.  Bit for bit what numpy gives on the downloaded fields; one streaming pass per
+        part asked for; reads only; synchronous.  Whole-domain contexts only."""
+        what, out = _stats_what(velocity, dye), np.zeros((), FLOW_STATS_DTYPE)
+        capi.check(self._lib.sfl_flow_stats(self._h, what, dx, out.ctypes.data_as(C.POINTER(capi.FlowStats))))
+        return out[()]
 
     def step(self, dt, dx=1.0, iters=10, omega=1.96):
         capi.check(self._lib.sfl_step(self._h, dt, dx, iters, omega))
@@ -469,6 +496,23 @@ class BatchSolver:
         a = np.empty(max(count, 0), np.float32)
         capi.check(self._lib.sfl_batch_residual(self._h, first, count, _fp(a), a.nbytes))
         return a
+
+    def flow_stats(self, dx=1.0, first: int = 0, count=None, velocity=True, dye=True) -> np.ndarray:
+        """The flow statistics of members [first, first + count) (sfl_batch_flow_stats[_each]; the definitions of
+        :meth:`Solver.flow_stats`): a FLOW_STATS_DTYPE array of `count` records.  `dx` a scalar, or a sequence of `batch`
+        values: member m's divergence is then scaled by its own.  A member reports what a context holding the same fields
+        reports.  One launch per part asked for, whatever the range; reads only (``residual()`` and ``iterations()``
+        stay valid); synchronous."""
+        what = _stats_what(velocity, dye)
+        count = self.batch - first if count is None else count
+        out = np.zeros(max(count, 0), FLOW_STATS_DTYPE)
+        ptr = out.ctypes.data_as(C.POINTER(capi.FlowStats))
+        if np.ndim(dx) == 0:
+            capi.check(self._lib.sfl_batch_flow_stats(self._h, what, dx, first, count, ptr, out.nbytes))
+        else:
+            prm, pptr = self._member_params(0.0, dx, 0, 0.0)
+            capi.check(self._lib.sfl_batch_flow_stats_each(self._h, what, pptr, first, count, ptr, out.nbytes))
+        return out
 
     def setup_sketch_fields(self):
         """Every member: velocity = 0, dye = the sketch's blurred three-sector pattern (setup(), ino:196-241)."""

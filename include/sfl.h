@@ -408,6 +408,45 @@ SFL_API int sfl_poisson_continue(sfl_context *ctx, float dx, int iters, float om
  * one launch, where a check is cheap (profiles/batch_until.txt).  Synchronous.                                        */
 SFL_API int sfl_poisson_solve_until(sfl_context *ctx, float dx, int iters, float omega, float tol, int every,
                                     int32_t *iterations, float *norm);
+/* --- what the FLOW looks like, without a download (20 bytes per cell): how fast it is, how divergence-free the velocity
+ *     is, how much dye there is.  WHOLE-DOMAIN contexts only: a slab gets SFL_ERR_STATE.  The batches' calls (group 4:
+ *     sfl_batch_flow_stats) report the same record per member, by the same definitions.                              */
+#define SFL_STATS_VELOCITY 1   /* max_abs_vx, max_abs_vy, max_abs_div : one pass over v, 8 B per cell  */
+#define SFL_STATS_DYE      2   /* dye_sum[3]                          : one pass over the dye, 12 B per cell */
+struct sfl_flow_stats {
+    float    max_abs_vx, max_abs_vy;   /* max over all cells of |v.x|, |v.y|                                   */
+    float    max_abs_div;              /* max over all cells of |calculate_divergence(v, dx)(c)|               */
+    uint32_t what;                     /* the SFL_STATS_* bits this record holds; the other members are 0      */
+    uint64_t dye_sum[3];               /* sum over all cells of the raw UQ32 value of each channel, exact      */
+};                                     /* 40 bytes: offsets 0, 4, 8, 12, 16.  Written `struct sfl_flow_stats`: the
+                                          call below has the name, and C keeps only struct tags apart from functions */
+/* Statistics of the context's CURRENT velocity and dye: the fields sfl_download would hand out at this moment -- after
+ * sfl_step_n with its fused step boundaries, after the one-workgroup path, after an sfl_upload; a fresh context reports
+ * zeros.  The call READS ONLY: no field changes (the context's divergence field included: nothing is written to it),
+ * nothing counts as written from outside, no ghost row or back-trace reach the context knew is forgotten.
+ *   max_abs_div: the divergence is calculate_divergence(v, dx) of the reference, operation for operation
+ * (finitediff.cpp:9-39): inside, (-v.x(i-1, j) + v.x(i+1, j)) + (-v.y(i, j-1) + v.y(i, j+1)) (div_expr_fast, :29); on the
+ * perimeter the terms added one by one to 0.0f in the order W, E, S, N with a missing neighbour's velocity taken as minus
+ * the cell's own (div_expr_safe, :15-20); both times 1.0f / (2.0f * dx) (:36); float32, every operation rounded on its
+ * own.  Taken on the velocity a step leaves -- projected by subtract_gradient -- it is the physical figure of merit of
+ * iters, omega and tol; the update norm (sfl_residual) is only a proxy for it.
+ *   The three maxima are taken as the update norm's is: the maximum over the bit patterns of |x| as unsigned integers.
+ * Finite values and +inf order as floats do; any NaN wins, so a diverged field never reports a finite number (which NaN
+ * is reported is not defined); |-0.0f| reports +0.0f.
+ *   dye_sum: 64-bit integer sums of the raw uint32 values, the whole UQ32 range counting (values at and above 2^31
+ * included), exact for every input: 2^28 cells per context x 2^32 per value stay below 2^60.  Semi-Lagrangian advection
+ * does not conserve the dye; dye_sum against the step number shows how much it loses.
+ *   None of the figures depends on how the device tiles or reduces: reproducible bit for bit, and bit for bit what numpy
+ * gives on the downloaded fields.
+ *   max_abs_vx is the back-trace figure: the next advection traces cell c back by v.x(c) * dt columns (advect.h:78-80),
+ * float rounding is monotone and symmetric in sign, so max over c of |v.x(c) * dt| == |max_abs_vx * dt| bit for bit (and
+ * likewise for y and rows): the longest back-trace of a step with any dt follows from one call -- what to choose dt by,
+ * and the figure a slab's automatic advection halo (SFL_OPT_ADVECT_HALO: 64 rows, then a gather) depends on.
+ *   what: a non-empty subset of the SFL_STATS_* bits, else SFL_ERR_INVALID; with SFL_STATS_DYE alone dx is ignored.  ctx
+ * or out NULL return SFL_ERR_INVALID.  All of these are refused before any GPU work.  Synchronous: one launch per pass
+ * asked for, one copy of the 40 bytes, one wait; nothing is allocated per call.
+ *   Cost: one streaming pass per bit: not measured yet.                                                              */
+SFL_API int sfl_flow_stats(sfl_context *ctx, int what, float dx, struct sfl_flow_stats *out);
 /* next_p <- advect(p, velocity, dt, no_slip) for a field of the CALLER's, resident on the context's device
  * (advect.h:74-85; element = `channels` x `kind` as for sfl_host_advect_channels): further quantities carried by
  * the flow -- a temperature, a second dye -- without a round trip through the host.  Whole-domain contexts only;
@@ -561,6 +600,20 @@ SFL_API int sfl_batch_poisson_solve_until(sfl_batch *b, const sfl_member_params 
  * *_until call (n > 0): whatever makes sfl_batch_residual stale makes this stale, and so does an *_each call --
  * SFL_ERR_STATE, and the message says to call sfl_batch_step_n_until or sfl_batch_poisson_solve_until.    */
 SFL_API int sfl_batch_iterations(sfl_batch *b, int first, int count, int32_t *host, size_t bytes);
+/* --- the flow statistics of members [first, first + count): one sfl_flow_stats record per member (group 2,
+ *     sfl_flow_stats: the definitions, word for word), of the member's CURRENT velocity and dye -- what sfl_batch_download
+ *     would hand out -- with the divergence scaled by dx.  A member reports, bit for bit, what a context holding the
+ *     same fields reports.  Every member's record is evaluated by ONE launch per pass asked for, whatever the range;
+ *     [first, first + count) is copied out.  Reads only: the reports of sfl_batch_residual and sfl_batch_iterations do
+ *     not go stale.  Synchronous; the device and pinned records are allocated once per batch, nothing per call.
+ *     `what` empty or with other bits, b or host NULL, bytes != count * 40 and a range that is not inside the batch
+ *     return SFL_ERR_INVALID before any GPU work.                                                                  */
+SFL_API int sfl_batch_flow_stats(sfl_batch *b, int what, float dx, int first, int count,
+                                 struct sfl_flow_stats *host, size_t bytes);
+/* The same with member m's divergence scaled by params[m].dx: params is an array of `batch` records (HOST memory, read
+ * before the call returns; NULL returns SFL_ERR_INVALID), whose other members are ignored.                            */
+SFL_API int sfl_batch_flow_stats_each(sfl_batch *b, int what, const sfl_member_params *params,
+                                      int first, int count, struct sfl_flow_stats *host, size_t bytes);
 /* sfl_setup_sketch_fields for every member (the saturating definition included).  Asynchronous.    */
 SFL_API int sfl_batch_setup_sketch_fields(sfl_batch *b);
 /* sfl_render_rgb565 of one member's dye.  Synchronous.                                            */
