@@ -30,6 +30,7 @@ CHANNEL_F32, CHANNEL_UQ32 = 0, 1
 STEP_EXCHANGE, STEP_SOR, STEP_ZERO = 1, 2, 3
 STATS_VELOCITY, STATS_DYE = 1, 2
 UNIQUE_ID_BYTES = 128
+BATCH_LARGE_MAX_CELLS = 20224   # SFL_BATCH_LARGE_MAX_CELLS: cells of one member of sfl_batch_create_large
 
 
 class PlanStep(C.Structure):
@@ -153,6 +154,8 @@ SIGNATURES = {
     "sfl_timer_stop": (_i, [_ctx, _pf]),
     "sfl_last_solve_info": (_i, [_ctx, _pi, _pi, _pi]),
     "sfl_batch_create": (_i, [C.POINTER(_ctx), _i, _i, _i, _i]),
+    "sfl_batch_create_large": (_i, [C.POINTER(_ctx), _i, _i, _i, _i]),
+    "sfl_batch_is_large": (_i, [_ctx, _pi]),
     "sfl_batch_destroy": (_i, [_ctx]),
     "sfl_batch_shape": (_i, [_ctx, _pi, _pi, _pi]),
     "sfl_batch_upload": (_i, [_ctx, _i, _i, _i, C.c_void_p, _sz]),

@@ -1,7 +1,9 @@
 // batch.cpp -- batches of the C ABI (include/sfl.h group 4, sfl_batch_*): B independent whole-domain simulations of one
-// small grid on one device, stepped by ONE launch of B workgroups (batch_grid.hip).  Argument checks, field I/O, the
-// staging of queued forces into per-member order, of per-member parameters into device records, and the ping-pong of
-// velocity and dye.  Host C++ only; it shares the error plumbing of context.h and nothing else with the context units.
+// small grid on one device, stepped by ONE launch of B workgroups (batch_grid.hip; batch_large.hip for the batches of
+// sfl_batch_create_large -- the only difference on this side is which of the two families of six launchers a call takes).
+// Argument checks, field I/O, the staging of queued forces into per-member order, of per-member parameters into device
+// records, and the ping-pong of velocity and dye.  Host C++ only; it shares the error plumbing of context.h and nothing
+// else with the context units.
 #include "batch.h"
 
 #include "context.h"
@@ -15,6 +17,7 @@ struct sfl_batch {
     int device = 0;
     int dim_x = 0, dim_y = 0, batch = 0;
     size_t cells = 0;   // per member
+    bool large = false;   // made by sfl_batch_create_large: every launch is one of batch_large.hip, whatever the shape
     hipStream_t stream = nullptr;
     // fields, member-major; velocity and dye ping-pong between two buffers (ino:255, :286)
     float *vel = nullptr, *vel_tmp = nullptr;
@@ -318,6 +321,33 @@ int flow_stats(sfl_batch *b, int what, float dx, bool each, const sfl_member_par
     return SFL_OK;
 }
 
+// what both constructors do once their limits have passed: the device, the stream, the six zeroed fields
+int make_batch(sfl_batch **out, int device, int dim_x, int dim_y, int batch, bool large)
+{
+    int ndev = 0;
+    SFL_TRY(sfl_device_count(&ndev));
+    if (device < 0 || device >= ndev) return fail(SFL_ERR_HIP, "device %d not available (%d visible)", device, ndev);
+
+    std::unique_ptr<sfl_batch, Release> b(new sfl_batch);
+    b->device = device;
+    b->dim_x = dim_x;
+    b->dim_y = dim_y;
+    b->batch = batch;
+    b->cells = (size_t)dim_x * (size_t)dim_y;
+    b->large = large;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->vel, 8, true));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->vel_tmp, 8, false));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->col, 12, true));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->col_tmp, 12, false));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->div, 4, true));
+    SFL_TRY(alloc_field(b.get(), (void **)&b->p, 4, true));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    *out = b.release();
+    return SFL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -338,26 +368,33 @@ int sfl_batch_create(sfl_batch **out, int device, int dim_x, int dim_y, int batc
                     (long long)dim_y * ((dim_x + 1) / 2));
     if ((int64_t)batch * cells > INT32_MAX)
         return fail(SFL_ERR_INVALID, "batch x cells must be <= 2^31 - 1 (got %d x %lld)", batch, (long long)cells);
-    int ndev = 0;
-    SFL_TRY(sfl_device_count(&ndev));
-    if (device < 0 || device >= ndev) return fail(SFL_ERR_HIP, "device %d not available (%d visible)", device, ndev);
+    return make_batch(out, device, dim_x, dim_y, batch, false);
+}
 
-    std::unique_ptr<sfl_batch, Release> b(new sfl_batch);
-    b->device = device;
-    b->dim_x = dim_x;
-    b->dim_y = dim_y;
-    b->batch = batch;
-    b->cells = (size_t)cells;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    SFL_TRY(alloc_field(b.get(), (void **)&b->vel, 8, true));
-    SFL_TRY(alloc_field(b.get(), (void **)&b->vel_tmp, 8, false));
-    SFL_TRY(alloc_field(b.get(), (void **)&b->col, 12, true));
-    SFL_TRY(alloc_field(b.get(), (void **)&b->col_tmp, 12, false));
-    SFL_TRY(alloc_field(b.get(), (void **)&b->div, 4, true));
-    SFL_TRY(alloc_field(b.get(), (void **)&b->p, 4, true));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    *out = b.release();
+int sfl_batch_create_large(sfl_batch **out, int device, int dim_x, int dim_y, int batch)
+{
+    static_assert(SFL_BATCH_LARGE_MAX_CELLS == sfl::kLargeMemberMaxCells, "include/sfl.h and batch.h state one limit");
+    if (!out) return fail(SFL_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (dim_x < 2 || dim_y < 2) return fail(SFL_ERR_INVALID, "dim_x and dim_y must be >= 2 (got %d x %d)", dim_x, dim_y);
+    if (batch < 1) return fail(SFL_ERR_INVALID, "batch must be >= 1 (got %d)", batch);
+    const int64_t cells = (int64_t)dim_x * dim_y;
+    if (cells > sfl::kLargeMemberMaxCells)
+        return fail(SFL_ERR_INVALID, "a large batch member holds at most %d cells (its divergence and pressure in one "
+                    "workgroup's LDS): %d x %d has %lld", sfl::kLargeMemberMaxCells, dim_x, dim_y, (long long)cells);
+    if (!sfl::large_member_fits(dim_x, dim_y))
+        return fail(SFL_ERR_INVALID, "a large batch member holds at most %d cells of one colour (dim_y * ceil(dim_x / 2), the "
+                    "cells one workgroup's threads own): %d x %d has %lld", sfl::kLargeMemberMaxColour, dim_x, dim_y,
+                    (long long)dim_y * ((dim_x + 1) / 2));
+    if ((int64_t)batch * cells > INT32_MAX)
+        return fail(SFL_ERR_INVALID, "batch x cells must be <= 2^31 - 1 (got %d x %lld)", batch, (long long)cells);
+    return make_batch(out, device, dim_x, dim_y, batch, true);
+}
+
+int sfl_batch_is_large(sfl_batch *b, int *large)
+{
+    if (!b || !large) return fail(SFL_ERR_INVALID, "NULL argument");
+    *large = b->large ? 1 : 0;
     return SFL_OK;
 }
 
@@ -445,7 +482,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
         a.step.v_out = b->vel_tmp;
         a.step.col_in = b->col;
         a.step.col_out = b->col_tmp;
-        HIP_TRY(sfl::launch_batch_step(b->stream, a, b->batch));
+        HIP_TRY((b->large ? sfl::launch_batch_large_step : sfl::launch_batch_step)(b->stream, a, b->batch));
         std::swap(b->vel, b->vel_tmp);  // ino:255
         std::swap(b->col, b->col_tmp);  // ino:286
     }
@@ -458,7 +495,8 @@ int sfl_batch_poisson_solve(sfl_batch *b, float dx, int iters, float omega)
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     SFL_TRY(use_device(b));
     b->report_valid = b->counts_valid = false;
-    HIP_TRY(sfl::launch_batch_solve(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch, iters, sor_params(dx, omega)));
+    HIP_TRY((b->large ? sfl::launch_batch_large_solve : sfl::launch_batch_solve)(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch,
+                                                                                 iters, sor_params(dx, omega)));
     return SFL_OK;
 }
 
@@ -482,7 +520,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
         a.step.v_out = b->vel_tmp;
         a.step.col_in = b->col;
         a.step.col_out = b->col_tmp;
-        HIP_TRY(sfl::launch_batch_step_each(b->stream, a, b->batch, b->d_members, b->d_report));
+        HIP_TRY((b->large ? sfl::launch_batch_large_step_each : sfl::launch_batch_step_each)(b->stream, a, b->batch, b->d_members, b->d_report));
         std::swap(b->vel, b->vel_tmp);  // ino:255
         std::swap(b->col, b->col_tmp);  // ino:286
     }
@@ -496,7 +534,8 @@ int sfl_batch_poisson_solve_each(sfl_batch *b, const sfl_member_params *params)
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
     b->report_valid = b->counts_valid = false;
-    HIP_TRY(sfl::launch_batch_solve_each(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch, b->d_members, b->d_report));
+    HIP_TRY((b->large ? sfl::launch_batch_large_solve_each : sfl::launch_batch_solve_each)(b->stream, b->p, b->div, b->dim_x, b->dim_y,
+                                                                                           b->batch, b->d_members, b->d_report));
     b->report_valid = true;
     return SFL_OK;
 }
@@ -522,7 +561,8 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
         a.step.col_in = b->col;
         a.step.col_out = b->col_tmp;
         // (the first step starts every member's sum of iterations, the later ones add to it)
-        HIP_TRY(sfl::launch_batch_step_until(b->stream, a, b->batch, b->d_members, b->d_stops, b->d_report, b->d_counts, k > 0));
+        HIP_TRY((b->large ? sfl::launch_batch_large_step_until : sfl::launch_batch_step_until)(b->stream, a, b->batch, b->d_members, b->d_stops,
+                                                                                           b->d_report, b->d_counts, k > 0));
         std::swap(b->vel, b->vel_tmp);  // ino:255
         std::swap(b->col, b->col_tmp);  // ino:286
     }
@@ -536,8 +576,8 @@ int sfl_batch_poisson_solve_until(sfl_batch *b, const sfl_member_params *params,
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params, stops));
     b->report_valid = b->counts_valid = false;
-    HIP_TRY(sfl::launch_batch_solve_until(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch, b->d_members, b->d_stops,
-                                          b->d_report, b->d_counts));
+    HIP_TRY((b->large ? sfl::launch_batch_large_solve_until : sfl::launch_batch_solve_until)(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch,
+                                                                                             b->d_members, b->d_stops, b->d_report, b->d_counts));
     b->report_valid = b->counts_valid = true;
     return SFL_OK;
 }

@@ -1,5 +1,6 @@
 // batch.h -- launch interface of the batched one-workgroup kernels (batch_grid.hip; internal, the public boundary is
-// include/sfl.h sfl_batch_*).  A batch is B independent whole-domain grids of one shape that passes small_grid_fits,
+// include/sfl.h sfl_batch_*).  A batch is B independent whole-domain grids of one shape that passes small_grid_fits (or
+// large_member_fits: the launchers of batch_large.hip at the end of this file),
 // stored member-major: member m of a field starts at element m * dim_x * dim_y.  Workgroup m steps / solves member m;
 // members never communicate.  Every launcher is asynchronous on the given stream and returns the hipError_t of the launch.
 #pragma once
@@ -53,5 +54,28 @@ hipError_t launch_batch_step_until(hipStream_t s, const BatchStep &a, int batch,
                                    const BatchStop *stops, float *report, int *counts, bool add);
 hipError_t launch_batch_solve_until(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
                                     const BatchMember *members, const BatchStop *stops, float *report, int *counts);
+
+// ---- large members: up to kLargeMemberMaxCells cells, 8 B of LDS per cell (batch_large.hip, large_member_core.h) ----
+// The same six launches for the batches of sfl_batch_create_large: one workgroup of 1024 threads per member whose LDS
+// holds the advected velocity first and the divergence and the pressure afterwards (DESIGN.md has the layout and its
+// barriers).  Same arguments, same results bit for bit; any shape that passes large_member_fits, however small.
+constexpr int kLargeMemberMaxCells = 20224;    // (163840 - 2048) / 8: SFL_BATCH_LARGE_MAX_CELLS of include/sfl.h
+constexpr int kLargeMemberMaxColour = 10240;   // cells of one colour: ten positions per thread and colour at 1024 threads
+inline bool large_member_fits(int dim_x, int dim_y)
+{
+    return dim_x >= 2 && dim_y >= 2 && (long long)dim_x * dim_y <= kLargeMemberMaxCells &&
+           (long long)dim_y * ((dim_x + 1) / 2) <= kLargeMemberMaxColour;
+}
+hipError_t launch_batch_large_step(hipStream_t s, const BatchStep &a, int batch);
+hipError_t launch_batch_large_solve(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch, int iters,
+                                    SorParams prm);
+hipError_t launch_batch_large_step_each(hipStream_t s, const BatchStep &a, int batch, const BatchMember *members,
+                                        float *report);
+hipError_t launch_batch_large_solve_each(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
+                                         const BatchMember *members, float *report);
+hipError_t launch_batch_large_step_until(hipStream_t s, const BatchStep &a, int batch, const BatchMember *members,
+                                         const BatchStop *stops, float *report, int *counts, bool add);
+hipError_t launch_batch_large_solve_until(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
+                                          const BatchMember *members, const BatchStop *stops, float *report, int *counts);
 
 }  // namespace sfl

@@ -343,12 +343,16 @@ class BatchSolver:
     """A batch (sfl_batch_*): `batch` independent whole-domain simulations of one dim_x * dim_y grid on one device,
     every member stepped by the same launch.  Member m holds, bit for bit, what a :class:`Solver` of the same shape
     holds after the same calls made with member m's data and forces.  Arrays of members are shaped
-    ``(count, dim_y, dim_x[, k])``."""
+    ``(count, dim_y, dim_x[, k])``.
 
-    def __init__(self, dim_x: int, dim_y: int, batch: int, device: int = 0):
+    ``large=True`` makes a batch of large members (sfl_batch_create_large): up to ``capi.BATCH_LARGE_MAX_CELLS`` cells
+    per member instead of 6144, 8 B of LDS per cell instead of 16, one member per CU.  Every method is the same."""
+
+    def __init__(self, dim_x: int, dim_y: int, batch: int, device: int = 0, large: bool = False):
         self._h = C.c_void_p()
         self._lib = capi.lib()
-        capi.check(self._lib.sfl_batch_create(C.byref(self._h), device, dim_x, dim_y, batch))
+        create = self._lib.sfl_batch_create_large if large else self._lib.sfl_batch_create
+        capi.check(create(C.byref(self._h), device, dim_x, dim_y, batch))
         self.dim_x, self.dim_y, self.batch, self.device = dim_x, dim_y, batch, device
 
     def close(self):
@@ -367,6 +371,13 @@ class BatchSolver:
             self.close()
         except Exception:
             pass
+
+    @property
+    def large(self) -> bool:
+        """True for a batch of large members (``large=True``), as the library reports it."""
+        flag = C.c_int()
+        capi.check(self._lib.sfl_batch_is_large(self._h, C.byref(flag)))
+        return bool(flag.value)
 
     @property
     def shape(self):

@@ -509,6 +509,14 @@ SFL_API int sfl_last_solve_info(sfl_context *ctx, int *launches, int *exchanges,
  *    per member with its fields in LDS.  After any sequence of batch calls member m holds,
  *    bit for bit, what a whole-domain context of the same shape holds after the same calls
  *    made with member m's data and member m's forces.
+ *    Two kinds of batch, made by two constructors and alike in every other call:
+ *    sfl_batch_create       members of at most 6144 cells, 16 B of LDS per cell (velocity,
+ *                           divergence and pressure side by side): two members share a CU
+ *                           at the sketch's 61 x 81;
+ *    sfl_batch_create_large members of at most 20224 cells (128 x 128, 160 x 120), 8 B of
+ *                           LDS per cell: the same bytes hold the advected velocity first
+ *                           and the divergence and the pressure afterwards.  One member per
+ *                           CU; speed not measured yet (profiles/batch_large.txt).
  * ===================================================================================== */
 
 /* Limits: the shapes the one-workgroup path of a context takes (SFL_OPT_SMALL_GRID): dim_x, dim_y >= 2, at most
@@ -516,6 +524,17 @@ SFL_API int sfl_last_solve_info(sfl_context *ctx, int *launches, int *exchanges,
  * <= 2^31 - 1.  Violations return SFL_ERR_INVALID before any GPU is touched; a failed allocation returns
  * SFL_ERR_NOMEM.  Every field is zero after create.                                               */
 SFL_API int sfl_batch_create(sfl_batch **out, int device, int dim_x, int dim_y, int batch);
+/* A batch of LARGE members: every sfl_batch_* call below takes it, with the same semantics, argument checks, staleness
+ * rules and messages, and member m holds the same bits as a context of its shape.  Such a batch always runs the
+ * large-member kernels, whatever its shape (a 2 x 2 or a 61 x 81 too: the layout can be priced against sfl_batch_create
+ * at a shape both take).  Limits: dim_x, dim_y >= 2; at most SFL_BATCH_LARGE_MAX_CELLS cells; at most 10240 cells of one
+ * colour (dim_y * ceil(dim_x / 2): ten per thread of a member's 1024); batch >= 1 and batch * dim_x * dim_y <= 2^31 - 1.
+ * Violations return SFL_ERR_INVALID before any GPU is touched; a failed allocation returns SFL_ERR_NOMEM.  Every field
+ * is zero after create.                                                                                               */
+#define SFL_BATCH_LARGE_MAX_CELLS 20224   /* (163840 - 2048) / 8: p and d of one member in one CU's LDS, 2 KB kept for the kernels' static words */
+SFL_API int sfl_batch_create_large(sfl_batch **out, int device, int dim_x, int dim_y, int batch);
+/* *large = 1 for a batch made by sfl_batch_create_large, else 0.                                   */
+SFL_API int sfl_batch_is_large(sfl_batch *b, int *large);
 SFL_API int sfl_batch_destroy(sfl_batch *b);
 /* Any out pointer may be NULL. */
 SFL_API int sfl_batch_shape(sfl_batch *b, int *dim_x, int *dim_y, int *batch);

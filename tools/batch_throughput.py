@@ -3,6 +3,7 @@
 
     python tools/batch_throughput.py --size 61 81 --iters 20 [--batches 1 64 256 1024 4096] [--steps K] [--warmup W] [--check]
                                      [--each uniform | spread | spread-sorted] [--until TOL [--every C] [--omega-mix]]
+                                     [--large]
 
 Every member starts from the sketch's fields (setup_sketch_fields) with a drag of its own in the first warm-up step, so
 that no two members hold the same numbers.  Per B: W warm-up steps, then step_n(K) timed with a host clock around a
@@ -24,6 +25,8 @@ stops at the first check, made in front of every C-th iteration (--every, defaul
 member an omega drawn from 1.0 .. 1.99 with a fixed seed instead of 1.96 (a parameter study whose members need different
 numbers of iterations).  Such a line carries iters_run_last_step and iters_run_timed: the iterations the members
 really ran in the last step and over the K timed steps, against sum_iters (one step at the caps).
+--large: a batch of large members (sfl_batch_create_large: up to 20224 cells per member, 8 B of LDS per cell) instead of
+sfl_batch_create's (6144 cells, 16 B per cell); a shape both take prices the layout.  Every line carries "large".
 --check: after the timed run, members {0, 1, B/2, B - 1} against single contexts given the same start, drag, steps and
 that member's parameters -- velocity, divergence, pressure and dye bit for bit."""
 import argparse
@@ -113,6 +116,7 @@ def main():
                     help="step through step_n_until: iters are caps, a solve stops at update norm <= TOL (-1: never)")
     ap.add_argument("--every", type=int, default=4, help="with --until: a check in front of every C-th iteration")
     ap.add_argument("--omega-mix", action="store_true", help="with --until: each member's omega drawn from 1.0 .. 1.99")
+    ap.add_argument("--large", action="store_true", help="a batch of large members (sfl_batch_create_large)")
     ap.add_argument("--label", default="", help="free text carried into every line (e.g. the build variant)")
     a = ap.parse_args()
     if a.until is None and a.omega_mix:
@@ -125,7 +129,7 @@ def main():
     ref_ms = reference_step_ms(dim_x, dim_y, a.iters)
     ok = True
     for batch in a.batches:
-        with sfl.BatchSolver(dim_x, dim_y, batch) as b:
+        with sfl.BatchSolver(dim_x, dim_y, batch, large=a.large) as b:
             b.setup_sketch_fields()
             drags = [drag_of(m, dim_x, dim_y) for m in range(batch)]
             b.queue_forces(np.arange(batch, dtype=np.int32), [d[0] for d in drags], [d[1] for d in drags])
@@ -153,7 +157,7 @@ def main():
             line = {
                 "grid": [dim_x, dim_y], "iters": a.iters if a.each in (None, "uniform") else "%d..%d" % SPREAD_ITERS,
                 "call": "step_n_until" if a.until is not None else "step_n_each" if a.each else "step_n", "each": a.each, "sum_iters": int(iters.sum()),
-                "mean_iters": float(iters.mean()), "batch": batch, "steps": a.steps, "warmup": a.warmup,
+                "mean_iters": float(iters.mean()), "batch": batch, "large": b.large, "steps": a.steps, "warmup": a.warmup,
                 "member_steps_per_s": rate, "us_per_batch_step": seconds / a.steps * 1e6,
                 "bytes_model_per_member_step": BYTES_PER_CELL_STEP * cells, "gb_per_s": gbs,
                 "frac_of_8tb_s": gbs * 1e9 / HBM_BYTES_PER_S,
