@@ -174,6 +174,11 @@ SIGNATURES = {
     "sfl_batch_flow_stats_each": (_i, [_ctx, _i, C.POINTER(MemberParams), _i, _i, C.POINTER(FlowStats), _sz]),
     "sfl_batch_setup_sketch_fields": (_i, [_ctx]),
     "sfl_batch_render_rgb565": (_i, [_ctx, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
+    "sfl_batch_render_members": (_i, [_ctx, _i, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
+    "sfl_batch_record_start": (_i, [_ctx, _i, _i, _i, _i, _i, _i]),
+    "sfl_batch_record_stop": (_i, [_ctx]),
+    "sfl_batch_record_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64)]),
+    "sfl_batch_record_read": (_i, [_ctx, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

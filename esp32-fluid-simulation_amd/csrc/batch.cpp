@@ -3,59 +3,12 @@
 // sfl_batch_create_large -- the only difference on this side is which of the two families of six launchers a call takes).
 // Argument checks, field I/O, the staging of queued forces into per-member order, of per-member parameters into device
 // records, and the ping-pong of velocity and dye.  Host C++ only; it shares the error plumbing of context.h and nothing
-// else with the context units.
-#include "batch.h"
-
-#include "context.h"
-#include "stats_kernels.h"
+// else with the context units.  batch_state.h has the struct; batch_frames.cpp the frames of many members and the recorder.
+#include "batch_state.h"
 
 #include <cmath>
 
 using sfl::host::fail;
-
-struct sfl_batch {
-    int device = 0;
-    int dim_x = 0, dim_y = 0, batch = 0;
-    size_t cells = 0;   // per member
-    bool large = false;   // made by sfl_batch_create_large: every launch is one of batch_large.hip, whatever the shape
-    hipStream_t stream = nullptr;
-    // fields, member-major; velocity and dye ping-pong between two buffers (ino:255, :286)
-    float *vel = nullptr, *vel_tmp = nullptr;
-    uint32_t *col = nullptr, *col_tmp = nullptr;
-    float *div = nullptr, *p = nullptr;
-    // queued point forces (ino:264-269), in queue order
-    std::vector<int> force_member, force_cells;
-    std::vector<float> force_vel;
-    // staged forces of a step: B + 1 member offsets, then the cells, then the velocities, in ONE device buffer filled
-    // from pinned memory; two host slots used alternately, each rewritten only after its last copy has completed
-    void *d_forces = nullptr;
-    size_t d_forces_bytes = 0;
-    struct Stage {
-        void *host = nullptr;
-        size_t bytes = 0;
-        hipEvent_t copied = nullptr;
-        bool pending = false;
-    } stage[2];
-    int slot = 0;
-    // per-member parameters (sfl_batch_*_each): `batch` device records, filled from pinned memory by the same two-slot rule,
-    // and one float per member for the update norm the *_each kernels leave (valid: see sfl_batch_residual)
-    sfl::BatchMember *d_members = nullptr;
-    Stage member_stage[2];
-    int member_slot = 0;
-    float *d_report = nullptr;
-    bool report_valid = false;
-    // stopping rules (sfl_batch_*_until): the members' sfl_member_stop behind their records, in the same device array and
-    // in launch order, and two ints per member for the iterations the *_until kernels ran (valid: see sfl_batch_iterations)
-    sfl::BatchStop *d_stops = nullptr;
-    int *d_counts = nullptr;
-    bool counts_valid = false;
-    // flow statistics (sfl_batch_flow_stats[_each]): one record per member that the two passes leave, behind them one
-    // 1 / (2 dx) per member; the same in pinned memory.  Allocated at the first call, nothing per call
-    sfl::FlowStatsRecord *d_stats = nullptr, *h_stats = nullptr;
-    // dye visualiser's device image, kept between frames
-    uint16_t *d_image = nullptr;
-    size_t d_image_bytes = 0;
-};
 
 namespace {
 
@@ -65,7 +18,7 @@ void release(sfl_batch *b)
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (void *m : {(void *)b->vel, (void *)b->vel_tmp, (void *)b->col, (void *)b->col_tmp, (void *)b->div, (void *)b->p,
                     b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_counts, (void *)b->d_image,
-                    (void *)b->d_stats})
+                    (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
     for (sfl_batch::Stage *pair : {b->stage, b->member_stage})
@@ -464,6 +417,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     if (n == 0) return SFL_OK;
+    SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
     SFL_TRY(use_device(b));
     b->report_valid = b->counts_valid = false;   // (the uniform kernels leave no update norm)
     sfl::BatchStep a{};
@@ -485,6 +439,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
         HIP_TRY((b->large ? sfl::launch_batch_large_step : sfl::launch_batch_step)(b->stream, a, b->batch));
         std::swap(b->vel, b->vel_tmp);  // ino:255
         std::swap(b->col, b->col_tmp);  // ino:286
+        SFL_TRY(sfl::host::record_step(b));
     }
     return SFL_OK;
 }
@@ -505,6 +460,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
     SFL_TRY(check_members(b, params));
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
     if (n == 0) return SFL_OK;
+    SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
     b->report_valid = b->counts_valid = false;   // until every launch below is queued; no iterations to report afterwards
@@ -523,6 +479,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
         HIP_TRY((b->large ? sfl::launch_batch_large_step_each : sfl::launch_batch_step_each)(b->stream, a, b->batch, b->d_members, b->d_report));
         std::swap(b->vel, b->vel_tmp);  // ino:255
         std::swap(b->col, b->col_tmp);  // ino:286
+        SFL_TRY(sfl::host::record_step(b));
     }
     b->report_valid = true;   // of the last step's solve: the divergence and pressure a download hands out now
     return SFL_OK;
@@ -545,6 +502,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
     SFL_TRY(check_members(b, params, stops));
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
     if (n == 0) return SFL_OK;
+    SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params, stops));
     b->report_valid = b->counts_valid = false;   // until every launch below is queued
@@ -565,6 +523,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
                                                                                            b->d_report, b->d_counts, k > 0));
         std::swap(b->vel, b->vel_tmp);  // ino:255
         std::swap(b->col, b->col_tmp);  // ino:286
+        SFL_TRY(sfl::host::record_step(b));
     }
     b->report_valid = b->counts_valid = true;   // of the last step's solve; the sum over all n
     return SFL_OK;

@@ -78,4 +78,12 @@ hipError_t launch_batch_large_step_until(hipStream_t s, const BatchStep &a, int 
 hipError_t launch_batch_large_solve_until(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
                                           const BatchMember *members, const BatchStop *stops, float *report, int *counts);
 
+// ---- the draw task of many members in one launch (batch_render.hip) -----------------------------------------------
+// Image k of `images` (k in [0, count), member-major: image k starts at pixel k * H * W, H = scaling * (dim_x - 1) rows of
+// W = scaling * (dim_y - 1) uint16) = launch_render_rgb565 of the dye at colour_of_first_member + 3 * k * dim_x * dim_y,
+// bit for bit.  Member bases are formed in 64-bit, offsets inside one member in 32-bit (H * W <= 2^31 - 1: the caller's
+// limits on cells and scaling see to it).  Either kind of batch; scaling >= 1; count == 0 launches nothing.
+hipError_t launch_batch_render(hipStream_t s, uint16_t *images, const uint32_t *colour_of_first_member, int dim_x, int dim_y,
+                               int count, int scaling, bool byteswap);
+
 }  // namespace sfl

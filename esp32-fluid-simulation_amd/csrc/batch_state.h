@@ -1,0 +1,77 @@
+// batch_state.h -- what a batch of the C ABI holds (include/sfl.h group 4), shared by the two host units of the batches:
+// batch.cpp (creation, field I/O, the step and solve calls) and batch_frames.cpp (the frames of many members in one
+// launch, and the recorder that renders them between the step launches).  Host C++ only.
+#pragma once
+#include "batch.h"
+#include "context.h"
+#include "stats_kernels.h"
+
+struct sfl_batch {
+    int device = 0;
+    int dim_x = 0, dim_y = 0, batch = 0;
+    size_t cells = 0;   // per member
+    bool large = false;   // made by sfl_batch_create_large: every launch is one of batch_large.hip, whatever the shape
+    hipStream_t stream = nullptr;
+    // fields, member-major; velocity and dye ping-pong between two buffers (ino:255, :286)
+    float *vel = nullptr, *vel_tmp = nullptr;
+    uint32_t *col = nullptr, *col_tmp = nullptr;
+    float *div = nullptr, *p = nullptr;
+    // queued point forces (ino:264-269), in queue order
+    std::vector<int> force_member, force_cells;
+    std::vector<float> force_vel;
+    // staged forces of a step: B + 1 member offsets, then the cells, then the velocities, in ONE device buffer filled
+    // from pinned memory; two host slots used alternately, each rewritten only after its last copy has completed
+    void *d_forces = nullptr;
+    size_t d_forces_bytes = 0;
+    struct Stage {
+        void *host = nullptr;
+        size_t bytes = 0;
+        hipEvent_t copied = nullptr;
+        bool pending = false;
+    } stage[2];
+    int slot = 0;
+    // per-member parameters (sfl_batch_*_each): `batch` device records, filled from pinned memory by the same two-slot rule,
+    // and one float per member for the update norm the *_each kernels leave (valid: see sfl_batch_residual)
+    sfl::BatchMember *d_members = nullptr;
+    Stage member_stage[2];
+    int member_slot = 0;
+    float *d_report = nullptr;
+    bool report_valid = false;
+    // stopping rules (sfl_batch_*_until): the members' sfl_member_stop behind their records, in the same device array and
+    // in launch order, and two ints per member for the iterations the *_until kernels ran (valid: see sfl_batch_iterations)
+    sfl::BatchStop *d_stops = nullptr;
+    int *d_counts = nullptr;
+    bool counts_valid = false;
+    // flow statistics (sfl_batch_flow_stats[_each]): one record per member that the two passes leave, behind them one
+    // 1 / (2 dx) per member; the same in pinned memory.  Allocated at the first call, nothing per call
+    sfl::FlowStatsRecord *d_stats = nullptr, *h_stats = nullptr;
+    // dye visualiser's device image, kept between frames
+    uint16_t *d_image = nullptr;
+    size_t d_image_bytes = 0;
+    // ... and the images of sfl_batch_render_members: as many members as the largest call so far rendered
+    uint16_t *d_images = nullptr;
+    size_t d_images_bytes = 0;
+    // the recorder (sfl_batch_record_*): `capacity` frames of members [first, first + count) at one scaling, frame f at
+    // pixel f * count * H * W of d_frames; `written` of them are rendered, `steps` steps counted since record_start
+    struct Recorder {
+        bool on = false;
+        int every = 0, first = 0, count = 0, scaling = 0, byteswap = 0, capacity = 0, written = 0;
+        int64_t steps = 0;
+    } rec;
+    uint16_t *d_frames = nullptr;   // kept by a restart that does not need more; freed by record_stop
+    size_t d_frames_bytes = 0;
+};
+
+namespace sfl {
+namespace host {
+
+// The two hooks of the step calls (batch.cpp) into the recorder (batch_frames.cpp); both do nothing for a batch that is
+// not recording.  record_admit: SFL_ERR_STATE if the n steps of a call would complete more frames than are free -- after
+// the call's own argument checks, before anything is staged or launched.  record_step: one step has been launched and
+// the ping-pong swapped; counts it and, when the count reaches a multiple of `every`, launches the frame's render on the
+// batch's stream behind it.
+int record_admit(sfl_batch *b, int n);
+int record_step(sfl_batch *b);
+
+}  // namespace host
+}  // namespace sfl

@@ -9,6 +9,7 @@
 // Reference citations are file:line under /root/reference/ESP32-fluid-simulation/.
 #include "advect_math.h"
 #include "kernels.h"
+#include "render_math.h"
 
 namespace sfl {
 namespace {
@@ -158,9 +159,8 @@ sor_half_sweep_kernel(float *p, const float *__restrict__ d, Slab g, int g_begin
 
 // ---- dye visualiser (draw task, ino:116-176) ---------------------------------
 // One thread per output pixel.  Pixel (sy, sx) belongs to cell block (i, j) = (sy / S, sx / S)
-// at offset (ii, jj); it replays the sketch's strength-reduced lerps for its own offsets only:
-// left / right edge values after ii increments (:134-153), then jj increments across (:156-161),
-// narrowing to UQ32 (:168), RGB565 pack (:170-172), optional byte swap (:173).
+// at offset (ii, jj); it replays the sketch's strength-reduced lerps for its own offsets only, by
+// the chain of render_math.h (which the batches' kernel, batch_render.hip, shares).
 __global__ void __launch_bounds__(kBlock)
 render_rgb565_kernel(uint16_t *__restrict__ image, const uint32_t *__restrict__ colour, int dim_x,
                      int dim_y, int scaling, int byteswap)
@@ -171,28 +171,14 @@ render_rgb565_kernel(uint16_t *__restrict__ image, const uint32_t *__restrict__ 
     if (sx >= width) return;
     const int i = sy / scaling, ii = sy - i * scaling;
     const int j = sx / scaling, jj = sx - j * scaling;
-    const float inv = 1.0f / (float)scaling;
+    const float inv = render_math::render_inv(scaling);
     const uint32_t *t1 = colour + 3 * ((size_t)dim_x * j + i);
     const uint32_t *t2 = colour + 3 * ((size_t)dim_x * (j + 1) + i);
     uint32_t raw[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float l = uq_widen(t1[k]), r = uq_widen(t2[k]);
-        const float dl = (uq_widen(t1[3 + k]) - l) * inv;
-        const float dr = (uq_widen(t2[3 + k]) - r) * inv;
-        for (int n = 0; n < ii; ++n) {
-            l += dl;
-            r += dr;
-        }
-        float c = l;
-        const float dc = (r - l) * inv;
-        for (int n = 0; n < jj; ++n) c += dc;
-        raw[k] = uq_narrow(c);
-    }
-    uint16_t px = (uint16_t)(((raw[0] & 0xF8000000u) >> 16) | ((raw[1] & 0xFC000000u) >> 21) |
-                             ((raw[2] & 0xF8000000u) >> 27));
-    if (byteswap) px = (uint16_t)((px >> 8) | (px << 8));
-    image[(size_t)sy * width + sx] = px;
+    for (int k = 0; k < 3; ++k)   // the chain of render_math.h, shared with the batches' kernel
+        raw[k] = render_math::render_channel(uq_widen(t1[k]), uq_widen(t1[3 + k]), uq_widen(t2[k]), uq_widen(t2[3 + k]), inv, ii, jj);
+    image[(size_t)sy * width + sx] = render_math::render_pack(raw[0], raw[1], raw[2], byteswap);
 }
 
 // ---- initial condition of the sketch's setup() (ino:196-241) ------------------

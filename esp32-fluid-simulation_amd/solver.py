@@ -354,6 +354,7 @@ class BatchSolver:
         create = self._lib.sfl_batch_create_large if large else self._lib.sfl_batch_create
         capi.check(create(C.byref(self._h), device, dim_x, dim_y, batch))
         self.dim_x, self.dim_y, self.batch, self.device = dim_x, dim_y, batch, device
+        self._rec = (0, 0, 1)   # (first, count, scaling) of the running recording: the shape of what frames() reads
 
     def close(self):
         if self._h:
@@ -535,6 +536,57 @@ class BatchSolver:
         capi.check(self._lib.sfl_batch_render_rgb565(self._h, member, scaling, int(byteswap),
                                                      img.ctypes.data_as(C.POINTER(C.c_uint16)), img.nbytes))
         return img
+
+    def render_members(self, first: int = 0, count=None, scaling: int = 4, byteswap: bool = True) -> np.ndarray:
+        """The dye of members [first, first + count) -> RGB565 images, uint16[count, H, W] with H = scaling*(dim_x-1) and
+        W = scaling*(dim_y-1): image k is ``render_rgb565(first + k)`` bit for bit, all of them from one launch and one
+        copy (sfl_batch_render_members).  Synchronous; count None = to the end of the batch."""
+        count = self.batch - first if count is None else count
+        img = np.empty((max(count, 0), max(scaling, 0) * (self.dim_x - 1), max(scaling, 0) * (self.dim_y - 1)), np.uint16)
+        capi.check(self._lib.sfl_batch_render_members(self._h, first, count, scaling, int(byteswap),
+                                                      img.ctypes.data_as(C.POINTER(C.c_uint16)), img.nbytes))
+        return img
+
+    def record_start(self, every: int = 1, first: int = 0, count=None, scaling: int = 4, byteswap: bool = True,
+                     capacity: int = 64):
+        """Start the recorder (sfl_batch_record_start): from now on every `every`-th step of ``step_n``, ``step_n_each``
+        and ``step_n_until`` -- counted across calls -- leaves a frame of members [first, first + count) in device memory,
+        rendered between the step launches without a wait; `capacity` frames fit (device memory: capacity * count * H * W
+        * 2 bytes).  A step call that would complete more frames than are free raises SflError with ERR_STATE and steps
+        nothing: read the frames (:meth:`frames`) and call record_start again.  Called while recording, it starts afresh."""
+        count = self.batch - first if count is None else count
+        rc = self._lib.sfl_batch_record_start(self._h, every, first, count, scaling, int(byteswap), capacity)
+        if rc == capi.OK:
+            self._rec = (first, count, scaling)
+        elif self.record_info()[1] == 0:   # a failed allocation: the batch is not recording any more
+            self._rec = (0, 0, 1)
+        capi.check(rc)
+
+    def record_stop(self):
+        """Stop recording and free the frames."""
+        capi.check(self._lib.sfl_batch_record_stop(self._h))
+        self._rec = (0, 0, 1)
+
+    def record_info(self):
+        """(frames written, capacity, steps counted since record_start); (0, 0, 0) when not recording.  Never waits."""
+        frames, capacity, steps = C.c_int(), C.c_int(), C.c_int64()
+        capi.check(self._lib.sfl_batch_record_info(self._h, C.byref(frames), C.byref(capacity), C.byref(steps)))
+        return frames.value, capacity.value, steps.value
+
+    def frames(self, frame_first: int = 0, frame_count=None, first=None, count=None) -> np.ndarray:
+        """Recorded frames [frame_first, frame_first + frame_count) of members [first, first + count), uint16[F, count, H, W]
+        (sfl_batch_record_read; frames are not consumed).  Defaults: every frame written so far, the recorded members.
+        Member numbers are the batch's.  Synchronous; an empty array when there is nothing to read."""
+        written, _, _ = self.record_info()
+        rec_first, rec_count, scaling = self._rec
+        frame_count = written - frame_first if frame_count is None else frame_count
+        first = rec_first if first is None else first
+        count = rec_first + rec_count - first if count is None else count
+        out = np.empty((max(frame_count, 0), max(count, 0), scaling * (self.dim_x - 1), scaling * (self.dim_y - 1)), np.uint16)
+        for f in range(max(frame_count, 0)):
+            capi.check(self._lib.sfl_batch_record_read(self._h, frame_first + f, first, count,
+                                                       out[f].ctypes.data_as(C.POINTER(C.c_uint16)), out[f].nbytes))
+        return out
 
     def synchronize(self):
         capi.check(self._lib.sfl_batch_synchronize(self._h))

@@ -638,6 +638,45 @@ SFL_API int sfl_batch_setup_sketch_fields(sfl_batch *b);
 /* sfl_render_rgb565 of one member's dye.  Synchronous.                                            */
 SFL_API int sfl_batch_render_rgb565(sfl_batch *b, int member, int scaling, int byteswap, uint16_t *host_image,
                                     size_t bytes);
+/* --- the frames of many members: the draw task of a whole batch in ONE launch (one workgroup per tile of cell blocks of
+ *     one member, the tile's corner texels staged in LDS), and a recorder that renders while the batch steps ----------- */
+/* The images of members [first, first + count) of the CURRENT dye, member-major: image k (H = scaling * (dim_x - 1) rows
+ * of W = scaling * (dim_y - 1) uint16, i down the screen and j across, as sfl_render_rgb565) starts at pixel k * H * W
+ * and is, bit for bit, what sfl_batch_render_rgb565(b, first + k, scaling, byteswap, ...) writes.  One launch and one
+ * device-to-host copy whatever count is; the device buffer stays with the batch and grows when needed.  Synchronous.
+ * count == 0 does nothing.  b NULL, host_images NULL (count > 0), scaling outside 1..64, a range that is not inside the
+ * batch and bytes != count * H * W * 2 return SFL_ERR_INVALID before any GPU work.                                      */
+SFL_API int sfl_batch_render_members(sfl_batch *b, int first, int count, int scaling, int byteswap,
+                                     uint16_t *host_images, size_t bytes);
+/* Start recording: `capacity` frames of members [first, first + count) at this scaling and byte order are allocated on
+ * the device and the recorder's step count is set to 0.  From now on every step of sfl_batch_step_n, sfl_batch_step_n_each
+ * and sfl_batch_step_n_until counts, across calls, and after the step that makes the count a multiple of `every`, frame
+ * count / every - 1 is rendered from the dye that step left -- the dye sfl_batch_download would hand out if the call ended
+ * there.  The render is one launch on the batch's stream between the step launches: the step calls stay asynchronous and
+ * the host never waits.  Nothing else about the step calls changes: every field keeps its bits, sfl_batch_residual and
+ * sfl_batch_iterations keep their validity, queued forces still go into the first step.  sfl_batch_poisson_solve*,
+ * uploads and sfl_batch_setup_sketch_fields neither count nor record.
+ *   A step call whose n steps would complete more frames than are free is refused as a whole with SFL_ERR_STATE (the
+ * message names sfl_batch_record_read and sfl_batch_record_start), after the call's own argument checks and before
+ * anything is launched: fields, force queue, reports and step count stay untouched.  The recorder fills up at a frame
+ * boundary, so a caller who reads the frames and calls sfl_batch_record_start again whenever it is full keeps the phase.
+ *   Called while recording, it starts afresh: the frames are dropped, the count is 0 again, and the device buffer is
+ * reallocated only if it must grow.  b NULL, every < 1, capacity < 1 (or so large that the frames' bytes do not fit a
+ * size_t), scaling outside 1..64, count < 1 and a range that
+ * is not inside the batch return SFL_ERR_INVALID before any GPU work and leave a running recording as it was; a failed
+ * allocation returns SFL_ERR_NOMEM and leaves the batch not recording.  One frame may exceed 4 GiB.                    */
+SFL_API int sfl_batch_record_start(sfl_batch *b, int every, int first, int count, int scaling, int byteswap, int capacity);
+/* Stop recording and free the frames (sfl_batch_destroy frees them too).  Stopping a batch that is not recording is
+ * SFL_OK.  Afterwards steps record nothing and sfl_batch_record_read returns SFL_ERR_STATE.                             */
+SFL_API int sfl_batch_record_stop(sfl_batch *b);
+/* Frames written so far, the capacity, and the steps counted since sfl_batch_record_start.  Any out pointer may be NULL.
+ * For a batch that is not recording all three are 0 and the call returns SFL_OK.  Never waits.                          */
+SFL_API int sfl_batch_record_info(sfl_batch *b, int *frames, int *capacity, int64_t *steps);
+/* Copy members [first, first + count) of frame `frame` out, member-major as sfl_batch_render_members lays them out.  The
+ * numbers are the batch's member numbers and must lie inside the recorded range.  Frames are not consumed.  Synchronous.
+ * Not recording: SFL_ERR_STATE.  b NULL, host NULL (count > 0), frame outside [0, frames written), a range that is not
+ * inside the recorded one and bytes != count * H * W * 2 return SFL_ERR_INVALID before any GPU work.                    */
+SFL_API int sfl_batch_record_read(sfl_batch *b, int frame, int first, int count, uint16_t *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
