@@ -147,6 +147,10 @@ SIGNATURES = {
     "sfl_step_n": (_i, [_ctx, _i, _f, _f, _i, _f]),
     "sfl_queue_forces": (_i, [_ctx, _pi, _pf, _i]),
     "sfl_queue_drags": (_i, [_ctx, C.c_void_p, _i]),
+    "sfl_queue_forces_at": (_i, [_ctx, _i, _pi, _pf, _i]),
+    "sfl_queue_drags_at": (_i, [_ctx, _i, C.c_void_p, _i]),
+    "sfl_forces_pending": (_i, [_ctx, _pi, _pi]),
+    "sfl_forget_forces": (_i, [_ctx]),
     "sfl_setup_sketch_fields": (_i, [_ctx]),
     "sfl_render_rgb565": (_i, [_ctx, _i, _i, C.POINTER(C.c_uint16), _sz]),
     "sfl_synchronize": (_i, [_ctx]),
@@ -162,6 +166,9 @@ SIGNATURES = {
     "sfl_batch_download": (_i, [_ctx, _i, _i, _i, C.c_void_p, _sz]),
     "sfl_batch_field_device_ptr": (_i, [_ctx, _i, C.POINTER(C.c_void_p)]),
     "sfl_batch_queue_forces": (_i, [_ctx, _pi, _pi, _pf, _i]),
+    "sfl_batch_queue_forces_at": (_i, [_ctx, _i, _pi, _pi, _pf, _i]),
+    "sfl_batch_forces_pending": (_i, [_ctx, _pi, _pi]),
+    "sfl_batch_forget_forces": (_i, [_ctx]),
     "sfl_batch_step_n": (_i, [_ctx, _i, _f, _f, _i, _f]),
     "sfl_batch_poisson_solve": (_i, [_ctx, _f, _i, _f]),
     "sfl_batch_step_n_each": (_i, [_ctx, _i, C.POINTER(MemberParams)]),

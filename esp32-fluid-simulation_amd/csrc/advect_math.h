@@ -132,6 +132,20 @@ __device__ __forceinline__ float2 sample_global_vec2f(const float2 *p, const Sla
                                  [&](int a, int b) { return p[t + b * gs.dim_x + a]; });
 }
 
+// the same of a float2 field in LDS: the pointer carries the address space, so the gathers are LDS reads whatever the
+// compiler can or cannot infer about where p points (batch_play.hip: the source region changes from step to step).
+// p = the field's first float; the two components of a texel are read as floats and put together.
+typedef const __attribute__((address_space(3))) float lds_cfloat;
+template <bool NO_SLIP>
+__device__ __forceinline__ float2 sample_lds_vec2f(lds_cfloat *p, const Slab &gs, const SrcPos &s, float si, float sj)
+{
+    const int t = (s.cj - gs.grow0) * gs.dim_x + s.ci;
+    return sample_vec2f<NO_SLIP>(s, si, sj, gs.dim_x, gs.gdim_y, [&](int a, int b) {
+        const int c = 2 * (t + b * gs.dim_x + a);
+        return make_float2(p[c], p[c + 1]);
+    });
+}
+
 // calculate_divergence for one cell (finitediff.cpp:9-31), before the factor 1 / (2 dx); q points at the cell,
 // in an LDS window or an array in memory, rows `stride` apart
 __device__ __forceinline__ float divergence_sum(const float2 *q, int stride, int i, int gj, int i_max, int j_max)

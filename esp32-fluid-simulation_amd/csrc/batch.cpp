@@ -85,17 +85,24 @@ int check_range(sfl_batch *b, int field, int first, int count, const void *host,
     return SFL_OK;
 }
 
-// The queued forces in member order -- a stable counting sort, so each member keeps its queue order (the last write
-// to a cell wins, ino:264-269) -- copied to the device behind the launches queued so far.  *offsets = nullptr: none.
-int stage_forces(sfl_batch *b, const int **offsets, const int **cells, const float **vel)
+// The last step of the timeline that has a record, plus one: 0 for an empty timeline.
+int64_t timeline_steps(const sfl_batch *b) { return std::max<int64_t>(b->force_last - b->force_base + 1, 0); }
+
+// The timeline as one CSR table on the device (batch_state.h has the layout), for a call of n steps: a stable counting
+// sort by (step, member), so each member keeps its queue order within a step (the last write to a cell wins,
+// ino:264-269), copied behind the launches queued so far.  Nothing is done while the table on the device still holds
+// the rows this call needs: the timeline is staged once per change, not once per step.  A timeline longer than the call
+// is staged beyond it, as far as a table of 2^20 rows x members goes; a later call stages the rest.
+int stage_timeline(sfl_batch *b, int n)
 {
-    *offsets = nullptr;
-    *cells = nullptr;
-    *vel = nullptr;
-    const size_t n = b->force_member.size();
-    if (n == 0) return SFL_OK;
-    const size_t n_off = (size_t)b->batch + 1;
-    const size_t bytes = sizeof(int) * (n_off + 2 * n) + sizeof(float) * 2 * n;
+    const int64_t steps = timeline_steps(b), need = std::min<int64_t>(n, steps);
+    if (need == 0) return SFL_OK;
+    if (b->forces_staged && b->staged_base <= b->force_base && b->force_base + need <= b->staged_base + b->staged_rows) return SFL_OK;
+    const int64_t rows = std::min(steps, std::max<int64_t>(need, (1 << 20) / b->batch));
+    size_t n_rec = 0;
+    for (const sfl_batch::Force &f : b->forces) n_rec += f.step - b->force_base < rows;
+    const size_t n_off = (size_t)rows * b->batch + 1;
+    const size_t bytes = sizeof(int) * (n_off + 2 * n_rec) + sizeof(float) * 2 * n_rec;
     sfl_batch::Stage &st = b->stage[b->slot];
     b->slot ^= 1;
     if (!st.copied) HIP_TRY(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
@@ -110,6 +117,7 @@ int stage_forces(sfl_batch *b, const int **offsets, const int **cells, const flo
         HIP_TRY(hipHostMalloc(&st.host, bytes, hipHostMallocDefault));
         st.bytes = bytes;
     }
+    b->forces_staged = false;
     if (bytes > b->d_forces_bytes) {
         HIP_TRY(hipStreamSynchronize(b->stream));   // an earlier step may still read the old buffer: drain on growth only
         if (b->d_forces) (void)hipFree(b->d_forces);
@@ -120,28 +128,129 @@ int stage_forces(sfl_batch *b, const int **offsets, const int **cells, const flo
     }
     int *off = static_cast<int *>(st.host);
     int *hc = off + n_off;
-    float *hv = reinterpret_cast<float *>(hc + 2 * n);
+    float *hv = reinterpret_cast<float *>(hc + 2 * n_rec);
     std::fill(off, off + n_off, 0);
-    for (size_t k = 0; k < n; ++k) ++off[b->force_member[k] + 1];
+    const auto row_of = [&](const sfl_batch::Force &f) { return (size_t)(f.step - b->force_base) * b->batch + f.member; };
+    for (const sfl_batch::Force &f : b->forces)
+        if (f.step - b->force_base < rows) ++off[row_of(f) + 1];
     for (size_t m = 1; m < n_off; ++m) off[m] += off[m - 1];
+    b->staged_row_has.assign((size_t)rows, 0);
+    for (int64_t r = 0; r < rows; ++r) b->staged_row_has[r] = off[(r + 1) * b->batch] > off[r * b->batch];
     std::vector<int> next(off, off + n_off - 1);
-    for (size_t k = 0; k < n; ++k) {
-        const int at = next[b->force_member[k]]++;
-        hc[2 * at] = b->force_cells[2 * k];
-        hc[2 * at + 1] = b->force_cells[2 * k + 1];
-        hv[2 * at] = b->force_vel[2 * k];
-        hv[2 * at + 1] = b->force_vel[2 * k + 1];
+    for (const sfl_batch::Force &f : b->forces) {
+        if (f.step - b->force_base >= rows) continue;
+        const int at = next[row_of(f)]++;
+        hc[2 * at] = f.i;
+        hc[2 * at + 1] = f.j;
+        hv[2 * at] = f.vx;
+        hv[2 * at + 1] = f.vy;
     }
     HIP_TRY(hipMemcpyAsync(b->d_forces, st.host, bytes, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipEventRecord(st.copied, b->stream));
     st.pending = true;
-    b->force_member.clear();
-    b->force_cells.clear();
-    b->force_vel.clear();
+    b->staged_base = b->force_base;
+    b->staged_rows = (int)rows;
+    b->staged_records = n_rec;
+    b->forces_staged = true;
+    return SFL_OK;
+}
+
+// The rows of the staged table from step k of the call on (stage_timeline has run): *rows of them, 0 and nullptr when
+// the table ends before that step.  cells and vel: the table's records, which a row's offsets index.
+const int *staged_rows_from(const sfl_batch *b, int k, int *rows, const int **cells, const float **vel)
+{
+    const int64_t r = b->force_base + k - b->staged_base;
+    *rows = 0;
+    *cells = nullptr;
+    *vel = nullptr;
+    if (!b->forces_staged || r < 0 || r >= b->staged_rows) return nullptr;
     const int *d_off = static_cast<const int *>(b->d_forces);
-    *offsets = d_off;
+    const size_t n_off = (size_t)b->staged_rows * b->batch + 1;
+    *rows = (int)(b->staged_rows - r);
     *cells = d_off + n_off;
-    *vel = reinterpret_cast<const float *>(d_off + n_off + 2 * n);
+    *vel = reinterpret_cast<const float *>(d_off + n_off + 2 * b->staged_records);
+    return d_off + (size_t)r * b->batch;
+}
+
+// does any of the steps [first, last) of the call have a record?  (stage_timeline has run: the table holds every row of
+// the call that has one)
+bool staged_has(const sfl_batch *b, int first, int last)
+{
+    if (!b->forces_staged) return false;
+    for (int64_t r = b->force_base + first - b->staged_base; r < b->force_base + last - b->staged_base && r < b->staged_rows; ++r)
+        if (r >= 0 && b->staged_row_has[(size_t)r]) return true;
+    return false;
+}
+
+// BatchStep::force_offsets of step k of the call: that step's row, nullptr for a step without records (as a call without
+// queued forces has always passed)
+void step_forces(const sfl_batch *b, int k, sfl::BatchStep *a)
+{
+    int rows = 0;
+    a->force_offsets = staged_rows_from(b, k, &rows, &a->step.force_cells, &a->step.force_vel);
+    if (a->force_offsets && !b->staged_row_has[(size_t)(b->force_base + k - b->staged_base)]) a->force_offsets = nullptr;
+}
+
+// n steps have been launched: their records go, the later ones move down by n
+void consume_forces(sfl_batch *b, int n)
+{
+    b->force_base += n;
+    const auto gone = [&](const sfl_batch::Force &f) { return f.step < b->force_base; };
+    b->forces.erase(std::remove_if(b->forces.begin(), b->forces.end(), gone), b->forces.end());
+    if (b->forces.empty()) b->force_last = -1;
+}
+
+// How a step call runs its solve: the same for every member, per member (and the update norm), per member by the
+// stopping rule (and the norm and the iterations).
+enum StepKind { kUniform, kEach, kUntil };
+
+// The n steps of a step call, behind its checks and the staging of its members: the timeline staged, the launches, the
+// ping-pong, the recorder, the timeline consumed.  `a`: the shape, div, p and, for kUniform, the parameters.
+// One launch per step -- but `steps` steps per launch (batch_play.hip) for a call that could not be made before there
+// was a timeline: n >= 2 steps of small members with a record in some step of [1, n), not by the stopping rule.  With a
+// recorder on, such a call is cut into launches that end at the steps whose frame is due, the render between them.
+int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
+{
+    SFL_TRY(stage_timeline(b, n));
+    if (kind != kUntil && !b->large && n >= 2 && staged_has(b, 1, n)) {
+        for (int done = 0; done < n;) {
+            const int steps = sfl::host::record_run(b, n - done);
+            sfl::BatchPlay play{};
+            play.step = a.step;
+            play.force_rows = staged_rows_from(b, done, &play.rows, &play.step.force_cells, &play.step.force_vel);
+            play.rows = std::min(play.rows, steps);
+            play.steps = steps;
+            play.step.v_in = b->vel;
+            play.step.v_out = b->vel_tmp;
+            play.step.col_in = b->col;
+            play.step.col_out = b->col_tmp;
+            HIP_TRY(sfl::launch_batch_play(b->stream, play, b->batch, kind == kEach ? b->d_members : nullptr, b->d_report));
+            std::swap(b->vel, b->vel_tmp);
+            if (steps & 1) std::swap(b->col, b->col_tmp);   // (the dye ping-pongs inside the launch)
+            SFL_TRY(sfl::host::record_step(b, steps));
+            done += steps;
+        }
+        consume_forces(b, n);
+        return SFL_OK;
+    }
+    for (int k = 0; k < n; ++k) {
+        step_forces(b, k, &a);
+        a.step.v_in = b->vel;
+        a.step.v_out = b->vel_tmp;
+        a.step.col_in = b->col;
+        a.step.col_out = b->col_tmp;
+        if (kind == kUniform)
+            HIP_TRY((b->large ? sfl::launch_batch_large_step : sfl::launch_batch_step)(b->stream, a, b->batch));
+        else if (kind == kEach)
+            HIP_TRY((b->large ? sfl::launch_batch_large_step_each : sfl::launch_batch_step_each)(b->stream, a, b->batch, b->d_members, b->d_report));
+        else   // (the first step starts every member's sum of iterations, the later ones add to it)
+            HIP_TRY((b->large ? sfl::launch_batch_large_step_until : sfl::launch_batch_step_until)(b->stream, a, b->batch, b->d_members, b->d_stops,
+                                                                                               b->d_report, b->d_counts, k > 0));
+        std::swap(b->vel, b->vel_tmp);  // ino:255
+        std::swap(b->col, b->col_tmp);  // ino:286
+        SFL_TRY(sfl::host::record_step(b));
+    }
+    consume_forces(b, n);
     return SFL_OK;
 }
 
@@ -398,16 +507,42 @@ int sfl_batch_field_device_ptr(sfl_batch *b, int field, void **dev_ptr)
     return SFL_OK;
 }
 
-int sfl_batch_queue_forces(sfl_batch *b, const int *members, const int *cells_ij, const float *vel_xy, int n)
+int sfl_batch_queue_forces_at(sfl_batch *b, int step, const int *members, const int *cells_ij, const float *vel_xy, int n)
 {
     if (!b || n < 0 || (n > 0 && (!members || !cells_ij || !vel_xy))) return fail(SFL_ERR_INVALID, "bad arguments");
+    if (step < 0) return fail(SFL_ERR_INVALID, "step must be >= 0 (got %d): nothing queued", step);
     for (int k = 0; k < n; ++k)   // all or nothing
         if (members[k] < 0 || members[k] >= b->batch)
             return fail(SFL_ERR_INVALID, "force %d names member %d, outside the batch's [0, %d): nothing queued", k,
                         members[k], b->batch);
-    b->force_member.insert(b->force_member.end(), members, members + n);
-    b->force_cells.insert(b->force_cells.end(), cells_ij, cells_ij + 2 * (size_t)n);
-    b->force_vel.insert(b->force_vel.end(), vel_xy, vel_xy + 2 * (size_t)n);
+    for (int k = 0; k < n; ++k)
+        b->forces.push_back({b->force_base + step, members[k], cells_ij[2 * k], cells_ij[2 * k + 1], vel_xy[2 * k], vel_xy[2 * k + 1]});
+    if (n > 0) {
+        b->forces_staged = false;
+        b->force_last = std::max(b->force_last, b->force_base + step);
+    }
+    return SFL_OK;
+}
+
+int sfl_batch_queue_forces(sfl_batch *b, const int *members, const int *cells_ij, const float *vel_xy, int n)
+{
+    return sfl_batch_queue_forces_at(b, 0, members, cells_ij, vel_xy, n);
+}
+
+int sfl_batch_forces_pending(sfl_batch *b, int *records, int *last_step)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    if (records) *records = (int)std::min<size_t>(b->forces.size(), INT_MAX);
+    if (last_step) *last_step = (int)(timeline_steps(b) - 1);
+    return SFL_OK;
+}
+
+int sfl_batch_forget_forces(sfl_batch *b)
+{
+    if (!b) return fail(SFL_ERR_INVALID, "batch is NULL");
+    b->forces.clear();
+    b->forces_staged = false;
+    b->force_last = -1;
     return SFL_OK;
 }
 
@@ -429,18 +564,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     a.step.dt = dt;
     a.step.two_dx_inv = two_dx_inv(dx);
     a.step.prm = sor_params(dx, omega);
-    for (int k = 0; k < n; ++k) {
-        // queued forces go into the first step (the queue is empty after it)
-        SFL_TRY(stage_forces(b, &a.force_offsets, &a.step.force_cells, &a.step.force_vel));
-        a.step.v_in = b->vel;
-        a.step.v_out = b->vel_tmp;
-        a.step.col_in = b->col;
-        a.step.col_out = b->col_tmp;
-        HIP_TRY((b->large ? sfl::launch_batch_large_step : sfl::launch_batch_step)(b->stream, a, b->batch));
-        std::swap(b->vel, b->vel_tmp);  // ino:255
-        std::swap(b->col, b->col_tmp);  // ino:286
-        SFL_TRY(sfl::host::record_step(b));
-    }
+    SFL_TRY(run_steps(b, n, kUniform, a));
     return SFL_OK;
 }
 
@@ -469,18 +593,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
     a.step.p = b->p;
     a.step.dim_x = b->dim_x;
     a.step.dim_y = b->dim_y;
-    for (int k = 0; k < n; ++k) {
-        // queued forces go into the first step (the queue is empty after it)
-        SFL_TRY(stage_forces(b, &a.force_offsets, &a.step.force_cells, &a.step.force_vel));
-        a.step.v_in = b->vel;
-        a.step.v_out = b->vel_tmp;
-        a.step.col_in = b->col;
-        a.step.col_out = b->col_tmp;
-        HIP_TRY((b->large ? sfl::launch_batch_large_step_each : sfl::launch_batch_step_each)(b->stream, a, b->batch, b->d_members, b->d_report));
-        std::swap(b->vel, b->vel_tmp);  // ino:255
-        std::swap(b->col, b->col_tmp);  // ino:286
-        SFL_TRY(sfl::host::record_step(b));
-    }
+    SFL_TRY(run_steps(b, n, kEach, a));
     b->report_valid = true;   // of the last step's solve: the divergence and pressure a download hands out now
     return SFL_OK;
 }
@@ -511,20 +624,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
     a.step.p = b->p;
     a.step.dim_x = b->dim_x;
     a.step.dim_y = b->dim_y;
-    for (int k = 0; k < n; ++k) {
-        // queued forces go into the first step (the queue is empty after it)
-        SFL_TRY(stage_forces(b, &a.force_offsets, &a.step.force_cells, &a.step.force_vel));
-        a.step.v_in = b->vel;
-        a.step.v_out = b->vel_tmp;
-        a.step.col_in = b->col;
-        a.step.col_out = b->col_tmp;
-        // (the first step starts every member's sum of iterations, the later ones add to it)
-        HIP_TRY((b->large ? sfl::launch_batch_large_step_until : sfl::launch_batch_step_until)(b->stream, a, b->batch, b->d_members, b->d_stops,
-                                                                                           b->d_report, b->d_counts, k > 0));
-        std::swap(b->vel, b->vel_tmp);  // ino:255
-        std::swap(b->col, b->col_tmp);  // ino:286
-        SFL_TRY(sfl::host::record_step(b));
-    }
+    SFL_TRY(run_steps(b, n, kUntil, a));
     b->report_valid = b->counts_valid = true;   // of the last step's solve; the sum over all n
     return SFL_OK;
 }

@@ -78,6 +78,23 @@ hipError_t launch_batch_large_step_until(hipStream_t s, const BatchStep &a, int 
 hipError_t launch_batch_large_solve_until(hipStream_t s, float *p, const float *d, int dim_x, int dim_y, int batch,
                                           const BatchMember *members, const BatchStop *stops, float *report, int *counts);
 
+// ---- `steps` consecutive steps of every member in ONE launch (batch_play.hip) ---------------------------------------
+// For the batches of sfl_batch_create (16 B of LDS per cell).  `step` describes member 0 as in BatchStep; the velocity is
+// read from step.v_in before the first step and written to step.v_out, with step.div and step.p, after the last one; the
+// dye ping-pongs between step.col_in and step.col_out inside the launch: step k reads col_in when k is even and col_out
+// when it is odd, and writes the other, so the dye ends in col_out when `steps` is odd and in col_in when it is even.
+// Forces: force_rows == nullptr = none; else row k, k in [0, rows), is the BatchStep::force_offsets of step k -- the
+// `batch` + 1 ints at force_rows + k * batch, indices into step.force_cells / step.force_vel -- and steps k >= rows have
+// none (rows <= steps).  members == nullptr: every member runs step's dt, two_dx_inv, iters and prm and nothing is
+// reported; else records and report as for launch_batch_step_each, the update norm being that of the last step's solve.
+// Every field ends up bit for bit where `steps` launches of launch_batch_step[_each] leave it.  steps >= 1.
+struct BatchPlay {
+    SmallStep step;
+    const int *force_rows;
+    int rows, steps;
+};
+hipError_t launch_batch_play(hipStream_t s, const BatchPlay &a, int batch, const BatchMember *members, float *report);
+
 // ---- the draw task of many members in one launch (batch_render.hip) -----------------------------------------------
 // Image k of `images` (k in [0, count), member-major: image k starts at pixel k * H * W, H = scaling * (dim_x - 1) rows of
 // W = scaling * (dim_y - 1) uint16) = launch_render_rgb565 of the dye at colour_of_first_member + 3 * k * dim_x * dim_y,

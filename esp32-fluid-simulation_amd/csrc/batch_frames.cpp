@@ -73,11 +73,18 @@ int record_admit(sfl_batch *b, int n)
     return SFL_OK;
 }
 
-int record_step(sfl_batch *b)
+int record_run(const sfl_batch *b, int n)
+{
+    const sfl_batch::Recorder &r = b->rec;
+    if (!r.on) return n;
+    return (int)std::min<int64_t>(n, r.every - r.steps % r.every);
+}
+
+int record_step(sfl_batch *b, int steps)
 {
     sfl_batch::Recorder &r = b->rec;
     if (!r.on) return SFL_OK;
-    ++r.steps;
+    r.steps += steps;
     if (r.steps % r.every != 0) return SFL_OK;
     const int frame = (int)(r.steps / r.every) - 1;   // < capacity: record_admit has let the call through
     uint16_t *images = b->d_frames + (size_t)frame * r.count * image_pixels(b, r.scaling);

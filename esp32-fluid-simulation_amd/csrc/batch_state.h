@@ -16,13 +16,28 @@ struct sfl_batch {
     float *vel = nullptr, *vel_tmp = nullptr;
     uint32_t *col = nullptr, *col_tmp = nullptr;
     float *div = nullptr, *p = nullptr;
-    // queued point forces (ino:264-269), in queue order
-    std::vector<int> force_member, force_cells;
-    std::vector<float> force_vel;
-    // staged forces of a step: B + 1 member offsets, then the cells, then the velocities, in ONE device buffer filled
-    // from pinned memory; two host slots used alternately, each rewritten only after its last copy has completed
+    // the timeline of queued point forces (ino:264-269; include/sfl.h, "the timeline rule"), in queue order.  A record
+    // carries the ABSOLUTE number of its step; force_base is the number of step 0, the next step any step call runs
+    struct Force {
+        int64_t step;
+        int member, i, j;
+        float vx, vy;
+    };
+    std::vector<Force> forces;
+    int64_t force_base = 0;
+    int64_t force_last = -1;   // the largest absolute step any record carries; < force_base: the timeline is empty
+    // the staged timeline: ONE CSR table on the device, filled from pinned memory (two host slots used alternately, each
+    // rewritten only after its last copy has completed).  Row r, r in [0, staged_rows), belongs to step staged_base + r
+    // and is the BatchStep::force_offsets of that step: the `batch` + 1 ints at r * batch.  staged_rows * batch + 1
+    // ints, then the cells of the staged_records records sorted by (step, member, queue order), then their velocities.
+    // Staged once per change of the timeline (forces_staged), not once per step; staged_row_has[r]: row r has a record.
     void *d_forces = nullptr;
     size_t d_forces_bytes = 0;
+    bool forces_staged = false;
+    int64_t staged_base = 0;
+    int staged_rows = 0;
+    size_t staged_records = 0;
+    std::vector<char> staged_row_has;
     struct Stage {
         void *host = nullptr;
         size_t bytes = 0;
@@ -68,10 +83,13 @@ namespace host {
 // The two hooks of the step calls (batch.cpp) into the recorder (batch_frames.cpp); both do nothing for a batch that is
 // not recording.  record_admit: SFL_ERR_STATE if the n steps of a call would complete more frames than are free -- after
 // the call's own argument checks, before anything is staged or launched.  record_step: one step has been launched and
-// the ping-pong swapped; counts it and, when the count reaches a multiple of `every`, launches the frame's render on the
+// the ping-pong swapped; counts it (or the `steps` steps of one launch) and, when the count reaches a multiple of `every`, launches the frame's render on the
 // batch's stream behind it.
 int record_admit(sfl_batch *b, int n);
-int record_step(sfl_batch *b);
+int record_step(sfl_batch *b, int steps = 1);
+// ... for a launch that runs several steps (batch_play.hip): how many of the next n steps may run before a frame is due
+// (n for a batch that is not recording), and record_step(b, steps) once they are launched: no frame falls inside them.
+int record_run(const sfl_batch *b, int n);
 
 }  // namespace host
 }  // namespace sfl

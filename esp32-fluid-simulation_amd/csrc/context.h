@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -218,9 +219,17 @@ struct sfl_context {
     bool wait_error_seen = false;  // word [2] was found raised (download, a step's report): every call fails until sfl_synchronize
                                    // has reported and cleared it
 
-    // queued point forces (ino:264-269)
+    // queued point forces (ino:264-269): the records of step 0 of the timeline (include/sfl.h, "the timeline rule"), in
+    // queue order; those of the steps behind it wait in force_later under their ABSOLUTE step number, force_base being
+    // the number of step 0 (forces_advance: one step has run)
     std::vector<int> force_cells;
     std::vector<float> force_vel;
+    struct StepForces {
+        std::vector<int> cells;
+        std::vector<float> vel;
+    };
+    std::map<int64_t, StepForces> force_later;
+    int64_t force_base = 0;
     int *d_force_cells = nullptr;
     float *d_force_vel = nullptr;
     int d_force_cap = 0;
@@ -359,6 +368,8 @@ int advect_velocity_planned(sfl_context *ctx, const std::vector<sfl_context *> &
 int advect_color_planned(sfl_context *ctx, const std::vector<sfl_context *> &peers, float dt, int no_slip,
                          const AdvectPlan &plan);
 int apply_queued_forces(sfl_context *c);
+// one step of the context (and of its in-process peers) has run: what is left of step 0 goes, step 1 becomes step 0
+void forces_advance(sfl_context *ctx);
 int stage_queued_forces(sfl_context *c, int *count);
 int project_and_advect_color(sfl_context *ctx, float dt, float dx, int halo, bool report, bool halo_sent = false);
 bool can_fuse_divergence(const sfl_context *c);

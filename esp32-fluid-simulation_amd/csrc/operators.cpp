@@ -209,6 +209,20 @@ int stage_queued_forces(sfl_context *c, int *count)
     return SFL_OK;
 }
 
+void forces_advance(sfl_context *ctx)
+{
+    for (sfl_context *c : peers_of(ctx)) {
+        c->force_cells.clear();
+        c->force_vel.clear();
+        ++c->force_base;
+        const auto next = c->force_later.find(c->force_base);
+        if (next == c->force_later.end()) continue;
+        c->force_cells.swap(next->second.cells);
+        c->force_vel.swap(next->second.vel);
+        c->force_later.erase(next);
+    }
+}
+
 int apply_queued_forces(sfl_context *c)
 {
     int n = 0;
@@ -392,22 +406,32 @@ int sfl_subtract_gradient(sfl_context *ctx, float dx)
     return SFL_OK;
 }
 
-int sfl_queue_forces(sfl_context *ctx, const int *cells_ij, const float *vel_xy, int n)
+int sfl_queue_forces_at(sfl_context *ctx, int step, const int *cells_ij, const float *vel_xy, int n)
 {
     if (!ctx || n < 0 || (n > 0 && (!cells_ij || !vel_xy))) return fail(SFL_ERR_INVALID, "bad arguments");
+    if (step < 0) return fail(SFL_ERR_INVALID, "step must be >= 0 (got %d): nothing queued", step);
+    if (n == 0) return SFL_OK;
     for (sfl_context *c : peers_of(ctx)) {
-        c->force_cells.insert(c->force_cells.end(), cells_ij, cells_ij + 2 * n);
-        c->force_vel.insert(c->force_vel.end(), vel_xy, vel_xy + 2 * n);
+        std::vector<int> &cells = step == 0 ? c->force_cells : c->force_later[c->force_base + step].cells;
+        std::vector<float> &vel = step == 0 ? c->force_vel : c->force_later[c->force_base + step].vel;
+        cells.insert(cells.end(), cells_ij, cells_ij + 2 * (size_t)n);
+        vel.insert(vel.end(), vel_xy, vel_xy + 2 * (size_t)n);
     }
     return SFL_OK;
+}
+
+int sfl_queue_forces(sfl_context *ctx, const int *cells_ij, const float *vel_xy, int n)
+{
+    return sfl_queue_forces_at(ctx, 0, cells_ij, vel_xy, n);
 }
 
 // The sketch's own message (ino:45-48) with the sketch's own transform (ino:264-269): the touch task speaks
 // graphics coordinates, the sim Cartesian ones rotated by 90 degrees -- cell = index(coords.y, coords.x),
 // velocity = (velocity.y, velocity.x).
-int sfl_queue_drags(sfl_context *ctx, const sfl_drag *msgs, int n)
+int sfl_queue_drags_at(sfl_context *ctx, int step, const sfl_drag *msgs, int n)
 {
     if (!ctx || n < 0 || (n > 0 && !msgs)) return fail(SFL_ERR_INVALID, "bad arguments");
+    if (step < 0) return fail(SFL_ERR_INVALID, "step must be >= 0 (got %d): nothing queued", step);
     std::vector<int> cells((size_t)2 * n);
     std::vector<float> vel((size_t)2 * n);
     for (int k = 0; k < n; ++k) {
@@ -420,7 +444,34 @@ int sfl_queue_drags(sfl_context *ctx, const sfl_drag *msgs, int n)
         vel[2 * k] = msgs[k].vel_y;                           // ino:266: swapped(msg.velocity.y, msg.velocity.x)
         vel[2 * k + 1] = msgs[k].vel_x;
     }
-    return sfl_queue_forces(ctx, cells.data(), vel.data(), n);
+    return sfl_queue_forces_at(ctx, step, cells.data(), vel.data(), n);
+}
+
+int sfl_queue_drags(sfl_context *ctx, const sfl_drag *msgs, int n) { return sfl_queue_drags_at(ctx, 0, msgs, n); }
+
+int sfl_forces_pending(sfl_context *ctx, int *records, int *last_step)
+{
+    if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
+    size_t count = ctx->force_cells.size() / 2;
+    int64_t last = count ? 0 : -1;
+    for (const auto &kv : ctx->force_later) {
+        count += kv.second.cells.size() / 2;
+        last = kv.first - ctx->force_base;   // (ascending keys: the last one stands)
+    }
+    if (records) *records = (int)std::min<size_t>(count, INT_MAX);
+    if (last_step) *last_step = (int)last;
+    return SFL_OK;
+}
+
+int sfl_forget_forces(sfl_context *ctx)
+{
+    if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
+    for (sfl_context *c : peers_of(ctx)) {
+        c->force_cells.clear();
+        c->force_vel.clear();
+        c->force_later.clear();
+    }
+    return SFL_OK;
 }
 
 int sfl_setup_sketch_fields(sfl_context *c)

@@ -291,20 +291,9 @@ static int step_seam(sfl_context *c, float dt, float dx)
     return SFL_OK;
 }
 
-}  // namespace host
-}  // namespace sfl
-
-using namespace sfl::host;
-
-extern "C" {
-
-int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
+// sfl_step behind its checks: the step that takes the records of step 0 of the timeline
+static int step_of_timeline(sfl_context *ctx, float dt, float dx, int iters, float omega)
 {
-    if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
-    if (ctx->nranks > 1 && ctx->opt.advect_halo == 0 && ctx->color_unsettled && ctx->unsettled_dt == dt && ctx->force_cells.empty())
-        SFL_TRY(advect_interior_early(ctx, dt));
-    SFL_TRY(settle_color(ctx, true));
-    SFL_TRY(check_wait_error(ctx));
     if (small_grid(ctx)) return small_grid_step(ctx, dt, dx, iters, omega);
     if (ctx->nranks > 1 && ctx->opt.advect_halo == 0) return slab_step_auto(ctx, dt, dx, iters, omega);
     if (can_fuse_divergence(ctx)) {
@@ -324,6 +313,26 @@ int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
     return SFL_OK;
 }
 
+}  // namespace host
+}  // namespace sfl
+
+using namespace sfl::host;
+
+extern "C" {
+
+int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
+{
+    if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
+    if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);   // (refused with the timeline untouched)
+    if (ctx->nranks > 1 && ctx->opt.advect_halo == 0 && ctx->color_unsettled && ctx->unsettled_dt == dt && ctx->force_cells.empty())
+        SFL_TRY(advect_interior_early(ctx, dt));
+    SFL_TRY(settle_color(ctx, true));
+    SFL_TRY(check_wait_error(ctx));
+    SFL_TRY(step_of_timeline(ctx, dt, dx, iters, omega));
+    forces_advance(ctx);   // the records of step 0 are consumed, the later ones move down by one (include/sfl.h)
+    return SFL_OK;
+}
+
 // The loop of the sim task (ino:249-289) calls the step back to back.  n steps in one call give the library the one
 // fusion a per-step API has no place for: between two steps the projected velocity is written by the last kernel of
 // one and read straight back by the first kernel of the next -- the seam kernel does both and never stores it
@@ -332,6 +341,7 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
 {
     if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
+    if (n > 0 && iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     SFL_TRY(settle_color(ctx, true));
     SFL_TRY(check_wait_error(ctx));
     const int64_t cells = (int64_t)ctx->dim_x * ctx->gdim_y;
@@ -342,17 +352,24 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
         for (int k = 0; k < n; ++k) SFL_TRY(sfl_step(ctx, dt, dx, iters, omega));
         return SFL_OK;
     }
-    // head of the first step: as sfl_step (queued forces go between its advection and its divergence, ino:264-269)
-    if (can_fuse_divergence(ctx)) {
-        SFL_TRY(advect_velocity_and_divergence(ctx, dt, dx));
-    } else {
-        SFL_TRY(sfl_advect_velocity(ctx, dt, 1));
-        SFL_TRY(apply_queued_forces(ctx));
-        SFL_TRY(sfl_calculate_divergence(ctx, dx));
-    }
+    // A step's head (advection, forces, divergence) is run as sfl_step runs it -- the step's records go between its
+    // advection and its divergence, ino:264-269 -- unless the seam kernel of the step before has run it already: that
+    // kernel joins the tail of step k with the head of step k + 1, which it can do when step k + 1 has no records.
+    bool head_done = false;
     for (int k = 0; k < n; ++k) {
+        if (!head_done) {
+            if (can_fuse_divergence(ctx)) {
+                SFL_TRY(advect_velocity_and_divergence(ctx, dt, dx));
+            } else {
+                SFL_TRY(sfl_advect_velocity(ctx, dt, 1));
+                SFL_TRY(apply_queued_forces(ctx));
+                SFL_TRY(sfl_calculate_divergence(ctx, dx));
+            }
+        }
         SFL_TRY(sfl_poisson_solve(ctx, dx, iters, omega));                                        // ino:275
-        if (k + 1 < n)
+        forces_advance(ctx);   // step k's records are applied: step 0 of the timeline is now step k + 1
+        head_done = k + 1 < n && ctx->force_cells.empty();
+        if (head_done)
             SFL_TRY(step_seam(ctx, dt, dx));                                                      // ino:276, :281-287 | :252-256, :274
         else
             SFL_TRY(project_and_advect_color(ctx, dt, dx, ctx->opt.advect_halo, false));          // ino:276 + ino:281-287

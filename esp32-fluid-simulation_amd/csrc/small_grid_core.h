@@ -180,7 +180,7 @@ struct UntilResult {
 // < cap and once more at the iteration the solve ends with: the update norm u_k of the pressure as it stands, formed
 // FROM THE REGISTERS OF THE SOLVE: p_gs = kf * (rhs - ((((z + W) + E) + S) + N)) with the neighbours of both colours
 // read from LDS (nothing is updated in between), |p_gs - own| as unsigned bits -- own is the bit pattern the thread
-// stored into p[c], rhs the product dx * d[c] of batch_grid.hip's update_norm_in_lds: term for term that walk's
+// stored into p[c], rhs the product dx * d[c] of update_norm_in_lds (below): term for term that walk's
 // arithmetic, without its reads of d and its index derivation.  One cell at a time, not a colour's cells together as a
 // pass reads them: what a check keeps in flight comes on top of everything the iteration loop keeps in registers, and
 // the budget is 64 (profiles/batch_until.txt has the forms tried).  The maximum: wave by __shfl_xor, then one LDS
@@ -259,6 +259,53 @@ __device__ __forceinline__ void sor_warm_in_lds(float *p, const float *d, int di
         for (int k = 0; k < kCellsPerColour; ++k)
             if (t.cm[colour][k] >> 20) t.own[colour][k] = p[t.cm[colour][k] & 0xffff];
     for (int it = 0; it < iters; ++it) sor_iteration(t, p, dim_x, prm);
+}
+
+// ---- the update norm of one member: max over all cells of |p_gs(c) - p(c)| on the pressure as it stands ------------
+// (what the *_each kernels of batch_grid.hip and batch_play.hip end with)
+// p_gs is the value a plain Gauss-Seidel update would put into the cell, in the algebra of sor_in_lds: (((z + W) + E)
+// + S) + N with -0.0f for an absent neighbour, z = -0.0f inside and +0.0f on the perimeter, k = -1/2, -1/3, -1/4
+// (poisson.cpp:67-89, :107-109).  Nothing is updated: both colours are read from the same p.  The maximum is taken over
+// the bit patterns of |p_gs - p| as unsigned integers, which orders finite values and +inf as floats do and lets any NaN
+// win: a diverged member reports a NaN, never a finite number.  A maximum does not depend on the order of reduction.
+// p and d are only read, so no barrier is needed in front as long as the caller's last writes to them are behind one;
+// `worst` is LDS of its own (static, 4 B), touched by nothing else.  One plain store by thread 0.
+template <int kT>
+__device__ __forceinline__ void update_norm_in_lds(const float *p, const float *d, int dim_x, int dim_y, float dx, float *out)
+{
+    __shared__ unsigned worst;
+    if (threadIdx.x == 0) worst = 0u;
+    const int cells = dim_x * dim_y, i_max = dim_x - 1, j_max = dim_y - 1;
+    unsigned m = 0u;
+    // (gj, i) of the thread's cells by stepping, one division per thread instead of one per cell: the pass costs about
+    // what the divisions cost (profiles/batch_params.txt)
+    const int step_j = kT / dim_x, step_i = kT - step_j * dim_x;   // workgroup-uniform
+    int gj = (int)threadIdx.x / dim_x, i = (int)threadIdx.x - gj * dim_x;
+    for (int c = threadIdx.x; c < cells; c += kT, gj += step_j, i += step_i) {
+        if (i >= dim_x) {
+            i -= dim_x;
+            ++gj;
+        }
+        const int present = (i > 0) + (i < i_max) + (gj > 0) + (gj < j_max);
+        const float w = (i > 0) ? p[c - 1] : -0.0f;
+        const float e = (i < i_max) ? p[c + 1] : -0.0f;
+        const float s = (gj > 0) ? p[c - dim_x] : -0.0f;
+        const float n = (gj < j_max) ? p[c + dim_x] : -0.0f;
+        const float z = (present == 4) ? -0.0f : 0.0f;
+        const float kf = (present == 2) ? (float)(-1.0 / 2.0) : (present == 3) ? (float)(-1.0 / 3.0) : -0.25f;
+        const float sum = (((z + w) + e) + s) + n;
+        const float p_gs = kf * (dx * d[c] - sum);
+        const unsigned bits = __float_as_uint(p_gs - p[c]) & 0x7fffffffu;   // |p_gs - p|
+        m = bits > m ? bits : m;
+    }
+    for (int o = 32; o > 0; o >>= 1) {   // the wave's maximum
+        const unsigned t = __shfl_xor(m, o);
+        m = t > m ? t : m;
+    }
+    __syncthreads();   // worst = 0 is visible
+    if ((threadIdx.x & 63) == 0) atomicMax(&worst, m);
+    __syncthreads();
+    if (threadIdx.x == 0) *out = __uint_as_float(worst);
 }
 
 // ---- poisson_solve (poisson.cpp:114-125) alone: d_in -> p_out of ONE grid ------------------------

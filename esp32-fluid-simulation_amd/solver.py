@@ -297,19 +297,30 @@ class Solver:
         """n steps in one call (sfl_step_n): the same results as n x step(), fused across the step boundaries."""
         capi.check(self._lib.sfl_step_n(self._h, n, dt, dx, iters, omega))
 
-    def queue_forces(self, cells_ij, vel_xy):
+    def queue_forces(self, cells_ij, vel_xy, step: int = 0):
+        """Point forces for step `step` of the steps to come (0: the next one); the timeline rule of include/sfl.h."""
         cells = np.ascontiguousarray(cells_ij, np.int32).reshape(-1, 2)
         vel = np.ascontiguousarray(vel_xy, np.float32).reshape(-1, 2)
-        capi.check(self._lib.sfl_queue_forces(
-            self._h, cells.ctypes.data_as(C.POINTER(C.c_int)),
+        capi.check(self._lib.sfl_queue_forces_at(
+            self._h, step, cells.ctypes.data_as(C.POINTER(C.c_int)),
             vel.ctypes.data_as(C.POINTER(C.c_float)), len(cells)))
 
-    def queue_drags(self, drags):
+    def forces_pending(self):
+        """(records, last_step) of the timeline of queued forces; last_step is -1 when it is empty."""
+        records, last = C.c_int(0), C.c_int(0)
+        capi.check(self._lib.sfl_forces_pending(self._h, C.byref(records), C.byref(last)))
+        return records.value, last.value
+
+    def forget_forces(self):
+        """Empties the timeline of queued forces."""
+        capi.check(self._lib.sfl_forget_forces(self._h))
+
+    def queue_drags(self, drags, step: int = 0):
         """drags: iterable of (coords_x, coords_y, velocity_x, velocity_y) in the sketch's graphics coordinates
-        (struct drag, ino:45-48); transformed like ino:264-269 by the library."""
+        (struct drag, ino:45-48); transformed like ino:264-269 by the library.  step: as for queue_forces."""
         drags = list(drags)
         arr = (capi.Drag * max(len(drags), 1))(*[capi.Drag(int(a), int(b), float(c), float(d)) for a, b, c, d in drags])
-        capi.check(self._lib.sfl_queue_drags(self._h, C.cast(arr, C.c_void_p), len(drags)))
+        capi.check(self._lib.sfl_queue_drags_at(self._h, step, C.cast(arr, C.c_void_p), len(drags)))
 
     def setup_sketch_fields(self):
         """Velocity = 0, dye = the sketch's blurred three-sector pattern (setup(), ino:196-241)."""
@@ -413,16 +424,27 @@ class BatchSolver:
         capi.check(self._lib.sfl_batch_field_device_ptr(self._h, field, C.byref(p)))
         return p.value
 
-    def queue_forces(self, members, cells_ij, vel_xy):
-        """Point forces of the next step: record k sets member members[k]'s velocity at cell cells_ij[k] to vel_xy[k]."""
+    def queue_forces(self, members, cells_ij, vel_xy, step: int = 0):
+        """Point forces of step `step` of the steps to come (0: the next one; the timeline rule of include/sfl.h): record k
+        sets member members[k]'s velocity at cell cells_ij[k] to vel_xy[k]."""
         members = np.ascontiguousarray(members, np.int32).reshape(-1)
         cells = np.ascontiguousarray(cells_ij, np.int32).reshape(-1, 2)
         vel = np.ascontiguousarray(vel_xy, np.float32).reshape(-1, 2)
         if not len(members) == len(cells) == len(vel):
             raise ValueError("members, cells_ij and vel_xy need one entry per force")
-        capi.check(self._lib.sfl_batch_queue_forces(
-            self._h, members.ctypes.data_as(C.POINTER(C.c_int)), cells.ctypes.data_as(C.POINTER(C.c_int)),
+        capi.check(self._lib.sfl_batch_queue_forces_at(
+            self._h, step, members.ctypes.data_as(C.POINTER(C.c_int)), cells.ctypes.data_as(C.POINTER(C.c_int)),
             vel.ctypes.data_as(C.POINTER(C.c_float)), len(members)))
+
+    def forces_pending(self):
+        """(records, last_step) of the timeline of queued forces; last_step is -1 when it is empty."""
+        records, last = C.c_int(0), C.c_int(0)
+        capi.check(self._lib.sfl_batch_forces_pending(self._h, C.byref(records), C.byref(last)))
+        return records.value, last.value
+
+    def forget_forces(self):
+        """Empties the timeline of queued forces."""
+        capi.check(self._lib.sfl_batch_forget_forces(self._h))
 
     def step_n(self, n, dt, dx=1.0, iters=10, omega=1.96):
         capi.check(self._lib.sfl_batch_step_n(self._h, n, dt, dx, iters, omega))

@@ -4,11 +4,12 @@
     python examples/batch_movie.py --batch 16 --steps 120 --every 10 --out sheets
 
 Every member starts from the sketch's fields (setup(), ino:196-241: sfl_batch_setup_sketch_fields).  Member m's finger
-moves round a circle of its own radius and speed; the stroke is queued step by step -- queue_forces between step_n(1)
-calls (ino:264-269) -- and the recorder (sfl_batch_record_start) runs across those calls: after every `--every`-th step a
-frame of every member is rendered on the device, between the step launches, and the host never waits for one.  When the
-recorder is full, and at the end, the frames are read out (sfl_batch_record_read) and written as PPM contact sheets: one
-sheet per frame, the members side by side.  Needs a GPU: there is no CPU fallback.
+moves round a circle of its own radius and speed.  The whole stroke is queued before the first step -- queue_forces with
+step=k for the records of step k (ino:264-269; the timeline of include/sfl.h) -- and ONE step_n call then runs as many
+steps as fill the recorder (sfl_batch_record_start): after every `--every`-th step a frame of every member is rendered on
+the device, between the step launches, and the host never waits for one.  When the recorder is full, and at the end,
+the frames are read out (sfl_batch_record_read) and written as PPM contact sheets: one sheet per frame, the members side
+by side.  Needs a GPU: there is no CPU fallback.
 """
 import argparse
 import importlib
@@ -81,15 +82,15 @@ def main():
     written = 0
     with sfl.BatchSolver(dim_x, dim_y, args.batch, large=args.large) as b:
         b.setup_sketch_fields()
-        b.record_start(every=args.every, scaling=args.scaling, byteswap=False, capacity=args.capacity)
-        for step in range(args.steps):
-            frames, capacity, _ = b.record_info()
-            if frames == capacity:   # full, at a frame boundary: read out and start afresh -- the phase is kept
-                written = write_sheets(b.frames(), written, args.columns, args.out)
-                b.record_start(every=args.every, scaling=args.scaling, byteswap=False, capacity=args.capacity)
-            b.queue_forces(*stroke(step, args.batch, dim_x, dim_y))
-            b.step_n(1, DT, 1.0, args.iters, OMEGA)   # asynchronous: the frame's render is queued behind the step
-        written = write_sheets(b.frames(), written, args.columns, args.out)
+        for step in range(args.steps):   # the whole stroke, before the first step
+            b.queue_forces(*stroke(step, args.batch, dim_x, dim_y), step=step)
+        fill = args.every * args.capacity   # steps that fill the recorder
+        for first in range(0, args.steps, fill):
+            b.record_start(every=args.every, scaling=args.scaling, byteswap=False, capacity=args.capacity)
+            # one call per recorder fill, asynchronous: the steps between two frames are one launch, the frame's render
+            # is queued behind it, and the later records of the stroke move down by the steps run
+            b.step_n(min(fill, args.steps - first), DT, 1.0, args.iters, OMEGA)
+            written = write_sheets(b.frames(), written, args.columns, args.out)
     print(f"wrote {written} contact sheets of {args.batch} members to {args.out}")
 
 

@@ -456,9 +456,10 @@ SFL_API int sfl_advect_external(sfl_context *ctx, void *next_p_dev, const void *
 /* One sim step in the order of ino:252-287: advect velocity (no-slip), [apply queued
  * forces], divergence, poisson_solve, subtract_gradient, advect colour (free-slip).         */
 SFL_API int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega);
-/* n sim steps, exactly as n calls of sfl_step (the sim task's loop, ino:249-289, calls the step back to back); forces
- * queued before the call go into the FIRST step.  Knowing the next step lets the library fuse across the step boundary
- * (SFL_OPT_STEP_SEAMS).  n == 0 does nothing.                                                                       */
+/* n sim steps, exactly as n calls of sfl_step (the sim task's loop, ino:249-289, calls the step back to back); queued
+ * forces go into the steps they were queued for (the timeline rule below: sfl_queue_forces queues for the FIRST step).
+ * Knowing the next step lets the library fuse across the step boundary (SFL_OPT_STEP_SEAMS): a step with records runs
+ * its advection, its forces and its divergence unfused, the others take the fused kernel.  n == 0 does nothing.     */
 SFL_API int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float omega);
 /* Queue point forces applied by the next sfl_step between the velocity advection and the
  * divergence (ino:264-269): velocity[index(cells[2k], cells[2k+1])] = (vel[2k], vel[2k+1])
@@ -477,6 +478,32 @@ typedef struct sfl_drag {
     float vel_x, vel_y;        /* msg.velocity.x, msg.velocity.y */
 } sfl_drag;
 SFL_API int sfl_queue_drags(sfl_context *ctx, const sfl_drag *msgs, int n);
+/* --- THE TIMELINE RULE: forces queued for step `step` of the steps to come, so that one sfl_step_n replays a whole
+ *     recorded stroke (the sketch's loop() drains its drag_queue in every iteration, ino:264-269).  It holds for a
+ *     context and, with "within each member", for a batch (group 4):
+ *   - `step` counts the steps still to come.  0 is the next step any step call runs.  A record for step s is applied in
+ *     that step between the velocity advection and the divergence.
+ *   - Within one step, records are applied in the order of the calls that queued them (the last write wins).  For a
+ *     batch that order holds within each member.
+ *   - sfl_queue_forces, sfl_queue_drags and sfl_batch_queue_forces are the _at calls with step = 0, interleaved with
+ *     them in call order.
+ *   - A step call of n steps consumes the records of steps [0, n).  Later records move down by n.  This applies to
+ *     sfl_step (n = 1), sfl_step_n, sfl_batch_step_n, sfl_batch_step_n_each and sfl_batch_step_n_until.  n == 0 consumes
+ *     nothing.
+ *   - Solves, uploads, setup and render calls neither consume nor shift.
+ *   - A step call that is refused leaves the timeline exactly as it was.  Refusals are an argument check, or the
+ *     recorder's SFL_ERR_STATE when the call would complete more frames than are free.
+ *   - step < 0 and NULL pointers with n > 0 return SFL_ERR_INVALID and queue nothing.  So does a member outside the
+ *     batch, and, for drags, a coordinate outside the domain.  The message names the first offender.  Cells outside the
+ *     domain in sfl_[batch_]queue_forces_at are skipped at application.  All of it is checked before any GPU is touched.
+ *   - On slabs every rank queues the same timeline (sfl_queue_forces above: the same list on every rank, per step).   */
+SFL_API int sfl_queue_forces_at(sfl_context *ctx, int step, const int *cells_ij, const float *vel_xy, int n);
+SFL_API int sfl_queue_drags_at(sfl_context *ctx, int step, const sfl_drag *msgs, int n);
+/* What the timeline holds: *records = the records of all steps, *last_step = the last step that has one (-1 when the
+ * timeline is empty).  Either out pointer may be NULL.  No GPU is touched.                                          */
+SFL_API int sfl_forces_pending(sfl_context *ctx, int *records, int *last_step);
+/* Empties the timeline (of every rank of an in-process group): no step consumes what was queued before.            */
+SFL_API int sfl_forget_forces(sfl_context *ctx);
 
 /* --- initial condition of the sketch (setup(), ino:196-241): velocity = 0; dye = three
  *     120-degree sectors around the centre chosen by atan2f, then the sketch's two in-place
@@ -551,7 +578,17 @@ SFL_API int sfl_batch_field_device_ptr(sfl_batch *b, int field, void **dev_ptr);
  * queue order within each member (the last write wins).  Cells outside the domain are skipped; a member outside
  * [0, batch) fails the call with SFL_ERR_INVALID and queues nothing.                                */
 SFL_API int sfl_batch_queue_forces(sfl_batch *b, const int *members, const int *cells_ij, const float *vel_xy, int n);
-/* n sim steps of every member, as sfl_step_n (queued forces go into the first step; n == 0 does nothing).  dt, dx,
+/* The same for step `step` of the steps to come, what the timeline holds, and forgetting it: the timeline rule of
+ * group 3 (sfl_queue_forces_at), word for word; sfl_batch_queue_forces is step = 0.  The whole timeline is staged on the
+ * device once per change, not once per step.  A call of sfl_batch_step_n or sfl_batch_step_n_each on a batch of
+ * sfl_batch_create with n >= 2 and a record in some step of [1, n) runs its steps in ONE launch with every member's
+ * velocity kept in LDS from step to step (between two frames, where a recorder is on); the results are the same bits.  */
+SFL_API int sfl_batch_queue_forces_at(sfl_batch *b, int step, const int *members, const int *cells_ij,
+                                      const float *vel_xy, int n);
+SFL_API int sfl_batch_forces_pending(sfl_batch *b, int *records, int *last_step);
+SFL_API int sfl_batch_forget_forces(sfl_batch *b);
+/* n sim steps of every member, as sfl_step_n (queued forces go into the steps they were queued for, those of
+ * sfl_batch_queue_forces into the first step: the timeline rule; n == 0 does nothing).  dt, dx,
  * iters and omega are the same for every member (sfl_batch_step_n_each: one set per member).  Asynchronous on the
  * batch's stream.                                                                                 */
 SFL_API int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float omega);
@@ -565,7 +602,7 @@ typedef struct sfl_member_params {
     int32_t iters;
 } sfl_member_params;                       /* 16 bytes */
 /* n sim steps; member m runs every one of them with params[m] (an array of `batch` records, HOST memory, read before
- * the call returns).  Otherwise exactly sfl_batch_step_n: queued forces go into the first step, n == 0 does nothing
+ * the call returns).  Otherwise exactly sfl_batch_step_n: queued forces go into their steps (the timeline rule), n == 0 does nothing
  * (beyond checking its arguments), asynchronous.  Member m ends up, bit for bit, where a context of the same shape
  * ends up after sfl_step_n(ctx, n, params[m].dt, params[m].dx, params[m].iters, params[m].omega) with member m's data
  * and forces.  b or params NULL, n < 0 or any params[m].iters < 0 return SFL_ERR_INVALID (the message names the first
@@ -607,7 +644,7 @@ typedef struct sfl_member_stop {
  * included, and every count is the cap.  tol = +inf stops at k = 0: p = 0.  every < 1, a NaN tol or iters < 0 return
  * SFL_ERR_INVALID (the message names the first such member) before anything is launched or the force queue is
  * touched, as b, params or stops NULL and n < 0 do.  Members are started by cap, the largest first.          */
-/* sfl_batch_step_n_each with the solve of every step run by the rule (queued forces go into the first step; n == 0
+/* sfl_batch_step_n_each with the solve of every step run by the rule (queued forces go into their steps, the timeline rule; n == 0
  * launches nothing and leaves the reports as they were).  Asynchronous; params and stops are arrays of `batch` records
  * in HOST memory, read before the call returns.                                                       */
 SFL_API int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params, const sfl_member_stop *stops);
@@ -654,7 +691,7 @@ SFL_API int sfl_batch_render_members(sfl_batch *b, int first, int count, int sca
  * count / every - 1 is rendered from the dye that step left -- the dye sfl_batch_download would hand out if the call ended
  * there.  The render is one launch on the batch's stream between the step launches: the step calls stay asynchronous and
  * the host never waits.  Nothing else about the step calls changes: every field keeps its bits, sfl_batch_residual and
- * sfl_batch_iterations keep their validity, queued forces still go into the first step.  sfl_batch_poisson_solve*,
+ * sfl_batch_iterations keep their validity, queued forces still go into their steps.  sfl_batch_poisson_solve*,
  * uploads and sfl_batch_setup_sketch_fields neither count nor record.
  *   A step call whose n steps would complete more frames than are free is refused as a whole with SFL_ERR_STATE (the
  * message names sfl_batch_record_read and sfl_batch_record_start), after the call's own argument checks and before
