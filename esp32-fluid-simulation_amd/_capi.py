@@ -29,6 +29,8 @@ OPT_SOR_FOLD = 22
 CHANNEL_F32, CHANNEL_UQ32 = 0, 1
 STEP_EXCHANGE, STEP_SOR, STEP_ZERO = 1, 2, 3
 STATS_VELOCITY, STATS_DYE = 1, 2
+DIST_VELOCITY, DIST_DYE, DIST_PRESSURE = 1, 2, 4
+ENV_MEAN, ENV_MIN, ENV_MAX, ENV_SPREAD = 0, 1, 2, 3
 UNIQUE_ID_BYTES = 128
 BATCH_LARGE_MAX_CELLS = 20224   # SFL_BATCH_LARGE_MAX_CELLS: cells of one member of sfl_batch_create_large
 
@@ -57,6 +59,13 @@ class FlowStats(C.Structure):
     """struct sfl_flow_stats: what sfl_flow_stats and sfl_batch_flow_stats[_each] report, 40 bytes."""
     _fields_ = [("max_abs_vx", C.c_float), ("max_abs_vy", C.c_float), ("max_abs_div", C.c_float), ("what", C.c_uint32),
                 ("dye_sum", C.c_uint64 * 3)]
+
+
+class FieldDistance(C.Structure):
+    """struct sfl_field_distance: what sfl_distance and sfl_batch_distance report, 64 bytes."""
+    _fields_ = [("max_abs_dvx", C.c_float), ("max_abs_dvy", C.c_float), ("max_abs_dp", C.c_float), ("what", C.c_uint32),
+                ("velocity_cells_differ", C.c_uint32), ("dye_cells_differ", C.c_uint32), ("pressure_cells_differ", C.c_uint32),
+                ("max_abs_ddye", C.c_uint32 * 3), ("sum_abs_ddye", C.c_uint64 * 3)]
 
 
 class SflError(RuntimeError):
@@ -143,6 +152,7 @@ SIGNATURES = {
     "sfl_poisson_continue": (_i, [_ctx, _f, _i, _f]),
     "sfl_poisson_solve_until": (_i, [_ctx, _f, _i, _f, _f, _i, C.POINTER(C.c_int32), _pf]),
     "sfl_flow_stats": (_i, [_ctx, _i, _f, C.POINTER(FlowStats)]),
+    "sfl_distance": (_i, [_ctx, _ctx, _i, C.POINTER(FieldDistance)]),
     "sfl_step": (_i, [_ctx, _f, _f, _i, _f]),
     "sfl_step_n": (_i, [_ctx, _i, _f, _f, _i, _f]),
     "sfl_queue_forces": (_i, [_ctx, _pi, _pf, _i]),
@@ -179,6 +189,11 @@ SIGNATURES = {
     "sfl_batch_iterations": (_i, [_ctx, _i, _i, C.POINTER(C.c_int32), _sz]),
     "sfl_batch_flow_stats": (_i, [_ctx, _i, _f, _i, _i, C.POINTER(FlowStats), _sz]),
     "sfl_batch_flow_stats_each": (_i, [_ctx, _i, C.POINTER(MemberParams), _i, _i, C.POINTER(FlowStats), _sz]),
+    "sfl_batch_distance": (_i, [_ctx, _i, _ctx, _i, _i, _i, C.POINTER(FieldDistance), _sz]),
+    "sfl_batch_envelope": (_i, [_ctx, _i, _i]),
+    "sfl_batch_envelope_info": (_i, [_ctx, _pi, _pi]),
+    "sfl_batch_envelope_download": (_i, [_ctx, _i, _pu, _sz]),
+    "sfl_batch_envelope_render": (_i, [_ctx, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
     "sfl_batch_setup_sketch_fields": (_i, [_ctx]),
     "sfl_batch_render_rgb565": (_i, [_ctx, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
     "sfl_batch_render_members": (_i, [_ctx, _i, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),

@@ -18,9 +18,10 @@ void release(sfl_batch *b)
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (void *m : {(void *)b->vel, (void *)b->vel_tmp, (void *)b->col, (void *)b->col_tmp, (void *)b->div, (void *)b->p,
                     b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_counts, (void *)b->d_image,
-                    (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames})
+                    (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
+    if (b->h_dist) (void)hipHostFree(b->h_dist);
     for (sfl_batch::Stage *pair : {b->stage, b->member_stage})
         for (int k = 0; k < 2; ++k) {
             if (pair[k].host) (void)hipHostFree(pair[k].host);

@@ -60,6 +60,13 @@ struct sfl_batch {
     // flow statistics (sfl_batch_flow_stats[_each]): one record per member that the two passes leave, behind them one
     // 1 / (2 dx) per member; the same in pinned memory.  Allocated at the first call, nothing per call
     sfl::FlowStatsRecord *d_stats = nullptr, *h_stats = nullptr;
+    // sfl_batch_distance (ensemble.cpp): one record per member on the device and in pinned memory, allocated at the first call
+    struct sfl_field_distance *d_dist = nullptr, *h_dist = nullptr;
+    // sfl_batch_envelope (ensemble.cpp): ONE allocation made at the first call -- the four fields of the snapshot (mean, min,
+    // max, spread: 3 * cells words each), behind them the partial results of the member groups (ensemble_kernels.h) --
+    // and the range [env_first, env_first + env_count) the snapshot holds (env_count == 0: none yet)
+    uint32_t *d_env = nullptr;
+    int env_first = 0, env_count = 0;
     // dye visualiser's device image, kept between frames
     uint16_t *d_image = nullptr;
     size_t d_image_bytes = 0;

@@ -349,6 +349,8 @@ int sfl_destroy(sfl_context *c)
     if (c->h_norm) (void)hipHostFree(c->h_norm);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->h_stats) (void)hipHostFree(c->h_stats);
+    if (c->d_dist) (void)hipFree(c->d_dist);
+    if (c->h_dist) (void)hipHostFree(c->h_dist);
     if (c->ev_report) (void)hipEventDestroy(c->ev_report);
     if (c->ev_color_halo) (void)hipEventDestroy(c->ev_color_halo);
     if (c->ev_vel_final) (void)hipEventDestroy(c->ev_vel_final);

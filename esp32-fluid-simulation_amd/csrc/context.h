@@ -8,6 +8,7 @@
 //                     time counted on the device)
 //   solve_until.cpp   the update norm of a context, a continued solve, a solve stopped at a tolerance
 //   flow_stats.cpp    the flow statistics of a context: maximum speeds, remaining divergence, dye totals
+//   ensemble.cpp      the distance between two contexts or batch members, the dye envelope of a batch
 //   operators.cpp     advection, divergence, projection, forces, setup / render
 //   slab_step.cpp     sfl_step / sfl_step_n, the automatic advection halo of a slab's step
 //   host_dropin.cpp   the host-pointer drop-ins (sfl_host_*) and their per-thread context
@@ -216,6 +217,7 @@ struct sfl_context {
     unsigned *h_norm = nullptr;    // ... and their pinned host copy: allocated with the context, nothing is allocated per call
     struct sfl_flow_stats *d_stats = nullptr, *h_stats = nullptr;   // sfl_flow_stats: the device record the two passes leave and its pinned host
                                    //     copy, allocated at the first call (flow_stats.cpp), nothing per call
+    struct sfl_field_distance *d_dist = nullptr, *h_dist = nullptr;   // sfl_distance with this context as `a`: the same pair (ensemble.cpp)
     bool wait_error_seen = false;  // word [2] was found raised (download, a step's report): every call fails until sfl_synchronize
                                    // has reported and cleared it
 

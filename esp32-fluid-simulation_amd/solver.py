@@ -67,6 +67,26 @@ FLOW_STATS_DTYPE = np.dtype([("max_abs_vx", "<f4"), ("max_abs_vy", "<f4"), ("max
 FLOW_STATS_STRIP_COLS, FLOW_STATS_CHUNK_ROWS = 128, 8
 
 
+# struct sfl_field_distance: what Solver.distance returns (one record) and BatchSolver.distance (one per member)
+FIELD_DISTANCE_DTYPE = np.dtype([("max_abs_dvx", "<f4"), ("max_abs_dvy", "<f4"), ("max_abs_dp", "<f4"), ("what", "<u4"),
+                                 ("velocity_cells_differ", "<u4"), ("dye_cells_differ", "<u4"), ("pressure_cells_differ", "<u4"),
+                                 ("max_abs_ddye", "<u4", (3,)), ("sum_abs_ddye", "<u8", (3,))])
+# The tiles of the distance passes and of the envelope (csrc/ensemble_kernels.h): a lane of a distance pass holds
+# DIST_*_LANE_CELLS whole cells per load, a workgroup of DIST_THREADS lanes takes DIST_ITEM_LOADS loads per lane as one
+# item; the envelope gives a workgroup ENV_BLOCK_WORDS words of a group of ENV_GROUP_MEMBERS members.  Stated for the
+# tests, which put differing values on both sides of the boundaries; no result depends on them.
+DIST_THREADS, DIST_ITEM_LOADS = 256, 8
+DIST_VELOCITY_LANE_CELLS, DIST_PRESSURE_LANE_CELLS, DIST_DYE_LANE_CELLS = 2, 4, 1
+ENV_BLOCK_WORDS, ENV_GROUP_MEMBERS = 256, 32
+
+
+def _dist_what(velocity, dye, pressure) -> int:
+    what = (capi.DIST_VELOCITY if velocity else 0) | (capi.DIST_DYE if dye else 0) | (capi.DIST_PRESSURE if pressure else 0)
+    if not what:
+        raise ValueError("distance: ask for the velocity, the dye, the pressure or several of them")
+    return what
+
+
 def _stats_what(velocity, dye) -> int:
     what = (capi.STATS_VELOCITY if velocity else 0) | (capi.STATS_DYE if dye else 0)
     if not what:
@@ -288,6 +308,17 @@ class Solver:
         part asked for; reads only; synchronous.  Whole-domain contexts only."""
         what, out = _stats_what(velocity, dye), np.zeros((), FLOW_STATS_DTYPE)
         capi.check(self._lib.sfl_flow_stats(self._h, what, dx, out.ctypes.data_as(C.POINTER(capi.FlowStats))))
+        return out[()]
+
+    def distance(self, other: "Solver", velocity=True, dye=True, pressure=True):
+        """How far this context's fields are from `other`'s, without a download (sfl_distance): one record of
+        FIELD_DISTANCE_DTYPE.  max_abs_dvx / dvy / dp = max |a - b| in float32 (a NaN anywhere makes the figure a NaN),
+        max_abs_ddye / sum_abs_ddye = per channel the maximum and the exact uint64 sum of |a - b| on the raw values,
+        *_cells_differ = the cells whose BITS differ: all zero <=> the fields are identical bits.  Bit for bit what numpy
+        gives on the downloaded fields; one streaming pass per part asked for; reads only; synchronous.  Whole-domain
+        contexts of one shape on one device; ``other`` may be ``self``."""
+        what, out = _dist_what(velocity, dye, pressure), np.zeros((), FIELD_DISTANCE_DTYPE)
+        capi.check(self._lib.sfl_distance(self._h, other._h, what, out.ctypes.data_as(C.POINTER(capi.FieldDistance))))
         return out[()]
 
     def step(self, dt, dx=1.0, iters=10, omega=1.96):
@@ -547,6 +578,50 @@ class BatchSolver:
             prm, pptr = self._member_params(0.0, dx, 0, 0.0)
             capi.check(self._lib.sfl_batch_flow_stats_each(self._h, what, pptr, first, count, ptr, out.nbytes))
         return out
+
+    def distance(self, ref=None, ref_member=None, first: int = 0, count=None, velocity=True, dye=True,
+                 pressure=True) -> np.ndarray:
+        """The distance of members [first, first + count) from a reference (sfl_batch_distance; the definitions of
+        :meth:`Solver.distance`): a FIELD_DISTANCE_DTYPE array of `count` records.  Record k is member first + k against
+        member `ref_member` of `ref`, or, with ``ref_member=None``, against member first + k of `ref`: the pairwise form,
+        for twins.  ``ref=None`` is this batch; `ref` may be the other kind of batch of the same shape.  One launch per
+        part asked for, whatever the range; reads only (``residual()`` and ``iterations()`` stay valid); synchronous."""
+        what = _dist_what(velocity, dye, pressure)
+        count = self.batch - first if count is None else count
+        out = np.zeros(max(count, 0), FIELD_DISTANCE_DTYPE)
+        capi.check(self._lib.sfl_batch_distance(self._h, what, None if ref is None else ref._h,
+                                                -1 if ref_member is None else ref_member, first, count,
+                                                out.ctypes.data_as(C.POINTER(capi.FieldDistance)), out.nbytes))
+        return out
+
+    def envelope(self, first: int = 0, count=None):
+        """Take the per-cell envelope of the CURRENT dye over members [first, first + count) (sfl_batch_envelope): mean
+        (floor of the exact sum over count), minimum, maximum and spread = max - min of every cell and channel, exact
+        integers.  A snapshot kept on the device: later steps do not change it, the next call replaces it.
+        Asynchronous; count None = to the end of the batch."""
+        count = self.batch - first if count is None else count
+        capi.check(self._lib.sfl_batch_envelope(self._h, first, count))
+
+    def envelope_info(self):
+        """(first, count) of the snapshot held; count 0: none yet.  Never waits."""
+        first, count = C.c_int(0), C.c_int(0)
+        capi.check(self._lib.sfl_batch_envelope_info(self._h, C.byref(first), C.byref(count)))
+        return first.value, count.value
+
+    def envelope_field(self, which: int) -> np.ndarray:
+        """Field `which` (capi.ENV_MEAN / ENV_MIN / ENV_MAX / ENV_SPREAD) of the snapshot, uint32[dim_y, dim_x, 3] laid
+        out as a context's dye.  Synchronous."""
+        a = np.empty((self.dim_y, self.dim_x, 3), np.uint32)
+        capi.check(self._lib.sfl_batch_envelope_download(self._h, which, _up(a), a.nbytes))
+        return a
+
+    def envelope_render(self, which: int, scaling: int = 4, byteswap: bool = True) -> np.ndarray:
+        """Field `which` of the snapshot -> RGB565 image, bit for bit what ``Solver.render_rgb565`` draws for a context
+        whose dye is that field.  Synchronous."""
+        img = np.empty((max(scaling, 0) * (self.dim_x - 1), max(scaling, 0) * (self.dim_y - 1)), np.uint16)
+        capi.check(self._lib.sfl_batch_envelope_render(self._h, which, scaling, int(byteswap),
+                                                       img.ctypes.data_as(C.POINTER(C.c_uint16)), img.nbytes))
+        return img
 
     def setup_sketch_fields(self):
         """Every member: velocity = 0, dye = the sketch's blurred three-sector pattern (setup(), ino:196-241)."""

@@ -447,6 +447,42 @@ struct sfl_flow_stats {
  * asked for, one copy of the 40 bytes, one wait; nothing is allocated per call.
  *   Cost: one streaming pass per bit: not measured yet.                                                              */
 SFL_API int sfl_flow_stats(sfl_context *ctx, int what, float dx, struct sfl_flow_stats *out);
+/* --- how far two sets of fields are apart, without a download (20 bytes per cell and side): the distance of a's
+ *     velocity, dye and pressure from b's, and whether they are the same bits.  WHOLE-DOMAIN contexts only: a slab
+ *     gets SFL_ERR_STATE.  The batches' call (group 4: sfl_batch_distance) reports the same record per member.        */
+#define SFL_DIST_VELOCITY 1   /* max_abs_dvx, max_abs_dvy, velocity_cells_differ  : one pass, 8 B per cell and side  */
+#define SFL_DIST_DYE      2   /* max_abs_ddye, sum_abs_ddye, dye_cells_differ     : one pass, 12 B per cell and side */
+#define SFL_DIST_PRESSURE 4   /* max_abs_dp, pressure_cells_differ                : one pass, 4 B per cell and side  */
+struct sfl_field_distance {
+    float    max_abs_dvx, max_abs_dvy;  /* max over cells of |a.v.x - b.v.x|, |a.v.y - b.v.y|            */
+    float    max_abs_dp;                /* max over cells of |a.p - b.p|                                  */
+    uint32_t what;                      /* the SFL_DIST_* bits this record holds; the other members are 0 */
+    uint32_t velocity_cells_differ;     /* cells whose velocity differs in the BITS of either component   */
+    uint32_t dye_cells_differ;          /* cells whose dye differs in any channel                         */
+    uint32_t pressure_cells_differ;     /* cells whose pressure differs in its bits                       */
+    uint32_t max_abs_ddye[3];           /* per channel: max over cells of |a - b| of the raw UQ32 values  */
+    uint64_t sum_abs_ddye[3];           /* per channel: sum over cells of that, exact                     */
+};                                      /* 64 bytes: offsets 0, 4, 8, 12, 16, 20, 24, 28, 40              */
+/* The distance of a's CURRENT fields from b's: the fields sfl_download would hand out at this moment (settled as
+ * sfl_flow_stats settles them; the pressure is the one sfl_download(SFL_FIELD_PRESSURE) copies).  The call READS ONLY,
+ * on both sides, as sfl_flow_stats does.
+ *   Floats (velocity, pressure): a - b is ONE float32 subtraction per cell and component; the maximum is taken over the
+ * bit patterns of |a - b| as unsigned integers, as the maxima of sfl_flow_stats are.  Finite values and +inf order as
+ * floats do; any NaN wins (which NaN is reported is not defined).  inf - inf is a NaN: two fields that hold the SAME inf
+ * in a cell report a NaN distance and zero cells differing.  |+0 - -0| reports +0.0f while the cell counts as differing.
+ *   *_cells_differ compare BITS: the same NaN payload on both sides is equal, +0 against -0 differs; a cell counts once
+ * however many of its words differ.  All three counts zero <=> the fields asked for are identical bits: the library's
+ * "bit for bit" (a member against a context, step_n against n steps, a twin run) as one device-side call.
+ *   Dye: |a - b| is taken on the raw uint32 values, max(a, b) - min(a, b), no float involved, the whole UQ32 range
+ * counting.  The sums are 64-bit and exact: 2^28 cells x 2^32 stay below 2^60.
+ *   None of the figures depends on how the device tiles or reduces: bit for bit what numpy gives on the downloads.
+ *   Refused with SFL_ERR_INVALID before any GPU work, in this order: `what` empty or with other bits; a, b or out NULL;
+ * then a slab (SFL_ERR_STATE); then two contexts of different shape or on different devices.  a == b is allowed (all
+ * zeros, or NaNs where a field holds an inf or a NaN).  Synchronous: the call waits for b's stream, makes one launch
+ * per bit on a's stream, one copy of the 64 bytes and one wait; nothing is allocated per call (a's records are
+ * allocated at its first call).
+ *   Cost: two streaming reads per bit (profiles/ensemble.txt).                                                      */
+SFL_API int sfl_distance(sfl_context *a, sfl_context *b, int what, struct sfl_field_distance *out);
 /* next_p <- advect(p, velocity, dt, no_slip) for a field of the CALLER's, resident on the context's device
  * (advect.h:74-85; element = `channels` x `kind` as for sfl_host_advect_channels): further quantities carried by
  * the flow -- a temperature, a second dye -- without a round trip through the host.  Whole-domain contexts only;
@@ -670,6 +706,50 @@ SFL_API int sfl_batch_flow_stats(sfl_batch *b, int what, float dx, int first, in
  * before the call returns; NULL returns SFL_ERR_INVALID), whose other members are ignored.                            */
 SFL_API int sfl_batch_flow_stats_each(sfl_batch *b, int what, const sfl_member_params *params,
                                       int first, int count, struct sfl_flow_stats *host, size_t bytes);
+/* --- the distance of members [first, first + count) of b from a reference: one sfl_field_distance record per member
+ *     (group 2, sfl_distance: the definitions, word for word), of the members' CURRENT velocity, dye and pressure --
+ *     what sfl_batch_download would hand out.  Record k is member first + k of b against member ref_member of `ref`;
+ *     with ref_member == -1 it is against member first + k of `ref`: the pairwise form, for twins.  ref == NULL means
+ *     b itself.  `ref` may be the other kind of batch (sfl_batch_create_large against sfl_batch_create); it must have
+ *     b's dim_x and dim_y and sit on b's device.  A member's record is, bit for bit, what sfl_distance reports for two
+ *     contexts holding those fields.  ONE launch per bit whatever the range; the call waits for ref's stream first.
+ *     Reads only, on both sides: the reports of sfl_batch_residual and sfl_batch_iterations do not go stale, the
+ *     timeline of queued forces and the recorder are untouched.  Synchronous; the device and pinned records are
+ *     allocated once per batch, nothing per call.  count == 0 does nothing.
+ *       Refused with SFL_ERR_INVALID before any GPU work, in this order: `what` empty or with other bits; count < 0 or
+ *     bytes != count * 64 (the message names the bytes expected); b or host NULL; a range that is not inside b,
+ *     ref_member outside [-1, ref's batch), a pairwise range that is not inside ref; a ref of another shape or on
+ *     another device.                                                                                               */
+SFL_API int sfl_batch_distance(sfl_batch *b, int what, sfl_batch *ref, int ref_member, int first, int count,
+                               struct sfl_field_distance *host, size_t bytes);
+/* --- the per-cell envelope of the dye over members: the mean picture of an ensemble and the picture of where its
+ *     members disagree, without downloading B fields ---------------------------------------------------------------- */
+#define SFL_ENV_MEAN   0   /* floor(sum over the members / count), 64-bit integer arithmetic */
+#define SFL_ENV_MIN    1
+#define SFL_ENV_MAX    2
+#define SFL_ENV_SPREAD 3   /* max - min */
+/* Take the four fields, per cell and channel, over the CURRENT dye of members [first, first + count), count >= 1 --
+ * the dye sfl_batch_download would hand out if the stream were drained here.  All four are exact integers on the raw
+ * UQ32 values (the sum of up to 2^31 members x 2^32 stays below 2^63): no float, no tolerance, nothing depends on the
+ * order of reduction; bit for bit numpy's min, max and sum(uint64) // count over the members.  They are a SNAPSHOT kept
+ * on the device with the batch, four dye-typed fields of dim_x * dim_y * 3 words: later steps do not change them, the
+ * next call replaces them.  The members' fields are only read.  Asynchronous on the batch's stream: the call can sit
+ * between two step calls without a host wait.  The buffers are allocated at the first call and freed by
+ * sfl_batch_destroy.  b NULL, count < 1 and a range that is not inside the batch return SFL_ERR_INVALID before any GPU
+ * work and leave an earlier snapshot as it was.                                                                      */
+SFL_API int sfl_batch_envelope(sfl_batch *b, int first, int count);
+/* The range the snapshot holds; count 0: none has been taken yet.  Either out pointer may be NULL.  Never waits.      */
+SFL_API int sfl_batch_envelope_info(sfl_batch *b, int *first, int *count);
+/* Copy field `which` (SFL_ENV_*) of the snapshot out, laid out as one context's dye: dim_x * dim_y * 3 uint32.
+ * Synchronous.  Refused in this order: `which` outside 0..3, bytes != dim_x * dim_y * 12, b or host NULL
+ * (SFL_ERR_INVALID), then no snapshot yet (SFL_ERR_STATE).                                                           */
+SFL_API int sfl_batch_envelope_download(sfl_batch *b, int which, uint32_t *host, size_t bytes);
+/* Draw field `which` of the snapshot: the image is, bit for bit, what sfl_render_rgb565 writes for a context whose dye
+ * is that field (H = scaling * (dim_x - 1) rows of W = scaling * (dim_y - 1) uint16).  Synchronous.  Refused in this
+ * order: `which` outside 0..3, scaling outside 1..64, bytes != H * W * 2, b or host_image NULL (SFL_ERR_INVALID), then
+ * no snapshot yet (SFL_ERR_STATE).                                                                                   */
+SFL_API int sfl_batch_envelope_render(sfl_batch *b, int which, int scaling, int byteswap, uint16_t *host_image,
+                                      size_t bytes);
 /* sfl_setup_sketch_fields for every member (the saturating definition included).  Asynchronous.    */
 SFL_API int sfl_batch_setup_sketch_fields(sfl_batch *b);
 /* sfl_render_rgb565 of one member's dye.  Synchronous.                                            */
