@@ -16,6 +16,9 @@ typedef int v2i __attribute__((ext_vector_type(2)));
 #ifndef SFL_PRIO_ROWS
 #define SFL_PRIO_ROWS 2    // rows (pipeline iterations) a wave spends on one level; must divide 6
 #endif
+#ifndef SFL_SCALAR_PRODUCTS
+#define SFL_SCALAR_PRODUCTS 1  // Lane2::scalar_only; 0 for an A/B build: its worth hangs on the compiler's heuristics, measure it again with a new one
+#endif
 
 // DPP full-wave shifts (GFX9 wave_shr:1 / wave_shl:1).  Lane 0 / lane 63 receive 0, which only
 // ever feeds cells of the tile's invalid rim.
@@ -44,6 +47,7 @@ struct WaveCommon {
     int row_sign;        // +1: pipeline row index = domain row; -1: its negative (tile streamed top-down)
     int prio_turn;       // rotating issue priority: this wave's turn counter (see next_turn)
     int prio_on;         // ... enabled for this launch (wave-uniform)
+    int prio_step;       // ... what a turn adds to the counter (0: the level stays where start_turns() put it)
 
     // the pipeline speaks in row INDICES t; domain row = row_sign * t (same parity either way)
     __device__ __forceinline__ sor::RowFacts row_facts(int t) const
@@ -68,42 +72,46 @@ struct WaveCommon {
     // 228 -> 217 us; profiles/r03_priority_rotation.txt).
     __device__ __forceinline__ void start_turns()
     {
-        if (prio_on == 2) {   // a sender tile (HaloWait::done): top priority from the first instruction, no turns
-            __builtin_amdgcn_s_setprio(3);
-            return;
-        }
+        if (prio_on == 2) __builtin_amdgcn_s_setprio(3);  // a sender tile (HaloWait::done): top priority from the first instruction
         unsigned hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(hw));  // wave slot on the SIMD
-        prio_turn = (int)(hw % SFL_PRIO_LEVELS);
+        // turn counter and what a turn adds to it: a rotating launch starts on the slot's level and moves on by one; a sender tile
+        // stays at 3 and a launch without rotation at 0, the level every wave starts with (next_turn restates it).
+        // (readfirstlane: the values are wave-uniform, but the compiler cannot see that behind the kernel's tile selection, and
+        // next_turn's asm statement needs them in SGPRs)
+        prio_turn = __builtin_amdgcn_readfirstlane(prio_on == 1 ? (int)(hw % 4) : prio_on == 2 ? 3 : 0);
+        prio_step = __builtin_amdgcn_readfirstlane(prio_on == 1 ? 1 : 0);
     }
     __device__ __forceinline__ void next_turn()
     {
         if (SFL_PRIO_LEVELS <= 1) return;
-        prio_turn = prio_turn + 1 >= SFL_PRIO_LEVELS ? prio_turn + 1 - SFL_PRIO_LEVELS : prio_turn + 1;
-        // s_setprio takes an immediate: select it with scalar branches INSIDE one asm statement, so that the
-        // straight-line trip stays straight-line for the compiler (a visible branch makes its wait-count pass
-        // drain the loads in flight)
-        asm volatile("s_cmp_lg_u32 %1, 1\n\t"
-                     "s_cbranch_scc1 .Lsfl_pe_%=\n\t"
-                     "s_cmp_lg_u32 %0, 0\n\t"
-                     "s_cbranch_scc1 .Lsfl_p1_%=\n\t"
-                     "s_setprio 0\n\t"
-                     "s_branch .Lsfl_pe_%=\n"
-                     ".Lsfl_p1_%=:\n\t"
-                     "s_cmp_lg_u32 %0, 1\n\t"
-                     "s_cbranch_scc1 .Lsfl_p2_%=\n\t"
+        static_assert(SFL_PRIO_LEVELS == 4 || SFL_PRIO_LEVELS <= 1, "next_turn picks one of four levels by two bits");
+        // s_setprio takes an immediate: it is selected with scalar branches INSIDE one asm statement, so that the straight-line
+        // trip stays straight-line for the compiler (a visible branch makes its wait-count pass drain the loads in flight).
+        // The level is the counter's two low bits (the counter just runs on: no wrap to compute), picked by a binary tree: one add,
+        // two bit tests, two branches, the s_setprio and at most one jump to the end -- 6 or 7 scalar instructions a turn (a
+        // compare ladder with a wrapped counter and a test of prio_on took 8 to 13; worth nothing measurable,
+        // profiles/sor_trip_diet.txt).  A launch without rotation, and a sender tile, add 0 and restate the level they hold.
+        asm volatile("s_add_u32 %0, %0, %1\n\t"
+                     "s_bitcmp1_b32 %0, 1\n\t"
+                     "s_cbranch_scc1 .Lsfl_ph_%=\n\t"
+                     "s_bitcmp1_b32 %0, 0\n\t"
+                     "s_cbranch_scc0 .Lsfl_p0_%=\n\t"
                      "s_setprio 1\n\t"
                      "s_branch .Lsfl_pe_%=\n"
-                     ".Lsfl_p2_%=:\n\t"
-                     "s_cmp_lg_u32 %0, 2\n\t"
+                     ".Lsfl_ph_%=:\n\t"
+                     "s_bitcmp1_b32 %0, 0\n\t"
                      "s_cbranch_scc1 .Lsfl_p3_%=\n\t"
                      "s_setprio 2\n\t"
                      "s_branch .Lsfl_pe_%=\n"
                      ".Lsfl_p3_%=:\n\t"
-                     "s_setprio 3\n"
+                     "s_setprio 3\n\t"
+                     "s_branch .Lsfl_pe_%=\n"
+                     ".Lsfl_p0_%=:\n\t"
+                     "s_setprio 0\n"
                      ".Lsfl_pe_%=:"
-                     :
-                     : "s"(prio_turn), "s"(prio_on)
+                     : "+s"(prio_turn)
+                     : "s"(prio_step)
                      : "scc");
     }
     __device__ __forceinline__ int row_bytes(int t) const { return (row_sign * t - grow0) * dim_x * 4; }
@@ -179,6 +187,22 @@ struct Lane2 : WaveCommon {
     __device__ __forceinline__ M mask_and(M m, bool row) const { return m && row; }
     __device__ __forceinline__ V from_lower_lane(V x) const { return lane_below(x); }
     __device__ __forceinline__ V from_upper_lane(V x) const { return lane_above(x); }
+    // The relaxation's product by omega passes through an empty asm statement (no instruction of its own; the hazard pass puts an
+    // s_nop 0 behind it).  Without it the compiler's SLP pass pairs the two products of a relaxation, (1 - omega) * own and
+    // omega * gs, into a v_pk_mul_f32 + v_pk_add_f32 wherever a trip is one long basic block (the prologue trips: 790 packed
+    // instructions in the NS = 16 kernel, 250 with the statement) -- the same bits, but a packed fp32 instruction occupies the SIMD for
+    // two passes and every pair costs a v_mov_b32 to line its operands up.  The steady rows, which were never packed,
+    // change too: the product is formed as written (by -0.25f, then added) where the compiler otherwise multiplies by +0.25f and
+    // subtracts.  Measured with AMD clang 22.0.0git (ROCm 7.2.0): 8192^2 x 80 -2.9 %, the thin share -1.6 %, 16384^2 -1.1 %; the counters
+    // before and after are in profiles/sor_trip_diet.txt.  An effect of this compiler's heuristics: SFL_SCALAR_PRODUCTS = 0 is the
+    // A/B to repeat with another one.
+    __device__ __forceinline__ V scalar_only(V x) const
+    {
+#if SFL_SCALAR_PRODUCTS
+        asm("" : "+v"(x));
+#endif
+        return x;
+    }
     __device__ __forceinline__ V detach(V x) const
     {
         V r;

@@ -40,6 +40,7 @@
 //   perimeter sum = ((((+0 + W') + E') + S') + N'        poisson.cpp:69-86 (pois_gs_safe)
 // and both are evaluated as (((z + W) + E) + S) + N with z = -0.0f / +0.0f.
 #pragma once
+#include <type_traits>
 #include <utility>
 
 #ifndef SFL_EDGE_PROLOGUE_MAX_NS
@@ -95,6 +96,21 @@ struct Pipe {
     V da[B::kPrefetch], db[B::kPrefetch];  // prefetched d rows
 };
 
+// An optional backend hook: scalar_only(x) returns x and keeps the compiler from fusing its producer with a neighbour into one
+// packed instruction (sor_lane.h has why); a backend without it, like the emulator, gets x back.  No arithmetic: the same bits.
+template <class B, class = void>
+struct has_scalar_only : std::false_type {};
+template <class B>
+struct has_scalar_only<B, std::void_t<decltype(&B::scalar_only)>> : std::true_type {};
+template <class B>
+SFL_HD typename B::V scalar_only(const B &bk, const typename B::V &x)
+{
+    if constexpr (has_scalar_only<B>::value)
+        return bk.scalar_only(x);
+    else
+        return x;
+}
+
 // One relaxation (poisson.cpp:63-112).
 template <class B, bool EDGE>
 SFL_HD typename B::V relax(const B &bk, const Consts<B> &c, typename B::V own, typename B::V w,
@@ -107,7 +123,7 @@ SFL_HD typename B::V relax(const B &bk, const Consts<B> &c, typename B::V own, t
         const V sum = ((w + e) + s) + n;
         // poisson.cpp:107-111: p_gs = -0.25f * (dx * d - sum); p = (1 - omega) * p + omega * p_gs -- every product rounded on its
         // own, 8 vector instructions, the reference's bits on EVERY input.  This is what the library runs unless asked otherwise.
-        if (!B::kFoldQuarter) return c.one_minus_omega * own + c.omega * (bk.splat(-0.25f) * (rhs - sum));
+        if (!B::kFoldQuarter) return c.one_minus_omega * own + scalar_only(bk, c.omega * (bk.splat(-0.25f) * (rhs - sum)));
         // SFL_OPT_SOR_FOLD = 1 (opt-in): fl(omega * fl(-0.25f * t)), t = dx * d - sum, as ONE rounded product fl((-0.25f * omega) * t) --
         // 7 instructions, the relaxation's dependency chain one shorter (+2.4 .. 3 % on 8192^2).  Scaling by -0.25 is exact unless
         // the product underflows inexactly, so the two are the same bits whenever t is a multiple of 2^-147, i.e. unless an operand
@@ -116,7 +132,7 @@ SFL_HD typename B::V relax(const B &bk, const Consts<B> &c, typename B::V own, t
         // range from ~63 iterations on, and there the reference rounds -0.25f * t to a denormal first and the two products can differ
         // by one unit of 2^-149, which later passes carry along (tests/test_gpu_parity.py test_quiescent_*; an omega whose
         // own quarter would underflow is solved unfolded whatever the option says, sor_executor.cpp).
-        return c.one_minus_omega * own + c.neg_quarter_omega * (rhs - sum);
+        return c.one_minus_omega * own + scalar_only(bk, c.neg_quarter_omega * (rhs - sum));
     }
     const V z = rf.full ? ec.z_full : bk.splat(0.0f);
     const V k = rf.full ? ec.k_full : ec.k_part;
