@@ -32,6 +32,7 @@ STATS_VELOCITY, STATS_DYE = 1, 2
 DIST_VELOCITY, DIST_DYE, DIST_PRESSURE = 1, 2, 4
 ENV_MEAN, ENV_MIN, ENV_MAX, ENV_SPREAD = 0, 1, 2, 3
 UNIQUE_ID_BYTES = 128
+TRACER_THREADS = 256   # kTracerThreads of csrc/tracer_kernels.h: tracers per workgroup (stated for the tests)
 BATCH_LARGE_MAX_CELLS = 20224   # SFL_BATCH_LARGE_MAX_CELLS: cells of one member of sfl_batch_create_large
 
 
@@ -201,6 +202,24 @@ SIGNATURES = {
     "sfl_batch_record_stop": (_i, [_ctx]),
     "sfl_batch_record_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64)]),
     "sfl_batch_record_read": (_i, [_ctx, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
+    "sfl_tracers_set": (_i, [_ctx, _pf, _sz, _i]),
+    "sfl_tracers_count": (_i, [_ctx, C.POINTER(_sz)]),
+    "sfl_tracers_download": (_i, [_ctx, _pf, _sz]),
+    "sfl_tracers_advance": (_i, [_ctx, _f]),
+    "sfl_tracers_sample": (_i, [_ctx, _i, _i, C.c_void_p, _sz]),
+    "sfl_tracers_trail_start": (_i, [_ctx, _i, _i]),
+    "sfl_tracers_trail_stop": (_i, [_ctx]),
+    "sfl_tracers_trail_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64)]),
+    "sfl_tracers_trail_read": (_i, [_ctx, _i, _i, _pf, _sz]),
+    "sfl_batch_tracers_set": (_i, [_ctx, _pf, _sz, _i]),
+    "sfl_batch_tracers_count": (_i, [_ctx, C.POINTER(_sz)]),
+    "sfl_batch_tracers_download": (_i, [_ctx, _pf, _sz]),
+    "sfl_batch_tracers_advance": (_i, [_ctx, _f]),
+    "sfl_batch_tracers_sample": (_i, [_ctx, _i, _i, C.c_void_p, _sz]),
+    "sfl_batch_tracers_trail_start": (_i, [_ctx, _i, _i]),
+    "sfl_batch_tracers_trail_stop": (_i, [_ctx]),
+    "sfl_batch_tracers_trail_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64)]),
+    "sfl_batch_tracers_trail_read": (_i, [_ctx, _i, _i, _pf, _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

@@ -18,7 +18,8 @@ void release(sfl_batch *b)
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (void *m : {(void *)b->vel, (void *)b->vel_tmp, (void *)b->col, (void *)b->col_tmp, (void *)b->div, (void *)b->p,
                     b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_counts, (void *)b->d_image,
-                    (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env})
+                    (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env,
+                    (void *)b->tracers.d_xy, (void *)b->tracers.d_trail})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
     if (b->h_dist) (void)hipHostFree(b->h_dist);
@@ -210,10 +211,12 @@ enum StepKind { kUniform, kEach, kUntil };
 // One launch per step -- but `steps` steps per launch (batch_play.hip) for a call that could not be made before there
 // was a timeline: n >= 2 steps of small members with a record in some step of [1, n), not by the stopping rule.  With a
 // recorder on, such a call is cut into launches that end at the steps whose frame is due, the render between them.
+// With a following set of tracers (tracers_follow) every step is a launch of its own, the advance behind it: the tracers
+// read each step's projected velocity, which the launch of several steps never stores.
 int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
 {
     SFL_TRY(stage_timeline(b, n));
-    if (kind != kUntil && !b->large && n >= 2 && staged_has(b, 1, n)) {
+    if (kind != kUntil && !b->large && n >= 2 && !b->tracers_follow && staged_has(b, 1, n)) {
         for (int done = 0; done < n;) {
             const int steps = sfl::host::record_run(b, n - done);
             sfl::BatchPlay play{};
@@ -250,6 +253,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
         std::swap(b->vel, b->vel_tmp);  // ino:255
         std::swap(b->col, b->col_tmp);  // ino:286
         SFL_TRY(sfl::host::record_step(b));
+        if (b->tracers_follow) SFL_TRY(b->tracers_follow(b, kind == kUniform ? nullptr : b->d_members, a.step.dt));
     }
     consume_forces(b, n);
     return SFL_OK;
@@ -554,6 +558,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     if (n == 0) return SFL_OK;
     SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
+    SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
     SFL_TRY(use_device(b));
     b->report_valid = b->counts_valid = false;   // (the uniform kernels leave no update norm)
     sfl::BatchStep a{};
@@ -586,6 +591,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
     if (n == 0) return SFL_OK;
     SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
+    SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
     b->report_valid = b->counts_valid = false;   // until every launch below is queued; no iterations to report afterwards
@@ -617,6 +623,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
     if (n == 0) return SFL_OK;
     SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
+    SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params, stops));
     b->report_valid = b->counts_valid = false;   // until every launch below is queued

@@ -82,6 +82,12 @@ struct sfl_batch {
     } rec;
     uint16_t *d_frames = nullptr;   // kept by a restart that does not need more; freed by record_stop
     size_t d_frames_bytes = 0;
+    // tracers (tracers.cpp; context.h has TracerSet): `count` per member, positions [member][k][2], a trail slot the
+    // positions of every member.  tracers_follow: one step has been launched and the ping-pong swapped -- launch the
+    // advance on the batch's stream behind it, member by member by the dt of its record (members: the device records
+    // of the step's launch, in its launch order) or all by `dt` (members == nullptr)
+    sfl::host::TracerSet tracers;
+    int (*tracers_follow)(sfl_batch *b, const sfl::BatchMember *members, float dt) = nullptr;
 };
 
 namespace sfl {

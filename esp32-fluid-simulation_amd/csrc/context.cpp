@@ -333,7 +333,8 @@ int sfl_destroy(sfl_context *c)
     for (void *m : {(void *)c->vel, (void *)c->vel_tmp, (void *)c->col, (void *)c->col_tmp,
                     (void *)c->sor_block, (void *)c->halo_flag,
                     (void *)c->d_force_cells, (void *)c->d_force_vel, (void *)c->d_image,
-                    (void *)c->host_scratch, (void *)c->d_reach, c->gather_buf})
+                    (void *)c->host_scratch, (void *)c->d_reach, c->gather_buf, (void *)c->tracers.d_xy,
+                    (void *)c->tracers.d_trail})
         if (m) (void)hipFree(m);
     for (auto &st : c->force_stage) {
         if (st.cells) (void)hipHostFree(st.cells);

@@ -12,6 +12,7 @@
 //   operators.cpp     advection, divergence, projection, forces, setup / render
 //   slab_step.cpp     sfl_step / sfl_step_n, the automatic advection halo of a slab's step
 //   host_dropin.cpp   the host-pointer drop-ins (sfl_host_*) and their per-thread context
+//   tracers.cpp       points that move with the flow (sfl_tracers_*, sfl_batch_tracers_*): sets, advances, samples, trails
 //
 // There is deliberately no CPU compute path in any of them: every operator ends in a kernel launch and fails with
 // SFL_ERR_HIP when no device is usable.
@@ -179,6 +180,42 @@ constexpr OptionRow kOptions[] = {
 }  // namespace host
 }  // namespace sfl
 
+namespace sfl {
+namespace host {
+
+// A set of tracers (tracers.cpp; include/sfl.h "tracers"): what a context or a batch holds of it.  Plain data, so that the
+// two destroy paths free it and the step calls admit a trail's slots without a symbol of tracers.cpp -- the units that
+// step are linked without it by the host test harnesses; what launches is reached through the `tracers_follow` pointer
+// of the two structs, which tracers.cpp sets while a following set is attached (null: the step calls do what they did).
+struct TracerSet {
+    float *d_xy = nullptr;     // positions on the device: `count` float2 (a batch: of every member, member-major)
+    size_t count = 0;          // tracers of the context, or of ONE member of the batch; 0: no set
+    bool follow = false;
+    // the trail: after every `every`-th advance the positions also go to the next of `capacity` slots of d_trail
+    bool trail_on = false;
+    int every = 0, capacity = 0, written = 0;
+    int64_t advances = 0;      // counted since trail_start
+    float *d_trail = nullptr;
+};
+
+// SFL_ERR_STATE if the `advances` advances of a call would complete more slots than the trail has free: the rule of
+// record_admit (batch_state.h) -- after the call's own argument checks, before anything is staged or launched
+inline int trail_admit(const TracerSet &t, int64_t advances)
+{
+    if (!t.trail_on) return SFL_OK;
+    const int64_t due = (t.advances + advances) / t.every - t.advances / t.every, room = t.capacity - t.written;
+    if (due > room)
+        return fail(SFL_ERR_STATE, "the trail has room for %lld more slots (%d of %d written) and %lld advances would complete %lld: "
+                    "nothing stepped or advanced; read the trail and start it again to make room",
+                    (long long)room, t.written, t.capacity, (long long)advances, (long long)due);
+    return SFL_OK;
+}
+// ... of the steps of a step call: a set that does not follow is not advanced by them
+inline int trail_admit_steps(const TracerSet &t, int n) { return t.follow && t.count ? trail_admit(t, n) : SFL_OK; }
+
+}  // namespace host
+}  // namespace sfl
+
 struct sfl_context {
     int device = 0;
     int dim_x = 0, gdim_y = 0;
@@ -284,6 +321,11 @@ struct sfl_context {
     int known_reach_ext = -1;      // ... when own +- 1 rows are advected (reach_extended)
     uint64_t known_epoch = 0, vel_epoch = 1;   // vel_epoch counts the writes to the velocity field
     float known_dt = 0.0f;
+
+    // tracers (tracers.cpp): the set, and the advance behind every step while it follows (one step has run, its
+    // projected velocity is stored: launch the advance by dt on the context's stream)
+    sfl::host::TracerSet tracers;
+    int (*tracers_follow)(sfl_context *c, float dt) = nullptr;
 
     sfl::host::Options opt;   // what sfl_set_option stores (kOptions above: one row per option)
 

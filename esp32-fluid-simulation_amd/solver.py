@@ -163,7 +163,85 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
-class Solver:
+class _Tracers:
+    """Tracers: points that move with the flow and probes of the fields between the cell centres (include/sfl.h
+    "TRACERS").  Shared by :class:`Solver` (``xy`` is ``float32[n, 2]``) and :class:`BatchSolver` (``float32[B, K, 2]``, K
+    tracers in every member).  A position is (x along i, y along j) in grid coordinates, as ``sample()`` takes them."""
+
+    _tracer_prefix = "sfl_tracers_"
+
+    def _tracer_call(self, name):
+        return getattr(self._lib, self._tracer_prefix + name)
+
+    def _tracer_lead(self):   # the leading axes of every tracer array: () for a context, (B,) for a batch
+        return ()
+
+    def tracer_count(self) -> int:
+        """Tracers attached: of the context, or of ONE member of the batch; 0 without a set."""
+        n = C.c_size_t(0)
+        capi.check(self._tracer_call("count")(self._h, C.byref(n)))
+        return n.value
+
+    def set_tracers(self, xy, follow: bool = True):
+        """Attach tracers at `xy`, replacing the set held and ending its trail; an empty array removes the set.  With
+        `follow` every step of every step call advances them by that step's dt on that step's projected velocity: they
+        move as the dye does, and ``step_n(n)`` equals n x (``step``; ``advance_tracers(dt)``) bit for bit.  With a
+        following set ``Solver.step_n`` runs without the fused step boundaries (OPT_STEP_SEAMS) and a batch's replay of
+        a timeline runs one launch per step: same bits, the cost of single steps."""
+        a = np.ascontiguousarray(xy, np.float32)
+        lead = self._tracer_lead()
+        if a.size == 0:
+            capi.check(self._tracer_call("set")(self._h, None, 0, int(follow)))
+            return
+        if a.ndim != len(lead) + 2 or a.shape[:len(lead)] != lead or a.shape[-1] != 2:
+            raise ValueError(f"tracers: float32{list(lead) + ['n', 2]}, got shape {a.shape}")
+        capi.check(self._tracer_call("set")(self._h, _fp(a), a.shape[-2], int(follow)))
+
+    def tracers(self) -> np.ndarray:
+        """The positions now, ``float32[n, 2]`` (a batch: ``[B, K, 2]``).  Synchronous."""
+        out = np.empty(self._tracer_lead() + (self.tracer_count(), 2), np.float32)
+        capi.check(self._tracer_call("download")(self._h, _fp(out), out.size))
+        return out
+
+    def advance_tracers(self, dt):
+        """One advance by `dt` on the current velocity: x += u.x * dt, y += u.y * dt with u = sample(velocity, x, y,
+        no_slip=True); a tracer with a NaN coordinate stays as it is.  Asynchronous."""
+        capi.check(self._tracer_call("advance")(self._h, dt))
+
+    def sample_tracers(self, field: int, no_slip: bool = False) -> np.ndarray:
+        """``sample()`` of one field at every tracer, bit for bit the header's: velocity ``float32[n, 2]``, dye
+        ``uint32[n, 3]``, divergence and pressure ``float32[n]`` (a batch: a leading B).  A tracer with a NaN coordinate
+        reads NaN (the dye: 0).  Reads only; synchronous."""
+        dt, nc = _FIELD_SPEC.get(field, (np.float32, 1))
+        out = np.empty(self._tracer_lead() + (self.tracer_count(),) + ((nc,) if nc > 1 else ()), dt)
+        capi.check(self._tracer_call("sample")(self._h, field, int(no_slip), out.ctypes.data, out.nbytes))
+        return out
+
+    def trail_start(self, every: int = 1, capacity: int = 64):
+        """Start a trail: after every `every`-th advance (followed or manual) the positions are also written to the
+        next of `capacity` slots in device memory, by the advance's own launch.  A call whose advances would complete
+        more slots than are free raises SflError with ERR_STATE and does nothing."""
+        capi.check(self._tracer_call("trail_start")(self._h, every, capacity))
+
+    def trail_info(self):
+        """(slots written, capacity, advances counted since trail_start); zeros without a trail.  Never waits."""
+        written, capacity, advances = C.c_int(), C.c_int(), C.c_int64()
+        capi.check(self._tracer_call("trail_info")(self._h, C.byref(written), C.byref(capacity), C.byref(advances)))
+        return written.value, capacity.value, advances.value
+
+    def trail(self) -> np.ndarray:
+        """The slots written so far, ``float32[slots, n, 2]`` (a batch: ``[slots, B, K, 2]``); not consumed.  Synchronous."""
+        written = self.trail_info()[0]
+        out = np.empty((written,) + self._tracer_lead() + (self.tracer_count(), 2), np.float32)
+        capi.check(self._tracer_call("trail_read")(self._h, 0, written, _fp(out), out.size))
+        return out
+
+    def trail_stop(self):
+        """Stop the trail and free its slots."""
+        capi.check(self._tracer_call("trail_stop")(self._h))
+
+
+class Solver(_Tracers):
     """One solver context: rows [row_begin, row_end) of a dim_x * dim_y domain on one device."""
 
     def __init__(self, dim_x: int, dim_y: int, device: int = 0, rank: int = 0, nranks: int = 1):
@@ -381,7 +459,7 @@ class Solver:
         return {"launches": a.value, "exchanges": b.value, "fuse": c.value, "halo": self.get_option(capi.OPT_LAST_HALO)}
 
 
-class BatchSolver:
+class BatchSolver(_Tracers):
     """A batch (sfl_batch_*): `batch` independent whole-domain simulations of one dim_x * dim_y grid on one device,
     every member stepped by the same launch.  Member m holds, bit for bit, what a :class:`Solver` of the same shape
     holds after the same calls made with member m's data and forces.  Arrays of members are shaped
@@ -397,6 +475,11 @@ class BatchSolver:
         capi.check(create(C.byref(self._h), device, dim_x, dim_y, batch))
         self.dim_x, self.dim_y, self.batch, self.device = dim_x, dim_y, batch, device
         self._rec = (0, 0, 1)   # (first, count, scaling) of the running recording: the shape of what frames() reads
+
+    _tracer_prefix = "sfl_batch_tracers_"
+
+    def _tracer_lead(self):
+        return (self.batch,)
 
     def close(self):
         if self._h:

@@ -794,6 +794,74 @@ SFL_API int sfl_batch_record_info(sfl_batch *b, int *frames, int *capacity, int6
  * Not recording: SFL_ERR_STATE.  b NULL, host NULL (count > 0), frame outside [0, frames written), a range that is not
  * inside the recorded one and bytes != count * H * W * 2 return SFL_ERR_INVALID before any GPU work.                    */
 SFL_API int sfl_batch_record_read(sfl_batch *b, int frame, int first, int count, uint16_t *host, size_t bytes);
+/* --- TRACERS: points that move with the flow, and probes of the fields at positions that are no cell centres, without
+ *     a download.  A context (group 2; WHOLE-DOMAIN contexts only: a slab gets SFL_ERR_STATE) holds one set of n tracers;
+ *     a batch (sfl_batch_tracers_*) holds K tracers per member, laid out [member][k][2].
+ *   A position (x, y) is two floats in GRID coordinates: x along i (the fast axis) and y along j, exactly the coordinates
+ * sample(p, i, j, dim_x, dim_y, no_slip) of sfl/advect.h takes; cell (i, j) has its centre at (i, j).
+ *   ADVANCE by dt: u = sample<Vector2<float>>(velocity, x, y, dim_x, dim_y, true) on the velocity the context or member
+ * holds at that moment, then x' = x + u.x * dt, y' = y + u.y * dt: per component one rounded product and one rounded sum,
+ * no FMA.  no_slip is true, as the reference samples the velocity (ino:253): a tracer more than half a cell outside a
+ * wall samples zero and stops.
+ *   SAMPLE: at every tracer sample<T> of ONE field, bit for bit the header's: SFL_FIELD_VELOCITY as Vector2<float> (8
+ * bytes per tracer), SFL_FIELD_PRESSURE and SFL_FIELD_DIVERGENCE as float (4), SFL_FIELD_COLOR as Vector3<UQ32> (12, the
+ * raw values; narrowed to UQ32 exactly where the reference narrows).  The caller chooses no_slip.
+ *   NaN: a tracer with a NaN coordinate is never sampled: an advance leaves BOTH its coordinates as they are, a sample
+ * writes NaN for the float fields and 0 for the dye.  +-inf and huge finite coordinates are ordinary positions outside
+ * the domain and take sample's wall branches.  A NaN velocity makes a position NaN; it then stays.
+ *   FOLLOWING: a set made with follow != 0 is advanced after every step of every step call (sfl_step, sfl_step_n; a
+ * batch: sfl_batch_step_n, _each, _until), with that step's dt (a batch's _each and _until calls: each member's own) and
+ * that step's projected velocity -- the tracers move as the dye does.  sfl_step_n(n) with a following set == n x
+ * (sfl_step; sfl_tracers_advance(dt)), bit for bit in the positions and in every field.  The advance is one launch on
+ * the context's or batch's stream behind the step's: the step calls stay as asynchronous as they are.  A step call reads
+ * each step's projected velocity from memory, so with a following set sfl_step_n runs WITHOUT the fused step boundaries
+ * of SFL_OPT_STEP_SEAMS (which never store it), and a batch's call with records in its later steps runs one launch per
+ * step instead of one for all: the fields keep their bits, the call costs what n single steps cost.  Without a
+ * following set every call launches exactly what it launched before there were tracers.
+ *   TRAILS: after sfl_tracers_trail_start, every advance (followed or sfl_tracers_advance) counts, and after every
+ * `every`-th the positions are also written to the next of `capacity` slots in device memory (by the advance's own
+ * launch), read out afterwards.  A call whose advances would complete more slots than are free is refused WHOLE with
+ * SFL_ERR_STATE, after its argument checks and before anything is staged or launched: fields, positions, timeline and
+ * counts stay untouched.
+ *   Every refusal below is made before any GPU work and carries its own message (sfl_last_error).  capacity of a
+ * position buffer counts FLOATS.                                                                                        */
+/* Attach n tracers at xy[2 k], xy[2 k + 1] (copied; synchronous), replacing the set the context holds and ending its
+ * trail.  n == 0 removes the set (xy may be NULL).  ctx NULL, xy NULL with n > 0: SFL_ERR_INVALID; a slab: SFL_ERR_STATE. */
+SFL_API int sfl_tracers_set(sfl_context *ctx, const float *xy, size_t n, int follow);
+/* *n = the tracers attached (0: none).  NULL arguments: SFL_ERR_INVALID.                                                */
+SFL_API int sfl_tracers_count(sfl_context *ctx, size_t *n);
+/* The positions now (synchronous).  capacity < 2 n floats, NULL arguments: SFL_ERR_INVALID; no set: SFL_ERR_STATE.       */
+SFL_API int sfl_tracers_download(sfl_context *ctx, float *xy, size_t capacity);
+/* One advance by dt on the current velocity (asynchronous).  No set: SFL_ERR_STATE; a full trail: SFL_ERR_STATE.         */
+SFL_API int sfl_tracers_advance(sfl_context *ctx, float dt);
+/* sample<T> of `field` (SFL_FIELD_*) at every tracer, n elements in tracer order (synchronous; reads only).  An unknown
+ * field, capacity_bytes < n elements, NULL arguments: SFL_ERR_INVALID; no set: SFL_ERR_STATE.                           */
+SFL_API int sfl_tracers_sample(sfl_context *ctx, int field, int no_slip, void *out, size_t capacity_bytes);
+/* Start a trail of `capacity` slots, one after every `every`-th advance; the count of advances starts at 0.  Called with
+ * a trail running, it starts afresh.  every < 1, capacity < 1 (or slots whose bytes do not fit a size_t), ctx NULL:
+ * SFL_ERR_INVALID; no set attached: SFL_ERR_STATE.                                                                      */
+SFL_API int sfl_tracers_trail_start(sfl_context *ctx, int every, int capacity);
+/* Stop the trail and free its slots (sfl_tracers_set and sfl_destroy do too).  Without a trail: SFL_OK.                  */
+SFL_API int sfl_tracers_trail_stop(sfl_context *ctx);
+/* Slots written so far, the capacity, the advances counted since the start; all 0 without a trail.  Out pointers may be
+ * NULL.  Never waits.                                                                                                   */
+SFL_API int sfl_tracers_trail_info(sfl_context *ctx, int *written, int *capacity, int64_t *advances);
+/* Slots [first_slot, first_slot + slots) into xy, slot-major, each slot n positions (synchronous; not consumed).  A
+ * range that is not inside the slots written, capacity < slots * 2 n floats, NULL arguments: SFL_ERR_INVALID; no trail:
+ * SFL_ERR_STATE.                                                                                                        */
+SFL_API int sfl_tracers_trail_read(sfl_context *ctx, int first_slot, int slots, float *xy, size_t capacity);
+/* The same for a batch of either kind: k tracers per member, xy and every slot laid out [member][k][2], samples
+ * [member][k][element]; capacities count the floats (bytes) of ALL members.  sfl_batch_tracers_advance moves every
+ * member by the one dt.  *k of sfl_batch_tracers_count is the number per member.                                         */
+SFL_API int sfl_batch_tracers_set(sfl_batch *b, const float *xy, size_t k, int follow);
+SFL_API int sfl_batch_tracers_count(sfl_batch *b, size_t *k);
+SFL_API int sfl_batch_tracers_download(sfl_batch *b, float *xy, size_t capacity);
+SFL_API int sfl_batch_tracers_advance(sfl_batch *b, float dt);
+SFL_API int sfl_batch_tracers_sample(sfl_batch *b, int field, int no_slip, void *out, size_t capacity_bytes);
+SFL_API int sfl_batch_tracers_trail_start(sfl_batch *b, int every, int capacity);
+SFL_API int sfl_batch_tracers_trail_stop(sfl_batch *b);
+SFL_API int sfl_batch_tracers_trail_info(sfl_batch *b, int *written, int *capacity, int64_t *advances);
+SFL_API int sfl_batch_tracers_trail_read(sfl_batch *b, int first_slot, int slots, float *xy, size_t capacity);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
