@@ -31,6 +31,9 @@ STEP_EXCHANGE, STEP_SOR, STEP_ZERO = 1, 2, 3
 STATS_VELOCITY, STATS_DYE = 1, 2
 DIST_VELOCITY, DIST_DYE, DIST_PRESSURE = 1, 2, 4
 ENV_MEAN, ENV_MIN, ENV_MAX, ENV_SPREAD = 0, 1, 2, 3
+VIEW_SPEED, VIEW_VORTICITY, VIEW_PRESSURE, VIEW_DIVERGENCE = 0, 1, 2, 3
+VIEW_MAX_STOPS = 256
+VIEW_MAX_COLOUR = 0xFC000000
 UNIQUE_ID_BYTES = 128
 TRACER_THREADS = 256   # kTracerThreads of csrc/tracer_kernels.h: tracers per workgroup (stated for the tests)
 BATCH_LARGE_MAX_CELLS = 20224   # SFL_BATCH_LARGE_MAX_CELLS: cells of one member of sfl_batch_create_large
@@ -67,6 +70,12 @@ class FieldDistance(C.Structure):
     _fields_ = [("max_abs_dvx", C.c_float), ("max_abs_dvy", C.c_float), ("max_abs_dp", C.c_float), ("what", C.c_uint32),
                 ("velocity_cells_differ", C.c_uint32), ("dye_cells_differ", C.c_uint32), ("pressure_cells_differ", C.c_uint32),
                 ("max_abs_ddye", C.c_uint32 * 3), ("sum_abs_ddye", C.c_uint64 * 3)]
+
+
+class View(C.Structure):
+    """struct sfl_view: a scalar of the flow and the palette it is drawn with, 40 bytes."""
+    _fields_ = [("what", C.c_int32), ("dx", C.c_float), ("lo", C.c_float), ("hi", C.c_float), ("stops", C.c_int32),
+                ("nan_colour", C.c_uint32 * 3), ("colours", C.POINTER(C.c_uint32))]
 
 
 class SflError(RuntimeError):
@@ -220,6 +229,13 @@ SIGNATURES = {
     "sfl_batch_tracers_trail_stop": (_i, [_ctx]),
     "sfl_batch_tracers_trail_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64)]),
     "sfl_batch_tracers_trail_read": (_i, [_ctx, _i, _i, _pf, _sz]),
+    "sfl_view_scalar": (_i, [_ctx, _i, _f, _pf, _sz]),
+    "sfl_batch_view_scalar": (_i, [_ctx, _i, _f, _i, _i, _pf, _sz]),
+    "sfl_view_texels": (_i, [_ctx, C.POINTER(View), _pu, _sz]),
+    "sfl_batch_view_texels": (_i, [_ctx, C.POINTER(View), _i, _i, _pu, _sz]),
+    "sfl_view_render": (_i, [_ctx, C.POINTER(View), _i, _i, C.POINTER(C.c_uint16), _sz]),
+    "sfl_batch_view_render_members": (_i, [_ctx, C.POINTER(View), _i, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
+    "sfl_batch_record_view": (_i, [_ctx, C.POINTER(View)]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

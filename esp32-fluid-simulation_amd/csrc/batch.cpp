@@ -19,7 +19,8 @@ void release(sfl_batch *b)
     for (void *m : {(void *)b->vel, (void *)b->vel_tmp, (void *)b->col, (void *)b->col_tmp, (void *)b->div, (void *)b->p,
                     b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_counts, (void *)b->d_image,
                     (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env,
-                    (void *)b->tracers.d_xy, (void *)b->tracers.d_trail})
+                    (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
+                    (void *)b->d_rec_palette})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
     if (b->h_dist) (void)hipHostFree(b->h_dist);

@@ -2,6 +2,8 @@
 // members in one launch and one copy, and the recorder sfl_batch_record_*, which renders a frame of chosen members every
 // k-th step into device memory, between the step launches of sfl_batch_step_n* and on the batch's stream, so that the
 // step calls stay asynchronous and the frames are read out afterwards.  Host C++ only; the kernel is batch_render.hip.
+// A frame shows the dye unless sfl_batch_record_view (views.cpp) has set a view: then record_step calls through the batch's
+// record_view_frame pointer, so that this unit links without the views' kernels.
 #include "batch_state.h"
 
 using sfl::host::fail;
@@ -88,8 +90,11 @@ int record_step(sfl_batch *b, int steps)
     if (r.steps % r.every != 0) return SFL_OK;
     const int frame = (int)(r.steps / r.every) - 1;   // < capacity: record_admit has let the call through
     uint16_t *images = b->d_frames + (size_t)frame * r.count * image_pixels(b, r.scaling);
-    HIP_TRY(sfl::launch_batch_render(b->stream, images, b->col + 3 * (size_t)r.first * b->cells, b->dim_x, b->dim_y, r.count,
-                                     r.scaling, r.byteswap != 0));
+    if (r.view_on && b->record_view_frame)   // (sfl_batch_record_view: the frame shows a view of v or p, not the dye)
+        SFL_TRY(b->record_view_frame(b, images));
+    else
+        HIP_TRY(sfl::launch_batch_render(b->stream, images, b->col + 3 * (size_t)r.first * b->cells, b->dim_x, b->dim_y, r.count,
+                                         r.scaling, r.byteswap != 0));
     r.written = frame + 1;
     return SFL_OK;
 }

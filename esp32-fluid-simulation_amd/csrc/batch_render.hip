@@ -11,7 +11,8 @@
 //     along it.  A texel is fetched once per tile that touches it (the one-texel overlap with the neighbour included);
 //   * draw: consecutive lanes run along the image row, one thread per block and image row: it takes the block's four
 //     corners from LDS, walks both edges once and then across its `scaling` pixels by the chain of render_math.h (the
-//     chain of a pixel is a prefix of its right neighbour's), and stores them, in pairs where they are aligned.
+//     chain of a pixel is a prefix of its right neighbour's), and stores them, in pairs where they are aligned.  The
+//     tile's constants and this phase live in render_tile.h: field_view.hip draws its node colours with the same code.
 //
 // LDS layout: word 3 * it + k of column jt at jt * kPitch, kPitch = 3 * (kTileI + 1) = 51 words, no padding.  The guide's
 // bank rule (section 2) for ds_write_b32 / ds_read_b32: bank = word % 32, conflicts within each 32-lane half.  The
@@ -32,27 +33,20 @@
 // member's image starts on a 2-byte boundary only (H * W can be odd): every 32-bit store checks its own alignment, the
 // rest are 16-bit.
 #include "batch.h"
-#include "render_math.h"
+#include "render_tile.h"
 
 namespace sfl {
 namespace {
 
 using namespace render_math;
+using namespace render_tile;   // the tile's constants and its draw phase, shared with field_view.hip
 using advect_math::uq_widen;
-
-constexpr int kThreads = 256;
-constexpr int kTileI = 16, kTileJ = 32;         // cell blocks per tile, down (i) and across (j) the screen
-constexpr int kPitch = 3 * (kTileI + 1);        // words per staged column: odd (see above)
-// workgroups of a launch; they stride over the (member, tile) pairs.  32 per CU of the device's 256: every pair costs
-// the same, so more would balance nothing, and a batch of more than 65536 members takes the loop's later passes
-constexpr unsigned kMaxGrid = 1u << 16;
-static_assert(kPitch % 2 == 1, "an odd pitch keeps 32 consecutive columns on 32 banks");
 
 __global__ void __launch_bounds__(kThreads)
 batch_render_kernel(uint16_t *__restrict__ images, const uint32_t *__restrict__ colour, int dim_x, int dim_y, int scaling,
                     int byteswap, int tiles_i, int tiles_j, unsigned long long total)
 {
-    __shared__ float texel[(kTileJ + 1) * kPitch];
+    __shared__ float texel[kTexelWords];
     const int tiles = tiles_i * tiles_j;
     const int width = scaling * (dim_y - 1), height = scaling * (dim_x - 1);
     const float inv = render_inv(scaling);
@@ -73,35 +67,9 @@ batch_render_kernel(uint16_t *__restrict__ images, const uint32_t *__restrict__ 
         }
         __syncthreads();
 
-        // draw: rows * scaling image rows of cols blocks; one thread takes the `scaling` pixels of one block in one image
-        // row: both edge walks once, then ONE walk across (pixel jj + 1 continues the chain of pixel jj)
-        for (int n = threadIdx.x; n < rows * scaling * cols; n += kThreads) {
-            const int py = n / cols, jt = n - py * cols;
-            const int it = py / scaling, ii = py - it * scaling;
-            const float *t1 = texel + jt * kPitch + 3 * it, *t2 = t1 + kPitch;
-            RenderWalk red(render_walk(t1[0], t1[3], inv, ii), render_walk(t2[0], t2[3], inv, ii), inv);
-            RenderWalk green(render_walk(t1[1], t1[4], inv, ii), render_walk(t2[1], t2[4], inv, ii), inv);
-            RenderWalk blue(render_walk(t1[2], t1[5], inv, ii), render_walk(t2[2], t2[5], inv, ii), inv);
-            const auto next = [&]() {
-                const uint16_t px = render_pack(advect_math::uq_narrow(red.x), advect_math::uq_narrow(green.x),
-                                                advect_math::uq_narrow(blue.x), byteswap);
-                red.step();
-                green.step();
-                blue.step();
-                return px;
-            };
-            uint16_t *out = image + ((i0 * scaling + py) * width + (j0 + jt) * scaling);
-            // pairs of pixels as one 32-bit store where this thread's pixels allow it: an even count on a 4-byte boundary
-            // (a member's image starts on a 2-byte boundary only)
-            if ((scaling & 1) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0) {
-                for (int jj = 0; jj < scaling; jj += 2) {
-                    const uint32_t lo = next(), hi = next();
-                    *reinterpret_cast<uint32_t *>(out + jj) = lo | (hi << 16);
-                }
-            } else {
-                for (int jj = 0; jj < scaling; ++jj) out[jj] = next();
-            }
-        }
+        // draw (render_tile.h): rows * scaling image rows of cols blocks; one thread takes the `scaling` pixels of one
+        // block in one image row: both edge walks once, then ONE walk across (pixel jj + 1 continues the chain of pixel jj)
+        draw_tile(texel, image, i0, j0, rows, cols, scaling, width, inv, byteswap);
         __syncthreads();   // the next tile's load overwrites what this one's draw reads
     }
 }

@@ -5,6 +5,7 @@
 #include "batch.h"
 #include "context.h"
 #include "stats_kernels.h"
+#include "view_kernels.h"
 
 struct sfl_batch {
     int device = 0;
@@ -79,6 +80,9 @@ struct sfl_batch {
         bool on = false;
         int every = 0, first = 0, count = 0, scaling = 0, byteswap = 0, capacity = 0, written = 0;
         int64_t steps = 0;
+        // what the frames show (sfl_batch_record_view): the dye, or this view, its palette in the batch's d_rec_palette
+        bool view_on = false;
+        sfl::ViewParams view{};
     } rec;
     uint16_t *d_frames = nullptr;   // kept by a restart that does not need more; freed by record_stop
     size_t d_frames_bytes = 0;
@@ -88,6 +92,14 @@ struct sfl_batch {
     // of the step's launch, in its launch order) or all by `dt` (members == nullptr)
     sfl::host::TracerSet tracers;
     int (*tracers_follow)(sfl_batch *b, const sfl::BatchMember *members, float dt) = nullptr;
+    // views (views.cpp): the scratch of the view calls; the recorder's staged palette (allocated by the first
+    // sfl_batch_record_view, kept until the batch goes) and the host copy its upload reads; record_view_frame: a frame of
+    // the recorder's view (rec.view) is due -- launch its render into `images` on the batch's stream.  Set by
+    // sfl_batch_record_view: batch_frames.cpp, which the host test harnesses link without views.cpp, calls through it
+    sfl::host::ViewScratch views;
+    uint32_t *d_rec_palette = nullptr;
+    std::vector<uint32_t> rec_palette_host;
+    int (*record_view_frame)(sfl_batch *b, uint16_t *images) = nullptr;
 };
 
 namespace sfl {

@@ -213,6 +213,15 @@ inline int trail_admit(const TracerSet &t, int64_t advances)
 // ... of the steps of a step call: a set that does not follow is not advanced by them
 inline int trail_admit_steps(const TracerSet &t, int n) { return t.follow && t.count ? trail_admit(t, n) : SFL_OK; }
 
+// What the view calls (views.cpp; include/sfl.h "VIEWS") keep on the device for a context or a batch: the staged palette
+// of the call (kViewPaletteWords words, allocated at the first call) and the call's result, which only grows.  Plain
+// data, freed by the two destroy paths, so that they need no symbol of views.cpp.
+struct ViewScratch {
+    uint32_t *d_palette = nullptr;
+    void *d_out = nullptr;
+    size_t out_bytes = 0;
+};
+
 }  // namespace host
 }  // namespace sfl
 
@@ -326,6 +335,7 @@ struct sfl_context {
     // projected velocity is stored: launch the advance by dt on the context's stream)
     sfl::host::TracerSet tracers;
     int (*tracers_follow)(sfl_context *c, float dt) = nullptr;
+    sfl::host::ViewScratch views;   // sfl_view_* (views.cpp)
 
     sfl::host::Options opt;   // what sfl_set_option stores (kOptions above: one row per option)
 

@@ -163,6 +163,38 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
+# ---- views: the flow itself as pictures (include/sfl.h "VIEWS") ----------------------------------------------------
+_M = capi.VIEW_MAX_COLOUR   # the largest channel a palette may hold
+PALETTE_GREY = np.array([[(n * _M) // 255] * 3 for n in range(256)], np.uint32)                    # black -> white
+PALETTE_HEAT = np.array([[0, 0, 0], [_M, 0, 0], [_M, _M, 0], [_M, _M, _M]], np.uint32)             # black, red, yellow, white
+PALETTE_BLUE_WHITE_RED = np.array([[0, 0, _M], [_M, _M, _M], [_M, 0, 0]], np.uint32)               # for lo = -hi: zero is white
+
+
+class View:
+    """A scalar of the flow and how it is drawn (struct sfl_view): `what` is capi.VIEW_SPEED, VIEW_VORTICITY,
+    VIEW_PRESSURE or VIEW_DIVERGENCE; scalars lo .. hi map to the first .. last stop of `palette` (uint32[stops, 3], raw
+    UQ32, every value <= capi.VIEW_MAX_COLOUR; 2..256 stops), linearly between neighbouring stops and clamped outside;
+    a NaN gets `nan_colour`.  dx: the grid spacing of vorticity and divergence."""
+
+    def __init__(self, what: int, lo: float, hi: float, palette=None, dx: float = 1.0, nan_colour=(0, _M, 0)):
+        palette = PALETTE_GREY if palette is None else palette
+        self.palette = np.array(palette, np.uint32, order="C")   # (a copy: the struct points into it)
+        if self.palette.ndim != 2 or self.palette.shape[1] != 3:
+            raise ValueError(f"a palette is uint32[stops, 3], got {self.palette.shape}")
+        if len(nan_colour) != 3:
+            raise ValueError("nan_colour is three UQ32 values")
+        self.what, self.lo, self.hi, self.dx, self.nan_colour = int(what), float(lo), float(hi), float(dx), tuple(int(x) for x in nan_colour)
+
+    def struct(self) -> "capi.View":
+        """The C struct; it points into self.palette, which lives as long as this object."""
+        return capi.View(self.what, self.dx, self.lo, self.hi, self.palette.shape[0], (C.c_uint32 * 3)(*self.nan_colour),
+                         self.palette.ctypes.data_as(C.POINTER(C.c_uint32)))
+
+
+def _u16p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint16))
+
+
 class _Tracers:
     """Tracers: points that move with the flow and probes of the fields between the cell centres (include/sfl.h
     "TRACERS").  Shared by :class:`Solver` (``xy`` is ``float32[n, 2]``) and :class:`BatchSolver` (``float32[B, K, 2]``, K
@@ -440,6 +472,25 @@ class Solver(_Tracers):
         img = np.empty((scaling * (self.dim_x - 1), scaling * (self.dim_y - 1)), np.uint16)
         capi.check(self._lib.sfl_render_rgb565(self._h, scaling, int(byteswap),
                                                img.ctypes.data_as(C.POINTER(C.c_uint16)), img.nbytes))
+        return img
+
+    # -- views ---------------------------------------------------------------------------
+    def view_scalar(self, what: int, dx: float = 1.0) -> np.ndarray:
+        """Speed, vorticity, pressure or divergence (capi.VIEW_*) of the fields held now, float32[dim_y, dim_x]."""
+        out = np.empty((self.dim_y, self.dim_x), np.float32)
+        capi.check(self._lib.sfl_view_scalar(self._h, what, dx, out.ctypes.data_as(C.POINTER(C.c_float)), out.nbytes))
+        return out
+
+    def view_texels(self, view: View) -> np.ndarray:
+        """The node colours of a view, uint32[dim_y, dim_x, 3]: laid out as the dye."""
+        out = np.empty((self.dim_y, self.dim_x, 3), np.uint32)
+        capi.check(self._lib.sfl_view_texels(self._h, C.byref(view.struct()), out.ctypes.data_as(C.POINTER(C.c_uint32)), out.nbytes))
+        return out
+
+    def view_render(self, view: View, scaling: int = 4, byteswap: bool = True) -> np.ndarray:
+        """A view -> RGB565 image shaped as :meth:`render_rgb565`'s: the draw task's chain on the view's node colours."""
+        img = np.empty((max(scaling, 0) * (self.dim_x - 1), max(scaling, 0) * (self.dim_y - 1)), np.uint16)
+        capi.check(self._lib.sfl_view_render(self._h, C.byref(view.struct()), scaling, int(byteswap), _u16p(img), img.nbytes))
         return img
 
     def synchronize(self):
@@ -767,6 +818,39 @@ class BatchSolver(_Tracers):
             capi.check(self._lib.sfl_batch_record_read(self._h, frame_first + f, first, count,
                                                        out[f].ctypes.data_as(C.POINTER(C.c_uint16)), out[f].nbytes))
         return out
+
+    # -- views ---------------------------------------------------------------------------
+    def _view_count(self, first, count):
+        return self.batch - first if count is None else count
+
+    def view_scalar(self, what: int, dx: float = 1.0, first: int = 0, count=None) -> np.ndarray:
+        """Speed, vorticity, pressure or divergence (capi.VIEW_*) of members [first, first + count), float32[count, dim_y,
+        dim_x], from one launch and one copy."""
+        count = self._view_count(first, count)
+        out = np.empty((max(count, 0), self.dim_y, self.dim_x), np.float32)
+        capi.check(self._lib.sfl_batch_view_scalar(self._h, what, dx, first, count, out.ctypes.data_as(C.POINTER(C.c_float)), out.nbytes))
+        return out
+
+    def view_texels(self, view: View, first: int = 0, count=None) -> np.ndarray:
+        """The node colours of a view of members [first, first + count), uint32[count, dim_y, dim_x, 3]."""
+        count = self._view_count(first, count)
+        out = np.empty((max(count, 0), self.dim_y, self.dim_x, 3), np.uint32)
+        capi.check(self._lib.sfl_batch_view_texels(self._h, C.byref(view.struct()), first, count,
+                                                   out.ctypes.data_as(C.POINTER(C.c_uint32)), out.nbytes))
+        return out
+
+    def view_render_members(self, view: View, first: int = 0, count=None, scaling: int = 4, byteswap: bool = True) -> np.ndarray:
+        """A view of members [first, first + count) -> RGB565 images shaped as :meth:`render_members`'s, one launch."""
+        count = self._view_count(first, count)
+        img = np.empty((max(count, 0), max(scaling, 0) * (self.dim_x - 1), max(scaling, 0) * (self.dim_y - 1)), np.uint16)
+        capi.check(self._lib.sfl_batch_view_render_members(self._h, C.byref(view.struct()), first, count, scaling, int(byteswap),
+                                                           _u16p(img), img.nbytes))
+        return img
+
+    def record_view(self, view=None):
+        """What the recorder draws from the next frame on: a :class:`View`, or the dye (None).  Only while recording;
+        record_start and record_stop reset it to the dye.  The view is copied: it may be dropped after the call."""
+        capi.check(self._lib.sfl_batch_record_view(self._h, None if view is None else C.byref(view.struct())))
 
     def synchronize(self):
         capi.check(self._lib.sfl_batch_synchronize(self._h))

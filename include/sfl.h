@@ -862,6 +862,73 @@ SFL_API int sfl_batch_tracers_trail_start(sfl_batch *b, int every, int capacity)
 SFL_API int sfl_batch_tracers_trail_stop(sfl_batch *b);
 SFL_API int sfl_batch_tracers_trail_info(sfl_batch *b, int *written, int *capacity, int64_t *advances);
 SFL_API int sfl_batch_tracers_trail_read(sfl_batch *b, int first_slot, int slots, float *xy, size_t capacity);
+/* --- VIEWS: the flow itself as pictures -- speed, vorticity, pressure and divergence, without a download.  A view is a
+ *     scalar field derived from the velocity or the pressure, mapped through a palette to one Vector3<UQ32> texel per
+ *     grid node and drawn by the draw task's own chain.  A view image is, BY DEFINITION, sfl_batch_render_rgb565 of a
+ *     member whose dye is the view's node colours, bit for bit.  Whole-domain contexts (a slab: SFL_ERR_STATE) and
+ *     batches of either kind.  Every call reads only, runs on the object's stream behind whatever was launched before,
+ *     and is synchronous only where it copies to the host.
+ *   THE FOUR SCALARS are float32, every product, sum and quotient rounded on its own, node (i, j) at dim_x * j + i; all
+ * four use k = 1.0f / (2.0f * dx), formed as calculate_divergence forms it:
+ *     SFL_VIEW_SPEED       sqrtf(vx * vx + vy * vy), correctly rounded, denormals kept; dx plays no part.
+ *     SFL_VIEW_VORTICITY   ((E - W) - (N - S)) * k in this order for EVERY node (there is no separate edge order), E, W =
+ *                          vy at (i + 1, j) and (i - 1, j), N, S = vx at (i, j + 1) and (i, j - 1); a neighbour outside
+ *                          the domain is MINUS THE NODE'S OWN component, the ghost rule of calculate_divergence's edge
+ *                          expression ("ghost velocity is negative").  This is a definition stated here, not a result of
+ *                          the reference, which has no vorticity.
+ *     SFL_VIEW_PRESSURE    the pressure the object holds: what sfl_download(SFL_FIELD_PRESSURE) copies.
+ *     SFL_VIEW_DIVERGENCE  calculate_divergence(v, dx) bit for bit, edge nodes included, computed from the velocity the
+ *                          object holds now; nothing is stored (SFL_FIELD_DIVERGENCE keeps what the last step left).
+ *   SCALAR -> TEXEL: with r = 1.0f / (hi - lo) and t = (s - lo) * r: if s or t is NaN the texel is nan_colour.  Otherwise
+ * t is clamped to [0, 1] (+-inf included), x = t * (float)(stops - 1), n = min((int)x, stops - 2), f = x - (float)n and
+ * each channel = uq_narrow(a + (b - a) * f) with a, b = uq_widen of stops n and n + 1.  The texel is this narrowed
+ * uint32; the draw widens it again, exactly as it widens dye.
+ *   No stop and no nan_colour channel may exceed SFL_VIEW_MAX_COLOUR = 0xFC000000.  That value still gives RGB565 its
+ * full 5 / 6 / 5 bits, and it keeps every intermediate of the palette's lerp and of the draw's walks inside [0, 2^32),
+ * where narrowing is defined: the nearest excluded value, 0xFF000000, is 5 * 10^7 away, and a chain of 63 additions errs
+ * by about 10^4.  Saturation of UQ32 is not defined by this interface.
+ *   Refused with SFL_ERR_INVALID before any GPU work, each with its own message: `what` outside 0..3, stops outside
+ * 2..256, colours NULL, hi - lo (in float) not finite or not > 0, dx not finite or not > 0, a stop or nan_colour channel
+ * above SFL_VIEW_MAX_COLOUR; NULL objects and buffers, a byte count that is not the result's, a member range that is not
+ * inside the batch.  A context is settled as sfl_flow_stats settles it.                                                 */
+#define SFL_VIEW_SPEED 0
+#define SFL_VIEW_VORTICITY 1
+#define SFL_VIEW_PRESSURE 2
+#define SFL_VIEW_DIVERGENCE 3
+#define SFL_VIEW_MAX_STOPS 256
+#define SFL_VIEW_MAX_COLOUR 0xFC000000u
+/* 40 bytes on every supported target: what 0, dx 4, lo 8, hi 12, stops 16, nan_colour 20, colours 32.                  */
+struct sfl_view {
+    int32_t what;            /* SFL_VIEW_*                                                          */
+    float dx;                /* grid spacing of vorticity and divergence (ignored by the other two, but checked)         */
+    float lo, hi;            /* the scalars mapped to the first and the last stop                    */
+    int32_t stops;           /* 2 .. SFL_VIEW_MAX_STOPS                                             */
+    uint32_t nan_colour[3];  /* the texel of a NaN, raw UQ32                                        */
+    const uint32_t *colours; /* stops x 3 raw UQ32 values; read during the call only                */
+};
+/* The scalar field(s): dim_x * dim_y floats (a batch: of members [first, first + count), member-major); bytes must be
+ * exactly that.  dx as in struct sfl_view.  count == 0 does nothing.  Synchronous.                                      */
+SFL_API int sfl_view_scalar(sfl_context *ctx, int what, float dx, float *host, size_t bytes);
+SFL_API int sfl_batch_view_scalar(sfl_batch *b, int what, float dx, int first, int count, float *host, size_t bytes);
+/* The node colours, 3 words per node, laid out as SFL_FIELD_COLOR: for a caller's own renderer.  Synchronous.            */
+SFL_API int sfl_view_texels(sfl_context *ctx, const struct sfl_view *view, uint32_t *host, size_t bytes);
+SFL_API int sfl_batch_view_texels(sfl_batch *b, const struct sfl_view *view, int first, int count, uint32_t *host,
+                                  size_t bytes);
+/* The images.  Image shape, the scaling's range 1..64, the byte-count check and count == 0 are those of
+ * sfl_render_rgb565 / sfl_batch_render_members.  One launch whatever count is: the node colours are formed in LDS in
+ * front of the draw and never stored.  A context's image of more than 2^31 - 1 pixels is refused (SFL_ERR_INVALID): the
+ * kernel's offsets inside one image are 32-bit.  Synchronous.                                                           */
+SFL_API int sfl_view_render(sfl_context *ctx, const struct sfl_view *view, int scaling, int byteswap,
+                            uint16_t *host_image, size_t bytes);
+SFL_API int sfl_batch_view_render_members(sfl_batch *b, const struct sfl_view *view, int first, int count, int scaling,
+                                          int byteswap, uint16_t *host_images, size_t bytes);
+/* What the recorder draws from the next frame on: this view, or the dye (view NULL).  SFL_ERR_STATE unless a recording is
+ * on; sfl_batch_record_start and sfl_batch_record_stop reset it to the dye, and a recording that never calls it behaves
+ * exactly as before.  The view is copied, palette included, to a device buffer the batch owns and frees: the caller's
+ * memory is not read after the call returns.  Asynchronous: the copy runs on the batch's stream behind the frames
+ * already launched.  Frames keep their size: sfl_batch_record_info and sfl_batch_record_read do not change.  A view frame
+ * shows the velocity and the pressure the step that completed it left.                                                  */
+SFL_API int sfl_batch_record_view(sfl_batch *b, const struct sfl_view *view);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
