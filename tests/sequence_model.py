@@ -1,0 +1,1175 @@
+"""Model-based call sequences on live handles (contexts, groups of slabs, batches): the model, the vocabulary, a seeded
+generator and the runner.  tests/test_sequences.py checks all of it without a GPU, tests/test_sequences_gpu.py runs the
+sequences on the library.
+
+An op is a pair (kind, {argument: literal}): it can be applied to a model and to a handle and printed as a Python literal.
+A model holds whole-domain numpy fields and says what every field must hold after each op; every operation is composed
+from the oracle's operators and from the yardsticks the suite already has (tracer_rule, view_rule, update_norm, rule,
+sor_iteration, the numpy distance and envelope).  A handle is anything with ``apply(op)``, ``snapshot()`` and ``close()``:
+the library behind a Solver or a BatchSolver, or, for the CPU tests, another model.  Results of queries and snapshots are
+dicts of numpy arrays, compared bit for bit.
+
+A step is: advect the velocity, write the step's records, divergence, solve, subtract the gradient, advect the dye with the
+projected velocity, advance a following tracer set (include/sfl.h: sfl_step, the timeline rule, TRACERS)."""
+import numpy as np
+
+import tracer_rule
+import view_rule
+from conftest import assert_bit_equal, random_fields
+from test_batch_params import gs_target, update_norm
+from test_batch_until import rule, sor_iteration
+from test_ensemble_gpu import envelope_yardstick
+from test_ensemble_gpu import yardstick as distance_yardstick
+
+FV, FC, FD, FP = 0, 1, 2, 3
+FIELDS = {FV: "velocity", FC: "colour", FD: "divergence", FP: "pressure"}
+TEXTURES = ("noise", "still", "fast", "landing", "whole-cell")
+DTS, DXS, OMEGAS, MAX_ITERS = (1 / 30.0, 0.1, 0.25), (0.5, 1.0, 2.0), (1.0, 1.5, 1.96), 12
+TOLS, EVERYS = (-1.0, 0.01, 0.5, 1e30), (1, 3, 4)
+MAX_COLOUR = 0xFC000000
+PALETTE = [[0, 0, MAX_COLOUR], [MAX_COLOUR, MAX_COLOUR, MAX_COLOUR], [MAX_COLOUR, 0, 0]]
+NAN_COLOUR = (0, MAX_COLOUR, 0)
+VIEW_RANGE = {0: (0.0, 200.0), 1: (-100.0, 100.0), 2: (-50.0, 50.0), 3: (-50.0, 50.0)}   # lo, hi of every view
+CAPACITY = 128      # trail slots and recorder frames: more than the steps of one sequence (30 ops of at most 4 steps)
+FIXED_HALO, SAFE_REACH = 32, 24.0   # slabs: the fixed advection halo the generator sets, and the longest back-trace (rows) it keeps under it
+
+OPTION_VALUES = {"OPT_ADVECT_KERNEL": (0, 1, 2), "OPT_FUSE_DIVERGENCE": (0, 1), "OPT_FUSE_PROJECTION": (0, 1), "OPT_STEP_SEAMS": (0, 1),
+                 "OPT_SMALL_GRID": (0, 1), "OPT_SOR_KERNEL": (0, 1, 2), "OPT_SOR_FUSE": (0, 2, 16)}
+SLAB_OPTION_VALUES = dict(OPTION_VALUES, OPT_ADVECT_HALO=(0, FIXED_HALO), OPT_SOR_HALO=(0, 16, 32))
+
+CONTEXT_WRITERS = ("upload", "advect_velocity", "advect_color", "calculate_divergence", "poisson_solve", "poisson_continue",
+                   "poisson_solve_until", "subtract_gradient", "step", "step_n", "queue_forces", "queue_drags", "forget_forces",
+                   "set_tracers", "advance_tracers", "trail_start", "trail_stop", "set_option")
+CONTEXT_QUERIES = ("download", "residual", "flow_stats", "view_scalar", "view_texels", "render_rgb565", "sample_tracers", "tracers",
+                   "trail", "forces_pending", "last_solve_info", "distance")
+SLAB_WRITERS = ("upload", "advect_velocity", "advect_color", "calculate_divergence", "poisson_solve", "subtract_gradient", "step",
+                "step_n", "queue_forces", "queue_drags", "forget_forces", "set_option")
+SLAB_QUERIES = ("download", "forces_pending", "last_solve_info")
+BATCH_WRITERS = ("upload", "step_n", "step_n_each", "step_n_until", "poisson_solve", "poisson_solve_each", "poisson_solve_until",
+                 "queue_forces", "forget_forces", "record_start", "record_view", "record_stop", "set_tracers", "envelope")
+BATCH_QUERIES = ("download", "flow_stats", "distance", "envelope_field", "residual", "iterations", "render_members",
+                 "view_render_members", "frames", "forces_pending", "tracers")
+QUERIES = set(CONTEXT_QUERIES) | set(BATCH_QUERIES)
+
+
+def texture(kind, field, dim_x, dim_y, seed):
+    """The field an upload op writes: all of it behaviour the reference defines.  Dye covers [0, 0xFF000000) whatever the kind."""
+    rng = np.random.default_rng([seed, field, TEXTURES.index(kind)])
+    shape = (dim_y, dim_x) + {FV: (2,), FC: (3,), FD: (), FP: ()}[field]
+    if field == FC:
+        return rng.integers(0, 0xFF000000, shape, dtype=np.uint32)
+    if kind == "noise":
+        v, _, s = random_fields(dim_x, dim_y, seed)
+        return v if field == FV else s
+    if kind == "still":
+        return np.zeros(shape, np.float32)
+    if kind == "fast":
+        return (rng.uniform(-1, 1, shape) * 1500.0).astype(np.float32)
+    if kind == "landing":       # with dt = 0.25 every back-trace source is an exact quarter-lattice point
+        return rng.integers(-32, 33, shape).astype(np.float32)
+    return (4 * rng.integers(-8, 9, shape)).astype(np.float32)      # whole-cell: displacements of whole cells at dt = 0.25
+
+
+def as_result(**arrays):
+    return {k: np.asarray(a) for k, a in arrays.items()}
+
+
+def compare(got, want, what):
+    assert sorted(got) == sorted(want), (what, sorted(got), sorted(want))
+    for name in want:
+        g, w = np.asarray(got[name]), np.asarray(want[name])
+        if w.dtype in (np.float32, np.uint32):
+            assert_bit_equal(np.ascontiguousarray(g, w.dtype), np.ascontiguousarray(w), f"{what}: {name}")
+        else:
+            assert g.shape == w.shape and np.array_equal(g, w.astype(g.dtype)), f"{what}: {name}: got {g!r}, want {w!r}"
+
+
+def view_texels(what, v, p, dx):
+    lo, hi = VIEW_RANGE[what]
+    return view_rule.view_texels(what, v, p, dx, np.float32(lo), np.float32(hi), PALETTE, NAN_COLOUR)
+
+
+def stats_record(oracle, v, c, dx):
+    with np.errstate(all="ignore"):
+        return as_result(max_abs_vx=np.max(np.abs(v[..., 0])), max_abs_vy=np.max(np.abs(v[..., 1])),
+                         max_abs_div=np.max(np.abs(oracle.divergence(v, dx))), dye_sum=c.astype(np.uint64).sum(axis=(0, 1)))
+
+
+def distance_record(a, b):
+    """numpy's distance of (v, c, p) fields a from b, as the arrays of a sfl_field_distance record."""
+    w = distance_yardstick(a, b)
+    return as_result(max_abs_dvx=np.float32(w["max_abs_dvx"]), max_abs_dvy=np.float32(w["max_abs_dvy"]), max_abs_dp=np.float32(w["max_abs_dp"]),
+                     velocity_cells_differ=np.uint32(w["velocity_cells_differ"]), dye_cells_differ=np.uint32(w["dye_cells_differ"]),
+                     pressure_cells_differ=np.uint32(w["pressure_cells_differ"]), max_abs_ddye=np.array(w["max_abs_ddye"], np.uint32),
+                     sum_abs_ddye=np.array(w["sum_abs_ddye"], np.uint64))
+
+
+# ---- the model of a context (a group of slabs holds the same whole-domain fields) ------------------------------------
+class ContextModel:
+    def __init__(self, oracle, dim_x, dim_y):
+        self.o, self.dim_x, self.dim_y = oracle, dim_x, dim_y
+        self.v = np.zeros((dim_y, dim_x, 2), np.float32)
+        self.c = np.zeros((dim_y, dim_x, 3), np.uint32)
+        self.d = np.zeros((dim_y, dim_x), np.float32)
+        self.p = np.zeros((dim_y, dim_x), np.float32)
+        self.timeline = {}                       # step -> [((i, j), (vx, vy)), ...] in queue order
+        self.xy, self.follow, self.trail = None, False, None   # trail: [every, advances, [slots]]
+        self.reach = 0.0                         # the longest back-trace along j (rows) of the advections of the last op
+        self.peer = None                         # (a model used as a handle: the model it is compared with)
+
+    # -- plumbing
+    def apply(self, op):
+        kind, args = op
+        self.reach = 0.0
+        return getattr(self, ("q_" if kind in QUERIES else "do_") + kind)(**args)
+
+    def close(self):
+        pass
+
+    def fields(self):
+        return {"velocity": self.v, "colour": self.c, "divergence": self.d, "pressure": self.p}
+
+    def snapshot(self):
+        out = as_result(**self.fields())
+        if self.xy is not None:
+            out["tracers"] = self.xy
+        return out
+
+    def finite(self):
+        return all(np.isfinite(a).all() for a in (self.v, self.d, self.p)) and (self.xy is None or bool(np.isfinite(self.xy).all()))
+
+    def _advect(self, field, dt, no_slip):
+        with np.errstate(all="ignore"):
+            self.reach = max(self.reach, float(np.max(np.abs(self.v[..., 1]))) * dt)
+        adv = self.o.advect_vec2f if field.dtype == np.float32 else self.o.advect_vec3uq32
+        return adv(field, self.v, dt, no_slip)
+
+    def _advance(self, dt):
+        self.xy = tracer_rule.advance(self.v, self.xy, dt)
+        if self.trail is not None:
+            self.trail[1] += 1
+            if self.trail[1] % self.trail[0] == 0:
+                self.trail[2].append(self.xy.copy())
+
+    def step_once(self, dt, dx, iters, omega, until=None):
+        """One step; with until = (tol, every) the solve stops by the rule.  Returns (iterations, update norm or None)."""
+        records = self.timeline.pop(0, [])
+        self.timeline = {s - 1: r for s, r in self.timeline.items()}
+        va = self._advect(self.v, dt, True)
+        for (i, j), u in records:
+            if 0 <= i < self.dim_x and 0 <= j < self.dim_y:
+                va[j, i] = u
+        self.d = self.o.divergence(va, dx)
+        k, u = iters, None
+        if until is not None:
+            k, _, u = rule(self.d, dx, iters, omega, until[0], until[1])
+        self.p = self.o.poisson_solve(self.d, dx, k, omega)
+        self.v = self.o.subtract_gradient(va, self.p, dx)
+        self.c = self._advect(self.c, dt, False)
+        if self.follow and self.xy is not None:
+            self._advance(dt)
+        return k, u
+
+    # -- writers
+    def do_upload(self, field, texture_kind, seed):
+        a = texture(texture_kind, field, self.dim_x, self.dim_y, seed)
+        if field == FV: self.v = a
+        elif field == FC: self.c = a
+        elif field == FD: self.d = a
+        else: self.p = a
+
+    def do_advect_velocity(self, dt, no_slip):
+        self.v = self._advect(self.v, dt, no_slip)
+
+    def do_advect_color(self, dt, no_slip):
+        self.c = self._advect(self.c, dt, no_slip)
+
+    def do_calculate_divergence(self, dx):
+        self.d = self.o.divergence(self.v, dx)
+
+    def do_poisson_solve(self, dx, iters, omega):
+        self.p = self.o.poisson_solve(self.d, dx, iters, omega)
+
+    def do_poisson_continue(self, dx, iters, omega):
+        for _ in range(iters):
+            self.p = sor_iteration(self.p, self.d, dx, omega)
+
+    def do_poisson_solve_until(self, dx, iters, omega, tol, every):
+        k, _, u = rule(self.d, dx, iters, omega, tol, every)
+        self.p = self.o.poisson_solve(self.d, dx, k, omega)
+        return as_result(iterations=np.int32(k), norm=np.float32(u))
+
+    def do_subtract_gradient(self, dx):
+        self.v = self.o.subtract_gradient(self.v, self.p, dx)
+
+    def do_step(self, dt, dx, iters, omega):
+        self.step_once(dt, dx, iters, omega)
+
+    def do_step_n(self, n, dt, dx, iters, omega):
+        for _ in range(n):
+            self.step_once(dt, dx, iters, omega)
+
+    # The timeline rule of include/sfl.h: "A step call of n steps consumes the records of steps [0, n).  Later records move down
+    # by n.  This applies to sfl_step (n = 1), sfl_step_n, ..." and "Solves, uploads, setup and render calls neither consume nor
+    # shift": step_once is the only place that touches it; the stand-alone operators leave it alone.
+    def do_queue_forces(self, step, cells, vels):
+        self.timeline.setdefault(step, []).extend((tuple(cell), tuple(np.float32(x) for x in u)) for cell, u in zip(cells, vels))
+
+    def do_queue_drags(self, step, drags):     # cell = index(coords.y, coords.x), velocity = (velocity.y, velocity.x)
+        self.do_queue_forces(step, [(cy, cx) for cx, cy, _, _ in drags], [(vy, vx) for _, _, vx, vy in drags])
+
+    def do_forget_forces(self):
+        self.timeline = {}
+
+    def do_set_tracers(self, xy, follow):
+        self.xy, self.follow, self.trail = np.array(xy, np.float32), bool(follow), None
+
+    def do_advance_tracers(self, dt):
+        self._advance(dt)
+
+    def do_trail_start(self, every):
+        self.trail = [every, 0, []]
+
+    def do_trail_stop(self):
+        self.trail = None
+
+    def do_set_option(self, name, value):      # an option never changes a result
+        pass
+
+    # -- queries
+    def q_download(self, field):
+        return as_result(field=self.fields()[FIELDS[field]])
+
+    def q_residual(self, dx):
+        return as_result(norm=np.float32(update_norm(self.p, self.d, dx)))
+
+    def q_flow_stats(self, dx):
+        return stats_record(self.o, self.v, self.c, dx)
+
+    def q_view_scalar(self, what, dx):
+        return as_result(scalar=view_rule.scalar(what, self.v, self.p, dx))
+
+    def q_view_texels(self, what, dx):
+        return as_result(texels=view_texels(what, self.v, self.p, dx))
+
+    def q_render_rgb565(self, scaling, byteswap):
+        return as_result(image=view_rule.render(self.c, scaling, byteswap))
+
+    def q_sample_tracers(self, field, no_slip):
+        return as_result(samples=tracer_rule.sample(self.fields()[FIELDS[field]], self.xy[:, 0], self.xy[:, 1], no_slip))
+
+    def q_tracers(self):
+        return as_result(xy=self.xy)
+
+    def q_trail(self):
+        slots = self.trail[2]
+        return as_result(slots=np.stack(slots) if slots else np.zeros((0,) + self.xy.shape, np.float32))
+
+    def q_forces_pending(self):
+        return as_result(records=sum(len(r) for r in self.timeline.values()), last_step=max(self.timeline, default=-1))
+
+    def q_last_solve_info(self):               # launches and fuse depth are the kernels' business: the call must only leave the state alone
+        return {}
+
+    def q_distance(self):                      # (as a handle: against the model it is compared with; as the model: no distance)
+        mine = (self.v, self.c, self.p)
+        other = mine if self.peer is None else (self.peer.v, self.peer.c, self.peer.p)
+        return distance_record(mine, other)
+
+    def queries(self, rng, whole_domain=True):
+        """One op of every query that is valid now, arguments drawn from rng."""
+        dx = float(rng.choice(DXS))
+        out = [("download", {"field": int(rng.integers(4))}), ("forces_pending", {}), ("last_solve_info", {})]
+        if not whole_domain:
+            return out
+        out += [("residual", {"dx": dx}), ("flow_stats", {"dx": dx}), ("view_scalar", {"what": int(rng.integers(4)), "dx": dx}),
+                ("view_texels", {"what": int(rng.integers(4)), "dx": dx}), ("render_rgb565", {"scaling": int(rng.integers(1, 4)), "byteswap": bool(rng.integers(2))}),
+                ("distance", {})]
+        if self.xy is not None:
+            out += [("sample_tracers", {"field": int(rng.integers(4)), "no_slip": bool(rng.integers(2))}), ("tracers", {})]
+            if self.trail is not None:
+                out.append(("trail", {}))
+        return out
+
+
+class SlabsModel(ContextModel):
+    def queries(self, rng, whole_domain=False):
+        return super().queries(rng, False)
+
+
+# ---- the model of a batch --------------------------------------------------------------------------------------------
+class BatchModel:
+    def __init__(self, oracle, dim_x, dim_y, batch):
+        self.o, self.dim_x, self.dim_y, self.batch = oracle, dim_x, dim_y, batch
+        self.m = [ContextModel(oracle, dim_x, dim_y) for _ in range(batch)]
+        self.norms = self.iters = None           # the reports: float32[B] / int32[B, 2], None while stale
+        self.rec = None                          # the recorder: {"every", "first", "count", "scaling", "byteswap", "steps", "view", "frames"}
+        self.env = None                          # the envelope's four fields
+        self.peer = None
+
+    def apply(self, op):
+        kind, args = op
+        return getattr(self, ("q_" if kind in QUERIES else "do_") + kind)(**args)
+
+    def close(self):
+        pass
+
+    def _stack(self, name):
+        return np.stack([m.fields()[name] for m in self.m])
+
+    def snapshot(self):
+        out = as_result(**{name: self._stack(name) for name in FIELDS.values()})
+        if self.m[0].xy is not None:
+            out["tracers"] = np.stack([m.xy for m in self.m])
+        return out
+
+    def finite(self):
+        return all(m.finite() for m in self.m)
+
+    def _each(self, value):
+        return list(value) if isinstance(value, (list, tuple)) else [value] * self.batch
+
+    def _frame(self):
+        r = self.rec
+        r["steps"] += 1
+        if r["steps"] % r["every"]:
+            return
+        imgs = []
+        for m in self.m[r["first"]:r["first"] + r["count"]]:
+            dye = m.c if r["view"] is None else view_texels(r["view"], m.v, m.p, 1.0)
+            imgs.append(view_rule.render(dye, r["scaling"], r["byteswap"]))
+        r["frames"].append(np.stack(imgs))
+
+    def _steps(self, n, dt, dx, iters, omega, stops=None):
+        dt, dx, iters, omega = (self._each(x) for x in (dt, dx, iters, omega))
+        last, total = np.zeros(self.batch, np.int32), np.zeros(self.batch, np.int32)
+        for _ in range(n):
+            for k, m in enumerate(self.m):
+                last[k], _ = m.step_once(dt[k], dx[k], iters[k], omega[k], None if stops is None else stops[k])
+                total[k] += last[k]
+            if self.rec is not None:
+                self._frame()
+        return dx, np.stack([last, total], axis=1)
+
+    def _norms(self, dx):
+        self.norms = np.array([update_norm(m.p, m.d, dx[k]) for k, m in enumerate(self.m)], np.float32)
+
+    # -- writers
+    def do_upload(self, field, texture_kind, seed):
+        for k, m in enumerate(self.m):
+            m.do_upload(field, texture_kind, seed + k)
+        if field in (FD, FP):
+            self.norms = self.iters = None
+
+    def do_step_n(self, n, dt, dx, iters, omega):
+        self._steps(n, dt, dx, iters, omega)
+        self.norms = self.iters = None
+
+    def do_step_n_each(self, n, dt, dx, iters, omega):
+        dx, _ = self._steps(n, dt, dx, iters, omega)
+        self._norms(dx)
+        self.iters = None
+
+    def do_step_n_until(self, n, dt, dx, iters, omega, tol, every):
+        dx, self.iters = self._steps(n, dt, dx, iters, omega, list(zip(self._each(tol), self._each(every))))
+        self._norms(dx)
+
+    def do_poisson_solve(self, dx, iters, omega):
+        for m in self.m:
+            m.do_poisson_solve(dx, iters, omega)
+        self.norms = self.iters = None
+
+    def do_poisson_solve_each(self, dx, iters, omega):
+        for k, m in enumerate(self.m):
+            m.do_poisson_solve(dx[k], iters[k], omega[k])
+        self._norms(dx)
+        self.iters = None
+
+    def do_poisson_solve_until(self, dx, iters, omega, tol, every):
+        ks = [int(m.do_poisson_solve_until(dx[k], iters[k], omega[k], tol[k], every[k])["iterations"]) for k, m in enumerate(self.m)]
+        self._norms(dx)
+        self.iters = np.array([[k, k] for k in ks], np.int32)
+
+    def do_queue_forces(self, step, members, cells, vels):
+        for m, cell, u in zip(members, cells, vels):
+            self.m[m].do_queue_forces(step, [cell], [u])
+
+    def do_forget_forces(self):
+        for m in self.m:
+            m.do_forget_forces()
+
+    def do_record_start(self, every, first, count, scaling, byteswap):
+        self.rec = {"every": every, "first": first, "count": count, "scaling": scaling, "byteswap": byteswap, "steps": 0, "view": None, "frames": []}
+
+    def do_record_view(self, what):
+        self.rec["view"] = what
+
+    def do_record_stop(self):
+        self.rec = None
+
+    def do_set_tracers(self, xy, follow):
+        for m, a in zip(self.m, xy):
+            m.do_set_tracers(a, follow)
+
+    def do_envelope(self, first, count):
+        self.env = envelope_yardstick(self._stack("colour")[first:first + count])
+
+    # -- queries
+    def q_download(self, field):
+        return as_result(field=self._stack(FIELDS[field]))
+
+    def q_flow_stats(self, dx):
+        recs = [m.q_flow_stats(dx) for m in self.m]
+        return {k: np.stack([r[k] for r in recs]) for k in recs[0]}
+
+    def q_distance(self, ref_member):
+        ref = self if self.peer is None else self.peer
+        r = ref.m[ref_member]
+        recs = [distance_record((m.v, m.c, m.p), (r.v, r.c, r.p)) for m in self.m]
+        return {k: np.stack([x[k] for x in recs]) for k in recs[0]}
+
+    def q_envelope_field(self, which):
+        return as_result(field=self.env[which])
+
+    def q_residual(self):
+        return as_result(norms=self.norms)
+
+    def q_iterations(self):
+        return as_result(iterations=self.iters)
+
+    def q_render_members(self, scaling, byteswap):
+        return as_result(images=np.stack([view_rule.render(m.c, scaling, byteswap) for m in self.m]))
+
+    def q_view_render_members(self, what, scaling):
+        return as_result(images=np.stack([view_rule.render(view_texels(what, m.v, m.p, 1.0), scaling, True) for m in self.m]))
+
+    def q_frames(self):
+        r = self.rec
+        shape = (r["count"], r["scaling"] * (self.dim_x - 1), r["scaling"] * (self.dim_y - 1))
+        return as_result(frames=np.stack(r["frames"]) if r["frames"] else np.zeros((0,) + shape, np.uint16))
+
+    def q_forces_pending(self):
+        steps = [s for m in self.m for s in m.timeline]
+        return as_result(records=sum(len(r) for m in self.m for r in m.timeline.values()), last_step=max(steps, default=-1))
+
+    def q_tracers(self):
+        return as_result(xy=np.stack([m.xy for m in self.m]))
+
+    def queries(self, rng):
+        out = [("download", {"field": int(rng.integers(4))}), ("flow_stats", {"dx": float(rng.choice(DXS))}),
+               ("distance", {"ref_member": int(rng.integers(self.batch))}), ("forces_pending", {}),
+               ("render_members", {"scaling": int(rng.integers(1, 3)), "byteswap": bool(rng.integers(2))}),
+               ("view_render_members", {"what": int(rng.integers(4)), "scaling": int(rng.integers(1, 3))})]
+        if self.env is not None: out.append(("envelope_field", {"which": int(rng.integers(4))}))
+        if self.norms is not None: out.append(("residual", {}))
+        if self.iters is not None: out.append(("iterations", {}))
+        if self.rec is not None: out.append(("frames", {}))
+        if self.m[0].xy is not None: out.append(("tracers", {}))
+        return out
+
+
+# ---- the library behind the same interface ---------------------------------------------------------------------------
+def _record(rec, names):
+    return {k: np.asarray(rec[k]) for k in names}
+
+
+STATS_NAMES = ("max_abs_vx", "max_abs_vy", "max_abs_div", "dye_sum")
+DIST_NAMES = ("max_abs_dvx", "max_abs_dvy", "max_abs_dp", "velocity_cells_differ", "dye_cells_differ", "pressure_cells_differ",
+              "max_abs_ddye", "sum_abs_ddye")
+
+
+class LibraryContext:
+    """A whole-domain Solver, or a linked group of `nranks` slabs on one device: operators go to slab 0 (collective over the
+    group), field I/O to every slab's own rows."""
+
+    def __init__(self, sfl, dim_x, dim_y, nranks=1, options=()):
+        self.sfl, self.dim_x, self.dim_y, self.peer, self.twin = sfl, dim_x, dim_y, None, None
+        self.slabs = [sfl.Solver(dim_x, dim_y, 0, r, nranks) for r in range(nranks)]
+        if nranks > 1:
+            sfl.Solver.link_group(self.slabs)
+        self.s = self.slabs[0]
+        for name, value in options:
+            self.g_set_option(name, value)
+
+    def close(self):
+        for s in self.slabs + ([self.twin] if self.twin else []):
+            s.close()
+
+    def apply(self, op):
+        kind, args = op
+        return getattr(self, "g_" + kind)(**args)
+
+    def _cat(self, field):
+        return np.concatenate([s.download(field) for s in self.slabs], axis=0)
+
+    def snapshot(self):
+        out = as_result(**{name: self._cat(f) for f, name in FIELDS.items()})
+        if len(self.slabs) == 1 and self.s.tracer_count():
+            out["tracers"] = self.s.tracers()
+        return out
+
+    def _view(self, what, dx):
+        lo, hi = VIEW_RANGE[what]
+        return self.sfl.View(what, lo, hi, PALETTE, dx=dx, nan_colour=NAN_COLOUR)
+
+    def g_upload(self, field, texture_kind, seed):
+        a = texture(texture_kind, field, self.dim_x, self.dim_y, seed)
+        for s in self.slabs:
+            s.upload(field, a[s.row_begin:s.row_end])
+
+    def g_advect_velocity(self, dt, no_slip): self.s.advect_velocity(dt, no_slip)
+    def g_advect_color(self, dt, no_slip): self.s.advect_color(dt, no_slip)
+    def g_calculate_divergence(self, dx): self.s.calculate_divergence(dx)
+    def g_poisson_solve(self, dx, iters, omega): self.s.poisson_solve(dx, iters, omega)
+    def g_poisson_continue(self, dx, iters, omega): self.s.poisson_continue(dx, iters, omega)
+    def g_subtract_gradient(self, dx): self.s.subtract_gradient(dx)
+    def g_step(self, dt, dx, iters, omega): self.s.step(dt, dx, iters, omega)
+    def g_step_n(self, n, dt, dx, iters, omega): self.s.step_n(n, dt, dx, iters, omega)
+    def g_forget_forces(self): self.s.forget_forces()
+    def g_set_tracers(self, xy, follow): self.s.set_tracers(np.array(xy, np.float32), follow)
+    def g_advance_tracers(self, dt): self.s.advance_tracers(dt)
+    def g_trail_start(self, every): self.s.trail_start(every, CAPACITY)
+    def g_trail_stop(self): self.s.trail_stop()
+    def g_set_option(self, name, value): self.s.set_option(getattr(self.sfl.capi, name), value)
+
+    def g_poisson_solve_until(self, dx, iters, omega, tol, every):
+        k, u = self.s.poisson_solve_until(dx, iters, omega, tol=tol, every=every)
+        return as_result(iterations=np.int32(k), norm=np.float32(u))
+
+    def g_queue_forces(self, step, cells, vels):
+        if step == 0:
+            self.s.queue_forces(cells, vels)              # the call from before there was a timeline
+        else:
+            self.s.queue_forces(cells, vels, step=step)
+
+    def g_queue_drags(self, step, drags):
+        self.s.queue_drags(drags, step=step)
+
+    def g_download(self, field): return as_result(field=self._cat(field))
+    def g_residual(self, dx): return as_result(norm=self.s.residual(dx))
+    def g_flow_stats(self, dx): return _record(self.s.flow_stats(dx), STATS_NAMES)
+    def g_view_scalar(self, what, dx): return as_result(scalar=self.s.view_scalar(what, dx))
+    def g_view_texels(self, what, dx): return as_result(texels=self.s.view_texels(self._view(what, dx)))
+    def g_render_rgb565(self, scaling, byteswap): return as_result(image=self.s.render_rgb565(scaling, byteswap))
+    def g_sample_tracers(self, field, no_slip): return as_result(samples=self.s.sample_tracers(field, no_slip))
+    def g_tracers(self): return as_result(xy=self.s.tracers())
+    def g_trail(self): return as_result(slots=self.s.trail())
+
+    def g_forces_pending(self):
+        records, last = self.s.forces_pending()
+        return as_result(records=records, last_step=last)
+
+    def g_last_solve_info(self):
+        self.s.last_solve_info()
+        return {}
+
+    def g_distance(self):
+        """The distance to a twin that holds the model's fields: all zero when the handle holds them too."""
+        if self.twin is None:
+            self.twin = self.sfl.Solver(self.dim_x, self.dim_y)
+        for f, name in FIELDS.items():
+            self.twin.upload(f, self.peer.fields()[name])
+        return _record(self.s.distance(self.twin), DIST_NAMES)
+
+
+class LibraryBatch:
+    def __init__(self, sfl, dim_x, dim_y, batch, large=False):
+        self.sfl, self.dim_x, self.dim_y, self.batch, self.peer = sfl, dim_x, dim_y, batch, None
+        self.b = sfl.BatchSolver(dim_x, dim_y, batch, large=large)
+
+    def close(self):
+        self.b.close()
+
+    def apply(self, op):
+        kind, args = op
+        return getattr(self, "g_" + kind)(**args)
+
+    def snapshot(self):
+        out = as_result(**{name: self.b.download(f) for f, name in FIELDS.items()})
+        if self.b.tracer_count():
+            out["tracers"] = self.b.tracers()
+        return out
+
+    def _view(self, what):
+        lo, hi = VIEW_RANGE[what]
+        return self.sfl.View(what, lo, hi, PALETTE, dx=1.0, nan_colour=NAN_COLOUR)
+
+    def g_upload(self, field, texture_kind, seed):
+        self.b.upload(field, np.stack([texture(texture_kind, field, self.dim_x, self.dim_y, seed + k) for k in range(self.batch)]))
+
+    def g_step_n(self, n, dt, dx, iters, omega): self.b.step_n(n, dt, dx, iters, omega)
+    def g_step_n_each(self, n, dt, dx, iters, omega): self.b.step_n_each(n, dt, dx, iters, omega)
+    def g_step_n_until(self, n, dt, dx, iters, omega, tol, every): self.b.step_n_until(n, dt, dx, iters, omega, tol=tol, every=every)
+    def g_poisson_solve(self, dx, iters, omega): self.b.poisson_solve(dx, iters, omega)
+    def g_poisson_solve_each(self, dx, iters, omega): self.b.poisson_solve_each(dx, iters, omega)
+    def g_poisson_solve_until(self, dx, iters, omega, tol, every): self.b.poisson_solve_until(dx, iters, omega, tol=tol, every=every)
+    def g_forget_forces(self): self.b.forget_forces()
+    def g_record_start(self, every, first, count, scaling, byteswap): self.b.record_start(every, first, count, scaling, byteswap, CAPACITY)
+    def g_record_view(self, what): self.b.record_view(None if what is None else self._view(what))
+    def g_record_stop(self): self.b.record_stop()
+    def g_set_tracers(self, xy, follow): self.b.set_tracers(np.array(xy, np.float32), follow)
+    def g_envelope(self, first, count): self.b.envelope(first, count)
+
+    def g_queue_forces(self, step, members, cells, vels):
+        if step == 0:
+            self.b.queue_forces(members, cells, vels)
+        else:
+            self.b.queue_forces(members, cells, vels, step=step)
+
+    def g_download(self, field): return as_result(field=self.b.download(field))
+    def g_flow_stats(self, dx): return _record(self.b.flow_stats(dx), STATS_NAMES)
+    def g_distance(self, ref_member): return _record(self.b.distance(ref_member=ref_member), DIST_NAMES)
+    def g_envelope_field(self, which): return as_result(field=self.b.envelope_field(which))
+    def g_residual(self): return as_result(norms=self.b.residual())
+    def g_iterations(self): return as_result(iterations=self.b.iterations())
+    def g_render_members(self, scaling, byteswap): return as_result(images=self.b.render_members(scaling=scaling, byteswap=byteswap))
+    def g_view_render_members(self, what, scaling): return as_result(images=self.b.view_render_members(self._view(what), scaling=scaling))
+    def g_frames(self): return as_result(frames=self.b.frames())
+    def g_tracers(self): return as_result(xy=self.b.tracers())
+
+    def g_forces_pending(self):
+        records, last = self.b.forces_pending()
+        return as_result(records=records, last_step=last)
+
+
+# ---- subjects --------------------------------------------------------------------------------------------------------
+class Subject:
+    """What a set of sequences runs on: `cases` = [(dim_x, dim_y, seed)], one sequence each."""
+
+    def __init__(self, name, kind, cases, options=(), nranks=1, batch=0, large=False, still_solves=False, length=30):
+        self.name, self.kind, self.cases, self.options, self.nranks, self.batch, self.large = name, kind, cases, tuple(options), nranks, batch, large
+        self.still_solves, self.length = still_solves, length   # still_solves: steps on a lattice velocity run iters = 0 (it stays on the lattice)
+
+    def model(self, oracle, case):
+        dim_x, dim_y, _ = case
+        if self.kind == "batch":
+            return BatchModel(oracle, dim_x, dim_y, self.batch)
+        return (ContextModel if self.kind == "context" else SlabsModel)(oracle, dim_x, dim_y)
+
+    def library(self, sfl, case):
+        dim_x, dim_y, _ = case
+        if self.kind == "batch":
+            return LibraryBatch(sfl, dim_x, dim_y, self.batch, self.large)
+        return LibraryContext(sfl, dim_x, dim_y, self.nranks, self.options)
+
+    def kinds(self):
+        return {"context": CONTEXT_WRITERS + CONTEXT_QUERIES, "slabs": SLAB_WRITERS + SLAB_QUERIES, "batch": BATCH_WRITERS + BATCH_QUERIES}[self.kind]
+
+    def option_values(self):
+        return {"context": OPTION_VALUES, "slabs": SLAB_OPTION_VALUES, "batch": {}}[self.kind]
+
+
+def _cases(dim_x, dim_y, seeds, base):
+    return [(dim_x, dim_y, base + k) for k in range(seeds)]
+
+
+SUBJECTS = [
+    Subject("general", "context", _cases(130, 70, 4, 100), options=[("OPT_SMALL_GRID", 0)]),
+    Subject("seams", "context", _cases(300, 141, 4, 200), still_solves=True),
+    Subject("one-workgroup", "context", _cases(61, 81, 4, 300) + _cases(2, 2, 2, 350)),
+    Subject("slabs", "slabs", _cases(200, 131, 4, 400), nranks=3),
+    Subject("small-batch", "batch", _cases(61, 81, 4, 500) + _cases(7, 9, 2, 550), batch=3),
+    Subject("large-batch", "batch", _cases(96, 96, 4, 600), batch=2, large=True),
+]
+
+
+# ---- the generator ---------------------------------------------------------------------------------------------------
+class _Draw:
+    """Literal arguments of one case's ops; it follows the little state the choice of valid arguments needs."""
+
+    def __init__(self, subject, case, oracle):
+        self.sub, (self.dim_x, self.dim_y, seed) = subject, case
+        self.rng = np.random.default_rng([seed, 7])
+        self.lattice = False          # the velocity came from a landing / whole-cell upload: steps take dt = 0.25
+        self.halo_fixed = False
+        self.shadow = subject.model(oracle, case) if subject.kind == "slabs" else None   # slabs: the reach of every advection under a fixed halo
+
+    def pick(self, values):
+        v = values[int(self.rng.integers(len(values)))]
+        return v if v is None or isinstance(v, (str, bool)) else (int(v) if isinstance(v, (int, np.integer)) else float(v))
+
+    def dt(self): return 0.25 if self.lattice else self.pick(DTS)
+    def iters(self, still=False): return 0 if (still and self.lattice and self.sub.still_solves) else int(self.rng.integers(0, MAX_ITERS + 1))
+    def solve(self, still=False): return {"dx": self.pick(DXS), "iters": self.iters(still), "omega": self.pick(OMEGAS)}
+    def stepargs(self): return dict({"dt": self.dt()}, **self.solve(True))
+    def each(self, f): return [f() for _ in range(self.sub.batch)]
+
+    def cells(self, n):
+        edge = [(0, 0), (self.dim_x - 1, self.dim_y - 1), (self.dim_x, 1), (self.dim_x // 2, self.dim_y // 2)]
+        if self.sub.nranks > 1:       # both sides of the first cut
+            cut = self.dim_y // self.sub.nranks
+            edge += [(3, cut), (4, cut - 1)]
+        out = [edge[int(self.rng.integers(len(edge)))] if self.rng.integers(3) == 0 else
+               (int(self.rng.integers(self.dim_x)), int(self.rng.integers(self.dim_y))) for _ in range(n)]
+        return [list(c) for c in out]
+
+    def vels(self, n):
+        return [[float(x) for x in np.round(self.rng.uniform(-60, 60, 2) * 2) / 2] for _ in range(n)]
+
+    def positions(self, n):
+        return [[float(np.round(self.rng.uniform(-1.5, self.dim_x + 0.5) * 8) / 8), float(np.round(self.rng.uniform(-1.5, self.dim_y + 0.5) * 8) / 8)]
+                for _ in range(n)]
+
+    def make(self, kind, **fixed):
+        """The op of `kind` with drawn arguments (those in `fixed` as given).  plan() has ordered the kinds so that it is valid here."""
+        a = self._args(kind, self.sub.kind == "batch")
+        a.update(fixed)
+        op = (kind, a)
+        if self.shadow is not None:
+            op = self._under_the_halo(op)
+        self._follow(op)
+        return op
+
+    def _args(self, kind, batch):
+        r, B = self.rng, self.sub.batch
+        if kind == "upload":
+            return {"field": int(r.integers(4)), "texture_kind": self.pick(TEXTURES), "seed": int(r.integers(1000))}
+        if kind in ("advect_velocity", "advect_color"): return {"dt": self.dt(), "no_slip": bool(r.integers(2))}
+        if kind in ("calculate_divergence", "subtract_gradient"): return {"dx": self.pick(DXS)}
+        if kind in ("poisson_solve", "poisson_continue"): return self.solve()
+        if kind == "poisson_solve_until" and not batch: return dict(self.solve(), tol=self.pick(TOLS), every=self.pick(EVERYS))
+        if kind == "step": return self.stepargs()
+        if kind == "step_n" : return dict({"n": int(r.integers(1, 5))}, **self.stepargs())
+        if kind in ("step_n_each", "step_n_until", "poisson_solve_each", "poisson_solve_until"):
+            a = {"dx": self.each(lambda: self.pick(DXS)), "iters": self.each(self.iters), "omega": self.each(lambda: self.pick(OMEGAS))}
+            if kind.startswith("step"):
+                a = dict({"n": int(r.integers(1, 5)), "dt": self.each(self.dt)}, **a)
+            if kind.endswith("until"):
+                a.update(tol=self.each(lambda: self.pick(TOLS)), every=self.each(lambda: self.pick(EVERYS)))
+            return a
+        if kind == "queue_forces":
+            n = int(r.integers(1, 4))
+            a = {"step": int(r.integers(0, 4)), "cells": self.cells(n), "vels": self.vels(n)}
+            return dict(a, members=[int(r.integers(B)) for _ in range(n)]) if batch else a
+        if kind == "queue_drags":
+            return {"step": int(r.integers(0, 3)), "drags": [[int(r.integers(self.dim_y)), int(r.integers(self.dim_x))] + self.vels(1)[0] for _ in range(2)]}
+        if kind == "set_tracers":
+            return {"xy": self.each(lambda: self.positions(4)) if batch else self.positions(5), "follow": bool(r.integers(2))}
+        if kind == "advance_tracers": return {"dt": self.dt()}
+        if kind == "trail_start": return {"every": int(r.integers(1, 3))}
+        if kind == "set_option":
+            name = self.pick(sorted(self.sub.option_values()))
+            return {"name": name, "value": self.pick(self.sub.option_values()[name])}
+        if kind == "record_start":
+            first = int(r.integers(B))
+            return {"every": int(r.integers(1, 3)), "first": first, "count": int(r.integers(1, B - first + 1)), "scaling": int(r.integers(1, 3)), "byteswap": bool(r.integers(2))}
+        if kind == "record_view": return {"what": self.pick([None, 0, 1, 2, 3])}
+        if kind == "envelope":
+            first = int(r.integers(B))
+            return {"first": first, "count": int(r.integers(1, B - first + 1))}
+        if kind == "download": return {"field": int(r.integers(4))}
+        if kind == "residual": return {} if batch else {"dx": self.pick(DXS)}
+        if kind == "flow_stats": return {"dx": self.pick(DXS)}
+        if kind in ("view_scalar", "view_texels"): return {"what": int(r.integers(4)), "dx": self.pick(DXS)}
+        if kind in ("render_rgb565", "render_members"): return {"scaling": int(r.integers(1, 3)), "byteswap": bool(r.integers(2))}
+        if kind == "view_render_members": return {"what": int(r.integers(4)), "scaling": int(r.integers(1, 3))}
+        if kind == "sample_tracers": return {"field": int(r.integers(4)), "no_slip": bool(r.integers(2))}
+        if kind == "distance": return {"ref_member": int(r.integers(B))} if batch else {}
+        if kind == "envelope_field": return {"which": int(r.integers(4))}
+        return {}
+
+    def _under_the_halo(self, op):
+        """Slabs: include/sfl.h makes a back-trace that leaves a FIXED advection halo an error, so no op may make one: under
+        a fixed halo such an op takes the shortest dt, and where that is still too far it gives way to the option change
+        that ends the fixed halo; the halo is not fixed while the velocity held is too fast for it."""
+        kind, a = op
+        if kind == "set_option" and a["name"] == "OPT_ADVECT_HALO" and a["value"] > 0:
+            with np.errstate(all="ignore"):
+                if float(np.max(np.abs(self.shadow.v[..., 1]))) * min(DTS) > SAFE_REACH:
+                    op = (kind, dict(a, value=0))
+        trial = _copy_model(self.shadow)
+        if kind not in QUERIES:
+            trial.apply(op)
+            if self.halo_fixed and trial.reach > SAFE_REACH and "dt" in a:
+                op, trial = (kind, dict(a, dt=min(DTS))), _copy_model(self.shadow)
+                trial.apply(op)
+            if self.halo_fixed and trial.reach > SAFE_REACH:
+                op, trial = ("set_option", {"name": "OPT_ADVECT_HALO", "value": 0}), self.shadow
+        if op[0] == "set_option" and op[1]["name"] == "OPT_ADVECT_HALO":
+            self.halo_fixed = op[1]["value"] > 0
+        self.shadow = trial
+        return op
+
+    def _follow(self, op):
+        """Whether the velocity is still on the lattice its upload put it on (steps without a solve and advections by dt = 0.25 keep it there)."""
+        kind, a = op
+        if kind == "upload" and a["field"] == FV: self.lattice = a["texture_kind"] in ("landing", "whole-cell")
+        if kind in ("subtract_gradient", "queue_forces", "queue_drags"): self.lattice = False
+        if kind in ("step", "step_n", "step_n_each", "step_n_until") and not self.sub.still_solves: self.lattice = False
+
+
+def _copy_model(m):
+    twin = type(m)(m.o, m.dim_x, m.dim_y)
+    twin.v, twin.c, twin.d, twin.p = m.v, m.c, m.d, m.p          # (every op replaces arrays, none writes into one)
+    twin.timeline = {s: list(r) for s, r in m.timeline.items()}
+    return twin
+
+
+# a hand-over is a list of (kind, fixed arguments, predicate on the finished op)
+def _n2(a): return a["n"] >= 2
+
+
+HANDOVERS = {
+    "upload(velocity) -> step": [("upload", {"field": FV}, None), ("step", {}, None)],
+    "upload(pressure) -> poisson_continue": [("upload", {"field": FP, "texture_kind": "noise"}, None), ("poisson_continue", {"iters": 3}, None)],
+    "query -> poisson_continue": [("residual", {}, None), ("poisson_continue", {"iters": 2}, None)],
+    "set_option -> step_n(n >= 2)": [("set_option", {}, None), ("step_n", {}, _n2)],
+    "queue_forces(step >= 1) -> step_n(n >= 2) -> step": [("queue_forces", {"step": 2}, None), ("step_n", {"n": 2}, None), ("step", {}, None)],
+    "step_n -> queue_forces(step = 0) -> step": [("step_n", {}, None), ("queue_forces", {"step": 0}, None), ("step", {}, None)],
+    "set_tracers(follow) -> step_n(n >= 2) -> set_tracers(follow=False) -> step_n(n >= 2)":
+        [("set_tracers", {"follow": True}, None), ("step_n", {"n": 2}, None), ("set_tracers", {"follow": False}, None), ("step_n", {"n": 3}, None)],
+    "advect_color -> upload(velocity) -> step": [("advect_color", {}, None), ("upload", {"field": FV}, None), ("step", {}, None)],
+}
+SLAB_HANDOVERS = ("upload(velocity) -> step", "set_option -> step_n(n >= 2)", "queue_forces(step >= 1) -> step_n(n >= 2) -> step",
+                  "step_n -> queue_forces(step = 0) -> step", "advect_color -> upload(velocity) -> step")
+BATCH_HANDOVERS = {   # a call that runs one launch per step, a replay of the timeline in one launch (no following set, a record in
+                      # a later step), and a per-step call again, with the recorder started in between
+    "per-step call -> record_start -> one-launch replay -> per-step call":
+        [("set_tracers", {"follow": False}, None), ("step_n", {"n": 1}, None), ("record_start", {}, None),
+         ("queue_forces", {"step": 1}, None), ("step_n", {"n": 3}, None), ("step_n", {"n": 1}, None)],
+}
+
+
+def handovers_of(subject):
+    if subject.kind == "batch":
+        return BATCH_HANDOVERS
+    return HANDOVERS if subject.kind == "context" else {k: HANDOVERS[k] for k in SLAB_HANDOVERS}
+
+
+def has_handover(ops, chain):
+    """The chain's ops stand next to each other somewhere in ops."""
+    fits = lambda op, link: op[0] == link[0] and all(op[1].get(k) == v for k, v in link[1].items()) and (link[2] is None or link[2](op[1]))
+    return any(all(fits(ops[at + k], link) for k, link in enumerate(chain)) for at in range(len(ops) - len(chain) + 1))
+
+
+def _opt(name, value): return ("set_option", {"name": name, "value": value})
+def _up(texture_kind, field=FV): return ("upload", {"field": field, "texture_kind": texture_kind})
+
+
+def planted(subject):
+    """The items the generator plants whole (the ops of an item stay next to each other): the hand-overs, and every option
+    value in front of a writer it affects, so that no value is only ever set."""
+    kind = subject.kind
+    if kind == "batch":
+        pairs = [[(w, {}), (q, {})] for w, q in (("step_n_each", "residual"), ("poisson_solve_each", "residual"), ("step_n_each", "residual"),
+                                                  ("step_n_until", "iterations"), ("poisson_solve_until", "iterations"), ("step_n_until", "iterations"))]
+        return [[(k, dict(f)) for k, f, _ in BATCH_HANDOVERS["per-step call -> record_start -> one-launch replay -> per-step call"]]] + pairs
+    step, step2 = ("step", {}), ("step_n", {"n": 2})
+    items = [
+        [("forget_forces", {}), ("queue_forces", {"step": 2}), step2, step],     # (nothing else pending: both steps of the call are joined)
+        ([("forget_forces", {})] if subject.still_solves else []) + [("advect_color", {}), _up("landing"), step] + ([step2] if subject.still_solves else []),
+        # (the switches the fused step boundary depends on are only off inside their own items)
+        [_opt("OPT_FUSE_DIVERGENCE", 0), _opt("OPT_FUSE_PROJECTION", 0), step, _opt("OPT_FUSE_DIVERGENCE", 1), _opt("OPT_FUSE_PROJECTION", 1)],
+        [_opt("OPT_ADVECT_KERNEL", 2), ("advect_velocity", {}), ("calculate_divergence", {}), ("subtract_gradient", {}), ("advect_color", {})] +
+        ([step] if subject.name == "general" else []),
+        [_opt("OPT_ADVECT_KERNEL", 1), ("advect_velocity", {}), _opt("OPT_ADVECT_KERNEL", 0), ("advect_velocity", {})],
+        [_opt("OPT_SOR_KERNEL", 1), ("poisson_solve", {})], [_opt("OPT_SOR_KERNEL", 2), _opt("OPT_SOR_FUSE", 2), ("poisson_solve", {})],
+        [_opt("OPT_SOR_FUSE", 16), ("poisson_solve", {})],
+    ]
+    if kind == "context":
+        items += [
+            [_up("noise", FP), ("poisson_continue", {"iters": 3}), ("residual", {}), ("poisson_continue", {"iters": 2})],
+            [("set_tracers", {"follow": True}), step2, ("set_tracers", {"follow": False}), ("step_n", {"n": 3}), ("queue_forces", {"step": 0}), step],
+            [_opt("OPT_SOR_KERNEL", 0), ("poisson_solve_until", {})], [_opt("OPT_SOR_FUSE", 0), ("poisson_solve_until", {})],
+        ]
+        if subject.still_solves:    # exact sources at the fused step boundary: every condition of the seam set in front of it
+            items += [[("forget_forces", {}), _up("whole-cell"), ("step_n", {"n": 3})],
+                      [_opt("OPT_STEP_SEAMS", 0), step2, _opt("OPT_STEP_SEAMS", 1)], [_opt("OPT_SMALL_GRID", 0)], [_opt("OPT_SMALL_GRID", 1)]]
+        elif subject.name == "general":
+            items += [[_opt("OPT_STEP_SEAMS", 0), ("step_n", {"n": 3})], [_opt("OPT_STEP_SEAMS", 1), step2], [_opt("OPT_SMALL_GRID", 0)], [_opt("OPT_SMALL_GRID", 1)]]
+        else:                       # the one-workgroup path, the general kernels and back, a writer after each flip
+            items += [[_opt("OPT_STEP_SEAMS", 0), ("step_n", {"n": 3})], [_opt("OPT_STEP_SEAMS", 1), step2],
+                      [_up("noise"), _opt("OPT_SOR_KERNEL", 0), _opt("OPT_SOR_FUSE", 0), _opt("OPT_ADVECT_KERNEL", 0), _opt("OPT_SMALL_GRID", 1), step,
+                       _opt("OPT_SMALL_GRID", 0), step, ("poisson_solve", {}), _opt("OPT_SMALL_GRID", 1), step2, ("poisson_solve", {})],
+                      [_opt("OPT_SOR_KERNEL", 2), step, _opt("OPT_SOR_KERNEL", 0), step]]
+    else:                           # slabs: the velocity flips by upload on a handle that has stepped; both advection halos; both solve halos
+        items += [
+            [("step_n", {}), ("queue_forces", {"step": 0}), step],
+            [_opt("OPT_STEP_SEAMS", 0), ("step_n", {"n": 3})], [_opt("OPT_STEP_SEAMS", 1), step2], [_opt("OPT_SMALL_GRID", 0), step], [_opt("OPT_SMALL_GRID", 1), step],
+            [_opt("OPT_ADVECT_HALO", 0), step, _up("fast"), step, step, _up("still"), step, _up("noise"), step, step, _up("fast"), step],
+            [_up("noise"), _opt("OPT_ADVECT_HALO", FIXED_HALO), step, step, ("advect_velocity", {}), ("advect_color", {})],
+            [_opt("OPT_SOR_KERNEL", 0), _opt("OPT_SOR_FUSE", 0), _opt("OPT_SOR_HALO", 16), ("poisson_solve", {}), step],
+            [_opt("OPT_SOR_HALO", 32), ("poisson_solve", {}), step], [_opt("OPT_SOR_HALO", 0), ("poisson_solve", {}), step],
+        ]
+    return items
+
+
+def _prologue(subject, index):
+    """What every sequence starts with: fields and a tracer set with a trail; a batch a recording and an envelope."""
+    common = [_up(("noise", "still", "fast", "whole-cell", "noise", "fast")[index % 6]), ("upload", {"field": FC})]
+    if subject.kind == "slabs":
+        return common
+    common.append(("set_tracers", {"follow": False}))
+    return common + ([("trail_start", {})] if subject.kind == "context" else [("record_start", {}), ("envelope", {})])
+
+
+NEEDS = {"trail": "trail", "frames": "rec", "record_view": "rec", "residual": "norms", "iterations": "iters"}
+
+
+def _state_after(kind, fixed, st, batch):
+    """What the op of `kind` ends: the names of NEEDS that are gone behind it."""
+    before = dict(st)
+    if kind == "trail_start": st["trail"] = True
+    if kind in ("trail_stop", "set_tracers"): st["trail"] = False
+    if kind == "record_start": st["rec"] = True
+    if kind == "record_stop": st["rec"] = False
+    if batch:
+        if kind in ("step_n", "poisson_solve") or (kind == "upload" and fixed.get("field") in (FD, FP)): st["norms"] = st["iters"] = False
+        if kind in ("step_n_each", "poisson_solve_each"): st["norms"], st["iters"] = True, False
+        if kind in ("step_n_until", "poisson_solve_until"): st["norms"] = st["iters"] = True
+    return [name for name in st if before.get(name) and not st[name]]
+
+
+def _settle(subject, index, items):
+    """The sequence's items in an order in which every op is valid: a query that comes when what it reads is gone (a trail,
+    a recording, a report) moves in front of the item that ended it -- the last moment it can be asked."""
+    batch = subject.kind == "batch"
+    st = {"trail": True, "rec": True, "norms": not batch, "iters": False}      # (behind the prologue)
+    out, ended_by = [], {}                       # ended_by: name -> the item (its position in out) that ended it
+    for item in items:
+        if len(item) == 1 and item[0][0] in NEEDS and not st[NEEDS[item[0][0]]] and NEEDS[item[0][0]] in ended_by:
+            at = ended_by[NEEDS[item[0][0]]]
+            out.insert(at, item)
+            ended_by = {n: (k + 1 if k >= at else k) for n, k in ended_by.items()}
+            continue
+        out.append(item)
+        for kind, fixed in item:
+            for name in _state_after(kind, fixed, st, batch):
+                ended_by.setdefault(name, len(out) - 1)
+            for name in [n for n in ended_by if st[n]]:
+                del ended_by[name]
+    return [link for item in out for link in item]
+
+
+def plan(subject):
+    """Which kinds every case's sequence holds, in order: [[(kind, fixed arguments)]] -- a seeded permutation of a deck that
+    has every kind three times, every value of every option in front of a writer, every texture and every hand-over; what
+    room is left goes to writers."""
+    rng = np.random.default_rng([len(subject.name), subject.cases[0][2]])
+    batch = subject.kind == "batch"
+    items = planted(subject)
+    starts = [_prologue(subject, k) for k in range(len(subject.cases))]
+    have, set_already, textures = {}, set(), set()
+    for kind, fixed in [link for item in items + starts for link in item]:
+        have[kind] = have.get(kind, 0) + 1
+        if kind == "set_option": set_already.add((fixed["name"], fixed["value"]))
+        if kind == "upload" and fixed.get("field") == FV: textures.add(fixed["texture_kind"])
+    items += [[_opt(name, value)] for name, values in subject.option_values().items() for value in values if (name, value) not in set_already]
+    items += [[_up(t)] for t in TEXTURES if t not in textures]
+    for item in items:
+        if len(item) == 1 and item[0][0] in ("set_option", "upload"): have[item[0][0]] = have.get(item[0][0], 0) + 1
+    for kind in subject.kinds():
+        items += [[(kind, {})] for _ in range(max(0, 3 - have.get(kind, 0)))]
+    room = [subject.length - len(p) for p in starts]
+    dealt = [[] for _ in starts]
+    order = sorted(rng.permutation(len(items)), key=lambda at: -len(items[at]))   # (stable: the long items first, so that they fit)
+    # with the fused step boundaries: the items that reach it go round first, one to every sequence
+    seam = [at for at in order if subject.still_solves and any(k == "step_n" and f.get("n", 0) >= 2 for k, f in items[at])
+            and ("set_option", {"name": "OPT_STEP_SEAMS", "value": 0}) not in items[at]]
+    order = seam + [at for at in order if at not in seam]
+    for turn, at in enumerate(order):                   # to the sequence with the most room left
+        k = turn % len(room) if turn < len(seam) else int(np.argmax(room))
+        assert room[k] >= len(items[at]), f"{subject.name}: the deck does not fit {len(subject.cases)} sequences of {subject.length}"
+        dealt[k].append([(kind, dict(fixed)) for kind, fixed in items[at]])
+        room[k] -= len(items[at])
+    writers = [k for k in subject.kinds() if k not in QUERIES and k not in ("set_option", "forget_forces", "trail_stop", "record_stop") and
+               not (subject.still_solves and k == "set_tracers")]
+    plans = []
+    for k, mine in enumerate(dealt):
+        mine += [[(writers[int(rng.integers(len(writers)))], {})] for _ in range(room[k])]
+        # the planted items anywhere in the sequence, not in front, and the reads spread evenly between the items that write
+        mine = [mine[at] for at in rng.permutation(len(mine))]
+        loud = [item for item in mine if any(kind not in QUERIES and kind != "set_option" for kind, _ in item)]
+        quiet = [item for item in mine if item not in loud]
+        mine = [x for at, item in enumerate(loud) for x in [item] + quiet[at * len(quiet) // len(loud):(at + 1) * len(quiet) // len(loud)]]
+        for item in mine:
+            for kind, fixed in item:
+                if kind == "upload" and "field" not in fixed: fixed["field"] = int(rng.integers(4))
+        plans.append(starts[k] + _settle(subject, k, mine))
+    return plans
+
+
+OPTION_DEFAULTS = {"OPT_ADVECT_KERNEL": 0, "OPT_FUSE_DIVERGENCE": 1, "OPT_FUSE_PROJECTION": 1, "OPT_STEP_SEAMS": 1, "OPT_SMALL_GRID": 1,
+                   "OPT_SOR_KERNEL": 0, "OPT_SOR_FUSE": 0, "OPT_ADVECT_HALO": 0, "OPT_SOR_HALO": 0}
+STEPS = ("step", "step_n", "step_n_each", "step_n_until")
+SOLVES = ("poisson_solve", "poisson_continue", "poisson_solve_until") + STEPS
+AFFECTS = {"OPT_ADVECT_KERNEL": ("advect_velocity", "advect_color", "calculate_divergence", "subtract_gradient") + STEPS,
+           "OPT_FUSE_DIVERGENCE": STEPS, "OPT_FUSE_PROJECTION": STEPS, "OPT_STEP_SEAMS": ("step_n",), "OPT_SMALL_GRID": SOLVES,
+           "OPT_SOR_KERNEL": SOLVES, "OPT_SOR_FUSE": SOLVES, "OPT_SOR_HALO": SOLVES, "OPT_ADVECT_HALO": ("advect_velocity", "advect_color") + STEPS}
+
+
+def option_applies(subject, name):
+    """Whether the option changes the path of any call on the subject (the one-workgroup path needs at most 6144 cells, the
+    fused step boundary a whole-domain context, the halos a slab)."""
+    if name == "OPT_SMALL_GRID": return subject.name == "one-workgroup"
+    if name == "OPT_STEP_SEAMS": return subject.kind == "context"
+    return True
+
+
+def path_states(ops):
+    """For the census: (index, op, state in force WHILE the op runs) -- the option block, whether a set follows, the texture
+    the velocity is still on the lattice of (None otherwise), whether a step call has run, the steps of the timeline that
+    hold records -- followed from the op list alone."""
+    options, follow, lattice, stepped, pending = dict(OPTION_DEFAULTS), False, None, False, set()
+    for k, (kind, a) in enumerate(ops):
+        yield k, (kind, a), {"options": dict(options), "follow": follow, "lattice": lattice, "stepped": stepped, "pending": set(pending)}
+        if kind == "set_option": options[a["name"]] = a["value"]
+        if kind == "set_tracers": follow = a["follow"]
+        if kind == "upload" and a["field"] == FV: lattice = a["texture_kind"] if a["texture_kind"] in ("landing", "whole-cell") else None
+        if kind in ("subtract_gradient", "queue_forces", "queue_drags"): lattice = None
+        if kind in ("advect_velocity",) + STEPS and a["dt"] != 0.25: lattice = None
+        if kind in STEPS and a["iters"] != 0: lattice = None
+        if kind in ("queue_forces", "queue_drags"): pending.add(a["step"])
+        if kind == "forget_forces": pending = set()
+        if kind in STEPS:
+            stepped, n = True, a.get("n", 1)
+            pending = {step - n for step in pending if step >= n}
+
+
+def on_small_grid(state):
+    o = state["options"]
+    return o["OPT_SMALL_GRID"] == 1 and o["OPT_SOR_KERNEL"] == o["OPT_SOR_FUSE"] == o["OPT_ADVECT_KERNEL"] == 0
+
+
+def takes_the_seam(op, state):
+    """sfl_step_n joins its steps by the fused kernel: n >= 2, the four switches on, the tiled kernels, no following set, no
+    record in its steps."""
+    (kind, a), o = op, state["options"]
+    return (kind == "step_n" and a["n"] >= 2 and o["OPT_STEP_SEAMS"] == o["OPT_FUSE_DIVERGENCE"] == o["OPT_FUSE_PROJECTION"] == 1 and
+            o["OPT_ADVECT_KERNEL"] != 1 and not state["follow"] and not any(step < a["n"] for step in state["pending"]))
+
+
+def generate(subject, oracle):
+    """{case: ops}: the subject's sequences.  Deterministic: the same lists on every machine."""
+    out = {}
+    for case, kinds in zip(subject.cases, plan(subject)):
+        draw = _Draw(subject, case, oracle)
+        out[case] = [draw.make(kind, **fixed) for kind, fixed in kinds]
+        assert len(out[case]) == subject.length
+    return out
+
+
+# ---- the runner ------------------------------------------------------------------------------------------------------
+MODES = ("eager", "lazy", "probing")
+
+
+def _probe(model, seed, k):
+    rng = np.random.default_rng([seed, k, 11])
+    candidates = model.queries(rng)
+    return candidates[int(rng.integers(len(candidates)))]
+
+
+def _ask(model, handle, query, what):
+    handle.peer = model
+    compare(handle.apply(query), model.apply(query), what)
+
+
+def replay(model, handle, ops, mode, seed=0, label="", check_finite=False):
+    """Apply ops to the model and to the handle and compare: `eager` after every op all four fields and the tracers, `lazy`
+    nothing before the last op, `probing` after every op one query chosen by the seed; at the end everything, in every
+    mode.  An op that is a query is checked when issued (lazy skips it)."""
+    assert mode in MODES
+    k, op = -1, None
+    try:
+        for k, op in enumerate(ops):
+            if op[0] in QUERIES:
+                if mode != "lazy":
+                    _ask(model, handle, op, f"query {op[0]}")
+                continue
+            want, got = model.apply(op), handle.apply(op)
+            if want is not None:
+                compare(got, want, f"what {op[0]} returned")
+            if check_finite:
+                assert model.finite(), "the model holds a NaN or an Inf"
+            if mode == "eager":
+                compare(handle.snapshot(), model.snapshot(), "fields after the op")
+            elif mode == "probing":
+                query = _probe(model, seed, k)
+                _ask(model, handle, query, f"probe {query!r}")
+        k, op = len(ops), ("the final comparison", {})
+        compare(handle.snapshot(), model.snapshot(), "fields at the end")
+        for query in model.queries(np.random.default_rng([seed, 13])):
+            _ask(model, handle, query, f"at the end, {query!r}")
+    except AssertionError as e:
+        raise AssertionError(f"{label} seed {seed}, mode {mode}: op {k} ({op[0]}) disagrees: {e}\n"
+                             f"replay(model, handle, ops, {mode!r}, seed={seed}) with ops =\n{list(ops[:k + 1])!r}") from None
+
+
+def run(subject, case, ops, mode, oracle, make_handle, check_finite=False):
+    """One sequence on a fresh model and a fresh handle (make_handle(subject, case))."""
+    model, handle = subject.model(oracle, case), make_handle(subject, case)
+    try:
+        replay(model, handle, ops, mode, seed=case[2], label=f"{subject.name} {case[0]} x {case[1]}", check_finite=check_finite)
+    finally:
+        handle.close()
+
+
+# ---- three models with one planted fault each: what a state bug looks like to the runner -----------------------------
+# Each fault needs HISTORY on the handle: the first call of the faulty method on a fresh handle is right.
+class ContinuesFromTheOldPressure(ContextModel):
+    """Once a solve or a step has written the pressure, poisson_continue behind an upload of the pressure goes on from the
+    pressure held before that upload (a stale 'the solver's own pressure is current' flag)."""
+    solved, stale = False, None
+
+    def apply(self, op):
+        kind = op[0]
+        if kind == "upload" and op[1]["field"] == FP and self.solved:
+            self.stale = self.p
+        if kind == "poisson_continue" and self.stale is not None and op[1]["iters"] > 0:
+            self.p = self.stale
+        out = super().apply(op)
+        if kind in SOLVES:
+            self.solved, self.stale = True, None
+        return out
+
+
+class TimelineStaysAfterStepN(ContextModel):
+    """On a handle that has stepped before, step_n consumes its records but does not move the later ones down."""
+    stepped = False
+
+    def do_step(self, dt, dx, iters, omega):
+        super().do_step(dt, dx, iters, omega)
+        self.stepped = True
+
+    def do_step_n(self, n, dt, dx, iters, omega):
+        later = {s: r for s, r in self.timeline.items() if s >= n}
+        super().do_step_n(n, dt, dx, iters, omega)
+        if self.stepped:
+            self.timeline = later
+        self.stepped = True
+
+
+class ResidualLeavesItsTarget(ContextModel):
+    """From its second call on, residual leaves p_gs in the pressure."""
+    calls = 0
+
+    def q_residual(self, dx):
+        out = super().q_residual(dx)
+        self.calls += 1
+        if self.calls > 1:
+            with np.errstate(all="ignore"):
+                self.p = gs_target(self.p, self.d, dx).astype(np.float32)
+        return out
+
+
+STAND_INS = (ContinuesFromTheOldPressure, TimelineStaysAfterStepN, ResidualLeavesItsTarget)
+
+
+def fresh_handle_check(oracle, make_handle, dim_x=61, dim_y=81, seed=3):
+    """The kind of check the suite had: a fresh handle, one fixed order that calls everything once -- options, uploads, a
+    pressure uploaded and continued (the clause of tests/test_context_until.py), its update norm, a stroke queued over the
+    steps to come, step_n -- every read compared, and every field at the end."""
+    ops = [("set_option", {"name": "OPT_SOR_KERNEL", "value": 2}), ("upload", {"field": FV, "texture_kind": "noise", "seed": seed}),
+           ("upload", {"field": FC, "texture_kind": "noise", "seed": seed}), ("upload", {"field": FD, "texture_kind": "noise", "seed": seed}),
+           ("upload", {"field": FP, "texture_kind": "noise", "seed": seed}), ("poisson_continue", {"dx": 0.5, "iters": 3, "omega": 1.5}),
+           ("residual", {"dx": 0.5}), ("download", {"field": FP}),
+           ("queue_forces", {"step": 0, "cells": [[3, 4]], "vels": [[20.0, -10.0]]}), ("queue_forces", {"step": 2, "cells": [[30, 40]], "vels": [[-15.0, 5.0]]}),
+           ("queue_forces", {"step": 4, "cells": [[7, 7]], "vels": [[1.0, 2.0]]}),
+           ("step_n", {"n": 3, "dt": 1 / 30.0, "dx": 1.0, "iters": 5, "omega": 1.96}), ("forces_pending", {}),
+           ("step", {"dt": 1 / 30.0, "dx": 1.0, "iters": 5, "omega": 1.96}), ("step", {"dt": 1 / 30.0, "dx": 1.0, "iters": 5, "omega": 1.96})]
+    model, handle = ContextModel(oracle, dim_x, dim_y), make_handle(dim_x, dim_y)
+    for op in ops:
+        want, got = model.apply(op), handle.apply(op)
+        if want is not None:
+            compare(got, want, f"a fresh handle, one order: {op[0]}")
+    compare(handle.snapshot(), model.snapshot(), "a fresh handle, one order")
