@@ -4,6 +4,7 @@
 // It proves the drop-in claim: reference-style caller code builds and runs unchanged on the GPU
 // path.  TEST PROGRAM: reads initial fields from argv[1], runs argv[2] steps, writes the final
 // velocity / divergence / pressure / colour to argv[3]; pytest compares them with the oracle.
+// An optional argv[4] is the grid spacing of the three operators that take one (the sketch's is 1).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +20,7 @@
 
 static int N_ROWS, N_COLS;
 static const float DT = 1 / 30.0f;
+static float DX = 1;
 static Vector2<float> *velocity_field;
 static Vector3<UQ32> *color_field;
 static float *div_v, *p;
@@ -30,9 +32,9 @@ static void sim_step(int iters)
     SWAP(v_temp, velocity_field);
     delete[] v_temp;
 
-    calculate_divergence(div_v, velocity_field, N_ROWS, N_COLS, 1);
-    poisson_solve(p, div_v, N_ROWS, N_COLS, 1, iters, 1.96);
-    subtract_gradient(velocity_field, p, N_ROWS, N_COLS, 1);
+    calculate_divergence(div_v, velocity_field, N_ROWS, N_COLS, DX);
+    poisson_solve(p, div_v, N_ROWS, N_COLS, DX, iters, 1.96);
+    subtract_gradient(velocity_field, p, N_ROWS, N_COLS, DX);
 
     Vector3<UQ32> *c_temp = new Vector3<UQ32>[N_ROWS * N_COLS];
     advect(c_temp, color_field, velocity_field, N_ROWS, N_COLS, DT, false);
@@ -42,7 +44,8 @@ static void sim_step(int iters)
 
 int main(int argc, char **argv)
 {
-    if (argc != 4) return 2;
+    if (argc != 4 && argc != 5) return 2;
+    if (argc == 5) DX = std::strtof(argv[4], nullptr);
     FILE *in = std::fopen(argv[1], "rb");
     if (!in) return 3;
     int hdr[3];

@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from conftest import GOLDEN, assert_bit_equal
+from dx_cases import DX_A, DX_CASES, DX_TAGS
 
 OMEGA = np.float32(1.96)
 
@@ -66,6 +67,28 @@ def ops_files():
 
 def channel_files():
     return sorted(glob.glob(os.path.join(GOLDEN, "advc_*.npz")))
+
+
+def dx_files():
+    return sorted(glob.glob(os.path.join(GOLDEN, "dxn_*.npz")))
+
+
+def check_dx(impl, path):
+    """The operators that multiply by the grid spacing, at spacings where no such product is exact (tests/dx_cases.py), and
+    two whole steps at dx = 0.37 (fixture written by the reference)."""
+    z = np.load(path)
+    v, c, s, dt, omega = z["v"], z["c"], z["s"], z["dt"], z["omega"]
+    tag = os.path.basename(path)
+    assert_bit_equal(z["dxs"], np.array(DX_CASES, np.float32), f"{tag}: the spacings the fixture was written at")
+    for t, dx in zip(DX_TAGS, DX_CASES):
+        assert_bit_equal(impl.divergence(v, dx), z[f"div_{t}"], f"{tag} div dx {dx!r}")
+        assert_bit_equal(impl.subtract_gradient(v, s, dx), z[f"grad_{t}"], f"{tag} grad dx {dx!r}")
+        for iters in (1, 6):
+            assert_bit_equal(impl.poisson_solve(s, dx, iters, omega), z[f"pois_i{iters}_{t}"], f"{tag} pois i{iters} dx {dx!r}")
+    for k in (1, 2):
+        v, d, p, c = impl.step(v, c, dt, DX_A, 6, omega)
+        for name, a in (("v", v), ("div", d), ("p", p), ("c", c)):
+            assert_bit_equal(a, z[f"step{k}_{name}"], f"{tag} step {k} at dx {DX_A!r}: {name}")
 
 
 def check_channels(impl, path):

@@ -47,6 +47,16 @@ def test_ops_match_golden_baseline_sor(hip_baseline, path):
     G.check_ops(hip_baseline, path)
 
 
+@pytest.mark.parametrize("path", G.dx_files(), ids=lambda p: p.split("/")[-1])
+def test_inexact_spacings_match_golden(hip, path):
+    G.check_dx(hip, path)
+
+
+@pytest.mark.parametrize("path", G.dx_files(), ids=lambda p: p.split("/")[-1])
+def test_inexact_spacings_match_golden_baseline_sor(hip_baseline, path):
+    G.check_dx(hip_baseline, path)
+
+
 @pytest.mark.parametrize("path", G.step_files(), ids=lambda p: p.split("/")[-1])
 def test_steps_match_golden(hip, path):
     G.check_steps(hip, path)
@@ -1226,7 +1236,7 @@ def test_every_fuse_depth_from_zero_and_continuing(sfl, oracle, fuse):
     dim_x, dim_y = 1500, 1100
     _, _, d = random_fields(dim_x, dim_y, 40 + fuse)
     iters = fuse + fuse // 2          # three launches of this depth
-    for dx in (1.0, 0.75):
+    for dx in (1.0, 0.75, np.nextafter(np.float32(1), np.float32(2))):   # (the last: one unit above the kernels compiled for dx = 1)
         with sfl.Solver(dim_x, dim_y) as s:
             s.set_option(sfl.capi.OPT_SOR_KERNEL, 2)
             s.set_option(sfl.capi.OPT_SOR_FUSE, fuse)

@@ -22,8 +22,14 @@ def test_oracle_generic_advect_matches_golden(oracle, path):
     G.check_channels(oracle, path)
 
 
+@pytest.mark.parametrize("path", G.dx_files(), ids=lambda p: p.split("/")[-1])
+def test_oracle_inexact_spacings_match_golden(oracle, path):
+    G.check_dx(oracle, path)
+
+
 def test_fixture_inventory():
     assert len(G.step_files()) >= 7 and len(G.ops_files()) >= 6 and len(G.channel_files()) >= 4
+    assert len(G.dx_files()) >= 4
 
 
 def test_lcg_recipe_and_hash_helpers_agree(oracle):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_bit_equal, random_fields
+from dx_cases import DX_A, DX_B, DX_C, DX_CASES, DX_D, DX_E, dx_id
 
 SHAPES = [(2, 2), (2, 3), (3, 2), (3, 3), (4, 4), (5, 4), (17, 33), (33, 17), (61, 81), (64, 48),
           (128, 7), (7, 128)]
@@ -67,7 +68,7 @@ def test_advect_every_element_type(oracle, reference, dim_x, dim_y, channels, uq
 
 
 @pytest.mark.parametrize("dim_x,dim_y", SHAPES)
-@pytest.mark.parametrize("dx", [1.0, 0.5, 3.0])
+@pytest.mark.parametrize("dx", [1.0, 0.5, 3.0] + list(DX_CASES), ids=lambda dx: dx_id(dx) if isinstance(dx, np.float32) else None)
 def test_divergence_and_gradient(oracle, reference, dim_x, dim_y, dx):
     v, _, s = random_fields(dim_x, dim_y, 11, 50.0)
     assert_bit_equal(oracle.divergence(v, dx), reference.divergence(v, dx), "divergence")
@@ -77,7 +78,9 @@ def test_divergence_and_gradient(oracle, reference, dim_x, dim_y, dx):
 
 @pytest.mark.parametrize("dim_x,dim_y", SHAPES)
 @pytest.mark.parametrize("iters,omega,dx", [(1, 1.96, 1.0), (2, 1.0, 1.0), (7, 1.5, 0.25),
-                                            (20, 1.96, 1.0)])
+                                            (20, 1.96, 1.0)] +
+                         [pytest.param(i, w, dx, id=f"{i}-{w}-{dx_id(dx)}")
+                          for i, w, dx in ((5, 1.96, DX_A), (7, 1.5, DX_B), (4, 1.9, DX_E), (3, 1.0, DX_D))])
 def test_poisson_solve(oracle, reference, dim_x, dim_y, iters, omega, dx):
     _, _, s = random_fields(dim_x, dim_y, 5)
     assert_bit_equal(oracle.poisson_solve(s, dx, iters, np.float32(omega)),
@@ -93,14 +96,18 @@ def test_poisson_signed_zero_rhs(oracle, reference):
                          reference.poisson_solve(s, 1.0, 3, np.float32(1.96)), "signed zero")
 
 
-@pytest.mark.parametrize("dim_x,dim_y,iters", [(61, 81, 10), (33, 17, 4), (2, 2, 3), (96, 64, 6)])
-def test_full_step_sequence(oracle, reference, dim_x, dim_y, iters):
+STEP_SEQUENCES = [(61, 81, 10), (33, 17, 4), (2, 2, 3), (96, 64, 6)]
+
+
+@pytest.mark.parametrize("dim_x,dim_y,iters,dx", [pytest.param(x, y, i, 1.0, id=f"{x}-{y}-{i}") for x, y, i in STEP_SEQUENCES] + [
+    pytest.param(x, y, i, dx, id=f"{x}-{y}-{i}-{dx_id(dx)}") for dx in (DX_A, DX_C) for x, y, i in STEP_SEQUENCES])
+def test_full_step_sequence(oracle, reference, dim_x, dim_y, iters, dx):
     v, c, _ = random_fields(dim_x, dim_y, 77, 100.0)
     vo, co = v, c
     vr, cr = v, c
     for _ in range(3):
-        vo, do, po, co = oracle.step(vo, co, DT, 1.0, iters, np.float32(1.96))
-        vr, dr, pr, cr = reference.step(vr, cr, DT, 1.0, iters, np.float32(1.96))
+        vo, do, po, co = oracle.step(vo, co, DT, dx, iters, np.float32(1.96))
+        vr, dr, pr, cr = reference.step(vr, cr, DT, dx, iters, np.float32(1.96))
         for name, a, b in (("v", vo, vr), ("div", do, dr), ("p", po, pr), ("colour", co, cr)):
             assert_bit_equal(a, b, name)
 

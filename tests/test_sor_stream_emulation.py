@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, assert_bit_equal
+from dx_cases import DX_A
 
 OMEGA = np.float32(1.96)
 _F = C.POINTER(C.c_float)
@@ -65,6 +66,10 @@ def test_fused_passes_from_zero(emu, oracle, dim_x, dim_y, ns):
     assert_bit_equal(emu(None, d, ns, rows=16, uniform=True), want, "uniform tiling")
     if dim_x % 2 == 0:
         assert_bit_equal(emu(None, d, ns, rows=16, vec2=True), want, "vec2 access variant")
+    # an inexact dx * d (tests/dx_cases.py): the interior tiles' trip and the edge tiles' k * (dx * d - sum)
+    want = oracle.poisson_solve(d, DX_A, ns // 2, OMEGA)
+    assert_bit_equal(emu(None, d, ns, rows=16, dx=DX_A), want, "auto edge, dx 0.37")
+    assert_bit_equal(emu(None, d, ns, rows=40, force_edge=True, dx=DX_A), want, "forced edge path, dx 0.37")
 
 
 @pytest.mark.parametrize("dim_x,dim_y", SHAPES)
