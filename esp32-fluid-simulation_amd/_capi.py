@@ -65,6 +65,13 @@ class FlowStats(C.Structure):
                 ("dye_sum", C.c_uint64 * 3)]
 
 
+class HistoryRecord(C.Structure):
+    """struct sfl_history_record: one sample of a history, 64 bytes; the first 40 are a struct sfl_flow_stats."""
+    _fields_ = [("max_abs_vx", C.c_float), ("max_abs_vy", C.c_float), ("max_abs_div", C.c_float), ("what", C.c_uint32),
+                ("dye_sum", C.c_uint64 * 3), ("update_norm", C.c_float), ("iterations", C.c_int32), ("step", C.c_int64),
+                ("dt", C.c_float), ("dx", C.c_float)]
+
+
 class FieldDistance(C.Structure):
     """struct sfl_field_distance: what sfl_distance and sfl_batch_distance report, 64 bytes."""
     _fields_ = [("max_abs_dvx", C.c_float), ("max_abs_dvy", C.c_float), ("max_abs_dp", C.c_float), ("what", C.c_uint32),
@@ -236,6 +243,14 @@ SIGNATURES = {
     "sfl_view_render": (_i, [_ctx, C.POINTER(View), _i, _i, C.POINTER(C.c_uint16), _sz]),
     "sfl_batch_view_render_members": (_i, [_ctx, C.POINTER(View), _i, _i, _i, _i, C.POINTER(C.c_uint16), _sz]),
     "sfl_batch_record_view": (_i, [_ctx, C.POINTER(View)]),
+    "sfl_batch_history_start": (_i, [_ctx, _i, _i, _i, _i]),
+    "sfl_batch_history_stop": (_i, [_ctx]),
+    "sfl_batch_history_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64)]),
+    "sfl_batch_history_read": (_i, [_ctx, _i, _i, _i, _i, C.POINTER(HistoryRecord), _sz]),
+    "sfl_history_start": (_i, [_ctx, _i, _i]),
+    "sfl_history_stop": (_i, [_ctx]),
+    "sfl_history_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64)]),
+    "sfl_history_read": (_i, [_ctx, _i, _i, C.POINTER(HistoryRecord), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

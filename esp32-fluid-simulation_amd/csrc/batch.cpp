@@ -20,7 +20,7 @@ void release(sfl_batch *b)
                     b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_counts, (void *)b->d_image,
                     (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env,
                     (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
-                    (void *)b->d_rec_palette})
+                    (void *)b->d_rec_palette, b->history.d_records})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
     if (b->h_dist) (void)hipHostFree(b->h_dist);
@@ -213,13 +213,14 @@ enum StepKind { kUniform, kEach, kUntil };
 // was a timeline: n >= 2 steps of small members with a record in some step of [1, n), not by the stopping rule.  With a
 // recorder on, such a call is cut into launches that end at the steps whose frame is due, the render between them.
 // With a following set of tracers (tracers_follow) every step is a launch of its own, the advance behind it: the tracers
-// read each step's projected velocity, which the launch of several steps never stores.
+// read each step's projected velocity, which the launch of several steps never stores.  A history (history_step) cuts
+// the call as the recorder does: its sample reads the fields of the step it is due after.
 int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
 {
     SFL_TRY(stage_timeline(b, n));
     if (kind != kUntil && !b->large && n >= 2 && !b->tracers_follow && staged_has(b, 1, n)) {
         for (int done = 0; done < n;) {
-            const int steps = sfl::host::record_run(b, n - done);
+            const int steps = sfl::host::history_run(b->history, sfl::host::record_run(b, n - done));   // (cut at either's due steps)
             sfl::BatchPlay play{};
             play.step = a.step;
             play.force_rows = staged_rows_from(b, done, &play.rows, &play.step.force_cells, &play.step.force_vel);
@@ -233,6 +234,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
             std::swap(b->vel, b->vel_tmp);
             if (steps & 1) std::swap(b->col, b->col_tmp);   // (the dye ping-pongs inside the launch)
             SFL_TRY(sfl::host::record_step(b, steps));
+            if (b->history_step) SFL_TRY(b->history_step(b, steps, kind == kEach ? b->d_members : nullptr, false, a.step));
             done += steps;
         }
         consume_forces(b, n);
@@ -255,6 +257,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
         std::swap(b->col, b->col_tmp);  // ino:286
         SFL_TRY(sfl::host::record_step(b));
         if (b->tracers_follow) SFL_TRY(b->tracers_follow(b, kind == kUniform ? nullptr : b->d_members, a.step.dt));
+        if (b->history_step) SFL_TRY(b->history_step(b, 1, kind == kUniform ? nullptr : b->d_members, kind == kUntil, a.step));
     }
     consume_forces(b, n);
     return SFL_OK;
@@ -560,6 +563,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     if (n == 0) return SFL_OK;
     SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
     SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
+    SFL_TRY(sfl::host::history_admit(b->history, n));   // ... and a history without room for its samples
     SFL_TRY(use_device(b));
     b->report_valid = b->counts_valid = false;   // (the uniform kernels leave no update norm)
     sfl::BatchStep a{};
@@ -593,6 +597,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
     if (n == 0) return SFL_OK;
     SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
     SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
+    SFL_TRY(sfl::host::history_admit(b->history, n));   // ... and a history without room for its samples
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
     b->report_valid = b->counts_valid = false;   // until every launch below is queued; no iterations to report afterwards
@@ -625,6 +630,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
     if (n == 0) return SFL_OK;
     SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
     SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
+    SFL_TRY(sfl::host::history_admit(b->history, n));   // ... and a history without room for its samples
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params, stops));
     b->report_valid = b->counts_valid = false;   // until every launch below is queued

@@ -92,6 +92,12 @@ struct sfl_batch {
     // of the step's launch, in its launch order) or all by `dt` (members == nullptr)
     sfl::host::TracerSet tracers;
     int (*tracers_follow)(sfl_batch *b, const sfl::BatchMember *members, float dt) = nullptr;
+    // the history (history.cpp; context.h has History): history_step: `steps` steps have been launched (one launch) and the
+    // ping-pong swapped -- count them and, when a sample is due, launch it on the batch's stream behind them.  members: the
+    // device records of the launch, in its launch order (nullptr: every member ran `step`'s dt, dx and iters); until: the
+    // launch left each member's iterations in d_counts
+    sfl::host::History history;
+    int (*history_step)(sfl_batch *b, int steps, const sfl::BatchMember *members, bool until, const sfl::SmallStep &step) = nullptr;
     // views (views.cpp): the scratch of the view calls; the recorder's staged palette (allocated by the first
     // sfl_batch_record_view, kept until the batch goes) and the host copy its upload reads; record_view_frame: a frame of
     // the recorder's view (rec.view) is due -- launch its render into `images` on the batch's stream.  Set by

@@ -213,6 +213,41 @@ inline int trail_admit(const TracerSet &t, int64_t advances)
 // ... of the steps of a step call: a set that does not follow is not advanced by them
 inline int trail_admit_steps(const TracerSet &t, int n) { return t.follow && t.count ? trail_admit(t, n) : SFL_OK; }
 
+// A history (history.cpp; include/sfl.h "HISTORIES"): what a context or a batch holds of it.  Plain data, as TracerSet and
+// for the same reason: the destroy paths free the records and the step calls admit and count without a symbol of
+// history.cpp; the sample is launched through the `history_step` pointer of the two structs, which history.cpp sets
+// while a history is on (null: the step calls launch what they launched before there were histories).
+struct History {
+    bool on = false;
+    int every = 0, first = 0, count = 0, capacity = 0, written = 0;   // members [first, first + count) (a context: [0, 1))
+    int64_t steps = 0;            // counted since history_start
+    void *d_records = nullptr;    // `capacity` samples of `count` records of 64 bytes, sample-major; kept by a restart that
+    size_t d_bytes = 0;           //   does not need more, freed by history_stop and the destroy paths
+    // a context's sample is written by the streaming passes, which know nothing of the step: what the host knows of
+    // sample s waits here and is merged into the bytes read out
+    struct HostWords {
+        int32_t iterations;
+        int64_t step;
+        float dt, dx;
+    };
+    std::vector<HostWords> host_words;
+};
+
+// SFL_ERR_STATE if the n steps of a call would complete more samples than are free: the rule of record_admit
+// (batch_state.h) -- after the call's own argument checks, before anything is staged or launched
+inline int history_admit(const History &h, int64_t n)
+{
+    if (!h.on) return SFL_OK;
+    const int64_t due = (h.steps + n) / h.every - h.steps / h.every, room = h.capacity - h.written;
+    if (due > room)
+        return fail(SFL_ERR_STATE, "the history has room for %lld more samples (%d of %d written) and %lld steps would complete %lld: "
+                    "nothing stepped; read the samples (sfl_history_read, sfl_batch_history_read) and start the history again to make room",
+                    (long long)room, h.written, h.capacity, (long long)n, (long long)due);
+    return SFL_OK;
+}
+// how many of the next n steps may run in one launch before a sample is due (n without a history): record_run's rule
+inline int history_run(const History &h, int n) { return h.on ? (int)std::min<int64_t>(n, h.every - h.steps % h.every) : n; }
+
 // What the view calls (views.cpp; include/sfl.h "VIEWS") keep on the device for a context or a batch: the staged palette
 // of the call (kViewPaletteWords words, allocated at the first call) and the call's result, which only grows.  Plain
 // data, freed by the two destroy paths, so that they need no symbol of views.cpp.
@@ -336,8 +371,12 @@ struct sfl_context {
     sfl::host::TracerSet tracers;
     int (*tracers_follow)(sfl_context *c, float dt) = nullptr;
     sfl::host::ViewScratch views;   // sfl_view_* (views.cpp)
+    // the history (history.cpp), and its sample behind every step while it is on (one step has run and been counted by
+    // nobody yet: count it and, when a sample is due, launch the statistics' passes on the context's stream)
+    sfl::host::History history;
+    int (*history_step)(sfl_context *c, float dt, float dx, int iters) = nullptr;
 
-    sfl::host::Options opt;   // what sfl_set_option stores (kOptions above: one row per option)
+    sfl::host::Options opt;  // what sfl_set_option stores (kOptions above: one row per option)
 
     // how halo rows reach the neighbouring slabs (transport.h); null on a whole-domain context and on a slab that has
     // not been attached / linked yet.  `group` = the same object when it is an in-process group of virtual ranks.

@@ -325,6 +325,7 @@ int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
     if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);   // (refused with the timeline untouched)
     SFL_TRY(trail_admit_steps(ctx->tracers, 1));   // a trail of following tracers without a free slot refuses the step
+    SFL_TRY(history_admit(ctx->history, 1));       // ... and so does a history without a free sample
     if (ctx->nranks > 1 && ctx->opt.advect_halo == 0 && ctx->color_unsettled && ctx->unsettled_dt == dt && ctx->force_cells.empty())
         SFL_TRY(advect_interior_early(ctx, dt));
     SFL_TRY(settle_color(ctx, true));
@@ -332,6 +333,7 @@ int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
     SFL_TRY(step_of_timeline(ctx, dt, dx, iters, omega));
     forces_advance(ctx);   // the records of step 0 are consumed, the later ones move down by one (include/sfl.h)
     if (ctx->tracers_follow) SFL_TRY(ctx->tracers_follow(ctx, dt));   // a following set moves with this step's projected velocity
+    if (ctx->history_step) SFL_TRY(ctx->history_step(ctx, dt, dx, iters));   // a history counts the step and samples what it left
     return SFL_OK;
 }
 
@@ -345,13 +347,15 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
     if (n > 0 && iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     SFL_TRY(trail_admit_steps(ctx->tracers, n));   // a trail without room for the slots of n advances refuses the call whole
+    SFL_TRY(history_admit(ctx->history, n));       // ... and so does a history without room for the call's samples
     SFL_TRY(settle_color(ctx, true));
     SFL_TRY(check_wait_error(ctx));
     const int64_t cells = (int64_t)ctx->dim_x * ctx->gdim_y;
     const bool tiled = ctx->opt.advect_kernel == 2 || (ctx->opt.advect_kernel == 0 && cells >= sfl::kAdvectTiledMinCells);
-    // (a following set of tracers reads every step's projected velocity, which a seam never stores: no seams then)
+    // (a following set of tracers reads every step's projected velocity, which a seam never stores: no seams then; nor with
+    // a history on, whose samples read it too)
     const bool seams = n > 1 && ctx->opt.step_seams && ctx->nranks == 1 && !ctx->transport && !small_grid(ctx) && tiled &&
-                       ctx->opt.fuse_projection && ctx->opt.fuse_divergence && !ctx->tracers_follow;
+                       ctx->opt.fuse_projection && ctx->opt.fuse_divergence && !ctx->tracers_follow && !ctx->history_step;
     if (!seams) {
         for (int k = 0; k < n; ++k) SFL_TRY(sfl_step(ctx, dt, dx, iters, omega));
         return SFL_OK;

@@ -71,6 +71,15 @@ FLOW_STATS_STRIP_COLS, FLOW_STATS_CHUNK_ROWS = 128, 8
 FIELD_DISTANCE_DTYPE = np.dtype([("max_abs_dvx", "<f4"), ("max_abs_dvy", "<f4"), ("max_abs_dp", "<f4"), ("what", "<u4"),
                                  ("velocity_cells_differ", "<u4"), ("dye_cells_differ", "<u4"), ("pressure_cells_differ", "<u4"),
                                  ("max_abs_ddye", "<u4", (3,)), ("sum_abs_ddye", "<u8", (3,))])
+# struct sfl_history_record: one sample of a history (Solver.history: one per sample; BatchSolver.history: one per sample
+# and recorded member).  64 bytes; the first 40 are a FLOW_STATS_DTYPE record.
+HISTORY_DTYPE = np.dtype({"names": ["max_abs_vx", "max_abs_vy", "max_abs_div", "what", "dye_sum", "update_norm", "iterations", "step",
+                                    "dt", "dx"],
+                          "formats": ["<f4", "<f4", "<f4", "<u4", ("<u8", (3,)), "<f4", "<i4", "<i8", "<f4", "<f4"],
+                          "offsets": [0, 4, 8, 12, 16, 40, 44, 48, 56, 60], "itemsize": 64})
+HISTORY_THREADS = 1024  # kHistoryThreads of csrc/history_kernels.h: threads of the sampler's workgroup (stated for the tests)
+
+
 # The tiles of the distance passes and of the envelope (csrc/ensemble_kernels.h): a lane of a distance pass holds
 # DIST_*_LANE_CELLS whole cells per load, a workgroup of DIST_THREADS lanes takes DIST_ITEM_LOADS loads per lane as one
 # item; the envelope gives a workgroup ENV_BLOCK_WORDS words of a group of ENV_GROUP_MEMBERS members.  Stated for the
@@ -273,7 +282,61 @@ class _Tracers:
         capi.check(self._tracer_call("trail_stop")(self._h))
 
 
-class Solver(_Tracers):
+class _History:
+    """Histories: the flow statistics of every k-th step, recorded while stepping (include/sfl.h "HISTORIES").  Shared by
+    :class:`Solver` (one record per sample) and :class:`BatchSolver` (one per sample and recorded member)."""
+
+    _history_prefix = "sfl_history_"
+    _hist = (0, 1)   # the recorded members (first, count); a context: its one record
+
+    def _history_call(self, name):
+        return getattr(self._lib, self._history_prefix + name)
+
+    def _history_range(self, first, count):   # the arguments between `every` and `capacity`: none for a context
+        if first != 0 or count not in (None, 1):
+            raise ValueError("a context's history has one record per sample: first = 0, count = None")
+        return (0, 1), ()
+
+    def history_start(self, every: int, capacity: int, first: int = 0, count=None):
+        """Start a history: after every `every`-th step of any step call -- counted across calls -- one launch on the
+        stream writes one HISTORY_DTYPE record per recorded member (a batch: members [first, first + count), default all)
+        from the fields that step left; `capacity` samples fit.  The step calls stay asynchronous.  A step call that
+        would complete more samples than are free raises SflError with ERR_STATE and steps nothing: read them
+        (:meth:`history`) and call history_start again.  Called while a history is on, it starts afresh.  With a history
+        on, ``Solver.step_n`` runs without the fused step boundaries (OPT_STEP_SEAMS) and a batch's replay of a timeline
+        is cut at the steps whose sample is due: same bits in every field."""
+        hist, args = self._history_range(first, count)
+        rc = self._history_call("start")(self._h, every, *args, capacity)
+        if rc == capi.OK:
+            self._hist = hist
+        capi.check(rc)
+
+    def history_info(self):
+        """(samples written, capacity, steps counted since history_start); zeros without a history.  Never waits."""
+        samples, capacity, steps = C.c_int(), C.c_int(), C.c_int64()
+        capi.check(self._history_call("info")(self._h, C.byref(samples), C.byref(capacity), C.byref(steps)))
+        return samples.value, capacity.value, steps.value
+
+    def history(self) -> np.ndarray:
+        """The samples written so far as a HISTORY_DTYPE array of shape ``(samples,)`` (a batch: ``(samples, count)``, the
+        recorded members); not consumed.  A record equals, bit for bit, what ``flow_stats``, ``residual`` and
+        ``iterations`` return right after the same step.  Synchronous."""
+        samples = self.history_info()[0]
+        first, count = self._hist
+        out = np.zeros((samples, count), HISTORY_DTYPE)
+        ptr = out.ctypes.data_as(C.POINTER(capi.HistoryRecord))
+        if self._history_prefix == "sfl_history_":
+            capi.check(self._history_call("read")(self._h, 0, samples, ptr, out.nbytes))
+            return out[:, 0]
+        capi.check(self._history_call("read")(self._h, 0, samples, first, count, ptr, out.nbytes))
+        return out
+
+    def history_stop(self):
+        """Stop the history and free its samples."""
+        capi.check(self._history_call("stop")(self._h))
+
+
+class Solver(_Tracers, _History):
     """One solver context: rows [row_begin, row_end) of a dim_x * dim_y domain on one device."""
 
     def __init__(self, dim_x: int, dim_y: int, device: int = 0, rank: int = 0, nranks: int = 1):
@@ -510,7 +573,7 @@ class Solver(_Tracers):
         return {"launches": a.value, "exchanges": b.value, "fuse": c.value, "halo": self.get_option(capi.OPT_LAST_HALO)}
 
 
-class BatchSolver(_Tracers):
+class BatchSolver(_Tracers, _History):
     """A batch (sfl_batch_*): `batch` independent whole-domain simulations of one dim_x * dim_y grid on one device,
     every member stepped by the same launch.  Member m holds, bit for bit, what a :class:`Solver` of the same shape
     holds after the same calls made with member m's data and forces.  Arrays of members are shaped
@@ -528,9 +591,14 @@ class BatchSolver(_Tracers):
         self._rec = (0, 0, 1)   # (first, count, scaling) of the running recording: the shape of what frames() reads
 
     _tracer_prefix = "sfl_batch_tracers_"
+    _history_prefix = "sfl_batch_history_"
 
     def _tracer_lead(self):
         return (self.batch,)
+
+    def _history_range(self, first, count):
+        count = self.batch - first if count is None else count
+        return (first, count), (first, count)
 
     def close(self):
         if self._h:

@@ -929,6 +929,80 @@ SFL_API int sfl_batch_view_render_members(sfl_batch *b, const struct sfl_view *v
  * already launched.  Frames keep their size: sfl_batch_record_info and sfl_batch_record_read do not change.  A view frame
  * shows the velocity and the pressure the step that completed it left.                                                  */
 SFL_API int sfl_batch_record_view(sfl_batch *b, const struct sfl_view *view);
+/* --- HISTORIES: the flow statistics of every k-th step, recorded while stepping.  A history is `capacity` samples in
+ *     device memory; after every `every`-th step of any step call, ONE launch on the context's or batch's stream writes
+ *     one 64-byte record per recorded member from the fields that step left.  The step calls stay asynchronous and the
+ *     host never waits; the records are read out afterwards.  Batches of either kind, and whole-domain contexts (group 2;
+ *     a slab gets SFL_ERR_STATE).
+ *   THE RECORD.  Every figure is one the calls above already define, word for word:
+ *     max_abs_vx, max_abs_vy, max_abs_div, what, dye_sum   struct sfl_flow_stats (sfl_flow_stats: the definitions) of
+ *                   the velocity and the dye the step left, with what = SFL_STATS_VELOCITY | SFL_STATS_DYE and the
+ *                   divergence scaled by the step's dx: the first 40 bytes ARE a struct sfl_flow_stats;
+ *     update_norm   sfl_batch_residual's (sfl_residual's) definition on the pressure and the divergence the step left,
+ *                   with the step's dx.  A uniform sfl_batch_step_n leaves no valid sfl_batch_residual report; the
+ *                   history evaluates the norm all the same, from the pressure and divergence in memory;
+ *     iterations    of that step's solve: iters, or under sfl_batch_step_n_until the k the rule (sfl_member_stop)
+ *                   stopped the member at -- the first word of sfl_batch_iterations if the call ended with that step;
+ *     step          the history's step count when the sample was taken: every, 2 * every, ...;
+ *     dt, dx        that step's: the call's, or the member's own in the *_each and *_until calls.
+ *   A record equals, bit for bit, what sfl_batch_flow_stats[_each], sfl_batch_residual and sfl_batch_iterations (a
+ * context: sfl_flow_stats, sfl_residual) return when called right after the same step.  Maxima over bit patterns and
+ * integer sums do not depend on the order of reduction: no tolerance anywhere.
+ *   COUNTING.  Every step of sfl_batch_step_n, sfl_batch_step_n_each and sfl_batch_step_n_until counts, across calls
+ * (a context: every step of sfl_step and sfl_step_n).  Solves, uploads and setup_sketch_fields neither count nor sample.
+ * A step call whose steps would complete more samples than are free is refused WHOLE with SFL_ERR_STATE, after the
+ * call's own argument checks and before anything is staged or launched: fields, timeline, reports, frames and every
+ * count stay untouched.  The history fills up at a sample boundary, so a caller who reads the samples and starts the
+ * history again whenever it is full keeps the phase.
+ *   WHAT A HISTORY CHANGES.  Nothing about any result: all fields keep their bits, sfl_batch_residual and
+ * sfl_batch_iterations keep their validity, queued forces go into their steps, a recorder and following tracers run as
+ * they do.  It changes which launches a call makes: a batch call that would run several steps in one launch (a timeline
+ * with records in its later steps, small members) is cut into launches that end at the steps whose sample is due -- with
+ * a recorder on as well, at either's due steps -- and sfl_step_n on a context runs WITHOUT the fused step boundaries of
+ * SFL_OPT_STEP_SEAMS, as with a following set of tracers: a seam never stores the velocity a sample reads.  Without a
+ * history on, every call launches exactly what it launched before there were histories.
+ *   Cost: one launch per sample reading 28 bytes per cell and member (a batch; a context: the two passes of
+ * sfl_flow_stats and the pass of sfl_residual).  Measured on an MI355X (profiles/history.txt), a sample after EVERY
+ * step: 61 x 81 x 1024 members at 20 iterations, +30 us per sample beside a step of 125 us; 128 x 128 x 256 large members,
+ * +28 us beside a step of 168 us.  The loop of synchronous calls a history replaces -- step_n_until(1), flow_stats,
+ * residual, iterations -- took 292 us per step where the one call with a history takes 201.  Choose `every` accordingly.
+ *   Every refusal below is made before any GPU work, carries its own message (sfl_last_error) and leaves a running
+ * history as it was.                                                                                                    */
+struct sfl_history_record {
+    float    max_abs_vx, max_abs_vy, max_abs_div;
+    uint32_t what;
+    uint64_t dye_sum[3];
+    float    update_norm;
+    int32_t  iterations;
+    int64_t  step;
+    float    dt, dx;
+};                                     /* 64 bytes: offsets 0, 4, 8, 12, 16, 40, 44, 48, 56, 60 */
+/* Start a history of members [first, first + count): `capacity` samples of count records are allocated on the device
+ * and the history's step count is set to 0.  Called while a history is on, it starts afresh: the samples are dropped,
+ * the count is 0 again, and the device buffer is reallocated only if it must grow.  b NULL, every < 1, capacity < 1 (or
+ * so large that the samples' bytes do not fit a size_t), count < 1 and a range that is not inside the batch return
+ * SFL_ERR_INVALID; a failed allocation returns SFL_ERR_NOMEM and leaves the batch without a history.                    */
+SFL_API int sfl_batch_history_start(sfl_batch *b, int every, int first, int count, int capacity);
+/* Stop the history and free the samples (sfl_batch_destroy frees them too).  Without a history: SFL_OK.                  */
+SFL_API int sfl_batch_history_stop(sfl_batch *b);
+/* Samples written so far, the capacity, and the steps counted since the start; all 0 without a history.  Any out
+ * pointer may be NULL.  Never waits.                                                                                    */
+SFL_API int sfl_batch_history_info(sfl_batch *b, int *samples, int *capacity, int64_t *steps);
+/* Copy members [first, first + count) of samples [first_sample, first_sample + samples) out, sample-major: record
+ * [s][m] at host[s * count + m].  The numbers are the batch's member numbers and must lie inside the recorded range.
+ * Samples are not consumed.  Synchronous.  No history: SFL_ERR_STATE.  b NULL, host NULL (bytes > 0), first_sample or
+ * samples < 0, a sample range that is not inside the samples written, count < 1, a member range that is not inside the
+ * recorded one and bytes != samples * count * 64 return SFL_ERR_INVALID.                                                */
+SFL_API int sfl_batch_history_read(sfl_batch *b, int first_sample, int samples, int first, int count,
+                                   struct sfl_history_record *host, size_t bytes);
+/* The same for a whole-domain context: one record per sample, bytes == samples * 64.  A sample is the passes of
+ * sfl_flow_stats and sfl_residual launched on the context's stream and pointed at the record; the words the host knows
+ * (what, iterations, step, dt, dx) are merged in when the records are read.                                             */
+SFL_API int sfl_history_start(sfl_context *ctx, int every, int capacity);
+SFL_API int sfl_history_stop(sfl_context *ctx);
+SFL_API int sfl_history_info(sfl_context *ctx, int *samples, int *capacity, int64_t *steps);
+SFL_API int sfl_history_read(sfl_context *ctx, int first_sample, int samples, struct sfl_history_record *host,
+                             size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
