@@ -251,6 +251,9 @@ SIGNATURES = {
     "sfl_history_stop": (_i, [_ctx]),
     "sfl_history_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64)]),
     "sfl_history_read": (_i, [_ctx, _i, _i, C.POINTER(HistoryRecord), _sz]),
+    "sfl_batch_set_solids": (_i, [_ctx, C.POINTER(C.c_uint8), _i]),
+    "sfl_batch_solids_info": (_i, [_ctx, _pi, _pi]),
+    "sfl_batch_solids_download": (_i, [_ctx, _i, _i, C.POINTER(C.c_uint8), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

@@ -191,6 +191,47 @@ __device__ __forceinline__ float2 project_cell(float2 u, const float *q, int str
                         [=](int a, int b) { return q[(b - gj) * stride + (a - i)]; });
 }
 
+// ---- solid cells inside a grid (include/sfl.h "SOLIDS"; batch_solids.hip) -------------------------------------------
+// One code byte per cell says everything a stencil needs to know: bit 0 W, 1 E, 2 S, 3 N neighbour PRESENT (inside the
+// domain and fluid), bit 4 the cell itself is fluid; a solid cell's byte is 0.  A set neighbour bit implies that the
+// neighbour is inside the domain, so a stencil keyed on the byte reads nothing outside the field.
+constexpr int kSolidW = 1, kSolidE = 2, kSolidS = 4, kSolidN = 8, kSolidFluid = 16, kSolidAll = 15;
+
+// The stencils above know "absent" as "outside the domain": (i > 0), (i < i_max), (gj > 0), (gj < j_max).  A code byte says
+// the same through coordinates made for the purpose -- a cell at i = 1 or 0 (W present or not) of a row that ends at i + 1
+// or i (E present or not), and so for the rows -- so the ONE statement of each stencil serves solids too, and the kernels
+// that exist keep their instructions.
+struct SolidSpot {
+    int i, gj, i_max, j_max;
+};
+__device__ __forceinline__ SolidSpot solid_spot(int code)
+{
+    SolidSpot t;
+    t.i = (code & kSolidW) ? 1 : 0;
+    t.gj = (code & kSolidS) ? 1 : 0;
+    t.i_max = t.i + ((code & kSolidE) ? 1 : 0);
+    t.j_max = t.gj + ((code & kSolidN) ? 1 : 0);
+    return t;
+}
+
+// divergence_sum with "absent" read from the code byte: all four present div_expr_fast, otherwise div_expr_safe with an
+// absent neighbour's term the cell's own component (ghost velocity = -own); a solid cell has no divergence (0.0f)
+__device__ __forceinline__ float divergence_sum_solid(const float2 *q, int stride, int code)
+{
+    if (!(code & kSolidFluid)) return 0.0f;
+    const SolidSpot t = solid_spot(code);
+    return divergence_sum(q, stride, t.i, t.gj, t.i_max, t.j_max);
+}
+
+// project_cell with "absent" read from the code byte: an absent neighbour's pressure is the cell's own; a solid cell's
+// velocity is (0, 0).  q points at the cell's pressure, rows `stride` apart.
+__device__ __forceinline__ float2 project_cell_solid(float2 u, const float *q, int stride, int code, float two_dx_inv)
+{
+    if (!(code & kSolidFluid)) return make_float2(0.0f, 0.0f);
+    const SolidSpot t = solid_spot(code);
+    return project_cell(u, q, stride, t.i, t.gj, t.i_max, t.j_max, two_dx_inv);
+}
+
 struct uq3 {
     uint32_t x, y, z;
 };

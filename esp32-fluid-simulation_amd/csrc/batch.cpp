@@ -20,7 +20,7 @@ void release(sfl_batch *b)
                     b->d_forces, (void *)b->d_members, (void *)b->d_report, (void *)b->d_counts, (void *)b->d_image,
                     (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env,
                     (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
-                    (void *)b->d_rec_palette, b->history.d_records})
+                    (void *)b->d_rec_palette, b->history.d_records, (void *)b->solids.d_codes})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
     if (b->h_dist) (void)hipHostFree(b->h_dist);
@@ -214,11 +214,12 @@ enum StepKind { kUniform, kEach, kUntil };
 // recorder on, such a call is cut into launches that end at the steps whose frame is due, the render between them.
 // With a following set of tracers (tracers_follow) every step is a launch of its own, the advance behind it: the tracers
 // read each step's projected velocity, which the launch of several steps never stores.  A history (history_step) cuts
-// the call as the recorder does: its sample reads the fields of the step it is due after.
+// the call as the recorder does: its sample reads the fields of the step it is due after.  With solid cells set
+// (b->solids; solids.cpp) every step is a launch of its own too, made through the batch's pointer.
 int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
 {
     SFL_TRY(stage_timeline(b, n));
-    if (kind != kUntil && !b->large && n >= 2 && !b->tracers_follow && staged_has(b, 1, n)) {
+    if (kind != kUntil && !b->large && n >= 2 && !b->tracers_follow && !b->solids.set && staged_has(b, 1, n)) {
         for (int done = 0; done < n;) {
             const int steps = sfl::host::history_run(b->history, sfl::host::record_run(b, n - done));   // (cut at either's due steps)
             sfl::BatchPlay play{};
@@ -246,7 +247,9 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
         a.step.v_out = b->vel_tmp;
         a.step.col_in = b->col;
         a.step.col_out = b->col_tmp;
-        if (kind == kUniform)
+        if (b->solids.set)   // (never kUntil, never large: refused at the call and at sfl_batch_set_solids)
+            SFL_TRY(b->solids.step(b, kind == kEach, a));
+        else if (kind == kUniform)
             HIP_TRY((b->large ? sfl::launch_batch_large_step : sfl::launch_batch_step)(b->stream, a, b->batch));
         else if (kind == kEach)
             HIP_TRY((b->large ? sfl::launch_batch_large_step_each : sfl::launch_batch_step_each)(b->stream, a, b->batch, b->d_members, b->d_report));
@@ -384,12 +387,23 @@ int flow_stats(sfl_batch *b, int what, float dx, bool each, const sfl_member_par
         HIP_TRY(hipMemcpyAsync(b->d_stats + b->batch, scale, sizeof(float) * (size_t)b->batch, hipMemcpyHostToDevice, b->stream));
         d_scale = reinterpret_cast<const float *>(b->d_stats + b->batch);
     }
-    HIP_TRY(sfl::launch_flow_stats(b->stream, b->d_stats, what, b->vel, b->col, b->dim_x, b->dim_y, b->batch, two_dx_inv(dx), d_scale));
+    if (b->solids.set && (what & SFL_STATS_VELOCITY)) {   // the records zeroed and the dye pass as ever, the velocity pass by the solids' rule
+        HIP_TRY(sfl::launch_flow_stats(b->stream, b->d_stats, what & SFL_STATS_DYE, b->vel, b->col, b->dim_x, b->dim_y, b->batch, two_dx_inv(dx), d_scale));
+        SFL_TRY(b->solids.stats(b, two_dx_inv(dx), d_scale));
+    } else
+        HIP_TRY(sfl::launch_flow_stats(b->stream, b->d_stats, what, b->vel, b->col, b->dim_x, b->dim_y, b->batch, two_dx_inv(dx), d_scale));
     HIP_TRY(hipMemcpyAsync(b->h_stats + first, b->d_stats + first, (size_t)count * sizeof(struct sfl_flow_stats), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     memcpy(host, b->h_stats + first, (size_t)count * sizeof(struct sfl_flow_stats));
     for (int k = 0; k < count; ++k) host[k].what = (uint32_t)what;
     return SFL_OK;
+}
+
+// the *_until calls of a batch with solid cells: refused whole (include/sfl.h "SOLIDS"), nothing staged or launched
+int refuse_until(const char *call)
+{
+    return fail(SFL_ERR_STATE, "%s: the batch has solid cells set (sfl_batch_set_solids) and the solve to a tolerance does not know them: "
+                "nothing stepped or solved; use the _each call, or clear the solids with sfl_batch_set_solids(b, NULL, 0)", call);
 }
 
 // what both constructors do once their limits have passed: the device, the stream, the six zeroed fields
@@ -585,6 +599,7 @@ int sfl_batch_poisson_solve(sfl_batch *b, float dx, int iters, float omega)
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     SFL_TRY(use_device(b));
     b->report_valid = b->counts_valid = false;
+    if (b->solids.set) return b->solids.solve(b, false, iters, sor_params(dx, omega));
     HIP_TRY((b->large ? sfl::launch_batch_large_solve : sfl::launch_batch_solve)(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch,
                                                                                  iters, sor_params(dx, omega)));
     return SFL_OK;
@@ -617,8 +632,11 @@ int sfl_batch_poisson_solve_each(sfl_batch *b, const sfl_member_params *params)
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
     b->report_valid = b->counts_valid = false;
-    HIP_TRY((b->large ? sfl::launch_batch_large_solve_each : sfl::launch_batch_solve_each)(b->stream, b->p, b->div, b->dim_x, b->dim_y,
-                                                                                           b->batch, b->d_members, b->d_report));
+    if (b->solids.set)
+        SFL_TRY(b->solids.solve(b, true, 0, sfl::SorParams{}));
+    else
+        HIP_TRY((b->large ? sfl::launch_batch_large_solve_each : sfl::launch_batch_solve_each)(b->stream, b->p, b->div, b->dim_x, b->dim_y,
+                                                                                               b->batch, b->d_members, b->d_report));
     b->report_valid = true;
     return SFL_OK;
 }
@@ -627,6 +645,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
 {
     SFL_TRY(check_members(b, params, stops));
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
+    if (b->solids.set) return refuse_until("sfl_batch_step_n_until");
     if (n == 0) return SFL_OK;
     SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
     SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
@@ -647,6 +666,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
 int sfl_batch_poisson_solve_until(sfl_batch *b, const sfl_member_params *params, const sfl_member_stop *stops)
 {
     SFL_TRY(check_members(b, params, stops));
+    if (b->solids.set) return refuse_until("sfl_batch_poisson_solve_until");
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params, stops));
     b->report_valid = b->counts_valid = false;

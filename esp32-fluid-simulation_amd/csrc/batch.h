@@ -95,6 +95,31 @@ struct BatchPlay {
 };
 hipError_t launch_batch_play(hipStream_t s, const BatchPlay &a, int batch, const BatchMember *members, float *report);
 
+// ---- members with solid cells inside their grids (batch_solids.hip; include/sfl.h "SOLIDS") --------------------------
+// One code byte per cell (advect_math.h: bits 0..3 W, E, S, N neighbour present, bit 4 the cell is fluid, a solid cell's
+// byte 0), member-major like the fields: member m's bytes start at codes + m * member_stride, member_stride = dim_x * dim_y,
+// or 0 for one mask that all members share.  Formed by the host from the user's mask (solids.cpp), consistent with the
+// shape: a set neighbour bit never points outside the member.
+struct BatchSolids {
+    const uint8_t *codes;
+    size_t member_stride;
+};
+// launch_batch_step[_each] and launch_batch_solve[_each] by the rule of include/sfl.h "SOLIDS", for the batches of
+// sfl_batch_create (16 B of LDS per cell); report[m] = the update norm over member m's FLUID cells.  Same arguments
+// otherwise; with no solid cell in a member, the same results bit for bit.
+hipError_t launch_batch_solid_step(hipStream_t s, const BatchStep &a, const BatchSolids &solids, int batch);
+hipError_t launch_batch_solid_step_each(hipStream_t s, const BatchStep &a, const BatchSolids &solids, int batch,
+                                        const BatchMember *members, float *report);
+hipError_t launch_batch_solid_solve(hipStream_t s, float *p, const float *d, const BatchSolids &solids, int dim_x, int dim_y,
+                                    int batch, int iters, SorParams prm);
+hipError_t launch_batch_solid_solve_each(hipStream_t s, float *p, const float *d, const BatchSolids &solids, int dim_x, int dim_y,
+                                         int batch, const BatchMember *members, float *report);
+// The velocity part of launch_flow_stats (stats_kernels.h) with the divergence of the rule's item 4: atomic maxima into
+// out[m], which the caller has zeroed on the stream in front.
+struct FlowStatsRecord;
+hipError_t launch_solid_velocity_stats(hipStream_t s, FlowStatsRecord *out, const float *v, const BatchSolids &solids, int dim_x,
+                                       int dim_y, int members, float two_dx_inv, const float *member_two_dx_inv);
+
 // ---- the draw task of many members in one launch (batch_render.hip) -----------------------------------------------
 // Image k of `images` (k in [0, count), member-major: image k starts at pixel k * H * W, H = scaling * (dim_x - 1) rows of
 // W = scaling * (dim_y - 1) uint16) = launch_render_rgb565 of the dye at colour_of_first_member + 3 * k * dim_x * dim_y,

@@ -106,6 +106,21 @@ struct sfl_batch {
     uint32_t *d_rec_palette = nullptr;
     std::vector<uint32_t> rec_palette_host;
     int (*record_view_frame)(sfl_batch *b, uint16_t *images) = nullptr;
+    // solid cells (solids.cpp; include/sfl.h "SOLIDS"): the code bytes on the device (batch.h BatchSolids: `batch` x cells of
+    // them, or cells for a mask all members share), freed by the destroy path.  Plain data, as the history is and for the
+    // same reason; while `set`, the step, solve and statistics calls of batch.cpp launch through the three pointers, which
+    // solids.cpp sets and clears with it -- cleared, those calls launch exactly what they launched before there were solids.
+    struct Solids {
+        bool set = false, per_member = false;
+        uint8_t *d_codes = nullptr;
+        size_t d_bytes = 0;
+        // one step is due: launch it (each: by the records of d_members, and the update norm into d_report)
+        int (*step)(sfl_batch *b, bool each, const sfl::BatchStep &a) = nullptr;
+        // the solve of d into p (each: as above; else iters and prm)
+        int (*solve)(sfl_batch *b, bool each, int iters, sfl::SorParams prm) = nullptr;
+        // the velocity part of the flow statistics into d_stats, zeroed in front on the stream
+        int (*stats)(sfl_batch *b, float two_dx_inv, const float *d_member_two_dx_inv) = nullptr;
+    } solids;
 };
 
 namespace sfl {

@@ -47,6 +47,17 @@ int check_handle(sfl_batch *b, const char *call)
     return SFL_OK;
 }
 
+// a sample's divergence and update norm are those of a grid without solid cells (include/sfl.h "SOLIDS"): a batch that has
+// solids set starts no history (a running one is left as it is)
+int check_solids(sfl_context *, const char *) { return SFL_OK; }
+int check_solids(sfl_batch *b, const char *call)
+{
+    if (b->solids.set)
+        return fail(SFL_ERR_STATE, "%s: the batch has solid cells set (sfl_batch_set_solids) and a history's samples do not know them: "
+                    "no history started; clear the solids first (sfl_batch_set_solids(b, NULL, 0))", call);
+    return SFL_OK;
+}
+
 struct sfl_history_record *slot(const History &h, int sample) { return static_cast<struct sfl_history_record *>(h.d_records) + (size_t)sample * h.count; }
 
 // counts `steps` steps (one launch: history_run saw to it that no sample falls inside them); the sample that is due now, or -1
@@ -125,6 +136,7 @@ int start(H *x, int every, int first, int count, int capacity, const char *call)
     const Holder o = holder_of(x);
     if (first < 0 || (int64_t)first + count > o.members)
         return fail(SFL_ERR_INVALID, "%s: members [%d, %d + %d) are not inside the batch's [0, %d)", call, first, first, count, o.members);
+    SFL_TRY(check_solids(x, call));
     HIP_TRY(hipSetDevice(o.device));
     History &h = *o.h;
     // (samples of the history that ends here may still be in flight: they are ahead of the new ones on the stream)

@@ -95,6 +95,15 @@ int check_range(const char *call, sfl_batch *b, int first, int count)
         return fail(SFL_ERR_INVALID, "%s: members [%d, %d + %d) are not inside the batch's [0, %d)", call, first, first, count, b->batch);
     return SFL_OK;
 }
+// the divergence view is calculate_divergence of a grid without solid cells (include/sfl.h "SOLIDS"): refused on a batch
+// that has solids set, after the call's own argument checks
+int check_solids(const char *call, const sfl_batch *b, int what)
+{
+    if (what == SFL_VIEW_DIVERGENCE && b->solids.set)
+        return fail(SFL_ERR_STATE, "%s: the batch has solid cells set (sfl_batch_set_solids) and the divergence view does not know them; "
+                    "sfl_batch_flow_stats reports the divergence by the solids' rule, the other views work as ever", call);
+    return SFL_OK;
+}
 int check_bytes(const char *call, const Holder &h, size_t elem, const char *of, size_t bytes)
 {
     const size_t want = (size_t)h.fields.count * h.cells * elem;
@@ -241,6 +250,7 @@ int sfl_batch_view_scalar(sfl_batch *b, int what, float dx, int first, int count
     SFL_TRY(check_range(call, b, first, count));
     const Holder h = holder_of(b, first, count);
     SFL_TRY(check_bytes(call, h, sizeof(float), "scalars", bytes));
+    SFL_TRY(check_solids(call, b, what));
     if (count == 0) return SFL_OK;
     if (!host) return fail(SFL_ERR_INVALID, "%s: host is NULL", call);
     return scalar(h, what, dx, host, bytes);
@@ -264,6 +274,7 @@ int sfl_batch_view_texels(sfl_batch *b, const struct sfl_view *view, int first, 
     SFL_TRY(check_range(call, b, first, count));
     const Holder h = holder_of(b, first, count);
     SFL_TRY(check_bytes(call, h, 3 * sizeof(uint32_t), "texels", bytes));
+    SFL_TRY(check_solids(call, b, view->what));
     if (count == 0) return SFL_OK;
     if (!host) return fail(SFL_ERR_INVALID, "%s: host is NULL", call);
     return texels(h, view, host, bytes);
@@ -290,6 +301,7 @@ int sfl_batch_view_render_members(sfl_batch *b, const struct sfl_view *view, int
     SFL_TRY(check_range(call, b, first, count));
     const Holder h = holder_of(b, first, count);
     SFL_TRY(check_image_bytes(call, h, scaling, bytes));
+    SFL_TRY(check_solids(call, b, view->what));
     if (count == 0) return SFL_OK;
     if (!host_images) return fail(SFL_ERR_INVALID, "%s: host_images is NULL", call);
     return render(h, view, scaling, byteswap, host_images, bytes);
@@ -305,6 +317,7 @@ int sfl_batch_record_view(sfl_batch *b, const struct sfl_view *view)
         b->rec.view_on = false;
         return SFL_OK;
     }
+    SFL_TRY(check_solids(call, b, view->what));
     HIP_TRY(hipSetDevice(b->device));
     if (!b->d_rec_palette) SFL_TRY(device_alloc((void **)&b->d_rec_palette, sizeof(uint32_t) * sfl::kViewPaletteWords, "the recorder's palette"));
     // The copy is ordered on the stream behind the frames that read the palette it replaces.  Its source is the batch's

@@ -920,6 +920,36 @@ class BatchSolver(_Tracers, _History):
         record_start and record_stop reset it to the dye.  The view is copied: it may be dropped after the call."""
         capi.check(self._lib.sfl_batch_record_view(self._h, None if view is None else C.byref(view.struct())))
 
+    def set_solids(self, mask):
+        """Solid cells inside the members' grids (include/sfl.h "SOLIDS"): `mask` a bool or uint8 array, nonzero = solid,
+        of shape ``(dim_y, dim_x)`` -- one mask for all members -- or ``(batch, dim_y, dim_x)``; None clears the solids.
+        No field is touched.  Batches of small members only; step_n, step_n_each, poisson_solve[_each] and flow_stats
+        then follow the solids' rule, the ``_until`` calls, histories and the divergence view are refused while set."""
+        if mask is None:
+            capi.check(self._lib.sfl_batch_set_solids(self._h, None, 0))
+            return
+        mask = np.asarray(mask)
+        if mask.dtype != np.bool_ and mask.dtype != np.uint8:
+            raise ValueError(f"solids: a bool or uint8 mask, got {mask.dtype}")
+        if mask.shape not in ((self.dim_y, self.dim_x), (self.batch, self.dim_y, self.dim_x)):
+            raise ValueError(f"solids: shape {mask.shape}, want {(self.dim_y, self.dim_x)} or {(self.batch, self.dim_y, self.dim_x)}")
+        m = np.ascontiguousarray(mask != 0, dtype=np.uint8)
+        capi.check(self._lib.sfl_batch_set_solids(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), int(m.ndim == 3)))
+
+    def solids_info(self):
+        """(set, per_member) as the library reports it."""
+        s, p = C.c_int(0), C.c_int(0)
+        capi.check(self._lib.sfl_batch_solids_info(self._h, C.byref(s), C.byref(p)))
+        return bool(s.value), bool(p.value)
+
+    def solids(self, first: int = 0, count=None) -> np.ndarray:
+        """The masks of members [first, first + count), bool[count, dim_y, dim_x]: all False without solids, a shared
+        mask repeated.  Synchronous."""
+        count = self.batch - first if count is None else count
+        a = np.zeros((max(count, 0), self.dim_y, self.dim_x), np.uint8)
+        capi.check(self._lib.sfl_batch_solids_download(self._h, first, count, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.nbytes))
+        return a.astype(bool)
+
     def synchronize(self):
         capi.check(self._lib.sfl_batch_synchronize(self._h))
 

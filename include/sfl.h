@@ -1003,6 +1003,58 @@ SFL_API int sfl_history_stop(sfl_context *ctx);
 SFL_API int sfl_history_info(sfl_context *ctx, int *samples, int *capacity, int64_t *steps);
 SFL_API int sfl_history_read(sfl_context *ctx, int first_sample, int samples, struct sfl_history_record *host,
                              size_t bytes);
+/* --- SOLIDS: solid cells inside the grid of a batch member.  A mask marks cells as solid; every other cell is fluid.  The
+ *     rule below extends the reference's wall rule inward -- a solid neighbour is one more reason for a neighbour to be
+ *     absent -- and is a definition stated here, like the vorticity's: the reference knows no wall but the rim of its grid.
+ *     A neighbour of a cell is PRESENT when it is inside the domain and fluid.  With no solid cell the rule's step is
+ *     sfl_batch_step_n's bit for bit; a grid whose outer ring is solid computes in its inner cells, bit for bit, the
+ *     divergence, the solve and the gradient of the plain grid of those inner cells (the ring shifts (i, j) by (1, 1): the
+ *     colouring is kept), and so a whole step at dt = 0.
+ *   ONE STEP, in the order of sfl_step:
+ *     1. velocity advection  unchanged, advect(..., no_slip) on EVERY cell, reading the velocity as it stands: no special
+ *                            sampling near a solid.  Solid nodes hold zero velocity; the bilinear gather decays towards them.
+ *     2. forces              in queue order, unchanged.
+ *     3. zero the solids     after 1 and 2 the velocity of every solid cell is (0, 0): a force record on a solid cell has no
+ *                            effect.
+ *     4. divergence          of a fluid cell with all four neighbours present ((-W.x + E.x) + (-S.y + N.y)) * k; otherwise
+ *                            0.0f plus the four terms in the order W, E, S, N, then * k, an absent neighbour's term being the
+ *                            cell's own component with the ghost's sign: own.x for W, -own.x for E, own.y for S, -own.y for
+ *                            N.  k = 1.0f / (2.0f * dx).  A solid cell's divergence is 0.0f.
+ *     5. pressure            p = 0 everywhere; solid cells are never updated and never read.  A fluid cell relaxes as in
+ *                            sfl_poisson_solve with `present` counting its present neighbours: the sum is
+ *                            (((z + W) + E) + S) + N with -0.0f for an absent neighbour, z = -0.0f iff present == 4, else
+ *                            +0.0f; p_gs = k * (dx * d - sum) with k = -0.25f, (float)(-1.0 / 3.0), -0.5f, -1.0f for present
+ *                            = 4, 3, 2, 1 and k = 0.0f for present == 0 (a fluid cell walled in on all sides: the one case no
+ *                            plain grid can produce); p = (1 - omega) * p + omega * p_gs.  The colour of a cell is (i + j) & 1
+ *                            of the domain's coordinates, even first.
+ *     6. gradient            of a fluid cell: an absent neighbour's pressure is the cell's own.  A solid cell's velocity stays
+ *                            (0, 0), its pressure 0.
+ *     7. dye                 unchanged, on every cell, with the projected velocity: a solid cell traces back to itself and
+ *                            keeps its colour (less the UQ32 round trip of the first step).  Paint obstacles by uploading dye.
+ *   TWO DIAGNOSTICS follow the rule.  The update norm of the _each calls (sfl_batch_residual) is the maximum over FLUID cells
+ * of |p_gs - p| with the k, z and sum of item 5; a member without a fluid cell reports 0.0f.  max_abs_div of
+ * sfl_batch_flow_stats[_each] is the maximum over all cells of item 4's divergence of the velocity held.
+ *   WHICH CALLS HONOUR SOLIDS: sfl_batch_step_n, sfl_batch_step_n_each, sfl_batch_poisson_solve,
+ * sfl_batch_poisson_solve_each and sfl_batch_flow_stats[_each], on a batch made by sfl_batch_create.  While solids are set a
+ * step call runs one launch per step, as with following tracers, also where it would have replayed a timeline in one launch;
+ * the results are the same either way.  Everything that forms neither a divergence nor a pressure works unchanged: render,
+ * recorder, envelope, distance, tracers, and the speed, vorticity and pressure views -- the vorticity view reads the zero
+ * velocity of solid cells through its ordinary stencil.
+ *   REFUSED WHOLE with SFL_ERR_STATE, each with its own message: sfl_batch_set_solids on a batch of sfl_batch_create_large;
+ * sfl_batch_step_n_until and sfl_batch_poisson_solve_until, sfl_batch_history_start and SFL_VIEW_DIVERGENCE (the view calls
+ * and sfl_batch_record_view) while solids are set; sfl_batch_set_solids with a mask while a history is on or the recorder
+ * draws the divergence view.  A call's own argument checks come first, and nothing is staged or launched by a refused call. */
+/* Set the solids: mask = dim_y * dim_x bytes shared by all members (per_member 0), or batch * dim_y * dim_x bytes, member-
+ * major (per_member 1); cell (i, j) at dim_x * j + i, nonzero = solid.  The mask is read during the call only.  mask NULL
+ * clears the solids: the batch then launches exactly what it launched before they were set.  No field is touched -- a
+ * velocity or a pressure already held by a cell that becomes solid goes with the next step (items 3 and 5).  Synchronous.
+ * b NULL and per_member outside 0..1 return SFL_ERR_INVALID.                                                             */
+SFL_API int sfl_batch_set_solids(sfl_batch *b, const uint8_t *mask, int per_member);
+/* Whether solids are set, and whether per member.  Either out pointer may be NULL.  Never waits.                         */
+SFL_API int sfl_batch_solids_info(sfl_batch *b, int *set, int *per_member);
+/* The masks of members [first, first + count) as bytes 0 / 1, member-major (a shared mask: repeated; no solids: zeros);
+ * bytes must be count * dim_y * dim_x.  Synchronous.                                                                     */
+SFL_API int sfl_batch_solids_download(sfl_batch *b, int first, int count, uint8_t *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
