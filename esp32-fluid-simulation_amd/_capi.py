@@ -254,6 +254,9 @@ SIGNATURES = {
     "sfl_batch_set_solids": (_i, [_ctx, C.POINTER(C.c_uint8), _i]),
     "sfl_batch_solids_info": (_i, [_ctx, _pi, _pi]),
     "sfl_batch_solids_download": (_i, [_ctx, _i, _i, C.POINTER(C.c_uint8), _sz]),
+    "sfl_set_solids": (_i, [_ctx, C.POINTER(C.c_uint8)]),
+    "sfl_solids_info": (_i, [_ctx, _pi, C.POINTER(C.c_int64)]),
+    "sfl_solids_download": (_i, [_ctx, C.POINTER(C.c_uint8), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

@@ -13,6 +13,7 @@
 //   slab_step.cpp     sfl_step / sfl_step_n, the automatic advection halo of a slab's step
 //   host_dropin.cpp   the host-pointer drop-ins (sfl_host_*) and their per-thread context
 //   tracers.cpp       points that move with the flow (sfl_tracers_*, sfl_batch_tracers_*): sets, advances, samples, trails
+//   context_solids.cpp solid cells of a whole-domain context (sfl_set_solids, _solids_info, _solids_download) and the masked launches
 //
 // There is deliberately no CPU compute path in any of them: every operator ends in a kernel launch and fails with
 // SFL_ERR_HIP when no device is usable.
@@ -257,6 +258,28 @@ struct ViewScratch {
     size_t out_bytes = 0;
 };
 
+// Solid cells of a whole-domain context (context_solids.cpp; include/sfl.h "SOLIDS OF A CONTEXT"): what the context holds
+// of them.  Plain data, as TracerSet and History and for the same reason: sfl_destroy frees the code bytes, and the
+// calls that honour solids live in units that the host test harnesses link without context_solids.cpp -- they reach
+// the masked launches through these pointers, set there while a mask is set and null otherwise (then every call
+// launches exactly what it launched before there were solids).
+struct ContextSolids {
+    bool set = false;
+    uint8_t *d_codes = nullptr;   // one code byte per cell (solids.cpp solid_codes), dim_x * gdim_y of them
+    size_t d_bytes = 0;
+    int64_t solid_cells = 0;      // of the mask that is set (sfl_solids_info)
+    // one step by the rule, behind sfl_step's checks: the unfused sequence (no seams, no small-grid step)
+    int (*step)(sfl_context *c, float dt, float dx, int iters, float omega) = nullptr;
+    int (*divergence)(sfl_context *c, float dx) = nullptr;
+    // warm: `iters` more iterations on the pressure held instead of a solve from zero
+    int (*solve)(sfl_context *c, float dx, int iters, float omega, bool warm) = nullptr;
+    int (*gradient)(sfl_context *c, float dx) = nullptr;
+    // the masked update norm / max |divergence| of the fields held, as bits into a device word (launches only; the word
+    // is zeroed on the stream in front)
+    int (*norm)(sfl_context *c, float dx, unsigned *d_word) = nullptr;
+    int (*max_div)(sfl_context *c, float two_dx_inv, unsigned *d_word) = nullptr;
+};
+
 }  // namespace host
 }  // namespace sfl
 
@@ -375,6 +398,7 @@ struct sfl_context {
     // nobody yet: count it and, when a sample is due, launch the statistics' passes on the context's stream)
     sfl::host::History history;
     int (*history_step)(sfl_context *c, float dt, float dx, int iters) = nullptr;
+    sfl::host::ContextSolids solids;   // solid cells (context_solids.cpp)
 
     sfl::host::Options opt;  // what sfl_set_option stores (kOptions above: one row per option)
 

@@ -35,6 +35,8 @@ int sfl_flow_stats(sfl_context *ctx, int what, float dx, struct sfl_flow_stats *
     const float two_dx_inv = 1.0f / (2.0f * dx);  // finitediff.cpp:36
     sfl::FlowStatsRecord *rec = reinterpret_cast<sfl::FlowStatsRecord *>(ctx->d_stats);
     HIP_TRY(sfl::launch_flow_stats(ctx->stream, rec, what, ctx->vel, ctx->col, ctx->dim_x, ctx->gdim_y, 1, two_dx_inv, nullptr));
+    if ((what & SFL_STATS_VELOCITY) && ctx->solids.max_div)   // solid cells set: max_abs_div by item 4 of their rule
+        SFL_TRY(ctx->solids.max_div(ctx, two_dx_inv, &rec->max_abs_div));
     HIP_TRY(hipMemcpyAsync(ctx->h_stats, ctx->d_stats, sizeof(struct sfl_flow_stats), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *out = *ctx->h_stats;

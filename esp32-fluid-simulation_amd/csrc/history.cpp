@@ -110,7 +110,12 @@ int step_context(sfl_context *c, float dt, float dx, int iters)
     const float two_dx_inv = 1.0f / (2.0f * dx);  // finitediff.cpp:36
     HIP_TRY(sfl::launch_flow_stats(c->stream, reinterpret_cast<sfl::FlowStatsRecord *>(rec), SFL_STATS_VELOCITY | SFL_STATS_DYE, c->vel, c->col,
                                    c->dim_x, c->gdim_y, 1, two_dx_inv, nullptr));
-    HIP_TRY(sfl::launch_update_norm(c->stream, reinterpret_cast<unsigned *>(&rec->update_norm), c->p, c->div, c->geom, c->g0, c->g1, dx));
+    // (solid cells set: the divergence and the norm by their rule, as sfl_flow_stats and sfl_residual report them)
+    if (c->solids.max_div) SFL_TRY(c->solids.max_div(c, two_dx_inv, &reinterpret_cast<sfl::FlowStatsRecord *>(rec)->max_abs_div));
+    if (c->solids.norm)
+        SFL_TRY(c->solids.norm(c, dx, reinterpret_cast<unsigned *>(&rec->update_norm)));
+    else
+        HIP_TRY(sfl::launch_update_norm(c->stream, reinterpret_cast<unsigned *>(&rec->update_norm), c->p, c->div, c->geom, c->g0, c->g1, dx));
     h.host_words[(size_t)sample] = History::HostWords{iters, h.steps, dt, dx};
     h.written = sample + 1;
     return SFL_OK;

@@ -361,6 +361,7 @@ int sfl_calculate_divergence(sfl_context *ctx, float dx)
     if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
     SFL_TRY(settle_color(ctx, true));
     SFL_TRY(check_wait_error(ctx));
+    if (ctx->solids.divergence) return ctx->solids.divergence(ctx, dx);   // solid cells set: item 4 of their rule
     std::vector<sfl_context *> peers = peers_of(ctx);
     for (sfl_context *c : peers) {
         SFL_TRY(ensure_field(c, SFL_FIELD_VELOCITY));
@@ -381,6 +382,10 @@ int sfl_poisson_solve(sfl_context *ctx, float dx, int iters, float omega)
     if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
     SFL_TRY(settle_color(ctx, true));
     SFL_TRY(check_wait_error(ctx));
+    if (ctx->solids.solve) {   // solid cells set: item 5 of their rule, from p = 0
+        if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
+        return ctx->solids.solve(ctx, dx, iters, omega, false);
+    }
     return run_poisson(ctx, dx, iters, omega);
 }
 
@@ -389,6 +394,7 @@ int sfl_subtract_gradient(sfl_context *ctx, float dx)
     if (!ctx) return fail(SFL_ERR_INVALID, "ctx is NULL");
     SFL_TRY(settle_color(ctx, true));
     SFL_TRY(check_wait_error(ctx));
+    if (ctx->solids.gradient) return ctx->solids.gradient(ctx, dx);   // solid cells set: item 6 of their rule
     std::vector<sfl_context *> peers = peers_of(ctx);
     for (sfl_context *c : peers) {
         SFL_TRY(ensure_field(c, SFL_FIELD_VELOCITY));

@@ -11,6 +11,7 @@ namespace host {
 // `iters` more iterations on the pressure the context holds
 static int continue_poisson(sfl_context *ctx, float dx, int iters, float omega)
 {
+    if (ctx->solids.solve) return ctx->solids.solve(ctx, dx, iters, omega, true);   // solid cells set: their rule's iterations
     if (!small_grid(ctx)) return run_poisson(ctx, dx, iters, omega, true);
     SFL_TRY(ensure_field(ctx, SFL_FIELD_DIVERGENCE));
     SFL_TRY(ensure_field(ctx, SFL_FIELD_PRESSURE));
@@ -31,7 +32,10 @@ static int read_update_norm(sfl_context *c, float dx, float *norm)
     SFL_TRY(ensure_field(c, SFL_FIELD_DIVERGENCE));
     SFL_TRY(ensure_field(c, SFL_FIELD_PRESSURE));
     SFL_TRY(use_device(c));
-    HIP_TRY(sfl::launch_update_norm(c->stream, c->d_norm, c->p, c->div, c->geom, c->g0, c->g1, dx));
+    if (c->solids.norm)   // solid cells set: the maximum over the fluid cells
+        SFL_TRY(c->solids.norm(c, dx, c->d_norm));
+    else
+        HIP_TRY(sfl::launch_update_norm(c->stream, c->d_norm, c->p, c->div, c->geom, c->g0, c->g1, dx));
     HIP_TRY(hipMemcpyAsync(c->h_norm, c->d_norm, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     memcpy(norm, c->h_norm, sizeof *norm);
@@ -46,7 +50,9 @@ static int run_poisson_until(sfl_context *ctx, float dx, int cap, float omega, f
 {
     float u = 0.0f;
     int k = 0, launches = 0;
-    if (small_grid(ctx)) {
+    // (solid cells set: the host loop on every grid, over the masked solve and the masked norm)
+    const auto from_zero = [&](int iters) { return ctx->solids.solve ? ctx->solids.solve(ctx, dx, iters, omega, false) : run_poisson(ctx, dx, iters, omega); };
+    if (small_grid(ctx) && !ctx->solids.solve) {
         SFL_TRY(ensure_field(ctx, SFL_FIELD_DIVERGENCE));
         SFL_TRY(ensure_field(ctx, SFL_FIELD_PRESSURE));
         SFL_TRY(use_device(ctx));
@@ -61,12 +67,12 @@ static int run_poisson_until(sfl_context *ctx, float dx, int cap, float omega, f
         launches = 1;
         ctx->last_fuse = 2 * k;
     } else if (tol < 0.0f) {
-        SFL_TRY(run_poisson(ctx, dx, cap, omega));
+        SFL_TRY(from_zero(cap));
         launches = ctx->last_launches;
         k = cap;
         SFL_TRY(read_update_norm(ctx, dx, &u));
     } else {
-        SFL_TRY(run_poisson(ctx, dx, 0, omega));   // p = 0 (poisson.cpp:117-119): what the check at k = 0 sees
+        SFL_TRY(from_zero(0));   // p = 0 (poisson.cpp:117-119): what the check at k = 0 sees
         for (;;) {
             SFL_TRY(read_update_norm(ctx, dx, &u));
             if (k >= cap || !(u > tol)) break;   // !(u > tol): u <= tol, or u is a NaN

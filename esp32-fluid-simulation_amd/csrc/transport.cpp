@@ -571,10 +571,20 @@ static int attach_rccl(sfl_context *c, const ncclUniqueId &uid, bool self)
     return rc;
 }
 
+// solid cells live on whole-domain contexts that exchange nothing (include/sfl.h "SOLIDS OF A CONTEXT"): after the call's own checks
+static int no_solids(const sfl_context *c, const char *what)
+{
+    if (c->solids.set)
+        return fail(SFL_ERR_STATE, "the context has solid cells set (sfl_set_solids) and no halo exchange knows them: %s is refused, nothing attached "
+                    "or linked; clear the solids first (sfl_set_solids(ctx, NULL))", what);
+    return SFL_OK;
+}
+
 int sfl_comm_attach(sfl_context *c, const void *id, size_t id_bytes)
 {
     if (!c || !id || id_bytes < sizeof(ncclUniqueId)) return fail(SFL_ERR_INVALID, "bad arguments");
     if (c->transport) return fail(SFL_ERR_STATE, "context already has a transport");
+    SFL_TRY(no_solids(c, "a transport"));
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof uid);
     return attach_rccl(c, uid, false);
@@ -584,6 +594,7 @@ int sfl_comm_emulate(sfl_context *c)
 {
     if (!c) return fail(SFL_ERR_INVALID, "ctx is NULL");
     if (c->transport) return fail(SFL_ERR_STATE, "context already has a transport");
+    SFL_TRY(no_solids(c, "a transport"));
     if (c->nranks < 2) return fail(SFL_ERR_STATE, "a whole-domain context has nothing to exchange");
     Overlap o;   // the exchange stream exists from here on, not from the first solve on (see sfl_context::xstream)
     SFL_TRY(overlap_of(c, &o));
@@ -595,6 +606,7 @@ int sfl_comm_emulate_rccl(sfl_context *c)
 {
     if (!c) return fail(SFL_ERR_INVALID, "ctx is NULL");
     if (c->transport) return fail(SFL_ERR_STATE, "context already has a transport");
+    SFL_TRY(no_solids(c, "a transport"));
     if (c->nranks < 2) return fail(SFL_ERR_STATE, "a whole-domain context has nothing to exchange");
     ncclUniqueId uid;
     NCCL_TRY(ncclGetUniqueId(&uid));
@@ -634,6 +646,7 @@ int sfl_group_link(sfl_context **ctxs, int n)
             c->dim_x != ctxs[0]->dim_x || c->gdim_y != ctxs[0]->gdim_y || c->transport)
             return fail(SFL_ERR_INVALID, "ctxs[%d] is not slab %d of %d on the group's device", r, r, n);
     }
+    for (int r = 0; r < n; ++r) SFL_TRY(no_solids(ctxs[r], "a group"));
     auto g = std::make_shared<Group>();
     g->members.assign(ctxs, ctxs + n);
     HIP_TRY(hipSetDevice(ctxs[0]->device));

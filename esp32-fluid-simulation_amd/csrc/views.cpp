@@ -104,6 +104,14 @@ int check_solids(const char *call, const sfl_batch *b, int what)
                     "sfl_batch_flow_stats reports the divergence by the solids' rule, the other views work as ever", call);
     return SFL_OK;
 }
+// ... and on a context that has solids set (include/sfl.h "SOLIDS OF A CONTEXT")
+int check_solids(const char *call, const sfl_context *c, int what)
+{
+    if (what == SFL_VIEW_DIVERGENCE && c->solids.set)
+        return fail(SFL_ERR_STATE, "%s: the context has solid cells set (sfl_set_solids) and the divergence view does not know them; "
+                    "sfl_flow_stats reports the divergence by the solids' rule, the other views work as ever", call);
+    return SFL_OK;
+}
 int check_bytes(const char *call, const Holder &h, size_t elem, const char *of, size_t bytes)
 {
     const size_t want = (size_t)h.fields.count * h.cells * elem;
@@ -238,6 +246,7 @@ int sfl_view_scalar(sfl_context *ctx, int what, float dx, float *host, size_t by
     const Holder h = holder_of(ctx);
     SFL_TRY(check_bytes(call, h, sizeof(float), "scalars", bytes));
     if (!host) return fail(SFL_ERR_INVALID, "%s: host is NULL", call);
+    SFL_TRY(check_solids(call, ctx, what));
     SFL_TRY(settle(ctx, what));
     return scalar(holder_of(ctx), what, dx, host, bytes);   // (settling may have swapped the context's buffers)
 }
@@ -263,6 +272,7 @@ int sfl_view_texels(sfl_context *ctx, const struct sfl_view *view, uint32_t *hos
     SFL_TRY(check_handle(call, ctx));
     SFL_TRY(check_bytes(call, holder_of(ctx), 3 * sizeof(uint32_t), "texels", bytes));
     if (!host) return fail(SFL_ERR_INVALID, "%s: host is NULL", call);
+    SFL_TRY(check_solids(call, ctx, view->what));
     SFL_TRY(settle(ctx, view->what));
     return texels(holder_of(ctx), view, host, bytes);
 }
@@ -288,6 +298,7 @@ int sfl_view_render(sfl_context *ctx, const struct sfl_view *view, int scaling, 
     SFL_TRY(check_handle(call, ctx));
     SFL_TRY(check_image_bytes(call, holder_of(ctx), scaling, bytes));
     if (!host_image) return fail(SFL_ERR_INVALID, "%s: host_image is NULL", call);
+    SFL_TRY(check_solids(call, ctx, view->what));
     SFL_TRY(settle(ctx, view->what));
     return render(holder_of(ctx), view, scaling, byteswap, host_image, bytes);
 }

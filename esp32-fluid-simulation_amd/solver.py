@@ -556,6 +556,36 @@ class Solver(_Tracers, _History):
         capi.check(self._lib.sfl_view_render(self._h, C.byref(view.struct()), scaling, int(byteswap), _u16p(img), img.nbytes))
         return img
 
+    # -- solid cells ---------------------------------------------------------------------
+    def set_solids(self, mask):
+        """Solid cells inside the grid (include/sfl.h "SOLIDS OF A CONTEXT"): `mask` a bool or uint8 array of shape
+        ``(dim_y, dim_x)``, nonzero = solid; None clears the solids.  No field is touched.  Whole-domain contexts
+        without a transport, at any grid size; step, step_n, calculate_divergence, poisson_solve, poisson_continue,
+        poisson_solve_until, subtract_gradient, residual, flow_stats and histories then follow the solids' rule -- the
+        rule of :meth:`BatchSolver.set_solids`, bit for bit -- and the divergence view is refused while set."""
+        if mask is None:
+            capi.check(self._lib.sfl_set_solids(self._h, None))
+            return
+        mask = np.asarray(mask)
+        if mask.dtype != np.bool_ and mask.dtype != np.uint8:
+            raise ValueError(f"solids: a bool or uint8 mask, got {mask.dtype}")
+        if mask.shape != (self.dim_y, self.dim_x):
+            raise ValueError(f"solids: shape {mask.shape}, want {(self.dim_y, self.dim_x)}")
+        m = np.ascontiguousarray(mask != 0, dtype=np.uint8)
+        capi.check(self._lib.sfl_set_solids(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def solids_info(self):
+        """(set, solid_cells) as the library reports it."""
+        s, n = C.c_int(0), C.c_int64(0)
+        capi.check(self._lib.sfl_solids_info(self._h, C.byref(s), C.byref(n)))
+        return bool(s.value), n.value
+
+    def solids(self) -> np.ndarray:
+        """The mask, bool[dim_y, dim_x]: all False without solids.  Synchronous."""
+        a = np.zeros((self.dim_y, self.dim_x), np.uint8)
+        capi.check(self._lib.sfl_solids_download(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.nbytes))
+        return a.astype(bool)
+
     def synchronize(self):
         capi.check(self._lib.sfl_synchronize(self._h))
 

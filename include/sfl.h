@@ -1055,6 +1055,46 @@ SFL_API int sfl_batch_solids_info(sfl_batch *b, int *set, int *per_member);
 /* The masks of members [first, first + count) as bytes 0 / 1, member-major (a shared mask: repeated; no solids: zeros);
  * bytes must be count * dim_y * dim_x.  Synchronous.                                                                     */
 SFL_API int sfl_batch_solids_download(sfl_batch *b, int first, int count, uint8_t *host, size_t bytes);
+/* --- SOLIDS OF A CONTEXT: the same solid cells inside the grid of a whole-domain context, at any grid size.  The rule is the
+ *     one of "SOLIDS" above, items 1 to 7, unchanged: one step of a context with solids set computes, bit for bit, what one
+ *     step of a batch member of the same shape with the same mask computes, and with no solid cell in the mask what the
+ *     context computes without one.
+ *   WHICH CALLS HONOUR SOLIDS while a mask is set:
+ *     sfl_step, sfl_step_n      items 1 to 7 as ONE UNFUSED SEQUENCE per step: the velocity advection and the forces as ever,
+ *                               the divergence by item 4 (the same pass stores (0, 0) into the solid cells' velocity, item 3),
+ *                               the solve by item 5, the gradient by item 6, the dye advection as ever.  No step seams
+ *                               (SFL_OPT_STEP_SEAMS), no fused advection + divergence or projection, and no one-launch step of
+ *                               a small grid (SFL_OPT_SMALL_GRID): those kernels derive their walls from coordinates.
+ *     sfl_calculate_divergence  item 4 on the velocity held.  An absent neighbour is never read, so what the solid cells'
+ *                               velocity holds does not matter; it is not touched.
+ *     sfl_poisson_solve         item 5, from p = 0.
+ *     sfl_poisson_continue      item 5's iterations on the pressure held.
+ *     sfl_subtract_gradient     item 6; writes (0, 0) into solid cells.
+ *     sfl_residual              the masked update norm: the maximum over the fluid cells, 0.0f when there is none.
+ *     sfl_poisson_solve_until   the rule of that call as a loop on the host over the two calls above, on grids of every size.
+ *     sfl_flow_stats            max_abs_div by item 4; the other figures as ever.
+ *     sfl_history_*             a sample's max_abs_div and update_norm are what sfl_flow_stats and sfl_residual return after
+ *                               the same step, so they follow the rule too.
+ *   The masked solve runs ceil(iters / 8) launches of a kernel of its own between the pressure and its ping-pong partner
+ * (sfl_last_solve_info reports them).  That kernel knows only the rule's arithmetic: SFL_OPT_SOR_FOLD, SFL_OPT_SOR_KERNEL,
+ * SFL_OPT_SOR_FUSE and SFL_OPT_SOR_ROWS have no effect while solids are set.
+ *   UNCHANGED: sfl_advect_velocity and sfl_advect_color called on their own, upload and download, render, sfl_distance,
+ * tracers, and the speed, vorticity and pressure views.
+ *   REFUSED WHOLE with SFL_ERR_STATE, each with its own message and with nothing staged or launched: sfl_set_solids with a
+ * mask on a slab (nranks != 1) or on a context that has a transport attached; sfl_comm_attach, sfl_comm_emulate,
+ * sfl_comm_emulate_rccl and sfl_group_link while solids are set; SFL_VIEW_DIVERGENCE through sfl_view_scalar, sfl_view_texels
+ * and sfl_view_render while solids are set.  A call's own argument checks come first.                                      */
+/* Set the solids: mask = dim_y * dim_x bytes, cell (i, j) at dim_x * j + i, nonzero = solid; read during the call only.
+ * mask NULL clears the solids: the context then launches exactly what it launched before they were set -- the one-launch
+ * step of a small grid, the fused kernels and the step seams included.  No field is touched -- a velocity or a pressure
+ * already held by a cell that becomes solid goes with the next step (items 3 and 5).  Synchronous.  ctx NULL returns
+ * SFL_ERR_INVALID.                                                                                                         */
+SFL_API int sfl_set_solids(sfl_context *ctx, const uint8_t *mask);
+/* Whether solids are set, and how many cells of the mask are solid (0 when none is set).  Either out pointer may be NULL.
+ * Never waits.                                                                                                             */
+SFL_API int sfl_solids_info(sfl_context *ctx, int *set, int64_t *solid_cells);
+/* The mask as bytes 0 / 1 (no solids: zeros); bytes must be dim_y * dim_x.  Synchronous.                                   */
+SFL_API int sfl_solids_download(sfl_context *ctx, uint8_t *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
