@@ -10,9 +10,16 @@ the library behind a Solver or a BatchSolver, or, for the CPU tests, another mod
 dicts of numpy arrays, compared bit for bit.
 
 A step is: advect the velocity, write the step's records, divergence, solve, subtract the gradient, advect the dye with the
-projected velocity, advance a following tracer set (include/sfl.h: sfl_step, the timeline rule, TRACERS)."""
+projected velocity, advance a following tracer set (include/sfl.h: sfl_step, the timeline rule, TRACERS).
+
+Solids and histories are subjects of their own (Subject(solids=True)): while a model holds a mask its step and its operators
+follow items 1 to 7 of "SOLIDS" through tests/solid_rule.py, and while it holds a history it appends one record per sample.  A
+call include/sfl.h refuses in the state the model is in changes nothing and returns {"refused": ERR_STATE}; the library's
+wrappers turn an SflError into the same dict, and the runner compares the state behind a refused op like any other.  The
+generator follows the same state from the op list alone (Gate) so that only the refusals it planted happen."""
 import numpy as np
 
+import solid_rule
 import tracer_rule
 import view_rule
 from conftest import assert_bit_equal, random_fields
@@ -21,6 +28,7 @@ from test_batch_params import gs_target, update_norm
 from test_batch_until import rule, sor_iteration
 from test_ensemble_gpu import envelope_yardstick
 from test_ensemble_gpu import yardstick as distance_yardstick
+from test_solids_gpu import mask_of
 
 FV, FC, FD, FP = 0, 1, 2, 3
 FIELDS = {FV: "velocity", FC: "colour", FD: "divergence", FP: "pressure"}
@@ -51,7 +59,57 @@ BATCH_WRITERS = ("upload", "step_n", "step_n_each", "step_n_until", "poisson_sol
                  "queue_forces", "forget_forces", "record_start", "record_view", "record_stop", "set_tracers", "envelope")
 BATCH_QUERIES = ("download", "flow_stats", "distance", "envelope_field", "residual", "iterations", "render_members",
                  "view_render_members", "frames", "forces_pending", "tracers")
-QUERIES = set(CONTEXT_QUERIES) | set(BATCH_QUERIES)
+# the solids' and the histories' calls: tuples of their own, dealt only to the subjects made with solids=True (a kind added
+# to the tuples above would reshuffle every sequence the other subjects have)
+SOLID_WRITERS = ("set_solids", "clear_solids", "history_start", "history_stop")
+SOLID_QUERIES = ("solids", "history")
+QUERIES = set(CONTEXT_QUERIES) | set(BATCH_QUERIES) | set(SOLID_QUERIES)
+# (36 ops a sequence: the deck of the solids' subjects leaves out three calls that touch neither a field nor a launch's path)
+SOLID_LEFT_OUT = ("queue_drags", "trail_stop", "last_solve_info")
+MASK_KINDS = ("one", "disc", "plate", "channel", "isolated", "all", "seeded", "empty")     # mask_of of tests/test_solids_gpu.py
+MIXED_KINDS = tuple(k for k in MASK_KINDS if k not in ("all", "empty"))                     # at least one solid and one fluid cell
+ERR_STATE, VIEW_DIVERGENCE, D_SOLID = -5, 3, 8      # SFL_ERR_STATE; SFL_VIEW_DIVERGENCE; iterations of one launch of the masked solve
+REFUSED = {"refused": np.int32(ERR_STATE)}
+# struct sfl_history_record (HISTORY_DTYPE of the package): field -> dtype
+HISTORY_FIELDS = {"max_abs_vx": np.float32, "max_abs_vy": np.float32, "max_abs_div": np.float32, "what": np.uint32, "dye_sum": np.uint64,
+                  "update_norm": np.float32, "iterations": np.int32, "step": np.int64, "dt": np.float32, "dx": np.float32}
+
+
+def solid_mask(kind, dim_x, dim_y, seed, member=None):
+    """The mask a set_solids op sets; per member: member k takes the k-th kind behind `kind` and its own seed."""
+    if member is not None:
+        kind, seed = MASK_KINDS[(MASK_KINDS.index(kind) + member) % len(MASK_KINDS)], seed + member
+    return mask_of(kind, dim_x, dim_y, seed)
+
+
+def mixed(mask):
+    return mask is not None and bool(mask.any()) and not bool(mask.all())
+
+
+def masked_rule(d, solid, dx, cap, omega, tol, every):
+    """`rule` of tests/test_batch_until.py with the solids' iterations and their update norm: (k, p of k iterations, u_k)."""
+    tol, p, k = np.float32(tol), np.zeros_like(d), 0
+    while k < cap:
+        if k % every == 0:
+            u = np.float32(solid_rule.update_norm(p, d, solid, dx))
+            if tol >= 0 and (u <= tol or np.isnan(u)):
+                return k, p, u
+        p = solid_rule.iterate(p, d, solid, dx, 1, omega)
+        k += 1
+    return k, p, np.float32(solid_rule.update_norm(p, d, solid, dx))
+
+
+def samples_due(hist, n):
+    """How many samples n more steps complete, and how many are free (include/sfl.h "COUNTING")."""
+    return (hist["steps"] + n) // hist["every"] - hist["steps"] // hist["every"], hist["capacity"] - len(hist["records"])
+
+
+def history_result(hist, shape):
+    recs = hist["records"]
+    out = {name: (np.stack([r[name] for r in recs]) if recs else np.zeros((0,) + shape + ((3,) if name == "dye_sum" else ()), dtype))
+           for name, dtype in HISTORY_FIELDS.items()}
+    out["info"] = np.array([len(recs), hist["capacity"], hist["steps"]], np.int64)
+    return out
 
 
 def texture(kind, field, dim_x, dim_y, seed):
@@ -118,12 +176,25 @@ class ContextModel:
         self.xy, self.follow, self.trail = None, False, None   # trail: [every, advances, [slots]]
         self.reach = 0.0                         # the longest back-trace along j (rows) of the advections of the last op
         self.peer = None                         # (a model used as a handle: the model it is compared with)
+        self.mask = None                         # the solids: None or bool[dim_y, dim_x]
+        self.hist = None                         # the history: {"every", "capacity", "steps", "records"}
 
     # -- plumbing
     def apply(self, op):
         kind, args = op
         self.reach = 0.0
+        if self.refuses(kind, args):             # refused whole: nothing changes
+            return dict(REFUSED)
         return getattr(self, ("q_" if kind in QUERIES else "do_") + kind)(**args)
+
+    def refuses(self, kind, a):
+        """Whether include/sfl.h refuses the call with SFL_ERR_STATE in the state the model is in."""
+        if self.mask is not None and kind in ("view_scalar", "view_texels") and a["what"] == VIEW_DIVERGENCE:
+            return True
+        if self.hist is not None and kind in ("step", "step_n"):
+            due, free = samples_due(self.hist, a.get("n", 1))
+            return due > free
+        return False
 
     def close(self):
         pass
@@ -161,12 +232,20 @@ class ContextModel:
         for (i, j), u in records:
             if 0 <= i < self.dim_x and 0 <= j < self.dim_y:
                 va[j, i] = u
-        self.d = self.o.divergence(va, dx)
         k, u = iters, None
-        if until is not None:
-            k, _, u = rule(self.d, dx, iters, omega, until[0], until[1])
-        self.p = self.o.poisson_solve(self.d, dx, k, omega)
-        self.v = self.o.subtract_gradient(va, self.p, dx)
+        if self.mask is not None:                # items 3 to 6 of "SOLIDS"; the records above stand between items 1 and 3
+            va[self.mask] = 0.0
+            self.d = solid_rule.divergence(va, self.mask, dx)
+            if until is not None:
+                k, _, u = masked_rule(self.d, self.mask, dx, iters, omega, until[0], until[1])
+            self.p = solid_rule.solve(self.d, self.mask, dx, k, omega)
+            self.v = np.ascontiguousarray(solid_rule.gradient(va, self.p, self.mask, dx))
+        else:
+            self.d = self.o.divergence(va, dx)
+            if until is not None:
+                k, _, u = rule(self.d, dx, iters, omega, until[0], until[1])
+            self.p = self.o.poisson_solve(self.d, dx, k, omega)
+            self.v = self.o.subtract_gradient(va, self.p, dx)
         self.c = self._advect(self.c, dt, False)
         if self.follow and self.xy is not None:
             self._advance(dt)
@@ -187,29 +266,71 @@ class ContextModel:
         self.c = self._advect(self.c, dt, no_slip)
 
     def do_calculate_divergence(self, dx):
-        self.d = self.o.divergence(self.v, dx)
+        if self.mask is not None:                # 0 in solid cells; the velocity is not touched
+            self.d = solid_rule.divergence(self.v, self.mask, dx)
+        else:
+            self.d = self.o.divergence(self.v, dx)
 
     def do_poisson_solve(self, dx, iters, omega):
-        self.p = self.o.poisson_solve(self.d, dx, iters, omega)
+        if self.mask is not None:                # from p = 0
+            self.p = solid_rule.solve(self.d, self.mask, dx, iters, omega)
+        else:
+            self.p = self.o.poisson_solve(self.d, dx, iters, omega)
 
     def do_poisson_continue(self, dx, iters, omega):
+        if self.mask is not None:                # solid cells keep what they hold
+            self.p = solid_rule.iterate(self.p, self.d, self.mask, dx, iters, omega)
+            return
         for _ in range(iters):
             self.p = sor_iteration(self.p, self.d, dx, omega)
 
     def do_poisson_solve_until(self, dx, iters, omega, tol, every):
-        k, _, u = rule(self.d, dx, iters, omega, tol, every)
-        self.p = self.o.poisson_solve(self.d, dx, k, omega)
+        if self.mask is not None:
+            k, _, u = masked_rule(self.d, self.mask, dx, iters, omega, tol, every)
+            self.p = solid_rule.solve(self.d, self.mask, dx, k, omega)
+        else:
+            k, _, u = rule(self.d, dx, iters, omega, tol, every)
+            self.p = self.o.poisson_solve(self.d, dx, k, omega)
         return as_result(iterations=np.int32(k), norm=np.float32(u))
 
     def do_subtract_gradient(self, dx):
-        self.v = self.o.subtract_gradient(self.v, self.p, dx)
+        if self.mask is not None:                # (0, 0) in solid cells
+            self.v = np.ascontiguousarray(solid_rule.gradient(self.v, self.p, self.mask, dx))
+        else:
+            self.v = self.o.subtract_gradient(self.v, self.p, dx)
+
+    def history_record(self, step, dt, dx, iterations):
+        """One sfl_history_record of the fields as they stand: what flow_stats and residual return, and the step's words."""
+        out = dict(self.q_flow_stats(dx), what=np.uint32(3), update_norm=self.q_residual(dx)["norm"], iterations=np.int32(iterations),
+                   step=np.int64(step), dt=np.float32(dt), dx=np.float32(dx))
+        return {name: np.asarray(out[name], dtype) for name, dtype in HISTORY_FIELDS.items()}
+
+    def _counted_step(self, dt, dx, iters, omega):
+        k, _ = self.step_once(dt, dx, iters, omega)
+        if self.hist is not None:
+            self.hist["steps"] += 1
+            if self.hist["steps"] % self.hist["every"] == 0:
+                self.hist["records"].append(self.history_record(self.hist["steps"], dt, dx, k))
 
     def do_step(self, dt, dx, iters, omega):
-        self.step_once(dt, dx, iters, omega)
+        self._counted_step(dt, dx, iters, omega)
 
     def do_step_n(self, n, dt, dx, iters, omega):
         for _ in range(n):
-            self.step_once(dt, dx, iters, omega)
+            self._counted_step(dt, dx, iters, omega)
+
+    # Setting or clearing a mask touches no field (include/sfl.h sfl_set_solids).
+    def do_set_solids(self, mask_kind, seed):
+        self.mask = solid_mask(mask_kind, self.dim_x, self.dim_y, seed)
+
+    def do_clear_solids(self):
+        self.mask = None
+
+    def do_history_start(self, every, capacity):
+        self.hist = {"every": every, "capacity": capacity, "steps": 0, "records": []}
+
+    def do_history_stop(self):
+        self.hist = None
 
     # The timeline rule of include/sfl.h: "A step call of n steps consumes the records of steps [0, n).  Later records move down
     # by n.  This applies to sfl_step (n = 1), sfl_step_n, ..." and "Solves, uploads, setup and render calls neither consume nor
@@ -243,10 +364,23 @@ class ContextModel:
         return as_result(field=self.fields()[FIELDS[field]])
 
     def q_residual(self, dx):
+        if self.mask is not None:                # over the fluid cells; 0.0f without one
+            return as_result(norm=np.float32(solid_rule.update_norm(self.p, self.d, self.mask, dx)))
         return as_result(norm=np.float32(update_norm(self.p, self.d, dx)))
 
     def q_flow_stats(self, dx):
-        return stats_record(self.o, self.v, self.c, dx)
+        out = stats_record(self.o, self.v, self.c, dx)
+        if self.mask is not None:
+            with np.errstate(all="ignore"):
+                out["max_abs_div"] = np.asarray(np.max(np.abs(solid_rule.divergence(self.v, self.mask, dx))))
+        return out
+
+    def q_solids(self):
+        on = self.mask is not None
+        return as_result(mask=self.mask if on else np.zeros((self.dim_y, self.dim_x), bool), set=on, solid_cells=int(self.mask.sum()) if on else 0)
+
+    def q_history(self):
+        return history_result(self.hist, ())
 
     def q_view_scalar(self, what, dx):
         return as_result(scalar=view_rule.scalar(what, self.v, self.p, dx))
@@ -291,6 +425,10 @@ class ContextModel:
             out += [("sample_tracers", {"field": int(rng.integers(4)), "no_slip": bool(rng.integers(2))}), ("tracers", {})]
             if self.trail is not None:
                 out.append(("trail", {}))
+        if self.mask is not None:                # (the divergence view stays among them: refused, and nothing may move)
+            out.append(("solids", {}))
+        if self.hist is not None:
+            out.append(("history", {}))
         return out
 
 
@@ -308,10 +446,31 @@ class BatchModel:
         self.rec = None                          # the recorder: {"every", "first", "count", "scaling", "byteswap", "steps", "view", "frames"}
         self.env = None                          # the envelope's four fields
         self.peer = None
+        self.per_member = False                  # the solids: every member's model holds its mask (one shared, or its own)
+        self.hist = None                         # the history: {"every", "first", "count", "capacity", "steps", "records"}
 
     def apply(self, op):
         kind, args = op
+        if self.refuses(kind, args):             # refused whole: nothing changes
+            return dict(REFUSED)
         return getattr(self, ("q_" if kind in QUERIES else "do_") + kind)(**args)
+
+    def solids_set(self):
+        return self.m[0].mask is not None
+
+    def refuses(self, kind, a):
+        """Whether include/sfl.h refuses the call with SFL_ERR_STATE in the state the model is in ("SOLIDS", "HISTORIES")."""
+        if self.solids_set():
+            if kind in ("step_n_until", "poisson_solve_until", "history_start"):
+                return True
+            if kind in ("record_view", "view_render_members") and a["what"] == VIEW_DIVERGENCE:
+                return True
+        if kind == "set_solids" and (self.hist is not None or (self.rec is not None and self.rec["view"] == VIEW_DIVERGENCE)):
+            return True
+        if self.hist is not None and kind in ("step_n", "step_n_each", "step_n_until"):
+            due, free = samples_due(self.hist, a["n"])
+            return due > free
+        return False
 
     def close(self):
         pass
@@ -351,10 +510,17 @@ class BatchModel:
                 total[k] += last[k]
             if self.rec is not None:
                 self._frame()
+            if self.hist is not None:
+                h = self.hist
+                h["steps"] += 1
+                if h["steps"] % h["every"] == 0:
+                    members = range(h["first"], h["first"] + h["count"])
+                    recs = [self.m[k].history_record(h["steps"], dt[k], dx[k], last[k]) for k in members]
+                    h["records"].append({name: np.stack([r[name] for r in recs]) for name in HISTORY_FIELDS})
         return dx, np.stack([last, total], axis=1)
 
-    def _norms(self, dx):
-        self.norms = np.array([update_norm(m.p, m.d, dx[k]) for k, m in enumerate(self.m)], np.float32)
+    def _norms(self, dx):                        # (a member with a mask: over its fluid cells)
+        self.norms = np.array([m.q_residual(dx[k])["norm"] for k, m in enumerate(self.m)], np.float32)
 
     # -- writers
     def do_upload(self, field, texture_kind, seed):
@@ -416,6 +582,22 @@ class BatchModel:
     def do_envelope(self, first, count):
         self.env = envelope_yardstick(self._stack("colour")[first:first + count])
 
+    def do_set_solids(self, mask_kind, seed, per_member):
+        self.per_member = bool(per_member)
+        for k, m in enumerate(self.m):
+            m.mask = solid_mask(mask_kind, self.dim_x, self.dim_y, seed, k if per_member else None)
+
+    def do_clear_solids(self):
+        self.per_member = False
+        for m in self.m:
+            m.mask = None
+
+    def do_history_start(self, every, capacity, first, count):
+        self.hist = {"every": every, "first": first, "count": count, "capacity": capacity, "steps": 0, "records": []}
+
+    def do_history_stop(self):
+        self.hist = None
+
     # -- queries
     def q_download(self, field):
         return as_result(field=self._stack(FIELDS[field]))
@@ -457,6 +639,12 @@ class BatchModel:
     def q_tracers(self):
         return as_result(xy=np.stack([m.xy for m in self.m]))
 
+    def q_solids(self):
+        return as_result(mask=np.stack([m.q_solids()["mask"] for m in self.m]), set=self.solids_set(), per_member=self.per_member)
+
+    def q_history(self):
+        return history_result(self.hist, (self.hist["count"],))
+
     def queries(self, rng):
         out = [("download", {"field": int(rng.integers(4))}), ("flow_stats", {"dx": float(rng.choice(DXS))}),
                ("distance", {"ref_member": int(rng.integers(self.batch))}), ("forces_pending", {}),
@@ -467,6 +655,8 @@ class BatchModel:
         if self.iters is not None: out.append(("iterations", {}))
         if self.rec is not None: out.append(("frames", {}))
         if self.m[0].xy is not None: out.append(("tracers", {}))
+        if self.solids_set(): out.append(("solids", {}))
+        if self.hist is not None: out.append(("history", {}))
         return out
 
 
@@ -499,7 +689,10 @@ class LibraryContext:
 
     def apply(self, op):
         kind, args = op
-        return getattr(self, "g_" + kind)(**args)
+        try:
+            return getattr(self, "g_" + kind)(**args)
+        except self.sfl.capi.SflError as e:      # a refusal is a result like any other: the runner compares the state behind it
+            return as_result(refused=np.int32(e.code))
 
     def _cat(self, field):
         return np.concatenate([s.download(field) for s in self.slabs], axis=0)
@@ -533,6 +726,10 @@ class LibraryContext:
     def g_trail_start(self, every): self.s.trail_start(every, CAPACITY)
     def g_trail_stop(self): self.s.trail_stop()
     def g_set_option(self, name, value): self.s.set_option(getattr(self.sfl.capi, name), value)
+    def g_set_solids(self, mask_kind, seed): self.s.set_solids(solid_mask(mask_kind, self.dim_x, self.dim_y, seed))
+    def g_clear_solids(self): self.s.set_solids(None)
+    def g_history_start(self, every, capacity): self.s.history_start(every, capacity)
+    def g_history_stop(self): self.s.history_stop()
 
     def g_poisson_solve_until(self, dx, iters, omega, tol, every):
         k, u = self.s.poisson_solve_until(dx, iters, omega, tol=tol, every=every)
@@ -556,6 +753,14 @@ class LibraryContext:
     def g_sample_tracers(self, field, no_slip): return as_result(samples=self.s.sample_tracers(field, no_slip))
     def g_tracers(self): return as_result(xy=self.s.tracers())
     def g_trail(self): return as_result(slots=self.s.trail())
+
+    def g_solids(self):
+        on, cells = self.s.solids_info()
+        return as_result(mask=self.s.solids(), set=on, solid_cells=cells)
+
+    def g_history(self):
+        rec = self.s.history()
+        return dict({name: np.ascontiguousarray(rec[name]) for name in HISTORY_FIELDS}, info=np.array(self.s.history_info(), np.int64))
 
     def g_forces_pending(self):
         records, last = self.s.forces_pending()
@@ -584,7 +789,10 @@ class LibraryBatch:
 
     def apply(self, op):
         kind, args = op
-        return getattr(self, "g_" + kind)(**args)
+        try:
+            return getattr(self, "g_" + kind)(**args)
+        except self.sfl.capi.SflError as e:      # a refusal is a result like any other: the runner compares the state behind it
+            return as_result(refused=np.int32(e.code))
 
     def snapshot(self):
         out = as_result(**{name: self.b.download(f) for f, name in FIELDS.items()})
@@ -611,6 +819,14 @@ class LibraryBatch:
     def g_record_stop(self): self.b.record_stop()
     def g_set_tracers(self, xy, follow): self.b.set_tracers(np.array(xy, np.float32), follow)
     def g_envelope(self, first, count): self.b.envelope(first, count)
+    def g_clear_solids(self): self.b.set_solids(None)
+    def g_history_start(self, every, capacity, first, count): self.b.history_start(every, capacity, first, count)
+    def g_history_stop(self): self.b.history_stop()
+
+    def g_set_solids(self, mask_kind, seed, per_member):
+        members = range(self.batch) if per_member else [None]
+        masks = np.stack([solid_mask(mask_kind, self.dim_x, self.dim_y, seed, k) for k in members])
+        self.b.set_solids(masks if per_member else masks[0])
 
     def g_queue_forces(self, step, members, cells, vels):
         if step == 0:
@@ -629,6 +845,14 @@ class LibraryBatch:
     def g_frames(self): return as_result(frames=self.b.frames())
     def g_tracers(self): return as_result(xy=self.b.tracers())
 
+    def g_solids(self):
+        on, per_member = self.b.solids_info()
+        return as_result(mask=self.b.solids(), set=on, per_member=per_member)
+
+    def g_history(self):
+        rec = self.b.history()
+        return dict({name: np.ascontiguousarray(rec[name]) for name in HISTORY_FIELDS}, info=np.array(self.b.history_info(), np.int64))
+
     def g_forces_pending(self):
         records, last = self.b.forces_pending()
         return as_result(records=records, last_step=last)
@@ -638,9 +862,10 @@ class LibraryBatch:
 class Subject:
     """What a set of sequences runs on: `cases` = [(dim_x, dim_y, seed)], one sequence each."""
 
-    def __init__(self, name, kind, cases, options=(), nranks=1, batch=0, large=False, still_solves=False, length=30):
+    def __init__(self, name, kind, cases, options=(), nranks=1, batch=0, large=False, still_solves=False, length=30, solids=False):
         self.name, self.kind, self.cases, self.options, self.nranks, self.batch, self.large = name, kind, cases, tuple(options), nranks, batch, large
         self.still_solves, self.length = still_solves, length   # still_solves: steps on a lattice velocity run iters = 0 (it stays on the lattice)
+        self.solids = solids                                    # the solids' and the histories' calls are in the vocabulary
 
     def model(self, oracle, case):
         dim_x, dim_y, _ = case
@@ -655,7 +880,10 @@ class Subject:
         return LibraryContext(sfl, dim_x, dim_y, self.nranks, self.options)
 
     def kinds(self):
-        return {"context": CONTEXT_WRITERS + CONTEXT_QUERIES, "slabs": SLAB_WRITERS + SLAB_QUERIES, "batch": BATCH_WRITERS + BATCH_QUERIES}[self.kind]
+        own = {"context": CONTEXT_WRITERS + CONTEXT_QUERIES, "slabs": SLAB_WRITERS + SLAB_QUERIES, "batch": BATCH_WRITERS + BATCH_QUERIES}[self.kind]
+        if not self.solids:
+            return own
+        return tuple(k for k in own if k not in SOLID_LEFT_OUT) + SOLID_WRITERS + SOLID_QUERIES
 
     def option_values(self):
         return {"context": OPTION_VALUES, "slabs": SLAB_OPTION_VALUES, "batch": {}}[self.kind]
@@ -672,10 +900,85 @@ SUBJECTS = [
     Subject("slabs", "slabs", _cases(200, 131, 4, 400), nranks=3),
     Subject("small-batch", "batch", _cases(61, 81, 4, 500) + _cases(7, 9, 2, 550), batch=3),
     Subject("large-batch", "batch", _cases(96, 96, 4, 600), batch=2, large=True),
+    # solids and histories: a mask set, replaced and cleared on a handle that goes on stepping.  130 x 70 is 3 x 3 ragged tiles of
+    # the masked solve and, cleared, the general kernels and the step seams; 61 x 81 three tiles in a column and, cleared, the
+    # one-launch step of a small grid; the batch's members 61 x 81 and 7 x 9 (a large batch refuses solids)
+    Subject("solid-context", "context", _cases(130, 70, 3, 700) + _cases(61, 81, 2, 750), length=36, solids=True),
+    Subject("solid-batch", "batch", _cases(61, 81, 3, 800) + _cases(7, 9, 2, 850), batch=3, length=36, solids=True),
 ]
 
 
 # ---- the generator ---------------------------------------------------------------------------------------------------
+class Gate:
+    """What the generator and the census follow of a handle with solids and histories, from the op list alone: the masks, the
+    history's counts, the recorder's view, the trail and a batch's reports -- enough to say which calls include/sfl.h refuses
+    (the models decide the same from their own state; tests/test_sequences.py holds the two against each other)."""
+
+    def __init__(self, batch, dim_x, dim_y):
+        self.batch, self.dim_x, self.dim_y = batch, dim_x, dim_y
+        self.masks, self.hist = None, None                    # [mask] or one per member; [every, capacity, steps]
+        self.rec, self.view, self.trail = False, None, False
+        self.norms = self.iters = False
+
+    def mixed(self):
+        return self.masks is not None and any(mixed(m) for m in self.masks)
+
+    def remedy(self, kind, a):
+        """None when the header takes the call, else the kind of a call to make in its place: the one that ends what it is
+        refused for, or (the _until calls under a mask) its sibling that honours solids."""
+        on = self.masks is not None
+        if self.batch:
+            if on and kind in ("step_n_until", "poisson_solve_until"): return kind.replace("until", "each")
+            if on and kind == "history_start": return "clear_solids"
+            if on and kind in ("record_view", "view_render_members") and a["what"] == VIEW_DIVERGENCE: return "clear_solids"
+            if kind == "set_solids" and self.hist is not None: return "history_stop"
+            if kind == "set_solids" and self.rec and self.view == VIEW_DIVERGENCE: return "record_stop"
+        elif on and kind in ("view_scalar", "view_texels") and a["what"] == VIEW_DIVERGENCE:
+            return "clear_solids"
+        if self.hist is not None and kind in STEPS:
+            every, capacity, steps = self.hist
+            if (steps + a.get("n", 1)) // every - steps // every > capacity - steps // every: return "history_stop"
+        return None
+
+    def missing(self, kind):
+        """A query of something the handle does not hold now: the kind of the call that makes it."""
+        need = {"history": (self.hist is not None, "history_start"), "trail": (self.trail or self.batch > 0, "trail_start"),
+                "frames": (self.rec, "record_start"), "record_view": (self.rec, "record_start")}
+        if self.batch:
+            need.update(residual=(self.norms, "step_n_each"), iterations=(self.iters, "step_n_until"))
+        have, maker = need.get(kind, (True, None))
+        return None if have else maker
+
+    def after(self, kind, a):
+        """The state behind a call the header took."""
+        if kind == "set_solids":
+            members = range(self.batch) if a.get("per_member") else [None]
+            self.masks = [solid_mask(a["mask_kind"], self.dim_x, self.dim_y, a["seed"], k) for k in members]
+        if kind == "clear_solids": self.masks = None
+        if kind == "history_start": self.hist = [a["every"], a["capacity"], 0]
+        if kind == "history_stop": self.hist = None
+        if kind in STEPS and self.hist is not None: self.hist[2] += a.get("n", 1)
+        if kind == "record_start": self.rec, self.view = True, None
+        if kind == "record_view": self.view = a["what"]
+        if kind == "record_stop": self.rec, self.view = False, None
+        if kind == "trail_start": self.trail = True
+        if kind in ("trail_stop", "set_tracers"): self.trail = False
+        if self.batch:
+            if kind in ("step_n", "poisson_solve") or (kind == "upload" and a["field"] in (FD, FP)): self.norms = self.iters = False
+            if kind in ("step_n_each", "poisson_solve_each"): self.norms, self.iters = True, False
+            if kind in ("step_n_until", "poisson_solve_until"): self.norms = self.iters = True
+
+
+def gated(ops, subject, case):
+    """For the census of a subject with solids: (index, op, the Gate WHILE the op runs, whether the header refuses it)."""
+    gate = Gate(subject.batch, case[0], case[1])
+    for k, (kind, a) in enumerate(ops):
+        refused = gate.remedy(kind, a) is not None
+        yield k, (kind, a), gate, refused
+        if not refused:
+            gate.after(kind, a)
+
+
 class _Draw:
     """Literal arguments of one case's ops; it follows the little state the choice of valid arguments needs."""
 
@@ -685,6 +988,8 @@ class _Draw:
         self.lattice = False          # the velocity came from a landing / whole-cell upload: steps take dt = 0.25
         self.halo_fixed = False
         self.shadow = subject.model(oracle, case) if subject.kind == "slabs" else None   # slabs: the reach of every advection under a fixed halo
+        self.gate = Gate(subject.batch, self.dim_x, self.dim_y) if subject.solids else None
+        self.hints = {}
 
     def pick(self, values):
         v = values[int(self.rng.integers(len(values)))]
@@ -713,14 +1018,47 @@ class _Draw:
                 for _ in range(n)]
 
     def make(self, kind, **fixed):
-        """The op of `kind` with drawn arguments (those in `fixed` as given).  plan() has ordered the kinds so that it is valid here."""
+        """The op of `kind` with drawn arguments (those in `fixed` as given; a key that starts with "_" is a hint to the draw
+        and no argument).  plan() has ordered the kinds so that it is valid here."""
+        self.hints = {k: fixed.pop(k) for k in list(fixed) if k.startswith("_")}
         a = self._args(kind, self.sub.kind == "batch")
         a.update(fixed)
         op = (kind, a)
         if self.shadow is not None:
             op = self._under_the_halo(op)
+        if self.gate is not None:
+            op = self._give_way(op)
         self._follow(op)
         return op
+
+    def _give_way(self, op):
+        """Solids and histories: only the refusals that were planted happen.  Any other call the header would refuse in the
+        state the sequence has reached, and a query of what the handle does not hold, gives way to the call that ends the
+        cause (a mask cleared, a history stopped or started, a report written)."""
+        planted_refusal = self.hints.get("_refused", False)
+        for _ in range(4):
+            kind, a = op
+            instead = self.gate.missing(kind) or (None if planted_refusal else self.gate.remedy(kind, a))
+            if instead is None:
+                break
+            if a.get("what") == VIEW_DIVERGENCE and instead == "clear_solids":     # (another view will do)
+                op = (kind, dict(a, what=int(self.rng.integers(VIEW_DIVERGENCE))))
+                continue
+            self.hints, planted_refusal = {}, False
+            op = (instead, self._args(instead, self.sub.kind == "batch"))
+        if self.gate.remedy(*op) is None:
+            self.gate.after(*op)
+        return op
+
+    def cells_on(self, masks, members):
+        """One cell per entry of `members`, in turn a solid and a fluid cell of the member's mask (any cell where it has none)."""
+        out = []
+        for at, m in enumerate(members):
+            mask = masks[m if len(masks) > 1 else 0]
+            pool = np.argwhere(mask if at % 2 == 0 else ~mask)
+            j, i = pool[int(self.rng.integers(len(pool)))] if len(pool) else (int(self.rng.integers(self.dim_y)), int(self.rng.integers(self.dim_x)))
+            out.append([int(i), int(j)])
+        return out
 
     def _args(self, kind, batch):
         r, B = self.rng, self.sub.batch
@@ -738,6 +1076,22 @@ class _Draw:
                 a = dict({"n": int(r.integers(1, 5)), "dt": self.each(self.dt)}, **a)
             if kind.endswith("until"):
                 a.update(tol=self.each(lambda: self.pick(TOLS)), every=self.each(lambda: self.pick(EVERYS)))
+            return a
+        if kind == "queue_forces" and self.gate is not None and ("_mask" in self.hints or self.gate.masks is not None):
+            # with a mask in force (or, by the hint, about to be set): records on solid cells and on fluid ones
+            masks = [solid_mask(self.hints["_mask"][0], self.dim_x, self.dim_y, self.hints["_mask"][1])] if "_mask" in self.hints else self.gate.masks
+            n = int(r.integers(2, 4))
+            members = [int(r.integers(B)) for _ in range(n)] if batch else [0] * n
+            a = {"step": int(r.integers(0, 4)), "cells": self.cells_on(masks, members), "vels": self.vels(n)}
+            return dict(a, members=members) if batch else a
+        if kind == "set_solids":
+            a = {"mask_kind": self.pick(MIXED_KINDS), "seed": int(r.integers(100))}
+            return dict(a, per_member=bool(r.integers(2))) if batch else a
+        if kind == "history_start":
+            a = {"every": self.pick((1, 2, 3)), "capacity": self.pick((2, CAPACITY))}
+            if batch:
+                first = int(r.integers(B))
+                a.update(first=first, count=int(r.integers(1, B - first + 1)))
             return a
         if kind == "queue_forces":
             n = int(r.integers(1, 4))
@@ -832,7 +1186,53 @@ BATCH_HANDOVERS = {   # a call that runs one launch per step, a replay of the ti
 }
 
 
+def _link(kind, pred=None, **fixed): return (kind, fixed, pred)
+
+
+_DIV, _STEP2 = {"what": VIEW_DIVERGENCE}, _link("step_n", _n2)
+SOLID_HANDOVERS = {
+    "context": {
+        "set_solids -> step_n(n >= 2) -> set_solids (no clear) -> step -> clear_solids -> step_n(n >= 2)":
+            [_link("set_solids"), _STEP2, _link("set_solids"), _link("step"), _link("clear_solids"), _STEP2],
+        "clear_solids -> set_option(OPT_ADVECT_KERNEL, 2) -> step_n(n >= 2) -> set_solids -> step":
+            [_link("clear_solids"), _link("set_option", name="OPT_ADVECT_KERNEL", value=2), _STEP2, _link("set_solids"), _link("step")],
+        "clear_solids -> step -> set_solids -> poisson_solve -> clear_solids -> poisson_solve":
+            [_link("clear_solids"), _link("step"), _link("set_solids"), _link("poisson_solve"), _link("clear_solids"), _link("poisson_solve")],
+        "upload(pressure) -> set_solids -> poisson_continue(3) -> download(pressure) -> poisson_continue(9) -> residual -> poisson_solve_until":
+            [_link("upload", field=FP, texture_kind="noise"), _link("set_solids"), _link("poisson_continue", iters=3), _link("download", field=FP),
+             _link("poisson_continue", iters=9), _link("residual"), _link("poisson_solve_until")],
+        "queue_forces(step = 2) -> set_solids -> step_n(n = 2) -> step": [_link("queue_forces", step=2), _link("set_solids"), _link("step_n", n=2), _link("step")],
+        "set_tracers(follow) -> trail_start -> set_solids -> step_n(2) -> clear_solids -> step_n(2)":
+            [_link("set_tracers", follow=True), _link("trail_start"), _link("set_solids"), _link("step_n", n=2), _link("clear_solids"), _link("step_n", n=2)],
+        "history_start(every = 1) -> step -> set_solids -> step_n(2) -> history -> clear_solids -> step_n(2) -> history":
+            [_link("history_start", every=1), _link("step"), _link("set_solids"), _link("step_n", n=2), _link("history"), _link("clear_solids"),
+             _link("step_n", n=2), _link("history")],
+        "view_scalar(divergence), refused -> step": [_link("view_scalar", **_DIV), _link("step")],
+        "view_texels(divergence), refused -> step_n": [_link("view_texels", **_DIV), _link("step_n")],
+        "history_start(capacity = 2) -> step_n(3), refused -> step -> history": [_link("history_start", every=1, capacity=2), _link("step_n", n=3), _link("step"), _link("history")],
+    },
+    "batch": {
+        "set_solids -> step_n(n >= 2) -> set_solids (no clear) -> step_n -> clear_solids -> step_n(n >= 2)":
+            [_link("set_solids", per_member=False), _STEP2, _link("set_solids", per_member=True), _link("step_n"), _link("clear_solids"), _STEP2],
+        "queue_forces(step = 2) -> set_solids -> step_n(n = 2) -> step_n": [_link("queue_forces", step=2), _link("set_solids"), _link("step_n", n=2), _link("step_n", n=1)],
+        "set_tracers(follow) -> set_solids -> step_n(2) -> clear_solids -> step_n(2)":
+            [_link("set_tracers", follow=True), _link("set_solids"), _link("step_n", n=2), _link("clear_solids"), _link("step_n", n=2)],
+        "history_start -> set_solids, refused -> step_n -> history_stop -> set_solids -> history_start, refused -> step_n_each -> residual":
+            [_link("history_start"), _link("set_solids"), _link("step_n"), _link("history_stop"), _link("set_solids"), _link("history_start"),
+             _link("step_n_each"), _link("residual")],
+        "set_solids -> step_n_until, refused -> step_n -> poisson_solve_until, refused -> step_n_each":
+            [_link("set_solids"), _link("step_n_until"), _link("step_n"), _link("poisson_solve_until"), _link("step_n_each")],
+        "record_start -> set_solids -> record_view(divergence), refused -> step_n": [_link("record_start"), _link("set_solids"), _link("record_view", **_DIV), _link("step_n")],
+        "view_render_members(divergence), refused -> step_n": [_link("view_render_members", **_DIV), _link("step_n")],
+        "record_view(divergence) -> set_solids, refused -> step_n": [_link("record_view", **_DIV), _link("set_solids"), _link("step_n")],
+        "history_start(capacity = 2) -> step_n(3), refused -> step_n(1) -> history": [_link("history_start", every=1, capacity=2), _link("step_n", n=3), _link("step_n", n=1), _link("history")],
+    },
+}
+
+
 def handovers_of(subject):
+    if subject.solids:
+        return SOLID_HANDOVERS[subject.kind]
     if subject.kind == "batch":
         return BATCH_HANDOVERS
     return HANDOVERS if subject.kind == "context" else {k: HANDOVERS[k] for k in SLAB_HANDOVERS}
@@ -844,7 +1244,7 @@ def has_handover(ops, chain):
     return any(all(fits(ops[at + k], link) for k, link in enumerate(chain)) for at in range(len(ops) - len(chain) + 1))
 
 
-def _opt(name, value): return ("set_option", {"name": name, "value": value})
+def _opt(name, value, **hints): return ("set_option", dict({"name": name, "value": value}, **hints))
 def _up(texture_kind, field=FV): return ("upload", {"field": field, "texture_kind": texture_kind})
 
 
@@ -852,6 +1252,8 @@ def planted(subject):
     """The items the generator plants whole (the ops of an item stay next to each other): the hand-overs, and every option
     value in front of a writer it affects, so that no value is only ever set."""
     kind = subject.kind
+    if subject.solids:
+        return planted_solids(subject)
     if kind == "batch":
         pairs = [[(w, {}), (q, {})] for w, q in (("step_n_each", "residual"), ("poisson_solve_each", "residual"), ("step_n_each", "residual"),
                                                   ("step_n_until", "iterations"), ("poisson_solve_until", "iterations"), ("step_n_until", "iterations"))]
@@ -896,6 +1298,72 @@ def planted(subject):
     return items
 
 
+def _solid(mask_kind, **more): return ("set_solids", dict({"mask_kind": mask_kind}, **more))
+
+
+def planted_solids(subject):
+    """The items of the subjects with solids and histories.  A link may carry hints to the draw: "_refused" (the header
+    refuses the call here, on purpose), "_mask" (the mask the next link sets), "_shape" on an item's first link (the item goes
+    to a case of that shape).  Every item that needs the mask clear, the history off or nothing pending says so itself."""
+    clear, refused = ("clear_solids", {}), {"_refused": True}
+    div = dict(what=VIEW_DIVERGENCE, **refused)
+    if subject.kind == "context":
+        step, step2 = ("step", {}), ("step_n", {"n": 2})
+        return [
+            # a mask replaced without a clear in between, and cleared, on fields left as they are (no upload anywhere)
+            [_solid("disc"), step2, _solid("seeded"), step, clear, ("step_n", {"n": 3}), ("flow_stats", {})],
+            # cleared: the step seams run again (every condition of the seam set in front), then a mask again
+            [("forget_forces", {"_shape": (130, 70)}), ("history_stop", {}), ("set_tracers", {"follow": False}), clear, _opt("OPT_ADVECT_KERNEL", 2), step2,
+             _solid("plate"), step],
+            # cleared: the one-launch step of a small grid, and the small grid's solve behind a masked one
+            [_opt("OPT_SOR_KERNEL", 0, _shape=(61, 81)), _opt("OPT_SOR_FUSE", 0), _opt("OPT_ADVECT_KERNEL", 0), _opt("OPT_SMALL_GRID", 1), clear, step,
+             _solid("channel"), ("poisson_solve", {}), clear, ("poisson_solve", {}), ("residual", {})],
+            # a held pressure over one launch of the masked solve (it ends in the partner's buffer), then over two
+            [_up("noise", FP), _solid("seeded"), ("poisson_continue", {"iters": 3}), ("download", {"field": FP}), ("poisson_continue", {"iters": 9}),
+             ("residual", {}), ("poisson_solve_until", {})],
+            # a record queued for a later step on a solid cell and one on a fluid cell of the mask set behind it
+            [("forget_forces", {}), ("queue_forces", {"step": 2, "_mask": ("plate", 5)}), _solid("plate", seed=5), step2, step],
+            [("set_tracers", {"follow": True}), ("trail_start", {}), _solid("disc"), step2, clear, step2, ("trail", {})],
+            [("history_start", {"every": 1, "capacity": CAPACITY}), step, _solid("isolated"), step2, ("history", {}), clear, step2, ("history", {})],
+            # a full history refuses the call whole; the next one fits
+            [("history_start", {"every": 1, "capacity": 2}), ("step_n", dict(n=3, **refused)), step, ("history", {}), ("history_stop", {})],
+            # every mask kind in front of a step call, and under it every value of every option in front of a writer it
+            # would otherwise affect (no effect while solids are set); the divergence view refused in between
+            [_solid("one"), _opt("OPT_ADVECT_KERNEL", 1), ("calculate_divergence", {}), ("subtract_gradient", {}), _opt("OPT_ADVECT_KERNEL", 0), step],
+            [_solid("disc"), _opt("OPT_ADVECT_KERNEL", 2), ("calculate_divergence", {}), ("view_scalar", dict(div)), step, ("subtract_gradient", {}),
+             ("view_texels", dict(div)), step2],
+            [_solid("plate"), _opt("OPT_FUSE_DIVERGENCE", 0), _opt("OPT_FUSE_PROJECTION", 0), step, _opt("OPT_FUSE_DIVERGENCE", 1), _opt("OPT_FUSE_PROJECTION", 1)],
+            [_solid("channel"), _opt("OPT_STEP_SEAMS", 0), step2, _opt("OPT_STEP_SEAMS", 1), step2],
+            [_solid("isolated"), _opt("OPT_SMALL_GRID", 0), ("poisson_solve", {}), step, _opt("OPT_SMALL_GRID", 1), ("poisson_solve", {"iters": 0})],
+            [_solid("all"), _opt("OPT_SOR_KERNEL", 1), ("poisson_solve", {}), _opt("OPT_SOR_KERNEL", 2), ("poisson_continue", {}), _opt("OPT_SOR_KERNEL", 0), step],
+            [_solid("seeded"), _opt("OPT_SOR_FUSE", 2), ("poisson_solve", {}), _opt("OPT_SOR_FUSE", 16), ("poisson_solve_until", {}), _opt("OPT_SOR_FUSE", 0), step],
+            [_solid("empty"), step],
+        ]
+    s1, s2, sn = ("step_n", {"n": 1}), ("step_n", {"n": 2}), ("step_n", {})
+    again = ("set_solids", {})      # (an item that had to clear the mask sets one again: most of a sequence runs under a mask)
+    return [
+        [_solid("disc", per_member=False), s2, _solid("seeded", per_member=True), s1, clear, ("step_n", {"n": 3}), ("flow_stats", {}), again],
+        [("forget_forces", {}), ("queue_forces", {"step": 2, "_mask": ("plate", 5)}), _solid("plate", seed=5, per_member=False), s2, s1],
+        [("set_tracers", {"follow": True}), _solid("disc", per_member=True), s2, clear, s2, ("set_tracers", {"follow": False}), again],
+        [clear, ("history_start", {"capacity": CAPACITY}), _solid("one", **refused), sn, ("history_stop", {}), _solid("channel"),
+         ("history_start", dict(refused)), ("step_n_each", {}), ("residual", {})],
+        [_solid("one", per_member=True), ("step_n_until", dict(refused)), sn, ("poisson_solve_until", dict(refused)), ("step_n_each", {}), ("residual", {})],
+        # the recorder (the dye, then a view that is not the divergence) and the envelope next to a mask
+        [("record_start", {}), _solid("isolated", per_member=False), ("record_view", dict(div)), s2, ("frames", {}), ("record_view", {"what": 1}), s2, ("frames", {}),
+         ("view_render_members", dict(div)), sn, ("envelope", {}), ("envelope_field", {})],
+        [clear, ("record_start", {}), ("record_view", {"what": VIEW_DIVERGENCE}), _solid("disc", **refused), sn, ("record_view", {"what": None}), again],
+        [clear, ("history_start", {"every": 1, "capacity": 2, "first": 0, "count": 3}), ("step_n", dict(n=3, **refused)), s1, ("history", {}), ("history_stop", {}), again],
+        [clear, ("history_start", {"every": 1, "capacity": CAPACITY}), ("step_n_until", {}), ("iterations", {}), ("history", {}), ("step_n_each", {}), ("history", {}),
+         ("history_stop", {}), again, sn, ("poisson_solve", {})],
+        [_solid("all", per_member=False), ("step_n_each", {}), ("residual", {})], [_solid("empty", per_member=True), sn],
+        [_solid("seeded", per_member=False), ("poisson_solve", {}), ("poisson_solve_each", {}), ("residual", {}), ("flow_stats", {})],
+        [_solid("plate", per_member=True), ("step_n_each", {}), ("residual", {}), ("poisson_solve", {})],
+        [_solid("channel", per_member=True), ("poisson_solve_each", {}), ("residual", {}), s2],
+        [clear, ("poisson_solve_until", {}), ("iterations", {}), again, sn], [clear, ("step_n_until", {}), ("iterations", {}), again, ("step_n_each", {})],
+        [clear, ("poisson_solve_until", {}), ("iterations", {}), again, ("poisson_solve_each", {}), sn],
+    ]
+
+
 def _prologue(subject, index):
     """What every sequence starts with: fields and a tracer set with a trail; a batch a recording and an envelope."""
     common = [_up(("noise", "still", "fast", "whole-cell", "noise", "fast")[index % 6]), ("upload", {"field": FC})]
@@ -905,7 +1373,7 @@ def _prologue(subject, index):
     return common + ([("trail_start", {})] if subject.kind == "context" else [("record_start", {}), ("envelope", {})])
 
 
-NEEDS = {"trail": "trail", "frames": "rec", "record_view": "rec", "residual": "norms", "iterations": "iters"}
+NEEDS = {"trail": "trail", "frames": "rec", "record_view": "rec", "residual": "norms", "iterations": "iters", "history": "hist"}
 
 
 def _state_after(kind, fixed, st, batch):
@@ -915,6 +1383,8 @@ def _state_after(kind, fixed, st, batch):
     if kind in ("trail_stop", "set_tracers"): st["trail"] = False
     if kind == "record_start": st["rec"] = True
     if kind == "record_stop": st["rec"] = False
+    if kind == "history_start": st["hist"] = True
+    if kind == "history_stop": st["hist"] = False
     if batch:
         if kind in ("step_n", "poisson_solve") or (kind == "upload" and fixed.get("field") in (FD, FP)): st["norms"] = st["iters"] = False
         if kind in ("step_n_each", "poisson_solve_each"): st["norms"], st["iters"] = True, False
@@ -926,7 +1396,7 @@ def _settle(subject, index, items):
     """The sequence's items in an order in which every op is valid: a query that comes when what it reads is gone (a trail,
     a recording, a report) moves in front of the item that ended it -- the last moment it can be asked."""
     batch = subject.kind == "batch"
-    st = {"trail": True, "rec": True, "norms": not batch, "iters": False}      # (behind the prologue)
+    st = {"trail": True, "rec": True, "norms": not batch, "iters": False, "hist": False}      # (behind the prologue)
     out, ended_by = [], {}                       # ended_by: name -> the item (its position in out) that ended it
     for item in items:
         if len(item) == 1 and item[0][0] in NEEDS and not st[NEEDS[item[0][0]]] and NEEDS[item[0][0]] in ended_by:
@@ -941,6 +1411,15 @@ def _settle(subject, index, items):
             for name in [n for n in ended_by if st[n]]:
                 del ended_by[name]
     return [link for item in out for link in item]
+
+
+def _under_masks(items):
+    def leaves(item):           # True: the item leaves a mask set, False: it leaves none, None: it leaves what it found
+        ends = [kind == "set_solids" for kind, fixed in item if kind in ("set_solids", "clear_solids") and not fixed.get("_refused")]
+        return ends[-1] if ends else None
+    setters, clearers, others = ([item for item in items if leaves(item) is which] for which in (True, False, None))
+    part = lambda group, at: group[at * len(group) // len(setters):(at + 1) * len(group) // len(setters)]
+    return [x for at, item in enumerate(setters) for x in [item] + part(others, at) + part(clearers, at)]
 
 
 def plan(subject):
@@ -971,16 +1450,21 @@ def plan(subject):
     order = seam + [at for at in order if at not in seam]
     for turn, at in enumerate(order):                   # to the sequence with the most room left
         k = turn % len(room) if turn < len(seam) else int(np.argmax(room))
+        shape = items[at][0][1].get("_shape")           # (an item for one shape of the subject's: to the roomiest case of that shape)
+        if shape is not None:
+            k = max((c for c in range(len(room)) if subject.cases[c][:2] == shape), key=lambda c: room[c])
         assert room[k] >= len(items[at]), f"{subject.name}: the deck does not fit {len(subject.cases)} sequences of {subject.length}"
         dealt[k].append([(kind, dict(fixed)) for kind, fixed in items[at]])
         room[k] -= len(items[at])
-    writers = [k for k in subject.kinds() if k not in QUERIES and k not in ("set_option", "forget_forces", "trail_stop", "record_stop") and
+    writers = [k for k in subject.kinds() if k not in QUERIES and k not in ("set_option", "forget_forces", "trail_stop", "record_stop", "clear_solids", "history_stop") and
                not (subject.still_solves and k == "set_tracers")]
     plans = []
     for k, mine in enumerate(dealt):
         mine += [[(writers[int(rng.integers(len(writers)))], {})] for _ in range(room[k])]
         # the planted items anywhere in the sequence, not in front, and the reads spread evenly between the items that write
         mine = [mine[at] for at in rng.permutation(len(mine))]
+        if subject.solids:      # most of a sequence runs under a mask: the items that neither set nor clear one stand behind those that leave one set
+            mine = _under_masks(mine)
         loud = [item for item in mine if any(kind not in QUERIES and kind != "set_option" for kind, _ in item)]
         quiet = [item for item in mine if item not in loud]
         mine = [x for at, item in enumerate(loud) for x in [item] + quiet[at * len(quiet) // len(loud):(at + 1) * len(quiet) // len(loud)]]
@@ -1079,8 +1563,8 @@ def replay(model, handle, ops, mode, seed=0, label="", check_finite=False):
                     _ask(model, handle, op, f"query {op[0]}")
                 continue
             want, got = model.apply(op), handle.apply(op)
-            if want is not None:
-                compare(got, want, f"what {op[0]} returned")
+            if want is not None or got is not None:      # (a refusal on one side only is a disagreement)
+                compare({} if got is None else got, {} if want is None else want, f"what {op[0]} returned")
             if check_finite:
                 assert model.finite(), "the model holds a NaN or an Inf"
             if mode == "eager":
@@ -1155,6 +1639,55 @@ class ResidualLeavesItsTarget(ContextModel):
 
 
 STAND_INS = (ContinuesFromTheOldPressure, TimelineStaysAfterStepN, ResidualLeavesItsTarget)
+
+
+# ---- three more, for the state the solids add to a context --------------------------------------------------------------
+class ClearedSolidsStillWall(ContextModel):
+    """The first residual or flow_stats after clear_solids still follows the mask that was cleared (a stale hook)."""
+    stale = None
+
+    def apply(self, op):
+        kind = op[0]
+        if kind == "clear_solids":
+            self.stale = self.mask
+        if kind == "set_solids":
+            self.stale = None
+        if kind in ("residual", "flow_stats") and self.mask is None and self.stale is not None:
+            self.mask, self.stale = self.stale, None
+            try:
+                return super().apply(op)
+            finally:
+                self.mask = None
+        return super().apply(op)
+
+
+class SolidPressureFromThePartner(ContextModel):
+    """While a mask is set, a poisson_continue of an odd number of launches leaves in the solid cells what the pressure held
+    before its previous write (the ping-pong partner's contents)."""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.held, self.partner = self.p, self.p
+
+    def apply(self, op):
+        out = super().apply(op)
+        if self.p is not self.held:                     # (every op that writes the pressure replaces the array)
+            before, self.held = self.held, self.p
+            if op[0] == "poisson_continue" and self.mask is not None and -(-op[1]["iters"] // D_SOLID) % 2 == 1:
+                self.p = self.held = np.where(self.mask, self.partner, self.p).astype(np.float32)
+            self.partner = before
+        return out
+
+
+class ReplacedMaskIsIgnored(ContextModel):
+    """set_solids while a mask is set keeps the old mask."""
+
+    def do_set_solids(self, mask_kind, seed):
+        if self.mask is None:
+            super().do_set_solids(mask_kind, seed)
+
+
+SOLID_STAND_INS = (ClearedSolidsStillWall, SolidPressureFromThePartner, ReplacedMaskIsIgnored)
 
 
 def fresh_handle_check(oracle, make_handle, dim_x=61, dim_y=81, seed=3):

@@ -84,12 +84,18 @@ def _p_gs(p, rhs, solid, kf, z):
 
 def solve(d, solid, dx=1.0, iters=10, omega=1.96):
     """Item 5: p = 0, then `iters` times the even cells, then the odd ones; solid cells are never updated."""
+    return iterate(np.zeros(np.asarray(solid).shape, F), d, solid, dx, iters, omega)
+
+
+def iterate(p, d, solid, dx=1.0, iters=10, omega=1.96):
+    """Item 5's iterations on the pressure `p` as it stands: `iters` times the even cells, then the odd ones; a solid cell
+    keeps what it holds and is never read."""
     solid = np.asarray(solid, bool)
     dim_y, dim_x = solid.shape
     kf, z = _k_and_z(solid)
     j, i = np.mgrid[0:dim_y, 0:dim_x]
     om, one_minus = F(omega), F(1.0) - F(omega)
-    p = np.zeros((dim_y, dim_x), F)
+    p = np.array(p, F)
     with np.errstate(all="ignore"):
         rhs = (F(dx) * d.astype(F)).astype(F)
         for _ in range(iters):

@@ -4,6 +4,12 @@ small and a large batch -- taken through 30 seeded ops and compared with the mod
 same op list: every field after every op (eager), nothing read before the end (lazy), one seeded query after every op
 (probing).  tests/test_sequences.py has the census of what the lists contain.
 
+Two more subjects walk solids and histories, 36 ops each: a context (130 x 70: 3 x 3 ragged tiles of the masked solve and,
+cleared, the general kernels and the step seams; 61 x 81: cleared, the one-launch step of a small grid) and a batch of three
+(61 x 81, 7 x 9) on which a mask is set, replaced without a clear and cleared while the fields stay as they are, with options
+flipped, a timeline pending, tracers following, a trail and a history on.  A call the header refuses is an op like any other:
+both sides return the refusal, and the fields, the timeline and the tracers behind it are compared as after every op.
+
 A failure prints the seed, the mode, the first op that disagreed and the op list up to there as a literal for
 sequence_model.replay.  There is no tolerance anywhere."""
 import functools
@@ -30,12 +36,16 @@ def test_a_sequence_on_a_live_handle(sfl, oracle, name, case, mode):
     sm.run(subject, case, seqs[case], mode, oracle, lambda s, c: s.library(sfl, c))
 
 
+LIVE = [(cls, "general") for cls in sm.STAND_INS] + [(cls, "solid-context") for cls in sm.SOLID_STAND_INS]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("cls", sm.STAND_INS, ids=[c.__name__ for c in sm.STAND_INS])
-def test_the_comparisons_on_the_library_are_live(sfl, oracle, cls):
+@pytest.mark.parametrize("cls,name", LIVE, ids=[c.__name__ for c, _ in LIVE])
+def test_the_comparisons_on_the_library_are_live(sfl, oracle, cls, name):
     """A model with a planted state fault, taken as the truth: the library does not have the fault, so some sequence of the
-    general subject must disagree -- in lazy or probing mode, as tests/test_sequences.py shows for models on both sides."""
-    subject, seqs = sequences("general")
+    subject (general; solid-context for the faults in the solids' state) must disagree -- in lazy or probing mode, as
+    tests/test_sequences.py shows for models on both sides."""
+    subject, seqs = sequences(name)
     hits = 0
     for case, ops in seqs.items():
         for mode in ("lazy", "probing"):
@@ -46,4 +56,4 @@ def test_the_comparisons_on_the_library_are_live(sfl, oracle, cls):
                 hits += 1
             finally:
                 handle.close()
-    assert hits, f"{cls.__name__}: the library agreed with a faulty model in every sequence"
+    assert hits, f"{cls.__name__}: the library agreed with a faulty model in every sequence of {name}"
