@@ -34,6 +34,7 @@ ENV_MEAN, ENV_MIN, ENV_MAX, ENV_SPREAD = 0, 1, 2, 3
 VIEW_SPEED, VIEW_VORTICITY, VIEW_PRESSURE, VIEW_DIVERGENCE = 0, 1, 2, 3
 VIEW_MAX_STOPS = 256
 VIEW_MAX_COLOUR = 0xFC000000
+MAX_BODIES = 16   # SFL_MAX_BODIES
 UNIQUE_ID_BYTES = 128
 TRACER_THREADS = 256   # kTracerThreads of csrc/tracer_kernels.h: tracers per workgroup (stated for the tests)
 BATCH_LARGE_MAX_CELLS = 20224   # SFL_BATCH_LARGE_MAX_CELLS: cells of one member of sfl_batch_create_large
@@ -70,6 +71,12 @@ class HistoryRecord(C.Structure):
     _fields_ = [("max_abs_vx", C.c_float), ("max_abs_vy", C.c_float), ("max_abs_div", C.c_float), ("what", C.c_uint32),
                 ("dye_sum", C.c_uint64 * 3), ("update_norm", C.c_float), ("iterations", C.c_int32), ("step", C.c_int64),
                 ("dt", C.c_float), ("dx", C.c_float)]
+
+
+class BodyLoad(C.Structure):
+    """struct sfl_body_load: the pressure load on one solid body, 48 bytes."""
+    _fields_ = [("fx", C.c_int64), ("fy", C.c_int64), ("exp2", C.c_int32), ("max_abs_p", C.c_float), ("faces", C.c_uint32 * 4),
+                ("nonfinite", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class FieldDistance(C.Structure):
@@ -257,6 +264,22 @@ SIGNATURES = {
     "sfl_set_solids": (_i, [_ctx, C.POINTER(C.c_uint8)]),
     "sfl_solids_info": (_i, [_ctx, _pi, C.POINTER(C.c_int64)]),
     "sfl_solids_download": (_i, [_ctx, C.POINTER(C.c_uint8), _sz]),
+    "sfl_batch_set_bodies": (_i, [_ctx, C.POINTER(C.c_uint8), _i, _i]),
+    "sfl_batch_bodies_info": (_i, [_ctx, _pi, _pi, _pi]),
+    "sfl_batch_bodies_download": (_i, [_ctx, _i, _i, C.POINTER(C.c_uint8), _sz]),
+    "sfl_batch_loads": (_i, [_ctx, _i, _i, C.POINTER(BodyLoad), _sz]),
+    "sfl_batch_loads_start": (_i, [_ctx, _i, _i, _i, _i]),
+    "sfl_batch_loads_stop": (_i, [_ctx]),
+    "sfl_batch_loads_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), _pi]),
+    "sfl_batch_loads_read": (_i, [_ctx, _i, _i, C.POINTER(BodyLoad), _sz]),
+    "sfl_set_bodies": (_i, [_ctx, C.POINTER(C.c_uint8), _i]),
+    "sfl_bodies_info": (_i, [_ctx, _pi, _pi]),
+    "sfl_bodies_download": (_i, [_ctx, C.POINTER(C.c_uint8), _sz]),
+    "sfl_loads": (_i, [_ctx, C.POINTER(BodyLoad), _sz]),
+    "sfl_loads_start": (_i, [_ctx, _i, _i]),
+    "sfl_loads_stop": (_i, [_ctx]),
+    "sfl_loads_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), _pi]),
+    "sfl_loads_read": (_i, [_ctx, _i, _i, C.POINTER(BodyLoad), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

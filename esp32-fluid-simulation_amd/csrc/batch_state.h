@@ -121,6 +121,11 @@ struct sfl_batch {
         // the velocity part of the flow statistics into d_stats, zeroed in front on the stream
         int (*stats)(sfl_batch *b, float two_dx_inv, const float *d_member_two_dx_inv) = nullptr;
     } solids;
+    // loads (loads.cpp; context.h has Loads): loads_step: `steps` steps have been launched and the ping-pong swapped --
+    // count them and launch (without solids: zero) the samples that are due on the batch's stream behind them; called
+    // last, behind history_step
+    sfl::host::Loads loads;
+    int (*loads_step)(sfl_batch *b, int steps) = nullptr;
 };
 
 namespace sfl {

@@ -14,6 +14,7 @@
 //   host_dropin.cpp   the host-pointer drop-ins (sfl_host_*) and their per-thread context
 //   tracers.cpp       points that move with the flow (sfl_tracers_*, sfl_batch_tracers_*): sets, advances, samples, trails
 //   context_solids.cpp solid cells of a whole-domain context (sfl_set_solids, _solids_info, _solids_download) and the masked launches
+//   loads.cpp         the pressure load on solid bodies (sfl_loads*, sfl_batch_loads*, sfl_set_bodies, sfl_batch_set_bodies)
 //
 // There is deliberately no CPU compute path in any of them: every operator ends in a kernel launch and fails with
 // SFL_ERR_HIP when no device is usable.
@@ -249,6 +250,36 @@ inline int history_admit(const History &h, int64_t n)
 // how many of the next n steps may run in one launch before a sample is due (n without a history): record_run's rule
 inline int history_run(const History &h, int n) { return h.on ? (int)std::min<int64_t>(n, h.every - h.steps % h.every) : n; }
 
+// Loads (loads.cpp; include/sfl.h "LOADS"): what a context or a batch holds of its bodies' labels and of the loads
+// recorder.  Plain data, as History and for the same reason: the destroy paths free the two allocations and the step calls
+// admit without a symbol of loads.cpp; the sample is launched through the `loads_step` pointer of the two structs, which
+// loads.cpp sets while a recorder is on (null: the step calls launch what they launched before there were loads).
+struct Loads {
+    uint8_t *d_labels = nullptr;   // one label byte per cell (a batch: of every member when per_member); null: every solid is body 1
+    size_t d_label_bytes = 0;
+    bool per_member = false;
+    int bodies = 1;
+    bool on = false;
+    int every = 0, first = 0, count = 0, capacity = 0, written = 0;   // members [first, first + count) (a context: [0, 1))
+    int64_t steps = 0;            // counted since loads_start
+    // the records of 48 bytes: in front those of ONE sample of every member (what the synchronous call writes and copies
+    // out), behind them `capacity` samples of count * bodies, sample-major.  Kept by a restart that does not need more,
+    void *d_records = nullptr;    //   freed by loads_stop and the destroy paths
+    size_t d_bytes = 0;
+};
+
+// SFL_ERR_STATE if the n steps of a call would complete more samples than are free: history_admit's rule
+inline int loads_admit(const Loads &l, int64_t n)
+{
+    if (!l.on) return SFL_OK;
+    const int64_t due = (l.steps + n) / l.every - l.steps / l.every, room = l.capacity - l.written;
+    if (due > room)
+        return fail(SFL_ERR_STATE, "the loads recorder has room for %lld more samples (%d of %d written) and %lld steps would complete %lld: "
+                    "nothing stepped; read the samples (sfl_loads_read, sfl_batch_loads_read) and start the recorder again to make room",
+                    (long long)room, l.written, l.capacity, (long long)n, (long long)due);
+    return SFL_OK;
+}
+
 // What the view calls (views.cpp; include/sfl.h "VIEWS") keep on the device for a context or a batch: the staged palette
 // of the call (kViewPaletteWords words, allocated at the first call) and the call's result, which only grows.  Plain
 // data, freed by the two destroy paths, so that they need no symbol of views.cpp.
@@ -399,6 +430,10 @@ struct sfl_context {
     sfl::host::History history;
     int (*history_step)(sfl_context *c, float dt, float dx, int iters) = nullptr;
     sfl::host::ContextSolids solids;   // solid cells (context_solids.cpp)
+    // loads (loads.cpp), and the recorder's sample behind every step while it is on (one step has run: count it and, when a
+    // sample is due, launch it on the context's stream); called last, behind history_step
+    sfl::host::Loads loads;
+    int (*loads_step)(sfl_context *c) = nullptr;
 
     sfl::host::Options opt;  // what sfl_set_option stores (kOptions above: one row per option)
 

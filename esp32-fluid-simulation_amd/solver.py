@@ -77,6 +77,10 @@ HISTORY_DTYPE = np.dtype({"names": ["max_abs_vx", "max_abs_vy", "max_abs_div", "
                                     "dt", "dx"],
                           "formats": ["<f4", "<f4", "<f4", "<u4", ("<u8", (3,)), "<f4", "<i4", "<i8", "<f4", "<f4"],
                           "offsets": [0, 4, 8, 12, 16, 40, 44, 48, 56, 60], "itemsize": 64})
+# struct sfl_body_load: the pressure load on one solid body (Solver.loads: one per body; BatchSolver.loads: one per member
+# and body).  48 bytes; the load in pressure times cell widths is fx * 2^exp2, fy * 2^exp2.
+BODY_LOAD_DTYPE = np.dtype([("fx", "<i8"), ("fy", "<i8"), ("exp2", "<i4"), ("max_abs_p", "<f4"), ("faces", "<u4", (4,)),
+                            ("nonfinite", "<u4"), ("reserved", "<u4")])
 HISTORY_THREADS = 1024  # kHistoryThreads of csrc/history_kernels.h: threads of the sampler's workgroup (stated for the tests)
 
 
@@ -336,7 +340,127 @@ class _History:
         capi.check(self._history_call("stop")(self._h))
 
 
-class Solver(_Tracers, _History):
+class _Loads:
+    """Loads: the pressure force on solid bodies, as figures and as curves recorded while stepping (include/sfl.h
+    "LOADS").  Shared by :class:`Solver` (``[1, bodies]`` records per sample) and :class:`BatchSolver` (``[count, bodies]``)."""
+
+    _loads_batch = False
+    _loads_rec = (0, 1)   # the recorded members (first, count)
+
+    def _loads_call(self, name):
+        return getattr(self._lib, ("sfl_batch_" if self._loads_batch else "sfl_") + name)
+
+    def _loads_members(self):
+        return self.batch if self._loads_batch else 1
+
+    def set_bodies(self, labels, bodies=None):
+        """Label the bodies: a uint8 array of shape ``(dim_y, dim_x)`` (a batch: also ``(batch, dim_y, dim_x)``), 0 = in no
+        body, 1..bodies = that body; `bodies` defaults to the largest label (at least 1).  None goes back to "every solid
+        cell is body 1".  A label counts only where the cell is solid when a load is sampled.  Refused (ERR_STATE) while
+        the loads recorder is on."""
+        ptr = C.POINTER(C.c_uint8)
+        if labels is None:
+            args = (None, 0, 1) if self._loads_batch else (None, 1)
+            capi.check(self._loads_call("set_bodies")(self._h, *args))
+            return
+        a = np.ascontiguousarray(labels)
+        if a.dtype != np.uint8:
+            raise ValueError(f"bodies: a uint8 array of labels, got {a.dtype}")
+        shapes = [(self.dim_y, self.dim_x)] + ([(self.batch, self.dim_y, self.dim_x)] if self._loads_batch else [])
+        if a.shape not in shapes:
+            raise ValueError(f"bodies: shape {a.shape}, want one of {shapes}")
+        if bodies is None:
+            bodies = max(int(a.max()), 1)
+        args = (int(a.ndim == 3), int(bodies)) if self._loads_batch else (int(bodies),)
+        capi.check(self._loads_call("set_bodies")(self._h, a.ctypes.data_as(ptr), *args))
+
+    def bodies_info(self):
+        """(bodies, labelled) -- a batch: (bodies, labelled, per_member).  Never waits."""
+        out = [C.c_int() for _ in range(3 if self._loads_batch else 2)]
+        capi.check(self._loads_call("bodies_info")(self._h, *[C.byref(v) for v in out]))
+        return (out[0].value,) + tuple(bool(v.value) for v in out[1:])
+
+    def bodies(self, first: int = 0, count=None) -> np.ndarray:
+        """The labels, uint8[dim_y, dim_x] (a batch: uint8[count, dim_y, dim_x] of members [first, first + count)); all 1
+        without labels.  Synchronous."""
+        ptr = C.POINTER(C.c_uint8)
+        if not self._loads_batch:
+            a = np.empty((self.dim_y, self.dim_x), np.uint8)
+            capi.check(self._lib.sfl_bodies_download(self._h, a.ctypes.data_as(ptr), a.nbytes))
+            return a
+        count = self.batch - first if count is None else count
+        a = np.empty((count, self.dim_y, self.dim_x), np.uint8)
+        capi.check(self._lib.sfl_batch_bodies_download(self._h, first, count, a.ctypes.data_as(ptr), a.nbytes))
+        return a
+
+    def loads(self, first: int = 0, count=None) -> np.ndarray:
+        """The pressure load on every body from the pressure held: a BODY_LOAD_DTYPE array of shape ``(count, bodies)`` --
+        a context: ``(1, bodies)`` --, every field bit for bit what the rule of include/sfl.h "LOADS" gives on the
+        downloaded pressure, mask and labels.  All zeros without solids.  Synchronous; changes no field."""
+        n_bodies = self.bodies_info()[0]
+        if not self._loads_batch:
+            if first != 0 or count not in (None, 1):
+                raise ValueError("a context has one set of records: first = 0, count = None")
+            out = np.zeros((1, n_bodies), BODY_LOAD_DTYPE)
+            capi.check(self._lib.sfl_loads(self._h, out.ctypes.data_as(C.POINTER(capi.BodyLoad)), out.nbytes))
+            return out
+        count = self.batch - first if count is None else count
+        out = np.zeros((count, n_bodies), BODY_LOAD_DTYPE)
+        capi.check(self._lib.sfl_batch_loads(self._h, first, count, out.ctypes.data_as(C.POINTER(capi.BodyLoad)), out.nbytes))
+        return out
+
+    @staticmethod
+    def _xy(rec):
+        scale = np.ldexp(1.0, rec["exp2"].astype(np.int64))
+        return np.stack([rec["fx"].astype(np.float64) * scale, rec["fy"].astype(np.float64) * scale], axis=-1)
+
+    def loads_xy(self, first: int = 0, count=None) -> np.ndarray:
+        """:meth:`loads` as float64 ``(count, bodies, 2)``: fx * 2^exp2, fy * 2^exp2, in pressure times cell widths
+        (multiply by dx).  fx and fy have at most 63 bits: the product is rounded to double once."""
+        return self._xy(self.loads(first, count))
+
+    def loads_start(self, every: int, capacity: int, first: int = 0, count=None):
+        """Start the loads recorder: after every `every`-th step of any step call -- counted across calls -- one launch on
+        the stream writes the records of members [first, first + count) (a context: its own) from the fields that step
+        left; `capacity` samples fit.  The step calls stay asynchronous.  A step call that would complete more samples
+        than are free raises SflError with ERR_STATE and steps nothing.  A sample taken without solids set is zeros."""
+        if not self._loads_batch:
+            if first != 0 or count not in (None, 1):
+                raise ValueError("a context has one set of records per sample: first = 0, count = None")
+            rc = self._lib.sfl_loads_start(self._h, every, capacity)
+            rec = (0, 1)
+        else:
+            count = self.batch - first if count is None else count
+            rc = self._lib.sfl_batch_loads_start(self._h, every, first, count, capacity)
+            rec = (first, count)
+        if rc == capi.OK:
+            self._loads_rec = rec
+        capi.check(rc)
+
+    def loads_info(self):
+        """(samples written, capacity, steps counted since loads_start, bodies).  Never waits."""
+        samples, capacity, steps, n = C.c_int(), C.c_int(), C.c_int64(), C.c_int()
+        capi.check(self._loads_call("loads_info")(self._h, C.byref(samples), C.byref(capacity), C.byref(steps), C.byref(n)))
+        return samples.value, capacity.value, steps.value, n.value
+
+    def loads_history(self) -> np.ndarray:
+        """The samples written so far, BODY_LOAD_DTYPE of shape ``(samples, count, bodies)`` (a context: count = 1); sample
+        s belongs to step (s + 1) * every since loads_start.  Not consumed.  Synchronous."""
+        samples, _, _, n_bodies = self.loads_info()
+        out = np.zeros((samples, self._loads_rec[1], n_bodies), BODY_LOAD_DTYPE)
+        capi.check(self._loads_call("loads_read")(self._h, 0, samples, out.ctypes.data_as(C.POINTER(capi.BodyLoad)), out.nbytes))
+        return out
+
+    def loads_history_xy(self) -> np.ndarray:
+        """:meth:`loads_history` as float64 ``(samples, count, bodies, 2)``."""
+        return self._xy(self.loads_history())
+
+    def loads_stop(self):
+        """Stop the loads recorder and free its samples."""
+        capi.check(self._loads_call("loads_stop")(self._h))
+
+
+class Solver(_Tracers, _History, _Loads):
     """One solver context: rows [row_begin, row_end) of a dim_x * dim_y domain on one device."""
 
     def __init__(self, dim_x: int, dim_y: int, device: int = 0, rank: int = 0, nranks: int = 1):
@@ -603,7 +727,7 @@ class Solver(_Tracers, _History):
         return {"launches": a.value, "exchanges": b.value, "fuse": c.value, "halo": self.get_option(capi.OPT_LAST_HALO)}
 
 
-class BatchSolver(_Tracers, _History):
+class BatchSolver(_Tracers, _History, _Loads):
     """A batch (sfl_batch_*): `batch` independent whole-domain simulations of one dim_x * dim_y grid on one device,
     every member stepped by the same launch.  Member m holds, bit for bit, what a :class:`Solver` of the same shape
     holds after the same calls made with member m's data and forces.  Arrays of members are shaped
@@ -622,6 +746,7 @@ class BatchSolver(_Tracers, _History):
 
     _tracer_prefix = "sfl_batch_tracers_"
     _history_prefix = "sfl_batch_history_"
+    _loads_batch = True
 
     def _tracer_lead(self):
         return (self.batch,)

@@ -1095,6 +1095,89 @@ SFL_API int sfl_set_solids(sfl_context *ctx, const uint8_t *mask);
 SFL_API int sfl_solids_info(sfl_context *ctx, int *set, int64_t *solid_cells);
 /* The mask as bytes 0 / 1 (no solids: zeros); bytes must be dim_y * dim_x.  Synchronous.                                   */
 SFL_API int sfl_solids_download(sfl_context *ctx, uint8_t *host, size_t bytes);
+/* --- LOADS: how hard the flow pushes on solid bodies -- the pressure force on every body, as figures (sfl_batch_loads,
+ *     sfl_loads) and as curves recorded while stepping (sfl_batch_loads_start, sfl_loads_start), without a download.  The rule
+ *     below is a definition stated here, like the vorticity's and the solids': the reference knows no bodies.  It is the
+ *     PRESSURE load only -- no viscous and no momentum-flux part -- and there is no torque.
+ *   FACES.  A wet face is a pair (fluid cell F, solid cell S) where S is one of F's four neighbours, S is INSIDE THE DOMAIN
+ * and S belongs to a body.  The rim of the grid is not a body and has no faces.
+ *   BODIES.  Without labels every solid cell is body 1 and `bodies` is 1.  sfl_batch_set_bodies / sfl_set_bodies give one byte
+ * per cell: 0 = in no body (a channel wall that is not wanted in the drag), 1..bodies = that body, bodies <= SFL_MAX_BODIES.
+ * A label counts only where the cell is solid at the time of the sample; labels and masks are independent of each other,
+ * either may be set first, and either may be shared by all members or per member.
+ *   THE RECORD, per body, over its wet faces, from the pressure held (p of the face is the pressure of its FLUID cell):
+ *     nonfinite   the number of faces whose pressure is NaN or +-Inf; those faces take no further part;
+ *     max_abs_p   the maximum of |p| over the remaining faces; 0.0f when there is none;
+ *     exp2        q = floor(log2(max_abs_p)) - 32, denormals included: frexp((double)max_abs_p)'s exponent - 1 - 32; q = 0 when
+ *                 max_abs_p == 0;
+ *     a face's term  t = (int64_t)trunc(ldexp((double)p, -q)): exact in double, |t| < 2^33; the largest face keeps all of its
+ *                 24 bits, and a face is truncated only below 2^-32 of the largest;
+ *     fx          the sum of t over the faces whose fluid cell lies WEST of its solid cell minus the sum over those whose
+ *                 fluid cell lies EAST of it; fy the same with SOUTH and NORTH: pressure pushes the body away from the fluid;
+ *     faces[4]    the numbers of faces whose fluid cell lies W, E, S, N of the solid cell; faces[0] is the frontal area
+ *                 of a flow in +x.
+ *   A context holds at most 2^28 cells, hence fewer than 2^30 faces, and |sum| < 2^30 * 2^33 = 2^63: fx and fy never overflow.
+ *   The load in pressure times cell widths is fx * 2^exp2 (fy * 2^exp2); the caller multiplies by dx.  All zeros mean a body
+ * without a face, or no solids set.  Integer sums, maxima over bit patterns and counts do not depend on the order of
+ * reduction: every field of every record is, bit for bit, what the rule computes from the downloaded pressure, mask and
+ * labels, and a context and a batch member of the same shape, mask, labels and pressure report the same bytes.
+ *   THE RECORDER follows the histories' rules unchanged: after every `every`-th step of ANY step call -- counted across calls
+ * -- one launch on the stream (a context: two) writes count * bodies records from the fields that step left; the step calls
+ * stay asynchronous; a step call whose steps would complete more samples than are free is refused WHOLE with SFL_ERR_STATE
+ * before anything is staged or launched; a restart keeps the buffer; sample s belongs to step (s + 1) * every since the
+ * start.  A sample taken while no solids are set is zero records (a batch's one-launch replay of a timeline only runs
+ * without solids: the samples that fall inside it are zeros).  A loads recorder changes no result and, unlike a history, not
+ * even which step launches a call makes; with none on, every call launches exactly what it launched before there were loads.
+ *   Admission as everywhere: a call's own argument checks come first, then the state refusals, each with its own message;
+ * a refused call stages and launches nothing.                                                                              */
+#define SFL_MAX_BODIES 16
+struct sfl_body_load {
+    int64_t  fx, fy;
+    int32_t  exp2;
+    float    max_abs_p;
+    uint32_t faces[4];
+    uint32_t nonfinite, reserved;
+};                                     /* 48 bytes: offsets 0, 8, 16, 20, 24, 40, 44 */
+/* Label the bodies: labels = dim_y * dim_x bytes shared by all members (per_member 0) or batch * dim_y * dim_x bytes, member-
+ * major (per_member 1), cell (i, j) at dim_x * j + i; read during the call only.  labels NULL goes back to "every solid cell
+ * is body 1" (bodies is then 1, whatever is passed).  Batches of either kind.  Synchronous.  b NULL, per_member outside 0..1,
+ * bodies outside 1..SFL_MAX_BODIES and a label > bodies (the message names the first such cell) return SFL_ERR_INVALID; while
+ * the loads recorder is on the call is refused with SFL_ERR_STATE: the layout of its samples depends on `bodies`.           */
+SFL_API int sfl_batch_set_bodies(sfl_batch *b, const uint8_t *labels, int per_member, int bodies);
+/* The number of bodies, whether labels are set, and whether per member.  Any out pointer may be NULL.  Never waits.        */
+SFL_API int sfl_batch_bodies_info(sfl_batch *b, int *bodies, int *labelled, int *per_member);
+/* The labels of members [first, first + count), member-major (shared labels: repeated; no labels: every byte 1); bytes must
+ * be count * dim_y * dim_x.  Synchronous.                                                                                  */
+SFL_API int sfl_batch_bodies_download(sfl_batch *b, int first, int count, uint8_t *host, size_t bytes);
+/* The loads of members [first, first + count) from the pressure held: count * bodies records, member-major (record of body k
+ * of member m at host[(m - first) * bodies + k - 1]); bytes must be count * bodies * 48.  One launch, synchronous; changes
+ * no field.  A batch without solids set reports zero records without a launch.                                             */
+SFL_API int sfl_batch_loads(sfl_batch *b, int first, int count, struct sfl_body_load *host, size_t bytes);
+/* Start the recorder for members [first, first + count): `capacity` samples of count * bodies records are allocated on the
+ * device and the step count is set to 0.  Called while it is on, it starts afresh; the buffer is reallocated only if it must
+ * grow.  b NULL, every < 1, capacity < 1 (or too large for a size_t), count < 1 and a range outside the batch return
+ * SFL_ERR_INVALID; a failed allocation returns SFL_ERR_NOMEM and leaves the batch without a recorder.                      */
+SFL_API int sfl_batch_loads_start(sfl_batch *b, int every, int first, int count, int capacity);
+/* Stop the recorder and free its samples (sfl_batch_destroy frees them too).  Without one: SFL_OK.                         */
+SFL_API int sfl_batch_loads_stop(sfl_batch *b);
+/* Samples written so far, the capacity, the steps counted since the start (all 0 without a recorder) and the number of
+ * bodies.  Any out pointer may be NULL.  Never waits.                                                                      */
+SFL_API int sfl_batch_loads_info(sfl_batch *b, int *samples, int *capacity, int64_t *steps, int *bodies);
+/* Copy samples [first_sample, first_sample + samples) out whole, sample-major: the record of body k of recorded member m of
+ * sample s at host[(s * count + m) * bodies + k - 1]; bytes must be samples * count * bodies * 48.  Not consumed.
+ * Synchronous.  No recorder: SFL_ERR_STATE.                                                                                */
+SFL_API int sfl_batch_loads_read(sfl_batch *b, int first_sample, int samples, struct sfl_body_load *host, size_t bytes);
+/* The same for a whole-domain context: `bodies` records per sample.  A slab and a context with a transport attached get
+ * SFL_ERR_STATE, as from sfl_set_solids.  A sample is two streaming passes over the code bytes, the maximum and then the
+ * sums, behind a memset of the sample's records, all on the context's stream.                                              */
+SFL_API int sfl_set_bodies(sfl_context *ctx, const uint8_t *labels, int bodies);
+SFL_API int sfl_bodies_info(sfl_context *ctx, int *bodies, int *labelled);
+SFL_API int sfl_bodies_download(sfl_context *ctx, uint8_t *host, size_t bytes);
+SFL_API int sfl_loads(sfl_context *ctx, struct sfl_body_load *host, size_t bytes);
+SFL_API int sfl_loads_start(sfl_context *ctx, int every, int capacity);
+SFL_API int sfl_loads_stop(sfl_context *ctx);
+SFL_API int sfl_loads_info(sfl_context *ctx, int *samples, int *capacity, int64_t *steps, int *bodies);
+SFL_API int sfl_loads_read(sfl_context *ctx, int first_sample, int samples, struct sfl_body_load *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
