@@ -280,6 +280,12 @@ SIGNATURES = {
     "sfl_loads_stop": (_i, [_ctx]),
     "sfl_loads_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), _pi]),
     "sfl_loads_read": (_i, [_ctx, _i, _i, C.POINTER(BodyLoad), _sz]),
+    "sfl_set_viscosity": (_i, [_ctx, _f, _i]),
+    "sfl_viscosity_info": (_i, [_ctx, _pf, _pi]),
+    "sfl_diffuse_velocity": (_i, [_ctx, _f, _f, _f, _i]),
+    "sfl_batch_set_viscosity": (_i, [_ctx, _pf, _i, _i]),
+    "sfl_batch_viscosity_info": (_i, [_ctx, _pi, _pi, _pi]),
+    "sfl_batch_viscosity_download": (_i, [_ctx, _i, _i, _pf, _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

@@ -21,11 +21,11 @@ void release(sfl_batch *b)
                     (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env,
                     (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
                     (void *)b->d_rec_palette, b->history.d_records, (void *)b->solids.d_codes,
-                    (void *)b->loads.d_labels, b->loads.d_records})
+                    (void *)b->loads.d_labels, b->loads.d_records, b->viscosity.d_table})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
     if (b->h_dist) (void)hipHostFree(b->h_dist);
-    for (sfl_batch::Stage *pair : {b->stage, b->member_stage})
+    for (sfl_batch::Stage *pair : {b->stage, b->member_stage, b->viscosity.stage_slot})
         for (int k = 0; k < 2; ++k) {
             if (pair[k].host) (void)hipHostFree(pair[k].host);
             if (pair[k].copied) (void)hipEventDestroy(pair[k].copied);
@@ -216,11 +216,12 @@ enum StepKind { kUniform, kEach, kUntil };
 // With a following set of tracers (tracers_follow) every step is a launch of its own, the advance behind it: the tracers
 // read each step's projected velocity, which the launch of several steps never stores.  A history (history_step) cuts
 // the call as the recorder does: its sample reads the fields of the step it is due after.  With solid cells set
-// (b->solids; solids.cpp) every step is a launch of its own too, made through the batch's pointer.
+// (b->solids; solids.cpp) every step is a launch of its own too, made through the batch's pointer, and so it is with a
+// viscosity set (b->viscosity; viscous.cpp), whose pointer picks the kernel with or without solids itself.
 int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
 {
     SFL_TRY(stage_timeline(b, n));
-    if (kind != kUntil && !b->large && n >= 2 && !b->tracers_follow && !b->solids.set && staged_has(b, 1, n)) {
+    if (kind != kUntil && !b->large && n >= 2 && !b->tracers_follow && !b->solids.set && !b->viscosity.set && staged_has(b, 1, n)) {
         for (int done = 0; done < n;) {
             const int steps = sfl::host::history_run(b->history, sfl::host::record_run(b, n - done));   // (cut at either's due steps)
             sfl::BatchPlay play{};
@@ -249,7 +250,9 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
         a.step.v_out = b->vel_tmp;
         a.step.col_in = b->col;
         a.step.col_out = b->col_tmp;
-        if (b->solids.set)   // (never kUntil, never large: refused at the call and at sfl_batch_set_solids)
+        if (b->viscosity.set)   // (never kUntil, never large: refused at the call and at sfl_batch_set_viscosity)
+            SFL_TRY(b->viscosity.step(b, kind == kEach, a));
+        else if (b->solids.set)   // (never kUntil, never large: refused at the call and at sfl_batch_set_solids)
             SFL_TRY(b->solids.step(b, kind == kEach, a));
         else if (kind == kUniform)
             HIP_TRY((b->large ? sfl::launch_batch_large_step : sfl::launch_batch_step)(b->stream, a, b->batch));
@@ -593,6 +596,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     a.step.dt = dt;
     a.step.two_dx_inv = two_dx_inv(dx);
     a.step.prm = sor_params(dx, omega);
+    if (b->viscosity.set) SFL_TRY(b->viscosity.stage(b, dt, dx, nullptr));   // every member's a and c of this call's dt and dx
     SFL_TRY(run_steps(b, n, kUniform, a));
     return SFL_OK;
 }
@@ -620,6 +624,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
     SFL_TRY(sfl::host::loads_admit(b->loads, n));       // ... and a loads recorder without room for its
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
+    if (b->viscosity.set) SFL_TRY(b->viscosity.stage(b, 0.0f, 0.0f, params));   // every member's a and c of its own dt and dx
     b->report_valid = b->counts_valid = false;   // until every launch below is queued; no iterations to report afterwards
     sfl::BatchStep a{};   // (dt, two_dx_inv, iters and prm come from the members' records)
     a.step.div = b->div;
@@ -651,6 +656,9 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
     SFL_TRY(check_members(b, params, stops));
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
     if (b->solids.set) return refuse_until("sfl_batch_step_n_until");
+    if (b->viscosity.set)
+        return fail(SFL_ERR_STATE, "sfl_batch_step_n_until: the batch has a viscosity set (sfl_batch_set_viscosity) and the step to a tolerance does not "
+                    "know it: nothing stepped; use sfl_batch_step_n_each, or clear the viscosity with sfl_batch_set_viscosity(b, NULL, 0, 0)");
     if (n == 0) return SFL_OK;
     SFL_TRY(sfl::host::record_admit(b, n));   // a recorder without room for this call's frames refuses it whole
     SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots

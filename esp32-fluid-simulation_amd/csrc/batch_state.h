@@ -126,6 +126,22 @@ struct sfl_batch {
     // last, behind history_step
     sfl::host::Loads loads;
     int (*loads_step)(sfl_batch *b, int steps) = nullptr;
+    // viscosity (viscous.cpp; include/sfl.h "VISCOSITY"): nu of every member on the host, and one record per member on the
+    // device (viscous_kernels.h BatchViscous: a, c, sweeps), indexed by the member, filled from pinned memory by the
+    // two-slot rule of member_stage.  Plain data, as the solids are and for the same reason: the destroy path frees the
+    // table and the slots; while `set`, the step calls of batch.cpp stage the table once per call through `stage`
+    // (params: the _each call's records, else dt and dx for all) and launch every step through `step`, which picks the
+    // kernel with or without solids itself.  viscous.cpp sets and clears both with `set`.
+    struct Viscosity {
+        bool set = false, per_member = false;
+        int sweeps = 0;
+        std::vector<float> nu;   // `batch` floats while set
+        void *d_table = nullptr;
+        Stage stage_slot[2];
+        int slot = 0;
+        int (*stage)(sfl_batch *b, float dt, float dx, const sfl_member_params *params) = nullptr;
+        int (*step)(sfl_batch *b, bool each, const sfl::BatchStep &a) = nullptr;
+    } viscosity;
 };
 
 namespace sfl {

@@ -15,6 +15,8 @@
 //   tracers.cpp       points that move with the flow (sfl_tracers_*, sfl_batch_tracers_*): sets, advances, samples, trails
 //   context_solids.cpp solid cells of a whole-domain context (sfl_set_solids, _solids_info, _solids_download) and the masked launches
 //   loads.cpp         the pressure load on solid bodies (sfl_loads*, sfl_batch_loads*, sfl_set_bodies, sfl_batch_set_bodies)
+//   context_viscous.cpp viscosity of a whole-domain context (sfl_set_viscosity, _viscosity_info, sfl_diffuse_velocity)
+//   viscous.cpp       viscosity of a batch (sfl_batch_set_viscosity, _viscosity_info, _viscosity_download)
 //
 // There is deliberately no CPU compute path in any of them: every operator ends in a kernel launch and fails with
 // SFL_ERR_HIP when no device is usable.
@@ -311,6 +313,20 @@ struct ContextSolids {
     int (*max_div)(sfl_context *c, float two_dx_inv, unsigned *d_word) = nullptr;
 };
 
+// Viscosity of a whole-domain context (context_viscous.cpp; include/sfl.h "VISCOSITY"): what the context holds of it.  Plain
+// data, as ContextSolids and for the same reason: sfl_destroy frees the third buffer, and the step and the transports
+// live in units that the host test harnesses link without context_viscous.cpp -- the step reaches the unfused sequence
+// through `step`, set there while a viscosity is set and null otherwise (then every call launches exactly what it
+// launched before there was viscosity).
+struct ContextViscosity {
+    bool set = false;
+    float nu = 0.0f;
+    int sweeps = 0;
+    float *d_third = nullptr;   // a third velocity-sized buffer: u0 survives the launches of more than kD sweeps in it; allocated at the first such call
+    // one step with item 3a, behind sfl_step's checks: the unfused sequence (no seams, no fused kernels, no small-grid step)
+    int (*step)(sfl_context *c, float dt, float dx, int iters, float omega) = nullptr;
+};
+
 }  // namespace host
 }  // namespace sfl
 
@@ -434,6 +450,7 @@ struct sfl_context {
     // sample is due, launch it on the context's stream); called last, behind history_step
     sfl::host::Loads loads;
     int (*loads_step)(sfl_context *c) = nullptr;
+    sfl::host::ContextViscosity viscosity;   // item 3a of a step (context_viscous.cpp)
 
     sfl::host::Options opt;  // what sfl_set_option stores (kOptions above: one row per option)
 

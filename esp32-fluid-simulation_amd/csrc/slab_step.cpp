@@ -294,6 +294,7 @@ static int step_seam(sfl_context *c, float dt, float dx)
 // sfl_step behind its checks: the step that takes the records of step 0 of the timeline
 static int step_of_timeline(sfl_context *ctx, float dt, float dx, int iters, float omega)
 {
+    if (ctx->viscosity.step) return ctx->viscosity.step(ctx, dt, dx, iters, omega);   // viscosity set: the unfused sequence with item 3a
     if (ctx->solids.step) return ctx->solids.step(ctx, dt, dx, iters, omega);   // solid cells set: the unfused sequence of their rule
     if (small_grid(ctx)) return small_grid_step(ctx, dt, dx, iters, omega);
     if (ctx->nranks > 1 && ctx->opt.advect_halo == 0) return slab_step_auto(ctx, dt, dx, iters, omega);
@@ -357,10 +358,10 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
     const int64_t cells = (int64_t)ctx->dim_x * ctx->gdim_y;
     const bool tiled = ctx->opt.advect_kernel == 2 || (ctx->opt.advect_kernel == 0 && cells >= sfl::kAdvectTiledMinCells);
     // (a following set of tracers reads every step's projected velocity, which a seam never stores: no seams then; nor with
-    // a history on, whose samples read it too; nor with solid cells set, whose step is an unfused sequence of its own)
+    // a history on, whose samples read it too; nor with solid cells or a viscosity set, whose step is an unfused sequence of its own)
     const bool seams = n > 1 && ctx->opt.step_seams && ctx->nranks == 1 && !ctx->transport && !small_grid(ctx) && tiled &&
                        ctx->opt.fuse_projection && ctx->opt.fuse_divergence && !ctx->tracers_follow && !ctx->history_step &&
-                       !ctx->solids.step;
+                       !ctx->solids.step && !ctx->viscosity.step;
     if (!seams) {
         for (int k = 0; k < n; ++k) SFL_TRY(sfl_step(ctx, dt, dx, iters, omega));
         return SFL_OK;

@@ -577,6 +577,9 @@ static int no_solids(const sfl_context *c, const char *what)
     if (c->solids.set)
         return fail(SFL_ERR_STATE, "the context has solid cells set (sfl_set_solids) and no halo exchange knows them: %s is refused, nothing attached "
                     "or linked; clear the solids first (sfl_set_solids(ctx, NULL))", what);
+    if (c->viscosity.set)   // ... and so does a viscosity (include/sfl.h "VISCOSITY")
+        return fail(SFL_ERR_STATE, "the context has a viscosity set (sfl_set_viscosity) and no halo exchange knows the diffusion's halo: %s is refused, "
+                    "nothing attached or linked; clear the viscosity first (sfl_set_viscosity(ctx, 0, 0))", what);
     return SFL_OK;
 }
 

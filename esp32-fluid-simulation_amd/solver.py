@@ -710,6 +710,23 @@ class Solver(_Tracers, _History, _Loads):
         capi.check(self._lib.sfl_solids_download(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.nbytes))
         return a.astype(bool)
 
+    # -- viscosity -----------------------------------------------------------------------
+    def set_viscosity(self, nu, sweeps: int):
+        """Viscosity (include/sfl.h "VISCOSITY"): step and step_n then run `sweeps` red-black sweeps of an implicit
+        diffusion of the velocity between the forces and the divergence, as one unfused sequence per step.  nu == 0 or
+        sweeps == 0 clears it.  Whole-domain contexts without a transport, at any grid size; honours the solids."""
+        capi.check(self._lib.sfl_set_viscosity(self._h, float(nu), int(sweeps)))
+
+    def viscosity(self):
+        """(nu, sweeps) as the library reports it: (0.0, 0) when none is set."""
+        nu, s = C.c_float(0), C.c_int(0)
+        capi.check(self._lib.sfl_viscosity_info(self._h, C.byref(nu), C.byref(s)))
+        return np.float32(nu.value), s.value
+
+    def diffuse_velocity(self, nu, dt, dx=1.0, sweeps: int = 1):
+        """The diffusion as an operator of its own on the velocity held; needs nothing set."""
+        capi.check(self._lib.sfl_diffuse_velocity(self._h, float(nu), float(dt), float(dx), int(sweeps)))
+
     def synchronize(self):
         capi.check(self._lib.sfl_synchronize(self._h))
 
@@ -1104,6 +1121,29 @@ class BatchSolver(_Tracers, _History, _Loads):
         a = np.zeros((max(count, 0), self.dim_y, self.dim_x), np.uint8)
         capi.check(self._lib.sfl_batch_solids_download(self._h, first, count, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.nbytes))
         return a.astype(bool)
+
+    def set_viscosity(self, nu, sweeps: int):
+        """Viscosity (include/sfl.h "VISCOSITY"): `nu` one number for all members or an array of `batch`; None clears it.
+        step_n and step_n_each then run `sweeps` sweeps of an implicit diffusion of the velocity between the forces and
+        the divergence, with and without solids; members with nu == 0 skip it.  Batches of small members only; the
+        ``_until`` step is refused while set."""
+        if nu is None:
+            capi.check(self._lib.sfl_batch_set_viscosity(self._h, None, 0, int(sweeps)))
+            return
+        a = np.asarray(nu, dtype=np.float32)
+        if a.shape not in ((), (self.batch,)):
+            raise ValueError(f"viscosity: nu of shape {a.shape}, want a number or {(self.batch,)}")
+        per_member = a.ndim == 1
+        a = np.ascontiguousarray(a.reshape(-1))
+        capi.check(self._lib.sfl_batch_set_viscosity(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), int(per_member), int(sweeps)))
+
+    def viscosity(self):
+        """(nu of every member, float32[batch] -- zeros when none is set --, sweeps)."""
+        s = C.c_int(0)
+        capi.check(self._lib.sfl_batch_viscosity_info(self._h, None, None, C.byref(s)))
+        a = np.zeros(self.batch, np.float32)
+        capi.check(self._lib.sfl_batch_viscosity_download(self._h, 0, self.batch, a.ctypes.data_as(C.POINTER(C.c_float)), a.nbytes))
+        return a, s.value
 
     def synchronize(self):
         capi.check(self._lib.sfl_batch_synchronize(self._h))

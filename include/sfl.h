@@ -1178,6 +1178,59 @@ SFL_API int sfl_loads_start(sfl_context *ctx, int every, int capacity);
 SFL_API int sfl_loads_stop(sfl_context *ctx);
 SFL_API int sfl_loads_info(sfl_context *ctx, int *samples, int *capacity, int64_t *steps, int *bodies);
 SFL_API int sfl_loads_read(sfl_context *ctx, int first_sample, int samples, struct sfl_body_load *host, size_t bytes);
+/* --- VISCOSITY: an implicit diffusion of the velocity between the forces and the divergence, opt-in, per member in a batch and
+ *     on whole-domain contexts of any size.  The reference knows no viscosity: the arithmetic below is a definition stated
+ *     here, like the vorticity's, the solids' and the loads'.  It is anchored on the reference through nu = 0, which gives the
+ *     existing step bit for bit.
+ *   ITEM 3a OF A STEP.  It runs behind items 1 to 3 of "SOLIDS" (velocity advection, forces, solids zeroed) and in front of
+ * item 4 (divergence); in a step without solids, between the forces and the divergence.
+ *   SKIPPED WHOLE for a member or a context whose nu == 0.0f or whose sweeps == 0: nothing is computed and no bit changes (a
+ * zero coefficient would turn a -0.0f into +0.0f).
+ *   COEFFICIENTS.  a = (nu * dt) / (dx * dx) and c = 1.0f / (1.0f + 4.0f * a), both float32, every operation rounded on its
+ * own; formed once on the host per call, or per member in the _each call with that member's dt and dx.
+ *   THE SWEEPS.  u0 is the velocity that items 1 to 3 left; u starts as u0.  `sweeps` times: first colour 0 -- (i + j) & 1 == 0
+ * in domain coordinates --, then colour 1; for every FLUID cell of the colour and for each component q of x, y:
+ *     u.q = (u0.q + a * (((W.q + E.q) + S.q) + N.q)) * c
+ * A neighbour OUTSIDE THE DOMAIN contributes -u.q, the cell's own component as it stands before this update, negated: the
+ * no-slip ghost, zero velocity half a cell beyond the rim node, as in sample() of advect.h.  A SOLID neighbour inside the
+ * domain is read as what it holds -- after item 3 that is (0, 0): the node-based wall that item 1 already uses.  Solid cells
+ * are never updated.  A colour's cell reads only itself and the other colour: the result does not depend on the order of
+ * execution.  Compiled with -ffp-contract=off, as everything.
+ *   WHICH CALLS HONOUR VISCOSITY.  Batches of sfl_batch_create: sfl_batch_step_n and sfl_batch_step_n_each, with and without
+ * solids set.  While viscosity is set a step call runs one launch per step, as with solids; it does not replay a timeline in
+ * one launch.  A batch with viscosity set whose members all have nu = 0 runs the viscous kernels and gives the plain batch's
+ * bits.  Everything that only reads fields works unchanged: render, recorder, envelope, distance, tracers, views,
+ * sfl_batch_flow_stats, histories and loads.  Whole-domain contexts of any size: sfl_step and sfl_step_n run ONE UNFUSED
+ * SEQUENCE per step -- the velocity advection, the forces, the diffusion (with solids set its first launch reads the solid
+ * cells' velocity as (0, 0) and stores it so: item 3), then the divergence, the solve, the gradient and the dye advection
+ * as the calls of their own run them, by the solids' rule where a mask is set.  No step seams, no fused kernels, no
+ * one-launch step of a small grid.  sfl_diffuse_velocity is item 3a as an operator of its own.  The diffusion of a context
+ * is blocked in time: ceil(sweeps / 8) launches; more than 8 sweeps need a third velocity-sized buffer, allocated at the
+ * first such call (a failed allocation returns SFL_ERR_NOMEM), fewer allocate nothing.
+ *   REFUSED WHOLE with SFL_ERR_STATE, each with its own message and with nothing staged or launched: sfl_batch_set_viscosity
+ * on a batch of sfl_batch_create_large (its 8 B of LDS per cell leave no room for u0); sfl_batch_step_n_until while
+ * viscosity is set; sfl_set_viscosity and sfl_diffuse_velocity with nu > 0 on a slab (nranks != 1) or on a context that has a
+ * transport attached; sfl_comm_attach, sfl_comm_emulate, sfl_comm_emulate_rccl and sfl_group_link while viscosity is set.  A
+ * call's own argument checks come first: SFL_ERR_INVALID for a NULL handle, a negative or NaN nu (a batch: the message names
+ * the first such member), sweeps < 0, per_member outside 0..1 and wrong download sizes.
+ *   NOT THERE: viscosity on the batches of sfl_batch_create_large, in the _until calls and on slabs; a viscous part of the
+ * loads; diffusion of the dye.                                                                                             */
+/* Set the viscosity of a whole-domain context: from now on sfl_step and sfl_step_n run item 3a with this nu and `sweeps`
+ * sweeps.  nu == 0 or sweeps == 0 clears it: every call then launches exactly what it launched before.  Never waits.       */
+SFL_API int sfl_set_viscosity(sfl_context *ctx, float nu, int sweeps);
+/* What is set (0.0f and 0 when nothing is).  Either out pointer may be NULL.  Never waits.                                 */
+SFL_API int sfl_viscosity_info(sfl_context *ctx, float *nu, int *sweeps);
+/* Item 3a on the velocity held, beside sfl_calculate_divergence and its siblings: its own arguments, nothing needs to be
+ * set.  Honours the context's solids where set (a solid cell is not updated and is read as what it holds; nothing is
+ * zeroed).  Touches neither the pressure nor the divergence.  nu == 0 or sweeps == 0 launch nothing.  Asynchronous.        */
+SFL_API int sfl_diffuse_velocity(sfl_context *ctx, float nu, float dt, float dx, int sweeps);
+/* Set the viscosity of a batch: nu = one float for all members (per_member 0) or `batch` floats (per_member 1), read during
+ * the call only.  nu NULL clears it: the batch then launches exactly what it launched before.  Never waits.                */
+SFL_API int sfl_batch_set_viscosity(sfl_batch *b, const float *nu, int per_member, int sweeps);
+/* Whether viscosity is set, whether per member, and the sweeps.  Any out pointer may be NULL.  Never waits.                */
+SFL_API int sfl_batch_viscosity_info(sfl_batch *b, int *set, int *per_member, int *sweeps);
+/* nu of members [first, first + count) (a shared nu: repeated; none set: zeros); bytes must be count * 4.  Never waits.    */
+SFL_API int sfl_batch_viscosity_download(sfl_batch *b, int first, int count, float *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
