@@ -16,12 +16,24 @@ Solids and histories are subjects of their own (Subject(solids=True)): while a m
 follow items 1 to 7 of "SOLIDS" through tests/solid_rule.py, and while it holds a history it appends one record per sample.  A
 call include/sfl.h refuses in the state the model is in changes nothing and returns {"refused": ERR_STATE}; the library's
 wrappers turn an SflError into the same dict, and the runner compares the state behind a refused op like any other.  The
-generator follows the same state from the op list alone (Gate) so that only the refusals it planted happen."""
+generator follows the same state from the op list alone (Gate) so that only the refusals it planted happen.
+
+Viscosity and loads are two more subjects (Subject(viscous=True)) on top of the solids' deck: a step with a viscosity in force is
+the step above with tests/viscosity_rule.py's diffuse between the forces and the divergence (item 3a of "VISCOSITY", the mask
+where one is held), diffuse_velocity is that function alone, a load is tests/load_rule.py's loads of the model's pressure, mask
+and labels, compared as the raw bytes of its records, and the loads recorder counts as a history does and appends zero records
+while no mask is held.  The refusals the two features add -- set_bodies while the recorder is on, a batch's step_n_until while a
+viscosity is set, a step call that a full loads recorder has no room for, loads_history without a recorder -- are in the models
+and in the Gate, from the header."""
+import ctypes
+
 import numpy as np
 
+import load_rule
 import solid_rule
 import tracer_rule
 import view_rule
+import viscosity_rule
 from conftest import assert_bit_equal, random_fields
 from dx_cases import DX_A, DX_C, widened
 from test_batch_params import gs_target, update_norm
@@ -63,7 +75,15 @@ BATCH_QUERIES = ("download", "flow_stats", "distance", "envelope_field", "residu
 # to the tuples above would reshuffle every sequence the other subjects have)
 SOLID_WRITERS = ("set_solids", "clear_solids", "history_start", "history_stop")
 SOLID_QUERIES = ("solids", "history")
-QUERIES = set(CONTEXT_QUERIES) | set(BATCH_QUERIES) | set(SOLID_QUERIES)
+# the viscosity's and the loads' calls, dealt only to the subjects made with viscous=True (on top of the solids' deck)
+VISCOUS_WRITERS = ("set_viscosity", "clear_viscosity", "diffuse_velocity", "set_bodies", "clear_bodies", "loads_start", "loads_stop")
+VISCOUS_QUERIES = ("viscosity", "bodies", "loads", "loads_history")
+BATCH_VISCOUS_WRITERS = tuple(k for k in VISCOUS_WRITERS if k != "diffuse_velocity")      # (a batch has no operator of its own)
+QUERIES = set(CONTEXT_QUERIES) | set(BATCH_QUERIES) | set(SOLID_QUERIES) | set(VISCOUS_QUERIES)
+NUS, CONTEXT_SWEEPS, BATCH_SWEEPS = (0.0, 0.05, 0.3, 2.5), (0, 1, 3, 8, 9, 17), (0, 1, 3, 10)
+D_DIFFUSE = 8                                           # sweeps of one launch of a context's diffusion (kD of csrc/diffuse_tile.h)
+LABEL_KINDS = {"all one": 1, "halves": 2, "with zeros": 3, "sixteen": 16}     # kind -> bodies
+LOAD_BYTES = load_rule.DTYPE.itemsize                   # struct sfl_body_load
 # (36 ops a sequence: the deck of the solids' subjects leaves out three calls that touch neither a field nor a launch's path)
 SOLID_LEFT_OUT = ("queue_drags", "trail_stop", "last_solve_info")
 MASK_KINDS = ("one", "disc", "plate", "channel", "isolated", "all", "seeded", "empty")     # mask_of of tests/test_solids_gpu.py
@@ -80,6 +100,34 @@ def solid_mask(kind, dim_x, dim_y, seed, member=None):
     if member is not None:
         kind, seed = MASK_KINDS[(MASK_KINDS.index(kind) + member) % len(MASK_KINDS)], seed + member
     return mask_of(kind, dim_x, dim_y, seed)
+
+
+def body_labels(kind, dim_x, dim_y, seed, member=None):
+    """The labels a set_bodies op sets over the WHOLE grid, fluid cells included: None ("all one": every solid cell is body 1),
+    two bodies split at the middle column, a seeded third of the cells in no body, or 1 + (i + j) % 16.  Per member: member k
+    shifts the pattern by k cells and takes its own seed."""
+    if kind == "all one":
+        return None
+    k = member or 0
+    j, i = np.mgrid[0:dim_y, 0:dim_x]
+    if kind == "halves":
+        lab = np.where(i + k < dim_x // 2, 1, 2)
+    elif kind == "sixteen":
+        lab = 1 + (i + j + k) % 16
+    else:
+        lab = np.where(np.random.default_rng([seed, k, 5]).random((dim_y, dim_x)) < 1 / 3.0, 0, 1 + (i + 2 * j + k) % 3)
+    return lab.astype(np.uint8)
+
+
+def load_bytes(records):
+    """sfl_body_load records as their raw bytes, uint8[..., 48]: what the loads are compared as."""
+    records = np.ascontiguousarray(records)
+    return records.view(np.uint8).reshape(records.shape + (LOAD_BYTES,))
+
+
+def launches_of(nu, sweeps):
+    """The launches of a context's diffusion: none where it is skipped, else ceil(sweeps / 8)."""
+    return 0 if np.float32(nu) == 0 or sweeps == 0 else -(-sweeps // D_DIFFUSE)
 
 
 def mixed(mask):
@@ -178,6 +226,10 @@ class ContextModel:
         self.peer = None                         # (a model used as a handle: the model it is compared with)
         self.mask = None                         # the solids: None or bool[dim_y, dim_x]
         self.hist = None                         # the history: {"every", "capacity", "steps", "records"}
+        self.viscous = False                     # (the viscosity's and the loads' queries are among those of queries())
+        self.visc = None                         # the viscosity: None or (nu, sweeps) with nu > 0 and sweeps > 0
+        self.labels, self.bodies = None, 1       # the bodies: None (every solid cell is body 1) or uint8[dim_y, dim_x]
+        self.loads = None                        # the loads recorder: {"every", "capacity", "steps", "records"}
 
     # -- plumbing
     def apply(self, op):
@@ -191,9 +243,15 @@ class ContextModel:
         """Whether include/sfl.h refuses the call with SFL_ERR_STATE in the state the model is in."""
         if self.mask is not None and kind in ("view_scalar", "view_texels") and a["what"] == VIEW_DIVERGENCE:
             return True
-        if self.hist is not None and kind in ("step", "step_n"):
-            due, free = samples_due(self.hist, a.get("n", 1))
-            return due > free
+        if kind in ("set_bodies", "clear_bodies") and self.loads is not None:
+            return True
+        if kind == "loads_history" and self.loads is None:
+            return True
+        for recorder in (self.hist, self.loads):
+            if recorder is not None and kind in ("step", "step_n"):
+                due, free = samples_due(recorder, a.get("n", 1))
+                if due > free:
+                    return True
         return False
 
     def close(self):
@@ -235,6 +293,8 @@ class ContextModel:
         k, u = iters, None
         if self.mask is not None:                # items 3 to 6 of "SOLIDS"; the records above stand between items 1 and 3
             va[self.mask] = 0.0
+        va = self._diffuse(va, dt, dx)           # item 3a of "VISCOSITY": between the forces (the solids zeroed) and the divergence
+        if self.mask is not None:
             self.d = solid_rule.divergence(va, self.mask, dx)
             if until is not None:
                 k, _, u = masked_rule(self.d, self.mask, dx, iters, omega, until[0], until[1])
@@ -250,6 +310,17 @@ class ContextModel:
         if self.follow and self.xy is not None:
             self._advance(dt)
         return k, u
+
+    def _diffuse(self, va, dt, dx):
+        if self.visc is None:
+            return va
+        return np.ascontiguousarray(viscosity_rule.diffuse(va, self.visc[0], dt, dx, self.visc[1], self.mask))
+
+    def load_records(self):
+        """The `bodies` records of "LOADS" from the pressure, the mask and the labels held; zeros while no mask is."""
+        if self.mask is None:
+            return np.zeros(self.bodies, load_rule.DTYPE)
+        return load_rule.loads(self.p, self.mask, self.labels, self.bodies)
 
     # -- writers
     def do_upload(self, field, texture_kind, seed):
@@ -311,6 +382,10 @@ class ContextModel:
             self.hist["steps"] += 1
             if self.hist["steps"] % self.hist["every"] == 0:
                 self.hist["records"].append(self.history_record(self.hist["steps"], dt, dx, k))
+        if self.loads is not None:
+            self.loads["steps"] += 1
+            if self.loads["steps"] % self.loads["every"] == 0:
+                self.loads["records"].append(self.load_records()[None])
 
     def do_step(self, dt, dx, iters, omega):
         self._counted_step(dt, dx, iters, omega)
@@ -331,6 +406,30 @@ class ContextModel:
 
     def do_history_stop(self):
         self.hist = None
+
+    # "VISCOSITY": nu == 0 or sweeps == 0 clears it; sfl_diffuse_velocity is item 3a alone (nothing zeroed, no other field touched)
+    def do_set_viscosity(self, nu, sweeps):
+        self.visc = None if np.float32(nu) == 0 or sweeps == 0 else (nu, sweeps)
+
+    def do_clear_viscosity(self):
+        self.visc = None
+
+    def do_diffuse_velocity(self, nu, dt, dx, sweeps):
+        self.v = np.ascontiguousarray(viscosity_rule.diffuse(self.v, nu, dt, dx, sweeps, self.mask))
+
+    # "LOADS": labels and masks are independent of each other; a restart of the recorder starts afresh
+    def do_set_bodies(self, label_kind, bodies, seed):
+        self.labels = body_labels(label_kind, self.dim_x, self.dim_y, seed)
+        self.bodies = 1 if self.labels is None else bodies
+
+    def do_clear_bodies(self):
+        self.labels, self.bodies = None, 1
+
+    def do_loads_start(self, every, capacity):
+        self.loads = {"every": every, "capacity": capacity, "steps": 0, "records": []}
+
+    def do_loads_stop(self):
+        self.loads = None
 
     # The timeline rule of include/sfl.h: "A step call of n steps consumes the records of steps [0, n).  Later records move down
     # by n.  This applies to sfl_step (n = 1), sfl_step_n, ..." and "Solves, uploads, setup and render calls neither consume nor
@@ -382,6 +481,22 @@ class ContextModel:
     def q_history(self):
         return history_result(self.hist, ())
 
+    def q_viscosity(self):
+        nu, sweeps = (0.0, 0) if self.visc is None else self.visc
+        return as_result(nu=np.float32(nu), sweeps=sweeps)
+
+    def q_bodies(self):
+        labels = np.ones((self.dim_y, self.dim_x), np.uint8) if self.labels is None else self.labels
+        return as_result(labels=labels, bodies=self.bodies, labelled=self.labels is not None)
+
+    def q_loads(self):
+        return as_result(records=load_bytes(self.load_records()[None]))
+
+    def q_loads_history(self):
+        recs = self.loads["records"]
+        stacked = np.stack(recs) if recs else np.zeros((0, 1, self.bodies), load_rule.DTYPE)
+        return as_result(records=load_bytes(stacked), info=np.array([len(recs), self.loads["capacity"], self.loads["steps"], self.bodies], np.int64))
+
     def q_view_scalar(self, what, dx):
         return as_result(scalar=view_rule.scalar(what, self.v, self.p, dx))
 
@@ -429,6 +544,10 @@ class ContextModel:
             out.append(("solids", {}))
         if self.hist is not None:
             out.append(("history", {}))
+        if self.viscous:
+            out += [("viscosity", {}), ("bodies", {}), ("loads", {})]
+            if self.loads is not None:
+                out.append(("loads_history", {}))
         return out
 
 
@@ -448,6 +567,10 @@ class BatchModel:
         self.peer = None
         self.per_member = False                  # the solids: every member's model holds its mask (one shared, or its own)
         self.hist = None                         # the history: {"every", "first", "count", "capacity", "steps", "records"}
+        self.viscous = False                     # (the viscosity's and the loads' queries are among those of queries())
+        self.visc = None                         # the viscosity: {"nu": [one per member], "sweeps", "per_member"}; the members hold (nu, sweeps)
+        self.bodies, self.labels_per_member = 1, False     # the bodies: every member's model holds its labels (or None)
+        self.loads = None                        # the loads recorder: {"every", "first", "count", "capacity", "steps", "records"}
 
     def apply(self, op):
         kind, args = op
@@ -467,9 +590,17 @@ class BatchModel:
                 return True
         if kind == "set_solids" and (self.hist is not None or (self.rec is not None and self.rec["view"] == VIEW_DIVERGENCE)):
             return True
-        if self.hist is not None and kind in ("step_n", "step_n_each", "step_n_until"):
-            due, free = samples_due(self.hist, a["n"])
-            return due > free
+        if kind == "step_n_until" and self.visc is not None:      # "VISCOSITY": refused while one is set, whatever its nu
+            return True
+        if kind in ("set_bodies", "clear_bodies") and self.loads is not None:
+            return True
+        if kind == "loads_history" and self.loads is None:
+            return True
+        for recorder in (self.hist, self.loads):
+            if recorder is not None and kind in ("step_n", "step_n_each", "step_n_until"):
+                due, free = samples_due(recorder, a["n"])
+                if due > free:
+                    return True
         return False
 
     def close(self):
@@ -517,7 +648,15 @@ class BatchModel:
                     members = range(h["first"], h["first"] + h["count"])
                     recs = [self.m[k].history_record(h["steps"], dt[k], dx[k], last[k]) for k in members]
                     h["records"].append({name: np.stack([r[name] for r in recs]) for name in HISTORY_FIELDS})
+            if self.loads is not None:
+                l = self.loads
+                l["steps"] += 1
+                if l["steps"] % l["every"] == 0:
+                    l["records"].append(self._load_records(l["first"], l["count"]))
         return dx, np.stack([last, total], axis=1)
+
+    def _load_records(self, first, count):
+        return np.stack([m.load_records() for m in self.m[first:first + count]])
 
     def _norms(self, dx):                        # (a member with a mask: over its fluid cells)
         self.norms = np.array([m.q_residual(dx[k])["norm"] for k, m in enumerate(self.m)], np.float32)
@@ -598,7 +737,50 @@ class BatchModel:
     def do_history_stop(self):
         self.hist = None
 
+    # "VISCOSITY": one nu for all members or one each; a member with nu == 0 skips the item; set is set, whatever the numbers
+    def do_set_viscosity(self, nu, sweeps, per_member):
+        self.visc = {"nu": list(nu) if per_member else [nu] * self.batch, "sweeps": sweeps, "per_member": bool(per_member)}
+        for m, x in zip(self.m, self.visc["nu"]):
+            m.visc = (x, sweeps)
+
+    def do_clear_viscosity(self):
+        self.visc = None
+        for m in self.m:
+            m.visc = None
+
+    def do_set_bodies(self, label_kind, bodies, seed, per_member):
+        for k, m in enumerate(self.m):
+            m.labels = body_labels(label_kind, self.dim_x, self.dim_y, seed, k if per_member else None)
+            m.bodies = 1 if m.labels is None else bodies
+        self.bodies, self.labels_per_member = self.m[0].bodies, bool(per_member) and self.m[0].labels is not None
+
+    def do_clear_bodies(self):
+        self.do_set_bodies("all one", 1, 0, False)
+
+    def do_loads_start(self, every, capacity, first, count):
+        self.loads = {"every": every, "first": first, "count": count, "capacity": capacity, "steps": 0, "records": []}
+
+    def do_loads_stop(self):
+        self.loads = None
+
     # -- queries
+    def q_viscosity(self):
+        on = self.visc is not None
+        return as_result(nu=np.array(self.visc["nu"] if on else [0.0] * self.batch, np.float32), sweeps=self.visc["sweeps"] if on else 0,
+                         set=on, per_member=on and self.visc["per_member"])
+
+    def q_bodies(self):
+        return as_result(labels=np.stack([m.q_bodies()["labels"] for m in self.m]), bodies=self.bodies, labelled=self.m[0].labels is not None,
+                         per_member=self.labels_per_member)
+
+    def q_loads(self, first, count):
+        return as_result(records=load_bytes(self._load_records(first, count)))
+
+    def q_loads_history(self):
+        l = self.loads
+        stacked = np.stack(l["records"]) if l["records"] else np.zeros((0, l["count"], self.bodies), load_rule.DTYPE)
+        return as_result(records=load_bytes(stacked), info=np.array([len(l["records"]), l["capacity"], l["steps"], self.bodies], np.int64))
+
     def q_download(self, field):
         return as_result(field=self._stack(FIELDS[field]))
 
@@ -657,6 +839,10 @@ class BatchModel:
         if self.m[0].xy is not None: out.append(("tracers", {}))
         if self.solids_set(): out.append(("solids", {}))
         if self.hist is not None: out.append(("history", {}))
+        if self.viscous:
+            first = int(rng.integers(self.batch))
+            out += [("viscosity", {}), ("bodies", {}), ("loads", {"first": first, "count": int(rng.integers(1, self.batch - first + 1))})]
+            if self.loads is not None: out.append(("loads_history", {}))
         return out
 
 
@@ -730,6 +916,28 @@ class LibraryContext:
     def g_clear_solids(self): self.s.set_solids(None)
     def g_history_start(self, every, capacity): self.s.history_start(every, capacity)
     def g_history_stop(self): self.s.history_stop()
+    def g_set_viscosity(self, nu, sweeps): self.s.set_viscosity(nu, sweeps)
+    def g_clear_viscosity(self): self.s.set_viscosity(0.0, 0)
+    def g_diffuse_velocity(self, nu, dt, dx, sweeps): self.s.diffuse_velocity(nu, dt, dx, sweeps)
+    def g_clear_bodies(self): self.s.set_bodies(None)
+    def g_loads_start(self, every, capacity): self.s.loads_start(every, capacity)
+    def g_loads_stop(self): self.s.loads_stop()
+
+    def g_set_bodies(self, label_kind, bodies, seed):
+        self.s.set_bodies(body_labels(label_kind, self.dim_x, self.dim_y, seed), bodies)
+
+    def g_viscosity(self):
+        nu, sweeps = self.s.viscosity()
+        return as_result(nu=np.float32(nu), sweeps=sweeps)
+
+    def g_bodies(self):
+        bodies, labelled = self.s.bodies_info()
+        return as_result(labels=self.s.bodies(), bodies=bodies, labelled=labelled)
+
+    def g_loads(self): return as_result(records=load_bytes(self.s.loads()))
+
+    def g_loads_history(self):
+        return as_result(records=load_bytes(self.s.loads_history()), info=np.array(self.s.loads_info(), np.int64))
 
     def g_poisson_solve_until(self, dx, iters, omega, tol, every):
         k, u = self.s.poisson_solve_until(dx, iters, omega, tol=tol, every=every)
@@ -822,6 +1030,32 @@ class LibraryBatch:
     def g_clear_solids(self): self.b.set_solids(None)
     def g_history_start(self, every, capacity, first, count): self.b.history_start(every, capacity, first, count)
     def g_history_stop(self): self.b.history_stop()
+    def g_set_viscosity(self, nu, sweeps, per_member): self.b.set_viscosity(np.array(nu, np.float32) if per_member else nu, sweeps)
+    def g_clear_viscosity(self): self.b.set_viscosity(None, 0)
+    def g_clear_bodies(self): self.b.set_bodies(None)
+    def g_loads_start(self, every, capacity, first, count): self.b.loads_start(every, capacity, first, count)
+    def g_loads_stop(self): self.b.loads_stop()
+
+    def g_set_bodies(self, label_kind, bodies, seed, per_member):
+        if label_kind == "all one":
+            return self.b.set_bodies(None)
+        labels = [body_labels(label_kind, self.dim_x, self.dim_y, seed, k) for k in (range(self.batch) if per_member else [None])]
+        self.b.set_bodies(np.stack(labels) if per_member else labels[0], bodies)
+
+    def g_viscosity(self):
+        nu, sweeps = self.b.viscosity()
+        on, per_member = ctypes.c_int(0), ctypes.c_int(0)
+        self.sfl.capi.check(self.b._lib.sfl_batch_viscosity_info(self.b._h, ctypes.byref(on), ctypes.byref(per_member), None))
+        return as_result(nu=nu, sweeps=sweeps, set=bool(on.value), per_member=bool(per_member.value))
+
+    def g_bodies(self):
+        bodies, labelled, per_member = self.b.bodies_info()
+        return as_result(labels=self.b.bodies(), bodies=bodies, labelled=labelled, per_member=per_member)
+
+    def g_loads(self, first, count): return as_result(records=load_bytes(self.b.loads(first, count)))
+
+    def g_loads_history(self):
+        return as_result(records=load_bytes(self.b.loads_history()), info=np.array(self.b.loads_info(), np.int64))
 
     def g_set_solids(self, mask_kind, seed, per_member):
         members = range(self.batch) if per_member else [None]
@@ -862,16 +1096,20 @@ class LibraryBatch:
 class Subject:
     """What a set of sequences runs on: `cases` = [(dim_x, dim_y, seed)], one sequence each."""
 
-    def __init__(self, name, kind, cases, options=(), nranks=1, batch=0, large=False, still_solves=False, length=30, solids=False):
+    def __init__(self, name, kind, cases, options=(), nranks=1, batch=0, large=False, still_solves=False, length=30, solids=False, viscous=False):
         self.name, self.kind, self.cases, self.options, self.nranks, self.batch, self.large = name, kind, cases, tuple(options), nranks, batch, large
         self.still_solves, self.length = still_solves, length   # still_solves: steps on a lattice velocity run iters = 0 (it stays on the lattice)
         self.solids = solids                                    # the solids' and the histories' calls are in the vocabulary
+        self.viscous = viscous                                  # ... and the viscosity's and the loads' (on top of the solids')
 
     def model(self, oracle, case):
         dim_x, dim_y, _ = case
         if self.kind == "batch":
-            return BatchModel(oracle, dim_x, dim_y, self.batch)
-        return (ContextModel if self.kind == "context" else SlabsModel)(oracle, dim_x, dim_y)
+            model = BatchModel(oracle, dim_x, dim_y, self.batch)
+        else:
+            model = (ContextModel if self.kind == "context" else SlabsModel)(oracle, dim_x, dim_y)
+        model.viscous = self.viscous
+        return model
 
     def library(self, sfl, case):
         dim_x, dim_y, _ = case
@@ -883,10 +1121,16 @@ class Subject:
         own = {"context": CONTEXT_WRITERS + CONTEXT_QUERIES, "slabs": SLAB_WRITERS + SLAB_QUERIES, "batch": BATCH_WRITERS + BATCH_QUERIES}[self.kind]
         if not self.solids:
             return own
-        return tuple(k for k in own if k not in SOLID_LEFT_OUT) + SOLID_WRITERS + SOLID_QUERIES
+        own = tuple(k for k in own if k not in SOLID_LEFT_OUT) + SOLID_WRITERS + SOLID_QUERIES
+        if not self.viscous:
+            return own
+        return own + (VISCOUS_WRITERS if self.kind == "context" else BATCH_VISCOUS_WRITERS) + VISCOUS_QUERIES
 
     def option_values(self):
         return {"context": OPTION_VALUES, "slabs": SLAB_OPTION_VALUES, "batch": {}}[self.kind]
+
+
+VISCOUS_LENGTH = {"context": 50, "batch": 48}     # ops of a sequence of the viscous subjects: the shortest the deck fits in
 
 
 def _cases(dim_x, dim_y, seeds, base):
@@ -905,13 +1149,21 @@ SUBJECTS = [
     # one-launch step of a small grid; the batch's members 61 x 81 and 7 x 9 (a large batch refuses solids)
     Subject("solid-context", "context", _cases(130, 70, 3, 700) + _cases(61, 81, 2, 750), length=36, solids=True),
     Subject("solid-batch", "batch", _cases(61, 81, 3, 800) + _cases(7, 9, 2, 850), batch=3, length=36, solids=True),
+    # viscosity and loads, on top of the solids' vocabulary: a viscosity set, cleared and set again with masks coming and going,
+    # the diffusion as an operator of one, two and three launches, labels, and a loads recorder counted across calls.  130 x 70 is
+    # 3 x 3 ragged diffusion tiles (64 x 32: the last column two cells wide, the last row six deep) and, cleared, the general
+    # kernels and the step seams; 61 x 81 one tile column of three rows and, cleared, the one-launch step of a small grid; 7 x 9 a
+    # batch member smaller than a wavefront (slabs and large batches refuse viscosity)
+    Subject("viscous-context", "context", _cases(130, 70, 3, 900) + _cases(61, 81, 2, 950), length=VISCOUS_LENGTH["context"], solids=True, viscous=True),
+    Subject("viscous-batch", "batch", _cases(61, 81, 3, 1000) + _cases(7, 9, 2, 1050), batch=3, length=VISCOUS_LENGTH["batch"], solids=True, viscous=True),
 ]
 
 
 # ---- the generator ---------------------------------------------------------------------------------------------------
 class Gate:
     """What the generator and the census follow of a handle with solids and histories, from the op list alone: the masks, the
-    history's counts, the recorder's view, the trail and a batch's reports -- enough to say which calls include/sfl.h refuses
+    history's counts, the recorder's view, the trail, a batch's reports, the viscosity set, the label kind, the loads recorder's
+    counts and how many two-launch diffusions the handle has made -- enough to say which calls include/sfl.h refuses
     (the models decide the same from their own state; tests/test_sequences.py holds the two against each other)."""
 
     def __init__(self, batch, dim_x, dim_y):
@@ -919,13 +1171,16 @@ class Gate:
         self.masks, self.hist = None, None                    # [mask] or one per member; [every, capacity, steps]
         self.rec, self.view, self.trail = False, None, False
         self.norms = self.iters = False
+        self.visc = None                                      # {"nu": [one per member, or one], "sweeps", "per_member"} while one is set
+        self.labels, self.loads = None, None                  # the label kind while labels are set; [every, capacity, steps]
+        self.two_launches = 0                                 # two-launch diffusions made so far: the third buffer has held a velocity
 
     def mixed(self):
         return self.masks is not None and any(mixed(m) for m in self.masks)
 
     def remedy(self, kind, a):
         """None when the header takes the call, else the kind of a call to make in its place: the one that ends what it is
-        refused for, or (the _until calls under a mask) its sibling that honours solids."""
+        refused for, or (the _until calls under a mask, step_n_until under a viscosity) its sibling that honours them."""
         on = self.masks is not None
         if self.batch:
             if on and kind in ("step_n_until", "poisson_solve_until"): return kind.replace("until", "each")
@@ -933,17 +1188,23 @@ class Gate:
             if on and kind in ("record_view", "view_render_members") and a["what"] == VIEW_DIVERGENCE: return "clear_solids"
             if kind == "set_solids" and self.hist is not None: return "history_stop"
             if kind == "set_solids" and self.rec and self.view == VIEW_DIVERGENCE: return "record_stop"
+            if kind == "step_n_until" and self.visc is not None: return "step_n_each"      # "VISCOSITY": refused while one is set
         elif on and kind in ("view_scalar", "view_texels") and a["what"] == VIEW_DIVERGENCE:
             return "clear_solids"
+        if kind in ("set_bodies", "clear_bodies") and self.loads is not None: return "loads_stop"   # "LOADS": the samples' layout
         if self.hist is not None and kind in STEPS:
             every, capacity, steps = self.hist
             if (steps + a.get("n", 1)) // every - steps // every > capacity - steps // every: return "history_stop"
+        if self.loads is not None and kind in STEPS:
+            every, capacity, steps = self.loads
+            if (steps + a.get("n", 1)) // every - steps // every > capacity - steps // every: return "loads_stop"
         return None
 
     def missing(self, kind):
         """A query of something the handle does not hold now: the kind of the call that makes it."""
         need = {"history": (self.hist is not None, "history_start"), "trail": (self.trail or self.batch > 0, "trail_start"),
-                "frames": (self.rec, "record_start"), "record_view": (self.rec, "record_start")}
+                "frames": (self.rec, "record_start"), "record_view": (self.rec, "record_start"),
+                "loads_history": (self.loads is not None, "loads_start")}
         if self.batch:
             need.update(residual=(self.norms, "step_n_each"), iterations=(self.iters, "step_n_until"))
         have, maker = need.get(kind, (True, None))
@@ -963,6 +1224,16 @@ class Gate:
         if kind == "record_stop": self.rec, self.view = False, None
         if kind == "trail_start": self.trail = True
         if kind in ("trail_stop", "set_tracers"): self.trail = False
+        if kind == "set_viscosity":
+            self.visc = {"nu": list(a["nu"]) if a.get("per_member") else [a["nu"]], "sweeps": a["sweeps"], "per_member": bool(a.get("per_member"))}
+            if not self.batch and (a["nu"] == 0 or a["sweeps"] == 0): self.visc = None      # (a context: cleared)
+        if kind == "clear_viscosity": self.visc = None
+        if kind == "diffuse_velocity" and launches_of(a["nu"], a["sweeps"]) == 2: self.two_launches += 1
+        if kind == "set_bodies": self.labels = None if a["label_kind"] == "all one" else a["label_kind"]
+        if kind == "clear_bodies": self.labels = None
+        if kind == "loads_start": self.loads = [a["every"], a["capacity"], 0]
+        if kind == "loads_stop": self.loads = None
+        if kind in STEPS and self.loads is not None: self.loads[2] += a.get("n", 1)
         if self.batch:
             if kind in ("step_n", "poisson_solve") or (kind == "upload" and a["field"] in (FD, FP)): self.norms = self.iters = False
             if kind in ("step_n_each", "poisson_solve_each"): self.norms, self.iters = True, False
@@ -1023,6 +1294,8 @@ class _Draw:
         self.hints = {k: fixed.pop(k) for k in list(fixed) if k.startswith("_")}
         a = self._args(kind, self.sub.kind == "batch")
         a.update(fixed)
+        if kind == "set_bodies":
+            a["bodies"] = LABEL_KINDS[a["label_kind"]]
         op = (kind, a)
         if self.shadow is not None:
             op = self._under_the_halo(op)
@@ -1093,6 +1366,24 @@ class _Draw:
                 first = int(r.integers(B))
                 a.update(first=first, count=int(r.integers(1, B - first + 1)))
             return a
+        if kind == "set_viscosity":
+            if not batch: return {"nu": self.pick(NUS), "sweeps": self.pick(CONTEXT_SWEEPS)}
+            per_member = bool(r.integers(2))
+            return {"nu": self.each(lambda: self.pick(NUS)) if per_member else self.pick(NUS), "sweeps": self.pick(BATCH_SWEEPS), "per_member": per_member}
+        if kind == "diffuse_velocity": return {"nu": self.pick(NUS), "dt": self.dt(), "dx": self.pick(DXS), "sweeps": self.pick(CONTEXT_SWEEPS)}
+        if kind == "set_bodies":
+            a = {"label_kind": self.pick(sorted(LABEL_KINDS)), "seed": int(r.integers(100))}
+            a["bodies"] = LABEL_KINDS[a["label_kind"]]
+            return dict(a, per_member=bool(r.integers(2))) if batch else a
+        if kind == "loads_start":
+            a = {"every": self.pick((1, 2, 3)), "capacity": self.pick((2, CAPACITY))}
+            if batch:
+                first = int(r.integers(B))
+                a.update(first=first, count=int(r.integers(1, B - first + 1)))
+            return a
+        if kind == "loads" and batch:
+            first = int(r.integers(B))
+            return {"first": first, "count": int(r.integers(1, B - first + 1))}
         if kind == "queue_forces":
             n = int(r.integers(1, 4))
             a = {"step": int(r.integers(0, 4)), "cells": self.cells(n), "vels": self.vels(n)}
@@ -1231,6 +1522,8 @@ SOLID_HANDOVERS = {
 
 
 def handovers_of(subject):
+    if subject.viscous:
+        return viscous_handovers(subject)
     if subject.solids:
         return SOLID_HANDOVERS[subject.kind]
     if subject.kind == "batch":
@@ -1252,6 +1545,8 @@ def planted(subject):
     """The items the generator plants whole (the ops of an item stay next to each other): the hand-overs, and every option
     value in front of a writer it affects, so that no value is only ever set."""
     kind = subject.kind
+    if subject.viscous:
+        return planted_viscous(subject)
     if subject.solids:
         return planted_solids(subject)
     if kind == "batch":
@@ -1364,6 +1659,120 @@ def planted_solids(subject):
     ]
 
 
+def _visc(nu, sweeps, **more): return ("set_viscosity", dict({"nu": nu, "sweeps": sweeps}, **more))
+def _diff(nu, sweeps): return ("diffuse_velocity", {"nu": nu, "sweeps": sweeps})
+def _bodies(label_kind, **more): return ("set_bodies", dict({"label_kind": label_kind}, **more))
+def _loads(every, capacity=CAPACITY, **more): return ("loads_start", dict({"every": every, "capacity": capacity}, **more))
+
+
+def viscous_items(subject):
+    """{what it walks: item} of the subjects with viscosity and loads, hints as in planted_solids.  An item says itself what it
+    needs ended in front of it (a recorder that refuses set_bodies, a history that refuses a batch's mask, a following set that
+    keeps the seams away); every history_start, loads_start and record_view of a sequence stands in one of these items, so that
+    no recorder of two samples is left on behind one."""
+    clear, clear_nu, refused = ("clear_solids", {}), ("clear_viscosity", {}), {"_refused": True}
+    no_loads, no_hist, noise = ("loads_stop", {}), ("history_stop", {}), _up("noise")
+    A, B = subject.cases[0][:2], subject.cases[-1][:2]
+    if subject.kind == "context":
+        step, step2, step3 = ("step", {}), ("step_n", {"n": 2}), ("step_n", {"n": 3})
+        solved = ("step", {"iters": 5})          # (a pressure that is not all zeros in front of a load)
+        return {
+            # the operator in each launch class, a reader of the velocity right behind each: the result of one launch lies in the
+            # step's second buffer, of two in the third, of three in the second again -- the second two-launch call finds the
+            # third buffer holding the velocity it was swapped for
+            "diffusions of two, three, two and one launches at 130 x 70":
+                [("upload", {"field": FV, "texture_kind": "noise", "_shape": A}), _diff(0.3, 9), ("advect_velocity", {}), _diff(0.05, 17), step, _diff(2.5, 9),
+                 ("calculate_divergence", {}), _diff(0.3, 1), ("advance_tracers", {}), step2],
+            "diffusions of three, two, two and one launches at 61 x 81":
+                [("upload", {"field": FV, "texture_kind": "noise", "_shape": B}), _diff(2.5, 17), step, _diff(0.3, 9), ("advance_tracers", {}), _diff(0.05, 9),
+                 ("advect_velocity", {}), _diff(0.3, 1), ("calculate_divergence", {}), step2],
+            # a viscosity of two launches in force: no mask, a mask set behind it, the mask cleared while it stays; a history samples
+            "a viscosity in force while masks come and go":
+                [clear, noise, ("history_start", {"every": 2, "capacity": CAPACITY}), _visc(0.3, 9), step, step2, _solid("disc"), step, step2, clear, step, step2,
+                 ("history", {})],
+            # cleared: each plain path again.  The seams (every condition set in front) with a loads recorder on: zero records
+            "cleared at 130 x 70: the step seams, and samples without solids inside their loop":
+                [("forget_forces", {"_shape": A}), no_hist, ("set_tracers", {"follow": False}), clear, _opt("OPT_ADVECT_KERNEL", 2), _loads(1), _visc(0.05, 8), step2,
+                 clear_nu, step3, ("loads_history", {})],
+            "cleared at 61 x 81: the one-launch step of a small grid":
+                [_opt("OPT_SOR_KERNEL", 0, _shape=B), _opt("OPT_SOR_FUSE", 0), _opt("OPT_ADVECT_KERNEL", 0), _opt("OPT_SMALL_GRID", 1), clear, _visc(0.3, 1), step,
+                 clear_nu, step, step2],
+            "cleared with OPT_FUSE_PROJECTION = 0":
+                [_opt("OPT_ADVECT_KERNEL", 1), _opt("OPT_FUSE_DIVERGENCE", 0), _opt("OPT_FUSE_PROJECTION", 0), _visc(0.3, 3), step, clear_nu, step, step2, _opt("OPT_FUSE_DIVERGENCE", 1),
+                 _opt("OPT_FUSE_PROJECTION", 1)],
+            "cleared with a mask still set": [_solid("plate"), _visc(2.5, 9), step2, clear_nu, step, ("flow_stats", {})],
+            "the solver's options in front of a solve":
+                [_opt("OPT_SOR_KERNEL", 1), ("poisson_solve", {}), _opt("OPT_SOR_KERNEL", 2), _opt("OPT_SOR_FUSE", 2), ("poisson_continue", {}), _opt("OPT_SOR_FUSE", 16),
+                 ("poisson_solve_until", {})],
+            # (the switch the seams depend on is only off inside its own item)
+            "a viscous step_n with the seams switched off": [_opt("OPT_STEP_SEAMS", 0), _visc(0.05, 3), step2, _opt("OPT_STEP_SEAMS", 1)],
+            # the companions of a step, all at once under a viscosity and a mask; the recorder spans three calls that leave remainders
+            "a history, a trail and a loads recorder under a viscosity and a mask":
+                [no_loads, ("clear_bodies", {}), noise, ("set_tracers", {"follow": True}), ("trail_start", {}), ("history_start", {"every": 1, "capacity": CAPACITY}), _solid("disc"),
+                 _bodies("halves"), _loads(2), _visc(0.3, 3), solved, step2, step3, ("history", {}), ("trail", {}), ("loads_history", {}), ("loads", {})],
+            "labels before the mask, a mask replaced and cleared under labels, labels replaced and reset":
+                [clear, no_loads, _bodies("sixteen"), _solid("disc"), solved, ("loads", {}), _solid("seeded"), ("loads", {}), clear, ("loads", {}),
+                 _bodies("with zeros"), _solid("channel"), solved, ("loads", {}), ("clear_bodies", {}), ("loads", {}), ("bodies", {})],
+            "a loads recorder across calls that leave remainders, restarted while on":
+                [_solid("isolated"), _loads(3), step2, solved, step2, ("loads_history", {}), _loads(2), step, step2, ("loads_history", {})],
+            "set_bodies, refused while the recorder is on": [_loads(1), _bodies("halves", **refused), step, ("bodies", {}), no_loads, ("clear_bodies", {})],
+            # three admission checks in a row: the third refuses, and the two counters in front of it and every field stay
+            "a full loads recorder refuses the call whole, a history and a trail on":
+                [("set_tracers", {"follow": True}), ("trail_start", {}), ("history_start", {"every": 1, "capacity": CAPACITY}), _loads(1, 2),
+                 ("step_n", dict(n=3, **refused)), ("history", {}), ("trail", {}), ("loads_history", {}), no_loads, step, no_hist],
+        }
+    s1, s2, sn, each = ("step_n", {"n": 1}), ("step_n", {"n": 2}), ("step_n", {}), ("step_n_each", {})
+    solved, whole = ("step_n", {"n": 1, "iters": 5}), {"first": 0, "count": subject.batch}
+    return {
+        # the coefficient table staged through its two slots by calls queued back to back: nothing is read in between
+        "four step calls back to back under a per-member nu, one member at 0":
+            [no_hist, noise, ("history_start", dict(every=2, capacity=CAPACITY, **whole)), _visc([0.3, 0.0, 2.5], 3, per_member=True), sn, each, sn, each,
+             ("download", {"field": FV}), ("history", {}), no_hist],
+        "three step calls back to back under a per-member nu and a mask":
+            [no_hist, ("record_start", {}), ("record_view", {"what": 2}), _solid("plate", per_member=False), _visc([0.0, 0.05, 0.3], 10, per_member=True), each, sn, each, ("residual", {})],
+        "a per-member nu replaced by a shared one":
+            [_visc([2.5, 0.0, 0.05], 3, per_member=True), sn, _visc(0.3, 1, per_member=False), each, ("residual", {}), ("viscosity", {})],
+        # cleared: the calls that are refused or switched off while a viscosity is set -- the step to a tolerance and the replay
+        # of a timeline in one launch (a record in a later step, no following set, no mask), a loads recorder counting through
+        "cleared: step_n_until and the one-launch replay":
+            [clear, no_hist, _visc(0.3, 3, per_member=False), sn, clear_nu, _loads(2, **whole), ("step_n_until", {}), ("iterations", {}), ("set_tracers", {"follow": False}),
+             ("forget_forces", {}), ("queue_forces", {"step": 1}), ("step_n", {"n": 3}), ("loads_history", {}), s1],
+        "step_n_until, refused while a viscosity is set": [clear, _visc(0.05, 1, per_member=False), ("step_n_until", dict(refused)), each, ("residual", {})],
+        "a history, the recorder and a following set under a viscosity":
+            [clear, ("record_start", {}), ("record_view", {"what": 1}), ("history_start", dict(every=1, capacity=CAPACITY, **whole)), ("set_tracers", {"follow": True}),
+             _visc(0.3, 3, per_member=False), sn, each, ("history", {}), ("frames", {}), ("tracers", {}), no_hist],
+        "a loads recorder under a per-member viscosity, mask and labels":
+            [no_hist, no_loads, ("clear_bodies", {}), ("record_start", {}), _solid("disc", per_member=True), _bodies("halves", per_member=True), _loads(2, **whole),
+             _visc([0.3, 0.0, 0.05], 3, per_member=True), solved, s2, ("step_n_each", {"n": 3}), ("loads_history", {}), ("loads", dict(whole))],
+        "labels before the mask, a mask replaced and cleared under labels, labels replaced and reset":
+            [clear, no_hist, no_loads, _bodies("sixteen", per_member=False), _solid("disc", per_member=False), solved, ("loads", dict(whole)),
+             _solid("seeded", per_member=True), ("loads", dict(whole)), clear, ("loads", dict(whole)), _bodies("with zeros", per_member=True), _solid("channel"), solved,
+             ("loads", dict(whole)), ("clear_bodies", {}), ("loads", dict(whole)), ("bodies", {})],
+        "a loads recorder across calls that leave remainders, restarted while on":
+            [no_hist, _solid("isolated", per_member=False), _loads(3), s2, solved, ("step_n_each", {"n": 2}), ("loads_history", {}), _loads(2), s1, s2, ("loads_history", {})],
+        "set_bodies, refused while the recorder is on": [_loads(1), _bodies("halves", **refused), sn, ("bodies", {}), no_loads, ("clear_bodies", {})],
+        # four admission checks in a row (frames, trail, history, loads): the last refuses, and the counters in front of it stay
+        "a full loads recorder refuses the call whole, a history and the recorder on":
+            [clear, ("record_start", {}), ("record_view", {"what": 0}), ("history_start", dict(every=1, capacity=CAPACITY, **whole)), _loads(1, 2, **whole), ("step_n", dict(n=3, **refused)), ("history", {}),
+             ("frames", {}), ("loads_history", {}), no_loads, s1, no_hist],
+        # (the calls to a tolerance need the mask and the viscosity gone: they stand in items that say so)
+        "cleared: a solve to a tolerance, then a viscosity again": [clear, clear_nu, ("poisson_solve_until", {}), ("iterations", {}), ("set_viscosity", {}), sn],
+        "cleared: a step to a tolerance, then a viscosity again": [clear, clear_nu, ("step_n_until", {}), ("iterations", {}), ("set_viscosity", {}), each],
+        "cleared: a solve to a tolerance": [clear, clear_nu, ("poisson_solve_until", {}), ("iterations", {}), sn],
+        "cleared: a solve to a tolerance behind a step call": [clear, clear_nu, sn, ("poisson_solve_until", {}), ("iterations", {})],
+    }
+
+
+def planted_viscous(subject):
+    return list(viscous_items(subject).values())
+
+
+def viscous_handovers(subject):
+    """The items as chains for has_handover: the fixed arguments without the hints."""
+    return {what: [_link(kind, **{k: v for k, v in fixed.items() if not k.startswith("_")}) for kind, fixed in item]
+            for what, item in viscous_items(subject).items()}
+
+
 def _prologue(subject, index):
     """What every sequence starts with: fields and a tracer set with a trail; a batch a recording and an envelope."""
     common = [_up(("noise", "still", "fast", "whole-cell", "noise", "fast")[index % 6]), ("upload", {"field": FC})]
@@ -1373,7 +1782,20 @@ def _prologue(subject, index):
     return common + ([("trail_start", {})] if subject.kind == "context" else [("record_start", {}), ("envelope", {})])
 
 
-NEEDS = {"trail": "trail", "frames": "rec", "record_view": "rec", "residual": "norms", "iterations": "iters", "history": "hist"}
+def _epilogue(subject):
+    """What every sequence of the viscous subjects ends with: a velocity that is not still, a mask with solid and fluid cells, a
+    viscosity, a step that diffuses and solves, and the loads of the pressure it left -- so that no sequence compares only loads
+    without a face or without a force, or steps without a diffusion that changes a bit."""
+    if not subject.viscous:
+        return []
+    if subject.kind == "context":
+        return [_up("noise"), ("set_solids", {}), _visc(0.3, 3), ("step", {"iters": 5}), ("loads", {})]
+    return [("history_stop", {}), _up("noise"), ("set_solids", {}), _visc([0.3, 0.0, 0.05], 3, per_member=True), ("step_n", {"n": 1, "iters": 5}),
+            ("loads", {"first": 0, "count": subject.batch})]
+
+
+NEEDS = {"trail": "trail", "frames": "rec", "record_view": "rec", "residual": "norms", "iterations": "iters", "history": "hist",
+         "loads_history": "loads"}
 
 
 def _state_after(kind, fixed, st, batch):
@@ -1385,6 +1807,8 @@ def _state_after(kind, fixed, st, batch):
     if kind == "record_stop": st["rec"] = False
     if kind == "history_start": st["hist"] = True
     if kind == "history_stop": st["hist"] = False
+    if kind == "loads_start": st["loads"] = True
+    if kind == "loads_stop": st["loads"] = False
     if batch:
         if kind in ("step_n", "poisson_solve") or (kind == "upload" and fixed.get("field") in (FD, FP)): st["norms"] = st["iters"] = False
         if kind in ("step_n_each", "poisson_solve_each"): st["norms"], st["iters"] = True, False
@@ -1396,7 +1820,7 @@ def _settle(subject, index, items):
     """The sequence's items in an order in which every op is valid: a query that comes when what it reads is gone (a trail,
     a recording, a report) moves in front of the item that ended it -- the last moment it can be asked."""
     batch = subject.kind == "batch"
-    st = {"trail": True, "rec": True, "norms": not batch, "iters": False, "hist": False}      # (behind the prologue)
+    st = {"trail": True, "rec": True, "norms": not batch, "iters": False, "hist": False, "loads": False}      # (behind the prologue)
     out, ended_by = [], {}                       # ended_by: name -> the item (its position in out) that ended it
     for item in items:
         if len(item) == 1 and item[0][0] in NEEDS and not st[NEEDS[item[0][0]]] and NEEDS[item[0][0]] in ended_by:
@@ -1418,6 +1842,8 @@ def _under_masks(items):
         ends = [kind == "set_solids" for kind, fixed in item if kind in ("set_solids", "clear_solids") and not fixed.get("_refused")]
         return ends[-1] if ends else None
     setters, clearers, others = ([item for item in items if leaves(item) is which] for which in (True, False, None))
+    if not setters:             # (no item of the sequence leaves a mask set: nothing to stand behind)
+        return items
     part = lambda group, at: group[at * len(group) // len(setters):(at + 1) * len(group) // len(setters)]
     return [x for at, item in enumerate(setters) for x in [item] + part(others, at) + part(clearers, at)]
 
@@ -1441,7 +1867,8 @@ def plan(subject):
         if len(item) == 1 and item[0][0] in ("set_option", "upload"): have[item[0][0]] = have.get(item[0][0], 0) + 1
     for kind in subject.kinds():
         items += [[(kind, {})] for _ in range(max(0, 3 - have.get(kind, 0)))]
-    room = [subject.length - len(p) for p in starts]
+    ends = [_epilogue(subject) for _ in starts]
+    room = [subject.length - len(p) - len(e) for p, e in zip(starts, ends)]
     dealt = [[] for _ in starts]
     order = sorted(rng.permutation(len(items)), key=lambda at: -len(items[at]))   # (stable: the long items first, so that they fit)
     # with the fused step boundaries: the items that reach it go round first, one to every sequence
@@ -1456,7 +1883,8 @@ def plan(subject):
         assert room[k] >= len(items[at]), f"{subject.name}: the deck does not fit {len(subject.cases)} sequences of {subject.length}"
         dealt[k].append([(kind, dict(fixed)) for kind, fixed in items[at]])
         room[k] -= len(items[at])
-    writers = [k for k in subject.kinds() if k not in QUERIES and k not in ("set_option", "forget_forces", "trail_stop", "record_stop", "clear_solids", "history_stop") and
+    writers = [k for k in subject.kinds() if k not in QUERIES and k not in ("set_option", "forget_forces", "trail_stop", "record_stop", "clear_solids", "history_stop", "clear_viscosity",
+                                                                   "clear_bodies", "loads_stop") and
                not (subject.still_solves and k == "set_tracers")]
     plans = []
     for k, mine in enumerate(dealt):
@@ -1471,7 +1899,7 @@ def plan(subject):
         for item in mine:
             for kind, fixed in item:
                 if kind == "upload" and "field" not in fixed: fixed["field"] = int(rng.integers(4))
-        plans.append(starts[k] + _settle(subject, k, mine))
+        plans.append(starts[k] + _settle(subject, k, mine) + ends[k])
     return plans
 
 
@@ -1688,6 +2116,151 @@ class ReplacedMaskIsIgnored(ContextModel):
 
 
 SOLID_STAND_INS = (ClearedSolidsStillWall, SolidPressureFromThePartner, ReplacedMaskIsIgnored)
+
+
+# ---- and five for the state the viscosity and the loads add ----------------------------------------------------------------
+class ThirdBufferComesBack(ContextModel):
+    """After a two-launch diffuse_velocity on a handle that has made one before, the velocity is what the third buffer held
+    before the call: the velocity the previous such call was given (the swap names the wrong buffer)."""
+    third = None
+
+    def do_diffuse_velocity(self, nu, dt, dx, sweeps):
+        before = self.v
+        super().do_diffuse_velocity(nu, dt, dx, sweeps)
+        if launches_of(nu, sweeps) == 2:
+            if self.third is not None:
+                self.v = self.third
+            self.third = before
+
+
+class ClearedViscosityStillDiffuses(ContextModel):
+    """The first step after clear_viscosity still diffuses where a mask is set (a stale hook in front of the solids')."""
+    stale = None
+
+    def do_clear_viscosity(self):
+        self.stale = self.visc
+        super().do_clear_viscosity()
+
+    def do_set_viscosity(self, nu, sweeps):
+        self.stale = None
+        super().do_set_viscosity(nu, sweeps)
+
+    def step_once(self, dt, dx, iters, omega, until=None):
+        if self.visc is None and self.stale is not None and self.mask is not None:
+            self.visc, self.stale = self.stale, None
+            try:
+                return super().step_once(dt, dx, iters, omega, until)
+            finally:
+                self.visc = None
+        self.stale = None
+        return super().step_once(dt, dx, iters, omega, until)
+
+
+class _MemberOfStaleCoefficients(ContextModel):
+    coefficients_of = None      # (dt, dx) the coefficients are formed from, where they are not the step's own
+
+    def _diffuse(self, va, dt, dx):
+        return super()._diffuse(va, *(self.coefficients_of or (dt, dx)))
+
+
+class EachKeepsThePreviousCoefficients(BatchModel):
+    """A step_n_each right behind a step_n diffuses with the a and c of that step_n (the table's other slot)."""
+    previous = None
+
+    def __init__(self, oracle, dim_x, dim_y, batch):
+        super().__init__(oracle, dim_x, dim_y, batch)
+        self.m = [_MemberOfStaleCoefficients(oracle, dim_x, dim_y) for _ in range(batch)]
+
+    def apply(self, op):
+        kind, a = op
+        if kind == "step_n_each" and self.previous is not None and not self.refuses(kind, a):
+            for m in self.m:
+                m.coefficients_of = self.previous
+        out = super().apply(op)
+        for m in self.m:
+            m.coefficients_of = None
+        self.previous = (a["dt"], a["dx"]) if kind == "step_n" and out is None else None     # (any other call in between: the fault sleeps)
+        return out
+
+
+class LoadsCountStartsAgainEveryCall(ContextModel):
+    """The loads recorder counts the steps of one call, not across calls."""
+
+    def apply(self, op):
+        if op[0] in ("step", "step_n") and self.loads is not None and not self.refuses(*op):
+            self.loads["steps"] = 0
+        return super().apply(op)
+
+
+class LabelsCountWhereSolidAtSetBodies(ContextModel):
+    """A label counts where the cell was solid when set_bodies was called, not at the time of the sample."""
+    counted = None
+
+    def _remember(self):
+        held = np.zeros((self.dim_y, self.dim_x), bool) if self.mask is None else self.mask
+        self.counted = np.where(held, np.uint8(1) if self.labels is None else self.labels, np.uint8(0)).astype(np.uint8)
+
+    def do_set_bodies(self, label_kind, bodies, seed):
+        super().do_set_bodies(label_kind, bodies, seed)
+        self._remember()
+
+    def do_clear_bodies(self):
+        super().do_clear_bodies()
+        self._remember()
+
+    def load_records(self):
+        if self.mask is None or self.counted is None:
+            return super().load_records()
+        return load_rule.loads(self.p, self.mask, self.counted, self.bodies)
+
+
+VISCOUS_STAND_INS = (ThirdBufferComesBack, ClearedViscosityStillDiffuses, EachKeepsThePreviousCoefficients)
+LOAD_STAND_INS = (LoadsCountStartsAgainEveryCall, LabelsCountWhereSolidAtSetBodies)
+
+
+def stand_in_subject(cls):
+    """The name of the subject whose sequences a faulty model of the viscosity or the loads is walked through."""
+    return "viscous-batch" if issubclass(cls, BatchModel) else "viscous-context"
+
+
+def viscous_fresh_handle_check(oracle, make_handle, dim_x=61, dim_y=81, seed=3):
+    """The kind of check the direct tests of the viscosity and the loads are: a fresh handle and every new call once, in one
+    fixed order -- mask, labels, recorder, viscosity, one step call, the reads; one diffusion of each launch class; cleared
+    ONCE with the mask cleared too, every field uploaded again, one step."""
+    up = lambda field: ("upload", {"field": field, "texture_kind": "noise", "seed": seed})
+    solve = {"dx": 0.5, "iters": 5, "omega": 1.5}
+    ops = [up(FV), up(FC), ("set_solids", {"mask_kind": "disc", "seed": 7}), ("set_bodies", {"label_kind": "halves", "bodies": 2, "seed": 1}), ("bodies", {}),
+           ("loads_start", {"every": 2, "capacity": 4}), ("set_viscosity", {"nu": 0.3, "sweeps": 3}), ("viscosity", {}),
+           ("step_n", dict({"n": 3, "dt": 1 / 30.0}, **solve)), ("loads", {}), ("loads_history", {}), ("loads_stop", {}), ("clear_bodies", {}), ("loads", {}),
+           ("diffuse_velocity", {"nu": 0.3, "dt": 0.1, "dx": 0.5, "sweeps": 1}), ("download", {"field": FV}),
+           ("diffuse_velocity", {"nu": 0.3, "dt": 0.1, "dx": 0.5, "sweeps": 9}), ("download", {"field": FV}),
+           ("diffuse_velocity", {"nu": 0.3, "dt": 0.1, "dx": 0.5, "sweeps": 17}), ("download", {"field": FV}),
+           ("clear_solids", {}), ("clear_viscosity", {}), ("viscosity", {}), up(FV), up(FC), up(FD), up(FP), ("step", dict({"dt": 1 / 30.0}, **solve))]
+    model, handle = ContextModel(oracle, dim_x, dim_y), make_handle(dim_x, dim_y)
+    for op in ops:
+        want, got = model.apply(op), handle.apply(op)
+        if want is not None:
+            compare(got, want, f"a fresh handle, one order: {op[0]}")
+    compare(handle.snapshot(), model.snapshot(), "a fresh handle, one order")
+
+
+def viscous_batch_fresh_handle_check(oracle, make_handle, dim_x=7, dim_y=9, batch=3, seed=3):
+    """The same for a batch: a per-member nu, one step_n, the reads, one step_n_each on other numbers, its norms; cleared once."""
+    up = lambda field: ("upload", {"field": field, "texture_kind": "noise", "seed": seed})
+    ops = [up(FV), up(FC), ("set_solids", {"mask_kind": "disc", "seed": 7, "per_member": False}),
+           ("set_bodies", {"label_kind": "halves", "bodies": 2, "seed": 1, "per_member": True}), ("bodies", {}),
+           ("loads_start", {"every": 2, "capacity": 4, "first": 0, "count": batch}), ("set_viscosity", {"nu": [0.3, 0.0, 2.5], "sweeps": 3, "per_member": True}),
+           ("viscosity", {}), ("step_n", {"n": 3, "dt": 1 / 30.0, "dx": 0.5, "iters": 5, "omega": 1.5}), ("loads", {"first": 0, "count": batch}), ("loads_history", {}),
+           ("download", {"field": FV}),
+           ("step_n_each", {"n": 2, "dt": [0.1, 0.25, 1 / 30.0], "dx": [1.0, 0.5, 1.0], "iters": [3, 4, 5], "omega": [1.0, 1.5, 1.96]}), ("residual", {}),
+           ("loads_stop", {}), ("clear_bodies", {}), ("clear_solids", {}), ("clear_viscosity", {}), ("viscosity", {}),
+           ("step_n", {"n": 1, "dt": 1 / 30.0, "dx": 0.5, "iters": 5, "omega": 1.5})]
+    model, handle = BatchModel(oracle, dim_x, dim_y, batch), make_handle(dim_x, dim_y)
+    for op in ops:
+        want, got = model.apply(op), handle.apply(op)
+        if want is not None:
+            compare(got, want, f"a fresh batch, one order: {op[0]}")
+    compare(handle.snapshot(), model.snapshot(), "a fresh batch, one order")
 
 
 def fresh_handle_check(oracle, make_handle, dim_x=61, dim_y=81, seed=3):

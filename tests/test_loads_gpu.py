@@ -424,3 +424,30 @@ def test_a_sample_without_solids_is_zeros_and_the_replay_of_a_timeline_is_not_cu
     fields, samples = run(True)
     assert samples.shape == (4, 3, 1) and samples.tobytes() == bytes(4 * 3 * 48)
     sg.assert_fields_equal(fields, plain, "fields")
+
+
+def test_a_contexts_recorder_counts_inside_the_seam_loop_where_its_samples_are_zeros(sfl):
+    """Without solids sfl_step_n keeps its step seams while a loads recorder is on (130 x 70 on the tiled kernels: every
+    condition of the seam holds) and counts each step inside that loop, across calls that leave a remainder: the samples are
+    zero records and the fields those of a run without a recorder.  (The seeded call sequences found that nothing else stood
+    on this count: a loop that skipped it passed every other test of this file.)"""
+    cap, dim_x, dim_y = sfl.capi, 130, 70
+
+    def run(recorder):
+        with sfl.Solver(dim_x, dim_y) as c:
+            v, col = random_fields(dim_x, dim_y, 303, vamp=40.0)[:2]
+            c.upload(cap.FIELD_VELOCITY, v)
+            c.upload(cap.FIELD_COLOR, col)
+            c.set_option(cap.OPT_ADVECT_KERNEL, 2)
+            if recorder:
+                c.loads_start(2, 4)
+            for n in (3, 3):
+                c.step_n(n, DT, DX, ITERS, OMEGA)
+            fields = tuple(c.download(f) for f in (cap.FIELD_VELOCITY, cap.FIELD_DIVERGENCE, cap.FIELD_PRESSURE, cap.FIELD_COLOR))
+            return fields, (c.loads_info(), c.loads_history()) if recorder else None
+
+    plain, _ = run(False)
+    fields, (info, samples) = run(True)
+    assert info == (3, 4, 6, 1), info
+    assert samples.shape == (3, 1, 1) and samples.tobytes() == bytes(3 * 48)
+    sg.assert_fields_equal(fields, plain, "the fields are those of a run without a recorder")

@@ -7,13 +7,23 @@ The subjects with solids and histories (solid-context, solid-batch) have a censu
 set, replaced without a clear, cleared, with the fields left as they are -- every mask kind, every call that honours solids
 under a mask with solid and fluid cells, masked solves of 0, 1 and 2 launches, the refusals where the generator planted them
 and nowhere else, and three more faulty models that only a walk catches.  The op lists of the six subjects from before them
-are pinned by digest: the new vocabulary must not move them."""
+are pinned by digest: the new vocabulary must not move them.
+
+The subjects with viscosity and loads (viscous-context, viscous-batch) have theirs: every launch class of the diffusion with a
+reader of the velocity behind it, a viscosity in force while masks come and go, every plain path right behind a clear, the
+companions of a viscous step, a batch's coefficients staged call after call, the loads' state (labels and masks in either order,
+replaced and reset, a recorder across calls, restarted, sampling without a mask), the new refusals, planted and nowhere else --
+all read from the op lists -- and, evaluated on the model, that no sequence compares only empty loads or diffusions that change
+nothing.  Five more faulty models are caught by these sequences and missed by a fresh handle that makes each new call once.
+The op lists of solid-context and solid-batch are pinned as they were before this vocabulary."""
+import copy
 import functools
 import hashlib
 
 import numpy as np
 import pytest
 
+import load_rule
 import sequence_model as sm
 from oracle import loader
 
@@ -50,6 +60,18 @@ def test_the_sequences_from_before_solids_have_not_moved(name):
     subject, seqs = sequences(name)
     assert not subject.solids and subject.length == 30
     assert hashlib.sha256(repr([seqs[case] for case in subject.cases]).encode()).hexdigest() == PINNED[name]
+
+
+# ... and the two subjects with solids and histories, as they were before the viscosity's and the loads' vocabulary was added
+PINNED_SOLIDS = {"solid-context": "bca90f5609b44f816b9c9b7e93268830bb59800d34cb65c037ba4929641d6e18",
+                 "solid-batch": "0606b2b680529158695b8c4aefa1b6deec695510de826aad615873ced9f4ad2e"}
+
+
+@pytest.mark.parametrize("name", sorted(PINNED_SOLIDS))
+def test_the_sequences_from_before_viscosity_and_loads_have_not_moved(name):
+    subject, seqs = sequences(name)
+    assert subject.solids and not subject.viscous and subject.length == 36
+    assert hashlib.sha256(repr([seqs[case] for case in subject.cases]).encode()).hexdigest() == PINNED_SOLIDS[name]
 
 
 @pytest.mark.parametrize("name", IDS)
@@ -220,7 +242,8 @@ def test_a_failure_message_carries_what_replay_needs(oracle):
 
 
 # ---- solids and histories ------------------------------------------------------------------------------------------------
-SOLID_IDS = [s.name for s in sm.SUBJECTS if s.solids]
+SOLID_IDS = [s.name for s in sm.SUBJECTS if s.solids and not s.viscous]
+VISCOUS_IDS = [s.name for s in sm.SUBJECTS if s.viscous]
 HONOURED = {"context": ("step", "step_n", "calculate_divergence", "poisson_solve", "poisson_continue", "subtract_gradient", "residual",
                         "poisson_solve_until", "flow_stats"),
             "batch": ("step_n", "step_n_each", "poisson_solve", "poisson_solve_each", "flow_stats")}
@@ -359,7 +382,7 @@ def test_census_a_queued_record_lies_on_a_solid_cell_and_one_on_a_fluid_cell_of_
     assert hits
 
 
-@pytest.mark.parametrize("name", SOLID_IDS)
+@pytest.mark.parametrize("name", SOLID_IDS + VISCOUS_IDS)
 def test_the_model_refuses_what_the_census_says_is_refused(name, oracle):
     """The models decide from the fields and counts they hold, the census from the op list: the same ops, and a refused op
     changes nothing in the model."""
@@ -404,3 +427,300 @@ def test_a_planted_solids_bug_is_caught_by_the_sequences_and_missed_by_a_fresh_h
     assert hits, f"{cls.__name__}: no sequence of solid-context saw the fault"
     solid_fresh_handle_check(oracle, lambda dim_x, dim_y: cls(oracle, dim_x, dim_y))     # one mask, one order, one clear: nothing seen
     sm.fresh_handle_check(oracle, lambda dim_x, dim_y: cls(oracle, dim_x, dim_y))
+
+
+# ---- viscosity and loads ---------------------------------------------------------------------------------------------------
+READS_THE_VELOCITY = ("advect_velocity", "step", "calculate_divergence", "advance_tracers")
+VISCOUS_REFUSALS = {"viscous-context": {("set_bodies", "recorder"), ("step_n", "full")},
+                    "viscous-batch": {("set_bodies", "recorder"), ("step_n", "full"), ("step_n_until", "viscosity")}}
+
+
+def viscous_walks(name):
+    """[(case, [(index, op, what the Gate knows while the op runs, the path state, refused)])]: read from the op lists alone."""
+    subject, seqs = sequences(name)
+    out = []
+    for case, ops in seqs.items():
+        walk = []
+        for (k, op, gate, refused), (_, _, path) in zip(sm.gated(ops, subject, case), sm.path_states(ops)):
+            st = {"set": gate.masks is not None, "mixed": gate.mixed(), "hist": None if gate.hist is None else list(gate.hist), "trail": gate.trail,
+                  "rec": gate.rec, "visc": None if gate.visc is None else dict(gate.visc), "labels": gate.labels,
+                  "loads": None if gate.loads is None else list(gate.loads), "two_launches": gate.two_launches}
+            walk.append((k, op, st, path, refused))
+        out.append((case, walk))
+    return subject, out
+
+
+def due(recorder, op):
+    """The samples the step call completes of a recorder [every, capacity, steps]."""
+    every, _, steps = recorder
+    return (steps + op[1].get("n", 1)) // every - steps // every
+
+
+def in_force(st):
+    """Whether a step call diffuses: a viscosity set, sweeps > 0 and some nu > 0."""
+    return st["visc"] is not None and st["visc"]["sweeps"] > 0 and any(nu > 0 for nu in st["visc"]["nu"])
+
+
+def test_the_two_viscous_subjects_and_their_shapes():
+    by_name = {s.name: s for s in sm.SUBJECTS}
+    assert [c for c in by_name["viscous-context"].cases] == sm._cases(130, 70, 3, 900) + sm._cases(61, 81, 2, 950)
+    assert [c for c in by_name["viscous-batch"].cases] == sm._cases(61, 81, 3, 1000) + sm._cases(7, 9, 2, 1050) and by_name["viscous-batch"].batch == 3
+    new = set(sm.VISCOUS_WRITERS + sm.VISCOUS_QUERIES)
+    for name in VISCOUS_IDS:
+        s = by_name[name]
+        assert s.solids and not s.large and 40 <= s.length <= 50
+        assert set(sm.SOLID_WRITERS + sm.SOLID_QUERIES) <= set(s.kinds())
+        assert new - set(s.kinds()) == (set() if s.kind == "context" else {"diffuse_velocity"})
+    assert not any(new & set(s.kinds()) for s in sm.SUBJECTS if not s.viscous), "no older subject's deck has a new kind"
+    assert set(sm.LABEL_KINDS) == {"all one", "halves", "with zeros", "sixteen"}
+
+
+def test_the_labels_cover_the_whole_grid_and_a_load_record_of_the_model_is_the_packages(sfl):
+    assert load_rule.DTYPE == sfl.BODY_LOAD_DTYPE and sm.LOAD_BYTES == 48
+    assert sm.body_labels("all one", 7, 9, 0) is None
+    halves, zeros, sixteen = (sm.body_labels(kind, 130, 70, 4) for kind in ("halves", "with zeros", "sixteen"))
+    assert halves.shape == (70, 130) and set(np.unique(halves)) == {1, 2} and (halves[:, :65] == 1).all() and (halves[:, 65:] == 2).all()
+    assert set(np.unique(zeros)) == {0, 1, 2, 3} and 0.25 < (zeros == 0).mean() < 0.42
+    assert set(np.unique(sixteen)) == set(range(1, 17)) and sixteen[3, 5] == 1 + 8
+    for kind, bodies in sm.LABEL_KINDS.items():
+        lab = sm.body_labels(kind, 7, 9, 1, member=2)
+        assert lab is None or (lab.dtype == np.uint8 and int(lab.max()) <= bodies)
+
+
+def test_census_every_launch_class_of_the_diffusion_hands_the_velocity_to_a_reader():
+    subject, cases = viscous_walks("viscous-context")
+    seen, again = set(), False
+    for case, walk in cases:
+        for k, (kind, a), st, _path, refused in walk[:-1]:
+            launches = sm.launches_of(a["nu"], a["sweeps"]) if kind == "diffuse_velocity" else 0
+            behind, later = walk[k + 1], walk[k + 2:]
+            if launches and not refused and behind[1][0] in READS_THE_VELOCITY and not behind[4] and \
+                    any(op[0] == "step_n" and op[1]["n"] >= 2 and not r for _, op, _, _, r in later):
+                seen.add((case[:2], a["sweeps"]))
+                again |= launches == 2 and st["two_launches"] >= 1
+    for shape in ((130, 70), (61, 81)):
+        assert {(shape, sweeps) for sweeps in (1, 9, 17)} <= seen, (shape, seen)
+    assert again, "a two-launch diffusion on a handle that has made one before: the third buffer holds an old velocity"
+
+
+def test_census_a_viscosity_is_in_force_while_masks_come_and_go():
+    subject, cases = viscous_walks("viscous-context")
+    seen = set()
+    for case, walk in cases:
+        set_behind = cleared_under = False          # a mask set / cleared since the viscosity was set
+        for k, (kind, a), st, _path, refused in walk:
+            if refused:
+                continue
+            if kind in ("set_viscosity", "clear_viscosity"):
+                set_behind = cleared_under = False
+            if kind == "set_solids" and in_force(st):
+                set_behind, cleared_under = True, False
+            if kind == "clear_solids" and in_force(st) and st["set"]:
+                set_behind, cleared_under = False, True
+            if kind in ("step", "step_n") and in_force(st):
+                seen |= {(kind, "no mask")} if not st["set"] else set()
+                seen |= {(kind, "a mixed mask")} if st["mixed"] else set()
+                seen |= {(kind, "a mask set behind the viscosity")} if st["mixed"] and set_behind else set()
+                seen |= {(kind, "the mask cleared while the viscosity stays")} if not st["set"] and cleared_under else set()
+                seen.add((kind, f"{sm.launches_of(max(st['visc']['nu']), st['visc']['sweeps'])} launches"))
+    for kind in ("step", "step_n"):
+        for what in ("no mask", "a mixed mask", "a mask set behind the viscosity", "the mask cleared while the viscosity stays", "1 launches", "2 launches"):
+            assert (kind, what) in seen, (kind, what, seen)
+
+
+def test_census_a_cleared_viscosity_gives_every_plain_path_back():
+    subject, cases = viscous_walks("viscous-context")
+    seen = set()
+    for case, walk in cases:
+        for k, op, st, path, refused in walk[1:]:
+            before = walk[k - 1]
+            if before[1][0] != "clear_viscosity" or not in_force(before[2]) or op[0] not in ("step", "step_n") or refused:
+                continue                                # (the step call right behind the clear of a viscosity that was in force)
+            if case[:2] == (130, 70) and not st["set"] and st["hist"] is None and sm.takes_the_seam(op, path) and path["options"]["OPT_ADVECT_KERNEL"] == 2:
+                seen.add("the step seams")
+            if case[:2] == (61, 81) and not st["set"] and op[0] == "step" and sm.on_small_grid(path):
+                seen.add("the one-launch step of a small grid")
+            if not st["set"] and path["options"]["OPT_FUSE_PROJECTION"] == 0:
+                seen.add("OPT_FUSE_PROJECTION = 0")
+            if st["mixed"]:
+                seen.add("a mask still set")
+    assert seen == {"the step seams", "the one-launch step of a small grid", "OPT_FUSE_PROJECTION = 0", "a mask still set"}, seen
+
+
+def test_census_a_viscous_step_has_every_companion():
+    subject, cases = viscous_walks("viscous-context")
+    seen = set()
+    for case, walk in cases:
+        for k, op, st, path, refused in walk:
+            if op[0] in ("step", "step_n") and in_force(st) and not refused:
+                hist, trail, loads = st["hist"] is not None and due(st["hist"], op) > 0, path["follow"] and st["trail"], st["loads"] is not None and due(st["loads"], op) > 0
+                seen |= {name for name, on in (("history", hist), ("trail", trail), ("loads", loads)) if on}
+                if hist and trail and loads and st["mixed"]:
+                    seen.add("all three under a mixed mask")
+                if hist and st["mixed"]:
+                    seen.add("a history's sample under a viscosity and a mask")
+    assert seen == {"history", "trail", "loads", "all three under a mixed mask", "a history's sample under a viscosity and a mask"}, seen
+
+
+def test_census_a_batch_stages_its_coefficients_call_after_call():
+    subject, cases = viscous_walks("viscous-batch")
+    runs, seen = [], set()
+    for case, walk in cases:
+        run = []
+        for k, op, st, path, refused in walk:
+            kind, a = op
+            mixed_nu = st["visc"] is not None and st["visc"]["per_member"] and st["visc"]["sweeps"] > 0 and 0.0 in st["visc"]["nu"] and max(st["visc"]["nu"]) > 0
+            if kind in ("step_n", "step_n_each") and not refused and mixed_nu:
+                run.append((kind, st["set"]))
+            else:
+                runs.append(run)
+                run = []
+            if kind == "set_viscosity" and not a["per_member"] and st["visc"] is not None and st["visc"]["per_member"]:
+                seen.add("a per-member nu replaced by a shared one")
+            cleared = st["visc"] is None and any(op2[0] == "clear_viscosity" for _, op2, _, _, _ in walk[:k])
+            if cleared and kind == "step_n_until" and not refused:
+                seen.add("cleared: step_n_until is taken")
+            if cleared and kind == "step_n" and a["n"] >= 2 and not st["set"] and not path["follow"] and any(1 <= s < a["n"] for s in path["pending"]) and not refused:
+                seen.add("cleared: the one-launch replay")
+                if st["loads"] is not None and due(st["loads"], op) > 0:
+                    seen.add("a loads sample inside the one-launch replay")
+            if kind == "step_n_until" and refused and st["visc"] is not None and not st["set"]:
+                assert walk[k + 1][1][0] in sm.STEPS and not walk[k + 1][4]
+                seen.add("step_n_until refused for the viscosity alone")
+            if kind in sm.STEPS and not refused and in_force(st):
+                seen |= {"history"} if st["hist"] is not None and due(st["hist"], op) > 0 else set()
+                seen |= {"frames"} if st["rec"] else set()
+                seen |= {"following tracers"} if path["follow"] else set()
+                seen |= {"loads under a mask"} if st["loads"] is not None and due(st["loads"], op) > 0 and st["mixed"] else set()
+        runs.append(run)
+    long = [r for r in runs if len(r) >= 3 and {k for k, _ in r} == {"step_n", "step_n_each"}]
+    assert any(not any(m for _, m in r) for r in long), "three step calls in a row, both kinds, a per-member nu with a member at 0, no mask"
+    assert any(all(m for _, m in r) for r in long), "... and under a mask"
+    assert seen == {"a per-member nu replaced by a shared one", "cleared: step_n_until is taken", "cleared: the one-launch replay",
+                    "a loads sample inside the one-launch replay", "step_n_until refused for the viscosity alone", "history", "frames", "following tracers",
+                    "loads under a mask"}, seen
+
+
+@pytest.mark.parametrize("name", VISCOUS_IDS)
+def test_census_the_loads_state_is_walked(name):
+    subject, cases = viscous_walks(name)
+    seqs = sequences(name)[1]
+    seen = set()
+    for case, walk in cases:
+        early, calls = False, None          # labels set while no mask is held; [step calls, a remainder left] of the recorder that is on
+        for k, op, st, path, refused in walk:
+            kind, a = op
+            if refused:
+                continue
+            if kind == "set_bodies":
+                early = a["label_kind"] != "all one" and not st["set"]
+                seen |= {"labels replaced"} if st["labels"] is not None and a["label_kind"] != "all one" else set()
+            if kind == "clear_bodies":
+                early = False
+                seen |= {"labels reset"} if st["labels"] is not None else set()
+            if kind == "set_solids" and st["labels"] is not None:
+                seen |= {"a mask replaced under labels"} if st["set"] else set()
+            if kind == "clear_solids" and st["labels"] is not None and st["set"]:
+                seen.add("a mask cleared under labels")
+            if kind == "loads" and early and st["mixed"]:
+                seen.add("labels set before the mask")
+            if kind == "loads_start":
+                calls = [0, False]
+                seen |= {"a restart while on"} if st["loads"] is not None else set()
+            if kind == "loads_stop":
+                calls = None
+            if kind in sm.STEPS and st["loads"] is not None:
+                every, _, steps = st["loads"]
+                calls[0] += 1
+                calls[1] |= (steps + a.get("n", 1)) % every != 0
+                if every in (2, 3) and calls[0] >= 3 and calls[1]:
+                    seen.add("a recorder across three calls that leave a remainder")
+                seen.add(f"counted through {kind}")
+                if due(st["loads"], op) > 0 and not st["set"]:
+                    seen.add("a sample while no mask is set")
+                    if subject.kind == "context" and sm.takes_the_seam(op, path) and st["hist"] is None and case[:2] == (130, 70) and path["options"]["OPT_ADVECT_KERNEL"] == 2:
+                        seen.add("a sample inside the seam loop")
+    want = {"labels set before the mask", "a mask replaced under labels", "a mask cleared under labels", "labels replaced", "labels reset", "a restart while on",
+            "a recorder across three calls that leave a remainder", "a sample while no mask is set"}
+    want |= {"a sample inside the seam loop", "counted through step", "counted through step_n"} if subject.kind == "context" else \
+            {"counted through step_n", "counted through step_n_each", "counted through step_n_until"}
+    assert seen == want, (name, want - seen, seen - want)
+
+
+@pytest.mark.parametrize("name", VISCOUS_IDS)
+def test_census_the_new_refusals_are_the_planted_ones(name):
+    subject, cases = viscous_walks(name)
+    causes = set()
+    for case, walk in cases:
+        for k, (kind, a), st, path, refused in walk:
+            if not refused:
+                continue
+            if kind in ("set_bodies", "clear_bodies"):
+                assert st["loads"] is not None and walk[k + 1][1][0] in sm.STEPS and not walk[k + 1][4]
+                causes.add((kind, "recorder"))
+            elif kind == "step_n_until" and st["visc"] is not None and not st["set"]:
+                causes.add((kind, "viscosity"))
+            else:
+                # the third admission check refuses: the loads recorder is full, the history and the trail (a batch: the frames) are not
+                assert kind in sm.STEPS and st["loads"] is not None and due(st["loads"], (kind, a)) > st["loads"][1] - st["loads"][2] // st["loads"][0]
+                assert st["hist"] is not None and due(st["hist"], (kind, a)) <= st["hist"][1] - st["hist"][2] // st["hist"][0]
+                assert (path["follow"] and st["trail"]) if subject.kind == "context" else st["rec"]
+                behind = [op[0] for _, op, _, _, _ in walk[k + 1:k + 6]]
+                assert set(behind[:3]) == {"history", "trail" if subject.kind == "context" else "frames", "loads_history"}, behind
+                assert behind[3] == "loads_stop" and behind[4] in sm.STEPS and not walk[k + 5][4], behind
+                causes.add((kind, "full"))
+    assert causes == VISCOUS_REFUSALS[name], (name, causes)
+    assert sum(r for _, walk in cases for *_, r in walk) == len(VISCOUS_REFUSALS[name]), "only the planted refusals happen"
+
+
+@pytest.mark.parametrize("name", VISCOUS_IDS)
+def test_no_sequence_passes_vacuously(name, oracle):
+    """Evaluated on the model: in every sequence a compared load has faces and a force, and a viscous step changes the velocity's
+    bits against the same step with the viscosity taken away."""
+    subject, seqs = sequences(name)
+    for case, ops in seqs.items():
+        model = subject.model(oracle, case)
+        loaded = diffused = False
+        for op in ops:
+            kind = op[0]
+            twin = None
+            members = model.m if subject.kind == "batch" else [model]
+            if kind in sm.STEPS and any(m.visc is not None and m.visc[0] > 0 and m.visc[1] > 0 for m in members) and not model.refuses(*op):
+                twin = copy.deepcopy(model, {id(oracle): oracle})
+                for m in (twin.m if subject.kind == "batch" else [twin]):
+                    m.visc = None
+            out = model.apply(op)
+            if twin is not None:
+                twin.apply(op)
+                a, b = model.snapshot()["velocity"], twin.snapshot()["velocity"]
+                diffused |= a.tobytes() != b.tobytes()
+            if kind in ("loads", "loads_history") and "records" in out and out["records"].size:
+                rec = np.ascontiguousarray(out["records"]).view(load_rule.DTYPE).reshape(-1)
+                loaded |= bool(((rec["faces"].sum(axis=-1) > 0) & ((rec["fx"] != 0) | (rec["fy"] != 0))).any())
+        assert loaded, (name, case, "no compared load has faces and a force")
+        assert diffused, (name, case, "no viscous step changes the velocity")
+
+
+def make_stand_in(cls, oracle):
+    return lambda s, c: cls(oracle, c[0], c[1], s.batch) if s.kind == "batch" else cls(oracle, c[0], c[1])
+
+
+@pytest.mark.parametrize("cls", sm.VISCOUS_STAND_INS + sm.LOAD_STAND_INS, ids=[c.__name__ for c in sm.VISCOUS_STAND_INS + sm.LOAD_STAND_INS])
+def test_a_planted_viscosity_or_loads_bug_is_caught_by_the_sequences_and_missed_by_a_fresh_handle(cls, oracle):
+    subject, seqs = sequences(sm.stand_in_subject(cls))
+    hits = []
+    for case, ops in seqs.items():
+        for mode in ("lazy", "probing"):
+            try:
+                sm.run(subject, case, ops, mode, oracle, make_stand_in(cls, oracle))
+            except AssertionError as e:
+                hits.append((case, mode, str(e).splitlines()[0]))
+    print(cls.__name__, hits)
+    assert hits, f"{cls.__name__}: no sequence of {subject.name} saw the fault"
+    assert all("seed" in h[2] and "mode" in h[2] and "op " in h[2] for h in hits), "a failure names seed, mode and op"
+    if subject.kind == "batch":         # every new call once on a fresh handle, one order: nothing seen
+        sm.viscous_batch_fresh_handle_check(oracle, lambda dim_x, dim_y: cls(oracle, dim_x, dim_y, 3))
+    else:
+        sm.viscous_fresh_handle_check(oracle, lambda dim_x, dim_y: cls(oracle, dim_x, dim_y))
+        solid_fresh_handle_check(oracle, lambda dim_x, dim_y: cls(oracle, dim_x, dim_y))
+        sm.fresh_handle_check(oracle, lambda dim_x, dim_y: cls(oracle, dim_x, dim_y))

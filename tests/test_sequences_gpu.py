@@ -10,6 +10,16 @@ cleared, the general kernels and the step seams; 61 x 81: cleared, the one-launc
 flipped, a timeline pending, tracers following, a trail and a history on.  A call the header refuses is an op like any other:
 both sides return the refusal, and the fields, the timeline and the tracers behind it are compared as after every op.
 
+Two more walk the viscosity and the loads on top of that vocabulary, 50 and 48 ops each: a context (130 x 70: 3 x 3 ragged
+diffusion tiles; 61 x 81: one tile column) and a batch of three (61 x 81, 7 x 9).  The diffusion runs as an operator of one, two
+and three launches -- its result in the step's second buffer, in the third, in the second again -- with a reader of the velocity
+right behind it; a viscosity is set, cleared and set again while masks come and go, and cleared it gives the step seams, the
+one-launch step of a small grid and the unfused step back; a history, a trail and a loads recorder sample behind viscous steps;
+a batch stages its coefficient table for step calls queued back to back under a per-member nu with a member at 0; labels are
+set before the mask, masks replaced and cleared under labels, labels replaced and reset; a loads recorder counts across calls
+that leave remainders, is restarted while on, samples zeros where no mask is set -- inside a context's seam loop and a
+batch's one-launch replay -- and, full, refuses a step call whole behind a history and a trail that have room.
+
 A failure prints the seed, the mode, the first op that disagreed and the op list up to there as a literal for
 sequence_model.replay.  There is no tolerance anywhere."""
 import functools
@@ -37,19 +47,22 @@ def test_a_sequence_on_a_live_handle(sfl, oracle, name, case, mode):
 
 
 LIVE = [(cls, "general") for cls in sm.STAND_INS] + [(cls, "solid-context") for cls in sm.SOLID_STAND_INS]
+LIVE += [(cls, sm.stand_in_subject(cls)) for cls in sm.VISCOUS_STAND_INS + sm.LOAD_STAND_INS]      # (viscous-context; viscous-batch for the batch's fault)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cls,name", LIVE, ids=[c.__name__ for c, _ in LIVE])
 def test_the_comparisons_on_the_library_are_live(sfl, oracle, cls, name):
     """A model with a planted state fault, taken as the truth: the library does not have the fault, so some sequence of the
-    subject (general; solid-context for the faults in the solids' state) must disagree -- in lazy or probing mode, as
+    subject (general; solid-context for the faults in the solids' state; viscous-context and viscous-batch for those in the
+    viscosity's and the loads') must disagree -- in lazy or probing mode, as
     tests/test_sequences.py shows for models on both sides."""
     subject, seqs = sequences(name)
     hits = 0
     for case, ops in seqs.items():
         for mode in ("lazy", "probing"):
-            model, handle = cls(oracle, case[0], case[1]), subject.library(sfl, case)
+            model = cls(oracle, case[0], case[1], subject.batch) if subject.kind == "batch" else cls(oracle, case[0], case[1])
+            model.viscous, handle = subject.viscous, subject.library(sfl, case)
             try:
                 sm.replay(model, handle, ops, mode, seed=case[2])
             except AssertionError:
