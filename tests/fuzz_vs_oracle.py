@@ -3,7 +3,9 @@ single-GPU product path against the oracle (checker only): random grid shapes, k
 depths, dx / omega / dt, velocity scales, and -- since round 6 -- field TEXTURES: dense noise, a quiescent field with sparse forcing
 at 60..130 iterations (the solution's front decays through the denormals: where round 5's folded product left the reference's bits),
 and fields scaled down to the bottom of the float range; whole steps through sfl_step_n (all four fields), stand-alone solves and
-advect<T, float> of a random element type, bit for bit."""
+advect<T, float> of a random element type, bit for bit.  The collected version of the "sparse" and "tiny" textures, through
+batches, masked and viscous steps, stopping rules and readers as well: tests/value_cases.py, tests/test_values.py (CPU) and
+tests/test_values_gpu.py."""
 import sys, time, importlib
 import numpy as np
 sys.path.insert(0, ".")

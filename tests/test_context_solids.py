@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import solid_rule as rule
+import value_cases
 from conftest import ROOT, assert_bit_equal, random_fields
 from test_solids_gpu import mask_of
 
@@ -158,6 +159,34 @@ def test_the_tile_core_run_on_the_host_solves_by_the_rule(tmp_path, dim_x, dim_y
     got = np.fromfile(dst, np.float32).reshape(len(cases), dim_y, dim_x)
     for k, (kind, iters) in enumerate(cases):
         assert_bit_equal(got[k], rule.solve(d, mask(kind, dim_x, dim_y), DX, iters, OMEGA), f"{dim_x}x{dim_y} {kind} iters {iters}")
+
+
+VALUE_SHAPES = [(TX + 1, TY + 1), (257, 130)]
+VALUE_TEXTURES = [("quiescent", 1e-38), ("tiny", None)]   # (a quiescent right-hand side of 1e-30 leaves no denormals in 2 D + 3 iterations)
+
+
+@pytest.mark.parametrize("name,amplitude", VALUE_TEXTURES, ids=[t[0] for t in VALUE_TEXTURES])
+@pytest.mark.parametrize("dim_x,dim_y", VALUE_SHAPES, ids=[f"{x}x{y}" for x, y in VALUE_SHAPES])
+def test_the_tile_core_on_right_hand_sides_at_the_bottom_of_the_float_range(tmp_path, dim_x, dim_y, name, amplitude):
+    """The quiescent and the tiny texture of tests/value_cases.py through the same file and the same program: a pressure
+    front that decays through the denormals into cells that are still zero, and a field that is denormal throughout,
+    across the tile edges and the halo of the temporal blocking.  Every mask with a fluid cell keeps 100 denormal cells."""
+    d = value_cases.texture(name, dim_x, dim_y, amplitude).rhs
+    cases = [(kind, iters) for kind in MASKS for iters in (D - 1, 2 * D + 3)]
+    src, dst = tmp_path / "cases.bin", tmp_path / "p.bin"
+    with open(src, "wb") as f:
+        for kind, iters in cases:
+            f.write(np.array([dim_x, dim_y, iters], np.int32).tobytes())
+            f.write(np.array([DX, OMEGA], np.float32).tobytes())
+            f.write(d.tobytes())
+            f.write(mask(kind, dim_x, dim_y).astype(np.uint8).tobytes())
+    r = subprocess.run([driver(), str(src), str(dst)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and f"{len(cases)} cases solved tile by tile (TX {TX}, TY {TY}, D {D})" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    got = np.fromfile(dst, np.float32).reshape(len(cases), dim_y, dim_x)
+    for k, (kind, iters) in enumerate(cases):
+        want = rule.solve(d, mask(kind, dim_x, dim_y), DX, iters, OMEGA)
+        assert kind == "all" or value_cases.denormals(want) >= 100, (kind, iters, value_cases.denormals(want))
+        assert_bit_equal(got[k], want, f"{name} {dim_x}x{dim_y} {kind} iters {iters}")
 
 
 # ---- a guard on the shapes -----------------------------------------------------------------------------------------------

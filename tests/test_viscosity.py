@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import value_cases
 import viscosity_rule as rule
 from conftest import ROOT, assert_bit_equal, random_fields
 from test_context_solids import MASKS, mask
@@ -236,6 +237,35 @@ def test_the_tile_core_run_on_the_host_diffuses_by_the_rule(tmp_path, dim_x, dim
     for k, (kind, sweeps) in enumerate(cases):
         solid = None if kind is None else mask(kind, dim_x, dim_y)
         assert_bit_equal(got[k], rule.diffuse(v, NU, DT, DX, sweeps, solid), f"{dim_x}x{dim_y} {kind} sweeps {sweeps}")
+
+
+VALUE_SHAPES = [(TX + 1, TY + 1), (257, 130)]
+VALUE_TEXTURES = [("quiescent", 1e-30), ("tiny", None)]
+
+
+@pytest.mark.parametrize("name,amplitude", VALUE_TEXTURES, ids=[t[0] for t in VALUE_TEXTURES])
+@pytest.mark.parametrize("dim_x,dim_y", VALUE_SHAPES, ids=[f"{x}x{y}" for x, y in VALUE_SHAPES])
+def test_the_tile_core_on_velocities_at_the_bottom_of_the_float_range(tmp_path, dim_x, dim_y, name, amplitude):
+    """The quiescent texture of tests/value_cases.py with its two records written in -- the diffusion spreads them through
+    the denormals into cells that are still zero -- and the tiny one, denormal throughout, through the same file and the
+    same program.  Every mask with a fluid cell (and none) keeps 100 denormal components."""
+    v = value_cases.held_velocities(name, amplitude, dim_x, dim_y)[0]
+    cases = [(kind, sweeps) for kind in [None] + MASKS for sweeps in (D - 1, 2 * D + 3)]
+    src, dst = tmp_path / "cases.bin", tmp_path / "u.bin"
+    with open(src, "wb") as f:
+        for kind, sweeps in cases:
+            f.write(np.array([dim_x, dim_y, sweeps, kind is not None], np.int32).tobytes())
+            f.write(np.array([NU, DT, DX], np.float32).tobytes())
+            f.write(v.tobytes())
+            if kind is not None:
+                f.write(mask(kind, dim_x, dim_y).astype(np.uint8).tobytes())
+    r = subprocess.run([driver(), str(src), str(dst)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and f"{len(cases)} cases diffused tile by tile (TX {TX}, TY {TY}, D {D})" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    got = np.fromfile(dst, np.float32).reshape(len(cases), dim_y, dim_x, 2)
+    for k, (kind, sweeps) in enumerate(cases):
+        want = rule.diffuse(v, NU, DT, DX, sweeps, None if kind is None else mask(kind, dim_x, dim_y))
+        assert kind == "all" or value_cases.denormals(want) >= 100, (kind, sweeps, value_cases.denormals(want))
+        assert_bit_equal(got[k], want, f"{name} {dim_x}x{dim_y} {kind} sweeps {sweeps}")
 
 
 def test_the_shapes_straddle_the_tile():
