@@ -35,6 +35,7 @@ VIEW_SPEED, VIEW_VORTICITY, VIEW_PRESSURE, VIEW_DIVERGENCE = 0, 1, 2, 3
 VIEW_MAX_STOPS = 256
 VIEW_MAX_COLOUR = 0xFC000000
 MAX_BODIES = 16   # SFL_MAX_BODIES
+OPEN_INFLOW, OPEN_OUTFLOW = 1, 2   # SFL_OPEN_*: the bytes of an openings map
 UNIQUE_ID_BYTES = 128
 TRACER_THREADS = 256   # kTracerThreads of csrc/tracer_kernels.h: tracers per workgroup (stated for the tests)
 BATCH_LARGE_MAX_CELLS = 20224   # SFL_BATCH_LARGE_MAX_CELLS: cells of one member of sfl_batch_create_large
@@ -286,6 +287,15 @@ SIGNATURES = {
     "sfl_batch_set_viscosity": (_i, [_ctx, _pf, _i, _i]),
     "sfl_batch_viscosity_info": (_i, [_ctx, _pi, _pi, _pi]),
     "sfl_batch_viscosity_download": (_i, [_ctx, _i, _i, _pf, _sz]),
+    "sfl_batch_set_openings": (_i, [_ctx, C.POINTER(C.c_uint8), _i, _pf, _i]),
+    "sfl_batch_set_inflow": (_i, [_ctx, _pf, _i]),
+    "sfl_batch_openings_info": (_i, [_ctx, _pi, _pi, _pi, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sfl_batch_openings_download": (_i, [_ctx, _i, _i, C.POINTER(C.c_uint8), _sz]),
+    "sfl_batch_inflow_download": (_i, [_ctx, _i, _i, _pf, _sz]),
+    "sfl_set_openings": (_i, [_ctx, C.POINTER(C.c_uint8), _f, _f]),
+    "sfl_set_inflow": (_i, [_ctx, _f, _f]),
+    "sfl_openings_info": (_i, [_ctx, _pi, _pf, _pf, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sfl_openings_download": (_i, [_ctx, C.POINTER(C.c_uint8), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

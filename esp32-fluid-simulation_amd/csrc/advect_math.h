@@ -232,6 +232,53 @@ __device__ __forceinline__ float2 project_cell_solid(float2 u, const float *q, i
     return project_cell(u, q, stride, t.i, t.gj, t.i_max, t.j_max, two_dx_inv);
 }
 
+// ---- openings on the rim of a grid (include/sfl.h "OPENINGS"; batch_openings.hip) -----------------------------------
+// A cell's OPEN CODE is its code byte with the opening above it: bits 8..11 say which neighbour -- W, E, S, N, the one outside
+// the domain -- is OPEN, bit 12 that the opening is an outflow (else an inflow).  Set only in a fluid rim cell that is no
+// corner; the bit of the open side is never set among bits 0..3.  With bits 8..12 clear the functions below are the solids'.
+constexpr int kOpenShift = 8, kOpenOutflow = 1 << 12;
+__device__ __forceinline__ int open_sides(int code) { return (code >> kOpenShift) & kSolidAll; }
+// a fluid cell that holds the inflow velocity (item 2a)
+__device__ __forceinline__ bool is_inflow_cell(int code) { return open_sides(code) != 0 && !(code & kOpenOutflow); }
+
+// an absent neighbour's term of div_expr_safe: the wall's ghost term as it stands, or with the opposite sign where the
+// neighbour is open -- the ghost moves with the cell and the flow passes
+__device__ __forceinline__ float ghost_term(float wall_term, int open) { return open ? -wall_term : wall_term; }
+
+// divergence_sum_solid for open codes: a cell with an open neighbour takes the safe form
+__device__ __forceinline__ float divergence_sum_open(const float2 *q, int stride, int code)
+{
+    const int open = open_sides(code);
+    if (!open) return divergence_sum_solid(q, stride, code & 0xff);
+    const float2 own = q[0];
+    float s = 0.0f;
+    s += (code & kSolidW) ? -q[-1].x : ghost_term(own.x, open & kSolidW);
+    s += (code & kSolidE) ? q[1].x : ghost_term(-own.x, open & kSolidE);
+    s += (code & kSolidS) ? -q[-stride].y : ghost_term(own.y, open & kSolidS);
+    s += (code & kSolidN) ? q[stride].y : ghost_term(-own.y, open & kSolidN);
+    return s;
+}
+
+// project_cell_solid for open codes: an outflow neighbour's pressure is +0.0f, an inflow neighbour's the cell's own as an
+// absent one's.  The outflow side is handed to project_cell as present and answered here, without a read.
+__device__ __forceinline__ float2 project_cell_open(float2 u, const float *q, int stride, int code, float two_dx_inv)
+{
+    if (!(code & kSolidFluid)) return make_float2(0.0f, 0.0f);
+    const int out = (code & kOpenOutflow) ? open_sides(code) : 0;
+    const SolidSpot t = solid_spot(code | out);
+    return project_cell(u, t.i, t.gj, t.i_max, t.j_max, two_dx_inv, [=](int a, int b) {
+        const int di = a - t.i, dj = b - t.gj;
+        const int side = di < 0 ? kSolidW : di > 0 ? kSolidE : dj < 0 ? kSolidS : dj > 0 ? kSolidN : 0;
+        return (side & out) ? 0.0f : q[dj * stride + di];
+    });
+}
+
+// the neighbours that count in item 5's k: the present ones, and an outflow's ghost pressure of zero
+__device__ __forceinline__ int open_neighbour_count(int code)
+{
+    return __builtin_popcount(code & kSolidAll) + ((code & kOpenOutflow) ? 1 : 0);
+}
+
 struct uq3 {
     uint32_t x, y, z;
 };

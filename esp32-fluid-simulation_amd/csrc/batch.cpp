@@ -21,7 +21,8 @@ void release(sfl_batch *b)
                     (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env,
                     (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
                     (void *)b->d_rec_palette, b->history.d_records, (void *)b->solids.d_codes,
-                    (void *)b->loads.d_labels, b->loads.d_records, b->viscosity.d_table})
+                    (void *)b->loads.d_labels, b->loads.d_records, b->viscosity.d_table, (void *)b->openings.d_codes,
+                    (void *)b->openings.d_inflow})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
     if (b->h_dist) (void)hipHostFree(b->h_dist);
@@ -221,7 +222,7 @@ enum StepKind { kUniform, kEach, kUntil };
 int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
 {
     SFL_TRY(stage_timeline(b, n));
-    if (kind != kUntil && !b->large && n >= 2 && !b->tracers_follow && !b->solids.set && !b->viscosity.set && staged_has(b, 1, n)) {
+    if (kind != kUntil && !b->large && n >= 2 && !b->tracers_follow && !b->solids.set && !b->viscosity.set && !b->openings.set && staged_has(b, 1, n)) {
         for (int done = 0; done < n;) {
             const int steps = sfl::host::history_run(b->history, sfl::host::record_run(b, n - done));   // (cut at either's due steps)
             sfl::BatchPlay play{};
@@ -252,6 +253,8 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
         a.step.col_out = b->col_tmp;
         if (b->viscosity.set)   // (never kUntil, never large: refused at the call and at sfl_batch_set_viscosity)
             SFL_TRY(b->viscosity.step(b, kind == kEach, a));
+        else if (b->openings.set)   // (never kUntil, never large, never with viscosity: refused at the calls; its codes hold the solids')
+            SFL_TRY(b->openings.step(b, kind == kEach, a));
         else if (b->solids.set)   // (never kUntil, never large: refused at the call and at sfl_batch_set_solids)
             SFL_TRY(b->solids.step(b, kind == kEach, a));
         else if (kind == kUniform)
@@ -393,9 +396,9 @@ int flow_stats(sfl_batch *b, int what, float dx, bool each, const sfl_member_par
         HIP_TRY(hipMemcpyAsync(b->d_stats + b->batch, scale, sizeof(float) * (size_t)b->batch, hipMemcpyHostToDevice, b->stream));
         d_scale = reinterpret_cast<const float *>(b->d_stats + b->batch);
     }
-    if (b->solids.set && (what & SFL_STATS_VELOCITY)) {   // the records zeroed and the dye pass as ever, the velocity pass by the solids' rule
+    if ((b->solids.set || b->openings.set) && (what & SFL_STATS_VELOCITY)) {   // the records zeroed and the dye pass as ever, the velocity pass by the solids' or the openings' rule
         HIP_TRY(sfl::launch_flow_stats(b->stream, b->d_stats, what & SFL_STATS_DYE, b->vel, b->col, b->dim_x, b->dim_y, b->batch, two_dx_inv(dx), d_scale));
-        SFL_TRY(b->solids.stats(b, two_dx_inv(dx), d_scale));
+        SFL_TRY((b->openings.set ? b->openings.stats : b->solids.stats)(b, two_dx_inv(dx), d_scale));
     } else
         HIP_TRY(sfl::launch_flow_stats(b->stream, b->d_stats, what, b->vel, b->col, b->dim_x, b->dim_y, b->batch, two_dx_inv(dx), d_scale));
     HIP_TRY(hipMemcpyAsync(b->h_stats + first, b->d_stats + first, (size_t)count * sizeof(struct sfl_flow_stats), hipMemcpyDeviceToHost, b->stream));
@@ -410,6 +413,13 @@ int refuse_until(const char *call)
 {
     return fail(SFL_ERR_STATE, "%s: the batch has solid cells set (sfl_batch_set_solids) and the solve to a tolerance does not know them: "
                 "nothing stepped or solved; use the _each call, or clear the solids with sfl_batch_set_solids(b, NULL, 0)", call);
+}
+
+// ... and of a batch with openings (include/sfl.h "OPENINGS")
+int refuse_until_open(const char *call)
+{
+    return fail(SFL_ERR_STATE, "%s: the batch has openings set (sfl_batch_set_openings) and the solve to a tolerance does not know them: "
+                "nothing stepped or solved; use the _each call, or clear the openings with sfl_batch_set_openings(b, NULL, 0, NULL, 0)", call);
 }
 
 // what both constructors do once their limits have passed: the device, the stream, the six zeroed fields
@@ -607,6 +617,7 @@ int sfl_batch_poisson_solve(sfl_batch *b, float dx, int iters, float omega)
     if (iters < 0) return fail(SFL_ERR_INVALID, "iters must be >= 0 (got %d)", iters);
     SFL_TRY(use_device(b));
     b->report_valid = b->counts_valid = false;
+    if (b->openings.set) return b->openings.solve(b, false, iters, sor_params(dx, omega));
     if (b->solids.set) return b->solids.solve(b, false, iters, sor_params(dx, omega));
     HIP_TRY((b->large ? sfl::launch_batch_large_solve : sfl::launch_batch_solve)(b->stream, b->p, b->div, b->dim_x, b->dim_y, b->batch,
                                                                                  iters, sor_params(dx, omega)));
@@ -642,7 +653,9 @@ int sfl_batch_poisson_solve_each(sfl_batch *b, const sfl_member_params *params)
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
     b->report_valid = b->counts_valid = false;
-    if (b->solids.set)
+    if (b->openings.set)
+        SFL_TRY(b->openings.solve(b, true, 0, sfl::SorParams{}));
+    else if (b->solids.set)
         SFL_TRY(b->solids.solve(b, true, 0, sfl::SorParams{}));
     else
         HIP_TRY((b->large ? sfl::launch_batch_large_solve_each : sfl::launch_batch_solve_each)(b->stream, b->p, b->div, b->dim_x, b->dim_y,
@@ -656,6 +669,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
     SFL_TRY(check_members(b, params, stops));
     if (n < 0) return fail(SFL_ERR_INVALID, "n must be >= 0 (got %d)", n);
     if (b->solids.set) return refuse_until("sfl_batch_step_n_until");
+    if (b->openings.set) return refuse_until_open("sfl_batch_step_n_until");
     if (b->viscosity.set)
         return fail(SFL_ERR_STATE, "sfl_batch_step_n_until: the batch has a viscosity set (sfl_batch_set_viscosity) and the step to a tolerance does not "
                     "know it: nothing stepped; use sfl_batch_step_n_each, or clear the viscosity with sfl_batch_set_viscosity(b, NULL, 0, 0)");
@@ -681,6 +695,7 @@ int sfl_batch_poisson_solve_until(sfl_batch *b, const sfl_member_params *params,
 {
     SFL_TRY(check_members(b, params, stops));
     if (b->solids.set) return refuse_until("sfl_batch_poisson_solve_until");
+    if (b->openings.set) return refuse_until_open("sfl_batch_poisson_solve_until");
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params, stops));
     b->report_valid = b->counts_valid = false;

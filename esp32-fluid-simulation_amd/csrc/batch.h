@@ -120,6 +120,28 @@ struct FlowStatsRecord;
 hipError_t launch_solid_velocity_stats(hipStream_t s, FlowStatsRecord *out, const float *v, const BatchSolids &solids, int dim_x,
                                        int dim_y, int members, float two_dx_inv, const float *member_two_dx_inv);
 
+// ---- members with openings on the rim of their grids (batch_openings.hip; include/sfl.h "OPENINGS") ------------------
+// One OPEN CODE of 16 bits per cell (advect_math.h: the code byte of the solids in bits 0..7, which neighbour is open in
+// bits 8..11, bit 12 = outflow), member-major: member m's start at codes + m * member_stride, member_stride = dim_x * dim_y
+// or 0 for codes that all members share.  An array of its own, formed by the host (openings.cpp): the code bytes that the
+// solids', loads' and viscous kernels read are not touched.  inflow: member m's (x, y) at inflow + 2 * m.
+struct BatchOpenings {
+    const uint16_t *codes;
+    size_t member_stride;
+    const float *inflow;
+};
+// launch_batch_solid_step[_each], _solve[_each] and launch_solid_velocity_stats by the rule of "OPENINGS"; with no opening
+// in a member, the same results bit for bit.
+hipError_t launch_batch_open_step(hipStream_t s, const BatchStep &a, const BatchOpenings &open, int batch);
+hipError_t launch_batch_open_step_each(hipStream_t s, const BatchStep &a, const BatchOpenings &open, int batch,
+                                       const BatchMember *members, float *report);
+hipError_t launch_batch_open_solve(hipStream_t s, float *p, const float *d, const BatchOpenings &open, int dim_x, int dim_y,
+                                   int batch, int iters, SorParams prm);
+hipError_t launch_batch_open_solve_each(hipStream_t s, float *p, const float *d, const BatchOpenings &open, int dim_x, int dim_y,
+                                        int batch, const BatchMember *members, float *report);
+hipError_t launch_open_velocity_stats(hipStream_t s, FlowStatsRecord *out, const float *v, const BatchOpenings &open, int dim_x,
+                                      int dim_y, int members, float two_dx_inv, const float *member_two_dx_inv);
+
 // ---- the draw task of many members in one launch (batch_render.hip) -----------------------------------------------
 // Image k of `images` (k in [0, count), member-major: image k starts at pixel k * H * W, H = scaling * (dim_x - 1) rows of
 // W = scaling * (dim_y - 1) uint16) = launch_render_rgb565 of the dye at colour_of_first_member + 3 * k * dim_x * dim_y,

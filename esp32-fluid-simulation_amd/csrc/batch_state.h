@@ -142,6 +142,26 @@ struct sfl_batch {
         int (*stage)(sfl_batch *b, float dt, float dx, const sfl_member_params *params) = nullptr;
         int (*step)(sfl_batch *b, bool each, const sfl::BatchStep &a) = nullptr;
     } viscosity;
+    // openings (openings.cpp; include/sfl.h "OPENINGS"): the map and the inflow as given, on the host; the open codes
+    // (batch.h BatchOpenings: the solids' code byte with the opening above it, `batch` x cells of them or cells where neither
+    // the map nor the mask is per member) and `batch` inflow velocities on the device, freed by the destroy path.  Plain data,
+    // as the solids are and for the same reason; while `set`, the step, solve and statistics calls of batch.cpp launch
+    // through the three pointers in front of the solids', and sfl_batch_set_solids calls `restage` behind a change of the
+    // mask, which forms the open codes again -- an opening counts only where the cell is fluid.  openings.cpp sets and
+    // clears all four with `set`.
+    struct Openings {
+        bool set = false, per_member = false, codes_per_member = false, inflow_per_member = false;
+        std::vector<uint8_t> map;     // cells bytes, or batch x cells (per_member)
+        std::vector<float> inflow;    // (x, y) of every member
+        uint16_t *d_codes = nullptr;
+        size_t d_bytes = 0;
+        float *d_inflow = nullptr;    // 2 x batch floats
+        int64_t inflow_cells = 0, outflow_cells = 0;   // live ones, over all members
+        int (*step)(sfl_batch *b, bool each, const sfl::BatchStep &a) = nullptr;
+        int (*solve)(sfl_batch *b, bool each, int iters, sfl::SorParams prm) = nullptr;
+        int (*stats)(sfl_batch *b, float two_dx_inv, const float *d_member_two_dx_inv) = nullptr;
+        int (*restage)(sfl_batch *b) = nullptr;
+    } openings;
 };
 
 namespace sfl {

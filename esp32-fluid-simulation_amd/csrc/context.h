@@ -17,6 +17,8 @@
 //   loads.cpp         the pressure load on solid bodies (sfl_loads*, sfl_batch_loads*, sfl_set_bodies, sfl_batch_set_bodies)
 //   context_viscous.cpp viscosity of a whole-domain context (sfl_set_viscosity, _viscosity_info, sfl_diffuse_velocity)
 //   viscous.cpp       viscosity of a batch (sfl_batch_set_viscosity, _viscosity_info, _viscosity_download)
+//   openings.cpp      inflow and outflow cells on the rim of a batch member (sfl_batch_set_openings, _set_inflow, _openings_info, ...)
+//   context_openings.cpp  the same on a whole-domain context (sfl_set_openings, _set_inflow, _openings_info, _openings_download)
 //
 // There is deliberately no CPU compute path in any of them: every operator ends in a kernel launch and fails with
 // SFL_ERR_HIP when no device is usable.
@@ -311,6 +313,25 @@ struct ContextSolids {
     // is zeroed on the stream in front)
     int (*norm)(sfl_context *c, float dx, unsigned *d_word) = nullptr;
     int (*max_div)(sfl_context *c, float two_dx_inv, unsigned *d_word) = nullptr;
+    // put the six pointers above back to what the mask alone makes them (context_openings.cpp, when its map is cleared)
+    void (*rehook)(sfl_context *c) = nullptr;
+};
+
+// Openings of a whole-domain context (context_openings.cpp; include/sfl.h "OPENINGS OF A CONTEXT"): what the context holds of
+// them.  Plain data, as ContextSolids and for the same reason; sfl_destroy frees the device arrays.  While `set`,
+// context_openings.cpp puts its own functions into the six pointers of ContextSolids -- the step, the operators, the solves,
+// the update norm, the statistics and the history's sample reach the openings' kernels through the pointers they already
+// call, and ContextSolids::set and ::d_codes stay what the solids made them -- and sfl_set_solids calls `restage` behind a
+// change of the mask, which forms the bytes again and puts the pointers back.
+struct ContextOpenings {
+    bool set = false;
+    std::vector<uint8_t> map;          // dim_x * gdim_y bytes as given
+    float inflow[2] = {0.0f, 0.0f};
+    uint8_t *d_codes = nullptr;        // a copy of the solids' code bytes, or those of an all-fluid grid
+    uint8_t *d_open = nullptr;         // the open byte of every cell (sor_open_tile.h)
+    uint32_t *d_inflow_cells = nullptr;   // the fluid inflow cells, a compact list
+    int64_t inflow_cells = 0, outflow_cells = 0;   // live ones
+    int (*restage)(sfl_context *c) = nullptr;
 };
 
 // Viscosity of a whole-domain context (context_viscous.cpp; include/sfl.h "VISCOSITY"): what the context holds of it.  Plain
@@ -451,6 +472,7 @@ struct sfl_context {
     sfl::host::Loads loads;
     int (*loads_step)(sfl_context *c) = nullptr;
     sfl::host::ContextViscosity viscosity;   // item 3a of a step (context_viscous.cpp)
+    sfl::host::ContextOpenings openings;     // inflow and outflow cells on the rim (context_openings.cpp)
 
     sfl::host::Options opt;  // what sfl_set_option stores (kOptions above: one row per option)
 

@@ -110,6 +110,7 @@ void set_hooks(sfl_context *c)
     c->solids.gradient = on ? gradient : nullptr;
     c->solids.norm = on ? norm : nullptr;
     c->solids.max_div = on ? max_div : nullptr;
+    c->solids.rehook = on ? set_hooks : nullptr;
 }
 
 }  // namespace
@@ -133,6 +134,7 @@ int sfl_set_solids(sfl_context *c, const uint8_t *mask)
             (void)hipFree(s.d_codes);
         }
         s = ContextSolids{};
+        if (c->openings.restage) SFL_TRY(c->openings.restage(c));   // (the openings' bytes and pointers: every cell is fluid again)
         return SFL_OK;
     }
     const size_t bytes = (size_t)c->dim_x * (size_t)c->gdim_y;
@@ -159,6 +161,7 @@ int sfl_set_solids(sfl_context *c, const uint8_t *mask)
     s.set = true;
     s.solid_cells = solid;
     set_hooks(c);
+    if (c->openings.restage) SFL_TRY(c->openings.restage(c));   // (an opening counts only where the cell is fluid)
     return SFL_OK;
 }
 

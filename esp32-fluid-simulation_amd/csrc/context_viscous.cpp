@@ -99,6 +99,9 @@ int sfl_set_viscosity(sfl_context *c, float nu, int sweeps)
         return SFL_OK;
     }
     SFL_TRY(check_whole_domain(c, call, "nothing set"));
+    if (c->openings.set)
+        return fail(SFL_ERR_STATE, "%s: the context has openings set (sfl_set_openings) and the viscous kernels do not know them: nothing set; "
+                    "clear the openings first (sfl_set_openings(ctx, NULL, 0, 0))", call);
     v.set = true;
     v.nu = nu;
     v.sweeps = sweeps;

@@ -55,6 +55,9 @@ int check_solids(sfl_batch *b, const char *call)
     if (b->solids.set)
         return fail(SFL_ERR_STATE, "%s: the batch has solid cells set (sfl_batch_set_solids) and a history's samples do not know them: "
                     "no history started; clear the solids first (sfl_batch_set_solids(b, NULL, 0))", call);
+    if (b->openings.set)   // (... nor those of a grid with openings: include/sfl.h "OPENINGS")
+        return fail(SFL_ERR_STATE, "%s: the batch has openings set (sfl_batch_set_openings) and a history's samples do not know them: "
+                    "no history started; clear the openings first (sfl_batch_set_openings(b, NULL, 0, NULL, 0))", call);
     return SFL_OK;
 }
 

@@ -107,6 +107,7 @@ int sfl_batch_set_solids(sfl_batch *b, const uint8_t *mask, int per_member)
             (void)hipFree(s.d_codes);
         }
         s = sfl_batch::Solids{};
+        if (b->openings.restage) SFL_TRY(b->openings.restage(b));   // (the openings' codes: every cell is fluid again)
         return SFL_OK;
     }
     const size_t members = per_member ? (size_t)b->batch : 1, bytes = members * b->cells;
@@ -132,6 +133,7 @@ int sfl_batch_set_solids(sfl_batch *b, const uint8_t *mask, int per_member)
     s.set = true;
     s.per_member = per_member != 0;
     set_hooks(b);
+    if (b->openings.restage) SFL_TRY(b->openings.restage(b));   // (an opening counts only where the cell is fluid)
     return SFL_OK;
 }
 

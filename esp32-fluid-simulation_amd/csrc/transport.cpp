@@ -580,6 +580,9 @@ static int no_solids(const sfl_context *c, const char *what)
     if (c->viscosity.set)   // ... and so does a viscosity (include/sfl.h "VISCOSITY")
         return fail(SFL_ERR_STATE, "the context has a viscosity set (sfl_set_viscosity) and no halo exchange knows the diffusion's halo: %s is refused, "
                     "nothing attached or linked; clear the viscosity first (sfl_set_viscosity(ctx, 0, 0))", what);
+    if (c->openings.set)   // ... and so do openings (include/sfl.h "OPENINGS OF A CONTEXT")
+        return fail(SFL_ERR_STATE, "the context has openings set (sfl_set_openings) and no halo exchange knows them: %s is refused, nothing attached "
+                    "or linked; clear the openings first (sfl_set_openings(ctx, NULL, 0, 0))", what);
     return SFL_OK;
 }
 

@@ -102,6 +102,9 @@ int check_solids(const char *call, const sfl_batch *b, int what)
     if (what == SFL_VIEW_DIVERGENCE && b->solids.set)
         return fail(SFL_ERR_STATE, "%s: the batch has solid cells set (sfl_batch_set_solids) and the divergence view does not know them; "
                     "sfl_batch_flow_stats reports the divergence by the solids' rule, the other views work as ever", call);
+    if (what == SFL_VIEW_DIVERGENCE && b->openings.set)   // (include/sfl.h "OPENINGS")
+        return fail(SFL_ERR_STATE, "%s: the batch has openings set (sfl_batch_set_openings) and the divergence view does not know them; "
+                    "sfl_batch_flow_stats reports the divergence by the openings' rule, the other views work as ever", call);
     return SFL_OK;
 }
 // ... and on a context that has solids set (include/sfl.h "SOLIDS OF A CONTEXT")
@@ -110,6 +113,9 @@ int check_solids(const char *call, const sfl_context *c, int what)
     if (what == SFL_VIEW_DIVERGENCE && c->solids.set)
         return fail(SFL_ERR_STATE, "%s: the context has solid cells set (sfl_set_solids) and the divergence view does not know them; "
                     "sfl_flow_stats reports the divergence by the solids' rule, the other views work as ever", call);
+    if (what == SFL_VIEW_DIVERGENCE && c->openings.set)   // (include/sfl.h "OPENINGS OF A CONTEXT")
+        return fail(SFL_ERR_STATE, "%s: the context has openings set (sfl_set_openings) and the divergence view does not know them; "
+                    "sfl_flow_stats reports the divergence by the openings' rule, the other views work as ever", call);
     return SFL_OK;
 }
 int check_bytes(const char *call, const Holder &h, size_t elem, const char *of, size_t bytes)

@@ -100,6 +100,9 @@ int sfl_batch_set_viscosity(sfl_batch *b, const float *nu, int per_member, int s
     if (b->large)
         return fail(SFL_ERR_STATE, "%s: a batch of sfl_batch_create_large has no viscosity: its 8 B of LDS per cell leave no room for u0 (members of "
                     "at most %d cells, made by sfl_batch_create, have it)", call, sfl::kSmallGridMaxCells);
+    if (b->openings.set)
+        return fail(SFL_ERR_STATE, "%s: the batch has openings set (sfl_batch_set_openings) and the viscous kernels do not know them: nothing set; "
+                    "clear the openings first (sfl_batch_set_openings(b, NULL, 0, NULL, 0))", call);
     v.nu.assign((size_t)b->batch, nu[0]);
     if (per_member) v.nu.assign(nu, nu + b->batch);
     v.set = true;

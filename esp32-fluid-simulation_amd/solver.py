@@ -711,6 +711,47 @@ class Solver(_Tracers, _History, _Loads):
         return a.astype(bool)
 
     # -- viscosity -----------------------------------------------------------------------
+    def set_openings(self, open, inflow=(0.0, 0.0)):
+        """Inflow and outflow cells on the rim of the grid (include/sfl.h "OPENINGS OF A CONTEXT"): `open` a uint8 array
+        ``(dim_y, dim_x)`` of 0, OPEN_INFLOW and OPEN_OUTFLOW, nonzero only on rim cells that are no corners; `inflow` the
+        ``(u, v)`` every fluid inflow cell holds after the forces; None clears the openings.  No field is touched.  step,
+        step_n, the operators, the solves, residual, flow_stats and histories then follow the openings' rule, with and
+        without solids; slabs, transports, the divergence view and viscosity are refused while set."""
+        if open is None:
+            capi.check(self._lib.sfl_set_openings(self._h, None, 0.0, 0.0))
+            return
+        m = np.asarray(open)
+        if m.dtype != np.uint8:
+            raise ValueError(f"openings: a uint8 map, got {m.dtype}")
+        if m.shape != (self.dim_y, self.dim_x):
+            raise ValueError(f"openings: shape {m.shape}, want {(self.dim_y, self.dim_x)}")
+        u = np.asarray(inflow, dtype=np.float32)
+        if u.shape != (2,):
+            raise ValueError(f"openings: inflow of shape {u.shape}, want (2,)")
+        m = np.ascontiguousarray(m)
+        capi.check(self._lib.sfl_set_openings(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_float(u[0]), C.c_float(u[1])))
+
+    def set_inflow(self, inflow):
+        """Change the inflow velocity ``(u, v)`` of a context with openings set.  The map stays."""
+        u = np.asarray(inflow, dtype=np.float32)
+        if u.shape != (2,):
+            raise ValueError(f"openings: inflow of shape {u.shape}, want (2,)")
+        capi.check(self._lib.sfl_set_inflow(self._h, C.c_float(u[0]), C.c_float(u[1])))
+
+    def openings_info(self):
+        """(set, live inflow cells, live outflow cells) as the library reports it."""
+        s, n_in, n_out = C.c_int(0), C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.sfl_openings_info(self._h, C.byref(s), None, None, C.byref(n_in), C.byref(n_out)))
+        return bool(s.value), n_in.value, n_out.value
+
+    def openings(self):
+        """(the map, uint8[dim_y, dim_x]; the inflow, float32[2]): zeros without openings."""
+        m = np.zeros((self.dim_y, self.dim_x), np.uint8)
+        capi.check(self._lib.sfl_openings_download(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), m.nbytes))
+        x, y = C.c_float(0), C.c_float(0)
+        capi.check(self._lib.sfl_openings_info(self._h, None, C.byref(x), C.byref(y), None, None))
+        return m, np.array([x.value, y.value], np.float32)
+
     def set_viscosity(self, nu, sweeps: int):
         """Viscosity (include/sfl.h "VISCOSITY"): step and step_n then run `sweeps` red-black sweeps of an implicit
         diffusion of the velocity between the forces and the divergence, as one unfused sequence per step.  nu == 0 or
@@ -1144,6 +1185,53 @@ class BatchSolver(_Tracers, _History, _Loads):
         a = np.zeros(self.batch, np.float32)
         capi.check(self._lib.sfl_batch_viscosity_download(self._h, 0, self.batch, a.ctypes.data_as(C.POINTER(C.c_float)), a.nbytes))
         return a, s.value
+
+    def _inflow(self, inflow):
+        a = np.asarray(inflow, dtype=np.float32)
+        if a.shape not in ((2,), (self.batch, 2)):
+            raise ValueError(f"openings: inflow of shape {a.shape}, want (2,) or {(self.batch, 2)}")
+        return np.ascontiguousarray(a.reshape(-1)), int(a.ndim == 2)
+
+    def set_openings(self, open, inflow=(0.0, 0.0)):
+        """Inflow and outflow cells on the rim of the members' grids (include/sfl.h "OPENINGS"): `open` a uint8 array of
+        0, OPEN_INFLOW and OPEN_OUTFLOW of shape ``(dim_y, dim_x)`` -- one map for all members -- or ``(batch, dim_y,
+        dim_x)``, nonzero only on rim cells that are no corners; `inflow` one ``(u, v)`` for all members or an array
+        ``(batch, 2)``; None clears the openings.  No field is touched.  Batches of small members only; step_n,
+        step_n_each, poisson_solve[_each] and flow_stats then follow the openings' rule, with and without solids; the
+        ``_until`` calls, histories, the divergence view and viscosity are refused while set."""
+        if open is None:
+            capi.check(self._lib.sfl_batch_set_openings(self._h, None, 0, None, 0))
+            return
+        m = np.asarray(open)
+        if m.dtype != np.uint8:
+            raise ValueError(f"openings: a uint8 map, got {m.dtype}")
+        if m.shape not in ((self.dim_y, self.dim_x), (self.batch, self.dim_y, self.dim_x)):
+            raise ValueError(f"openings: shape {m.shape}, want {(self.dim_y, self.dim_x)} or {(self.batch, self.dim_y, self.dim_x)}")
+        a, each = self._inflow(inflow)
+        m = np.ascontiguousarray(m)
+        capi.check(self._lib.sfl_batch_set_openings(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), int(m.ndim == 3),
+                                                    a.ctypes.data_as(C.POINTER(C.c_float)), each))
+
+    def set_inflow(self, inflow):
+        """Change the inflow velocity of a batch with openings set: one ``(u, v)`` or an array ``(batch, 2)``.  The map stays."""
+        a, each = self._inflow(inflow)
+        capi.check(self._lib.sfl_batch_set_inflow(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), each))
+
+    def openings_info(self):
+        """(set, per_member, inflow_per_member, live inflow cells, live outflow cells) as the library reports it."""
+        s, p, q, n_in, n_out = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.sfl_batch_openings_info(self._h, C.byref(s), C.byref(p), C.byref(q), C.byref(n_in), C.byref(n_out)))
+        return bool(s.value), bool(p.value), bool(q.value), n_in.value, n_out.value
+
+    def openings(self, first: int = 0, count=None):
+        """(the maps of members [first, first + count), uint8[count, dim_y, dim_x]; their inflow, float32[count, 2]): zeros
+        without openings, a shared map or inflow repeated."""
+        count = self.batch - first if count is None else count
+        m = np.zeros((max(count, 0), self.dim_y, self.dim_x), np.uint8)
+        capi.check(self._lib.sfl_batch_openings_download(self._h, first, count, m.ctypes.data_as(C.POINTER(C.c_uint8)), m.nbytes))
+        a = np.zeros((max(count, 0), 2), np.float32)
+        capi.check(self._lib.sfl_batch_inflow_download(self._h, first, count, a.ctypes.data_as(C.POINTER(C.c_float)), a.nbytes))
+        return m, a
 
     def synchronize(self):
         capi.check(self._lib.sfl_batch_synchronize(self._h))

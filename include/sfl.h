@@ -1231,6 +1231,97 @@ SFL_API int sfl_batch_set_viscosity(sfl_batch *b, const float *nu, int per_membe
 SFL_API int sfl_batch_viscosity_info(sfl_batch *b, int *set, int *per_member, int *sweeps);
 /* nu of members [first, first + count) (a shared nu: repeated; none set: zeros); bytes must be count * 4.  Never waits.    */
 SFL_API int sfl_batch_viscosity_download(sfl_batch *b, int first, int count, float *host, size_t bytes);
+/* --- OPENINGS: inflow and outflow cells on the rim of the grid of a batch member, so that a flow enters on one side and
+ *     leaves on another instead of circulating in a closed box.  The reference knows no opening: the rule below is a
+ *     definition stated here, like the solids', the loads' and the viscosity's.  It is anchored on what exists: a map
+ *     without an opening gives the bits of "SOLIDS", and with no solid cell either those of sfl_batch_step_n.
+ *   THE MAP.  One byte per cell: 0 = closed, SFL_OPEN_INFLOW, SFL_OPEN_OUTFLOW.  A nonzero byte is allowed only on a rim cell
+ * that is no corner: such a cell has exactly one neighbour outside the domain, and that side is the opening's.  An opening
+ * counts only where the cell is fluid at the time, as a body label counts only where the cell is solid; maps and masks are
+ * independent of each other, either may be set first, and either may be shared by all members or per member.
+ *   THE INFLOW VELOCITY is one (x, y) for all members or one per member -- one batch is then a sweep over the tunnel speed.
+ * It must be finite.  sfl_batch_set_inflow changes it without restaging the map.
+ *   THE RULE extends items 1 to 7 of "SOLIDS".  An OPEN neighbour is the outside neighbour of a fluid cell whose byte is
+ * nonzero; it is absent in the solids' sense.
+ *     2a. inflow            after the forces every fluid inflow cell holds the inflow velocity, both components: a force
+ *                           record on an inflow cell has no effect.  Then item 3 as ever.
+ *     4. divergence         a cell with an open neighbour takes the safe form, 0.0f plus the four terms in the order W, E, S,
+ *                           N.  The open neighbour's term is the cell's own component with the sign OPPOSITE to a wall's:
+ *                           -own.x for W, +own.x for E, -own.y for S, +own.y for N -- the ghost moves with the cell and the
+ *                           flow passes.  Both kinds.
+ *     5. pressure           n = present + 1 if the open neighbour is an OUTFLOW, else n = present.  k comes from n by the
+ *                           table of "SOLIDS" (n = 4: -0.25f).  z stays -0.0f iff all four neighbours are present, so it is
+ *                           +0.0f here, and the open neighbour contributes -0.0f to the sum as an absent one does.  An outflow
+ *                           is a ghost pressure of zero that counts as a neighbour; an inflow is a wall to the pressure.  The
+ *                           update norm uses the same k.
+ *     6. gradient           an outflow neighbour's pressure is +0.0f; an inflow neighbour's is the cell's own.
+ *   Items 1, 3 and 7 are unchanged.  The free-slip dye clamps at the rim, so an inflow cell's colour enters with the flow.
+ *   An inflow without any outflow is accepted: the Neumann problem is then incompatible and the solve drifts.
+ *   WHICH CALLS HONOUR OPENINGS, on a batch made by sfl_batch_create, with and without solids set: sfl_batch_step_n and
+ * sfl_batch_step_n_each (one launch per step, as with solids), sfl_batch_poisson_solve[_each], sfl_batch_flow_stats[_each]
+ * (max_abs_div follows item 4) and sfl_batch_residual.  Item 2a runs only in the step calls.  With openings and no mask the
+ * library forms the codes of an all-fluid grid itself; sfl_batch_solids_info still reports "not set".  Loads, render,
+ * recorder, envelope, distance, tracers and the speed, vorticity and pressure views work unchanged.
+ *   REFUSED WHOLE with SFL_ERR_STATE, each with its own message and with nothing staged or launched: sfl_batch_set_openings
+ * with a map on a batch of sfl_batch_create_large, while a history is on, while the recorder draws the divergence view and
+ * while viscosity is set; sfl_batch_step_n_until, sfl_batch_poisson_solve_until, sfl_batch_history_start,
+ * SFL_VIEW_DIVERGENCE and sfl_batch_set_viscosity with a nu while openings are set.  A call's own argument checks come first:
+ * SFL_ERR_INVALID for a NULL handle, flags outside 0..1, a byte above 2 or a nonzero byte on a corner or an interior cell (the
+ * message names the first such cell), a non-finite inflow (the first such member) and wrong download sizes.
+ *   A CHANGE OF THE MASK behind a map (sfl_batch_set_solids, sfl_set_solids) forms the openings' codes again.  If that fails
+ * (SFL_ERR_NOMEM, SFL_ERR_HIP) the call returns the error with the mask as it asked for and the openings OFF: the one case in
+ * which a failing call leaves a change behind.  Set the map again.
+ *   NOT THERE: openings together with viscosity and in the viscous kernels; a per-cell inflow profile; a flux diagnostic;
+ * openings on slabs and on the batches of sfl_batch_create_large.                                                          */
+#define SFL_OPEN_INFLOW  1
+#define SFL_OPEN_OUTFLOW 2
+/* Set the openings: open = dim_y * dim_x bytes shared by all members (per_member 0) or batch * dim_y * dim_x bytes, member-
+ * major (per_member 1), cell (i, j) at dim_x * j + i; inflow = one (x, y) for all members (inflow_per_member 0) or `batch` of
+ * them (1).  Both are read during the call only.  open NULL clears the openings (inflow is then ignored): the batch then
+ * launches exactly what it launched before they were set.  No field is touched.  Synchronous.                             */
+SFL_API int sfl_batch_set_openings(sfl_batch *b, const uint8_t *open, int per_member, const float *inflow, int inflow_per_member);
+/* Change the inflow velocity of a batch that has openings set (without: SFL_ERR_STATE).  The map stays.  Synchronous.      */
+SFL_API int sfl_batch_set_inflow(sfl_batch *b, const float *inflow, int per_member);
+/* Whether openings are set, whether the map and the inflow are per member, and the numbers of live -- fluid -- inflow and
+ * outflow cells over all members (a shared map counts once per member).  Any out pointer may be NULL.  Never waits.        */
+SFL_API int sfl_batch_openings_info(sfl_batch *b, int *set, int *per_member, int *inflow_per_member, int64_t *inflow_cells,
+                                    int64_t *outflow_cells);
+/* The maps of members [first, first + count) as given, member-major (a shared map: repeated; none set: zeros); bytes must be
+ * count * dim_y * dim_x.  Never waits.                                                                                     */
+SFL_API int sfl_batch_openings_download(sfl_batch *b, int first, int count, uint8_t *host, size_t bytes);
+/* The inflow (x, y) of members [first, first + count) (shared: repeated; none set: zeros); bytes must be count * 8.  Never
+ * waits.                                                                                                                   */
+SFL_API int sfl_batch_inflow_download(sfl_batch *b, int first, int count, float *host, size_t bytes);
+/* --- OPENINGS OF A CONTEXT: the same openings on the rim of a whole-domain context, at any grid size.  The map, the rule and
+ *     the inflow are those of "OPENINGS" above, unchanged, with ONE inflow velocity per context: one step of a context with
+ *     openings set computes, bit for bit, what one step of a batch member of the same shape with the same map, mask and inflow
+ *     computes, and with no opening in the map what the context computes without one.
+ *   WHICH CALLS HONOUR OPENINGS while a map is set, with and without a mask, as the calls of "SOLIDS OF A CONTEXT" honour solids:
+ *     sfl_step, sfl_step_n      ONE UNFUSED SEQUENCE per step: the velocity advection, the forces, item 2a over a compact list
+ *                               of the fluid inflow cells, the divergence (which also zeroes the solid cells), the solve, the
+ *                               gradient, the dye advection.  Item 2a runs only here: the operators never impose the inflow.
+ *     sfl_calculate_divergence, sfl_poisson_solve, sfl_poisson_continue, sfl_subtract_gradient   items 4, 5, 5 and 6.
+ *     sfl_residual, sfl_poisson_solve_until, sfl_flow_stats, sfl_history_*   the update norm with the k of item 5 and
+ *                               max_abs_div by item 4; a history's sample is what the two calls return after the same step.
+ *   The solve is the masked solve's tile, ceil(iters / 8) launches, with k set up from n.  With openings and no mask the library
+ * forms the codes of an all-fluid grid itself; sfl_solids_info still reports "not set".  Loads, render, sfl_distance, tracers
+ * and the speed, vorticity and pressure views work unchanged.
+ *   REFUSED WHOLE with SFL_ERR_STATE, each with its own message and with nothing staged or launched: sfl_set_openings with a map
+ * on a slab (nranks != 1), on a context that has a transport attached and while viscosity is set; sfl_comm_attach,
+ * sfl_comm_emulate, sfl_comm_emulate_rccl and sfl_group_link, SFL_VIEW_DIVERGENCE and sfl_set_viscosity with a nu while openings
+ * are set.  A call's own argument checks come first: a NULL handle, a non-finite inflow, a bad map (the message names the first
+ * such cell) and a wrong download size return SFL_ERR_INVALID.                                                              */
+/* Set the openings: open = dim_y * dim_x bytes, cell (i, j) at dim_x * j + i, read during the call only.  open NULL clears them
+ * (the inflow is then ignored): the context then launches exactly what it launched before.  No field is touched.  Synchronous. */
+SFL_API int sfl_set_openings(sfl_context *ctx, const uint8_t *open, float inflow_x, float inflow_y);
+/* Change the inflow velocity of a context that has openings set (without: SFL_ERR_STATE).  The map stays.  Never waits.    */
+SFL_API int sfl_set_inflow(sfl_context *ctx, float inflow_x, float inflow_y);
+/* Whether openings are set, the inflow, and the numbers of live -- fluid -- inflow and outflow cells.  Any out pointer may be
+ * NULL.  Never waits.                                                                                                      */
+SFL_API int sfl_openings_info(sfl_context *ctx, int *set, float *inflow_x, float *inflow_y, int64_t *inflow_cells,
+                              int64_t *outflow_cells);
+/* The map as given (none set: zeros); bytes must be dim_y * dim_x.  Never waits.                                           */
+SFL_API int sfl_openings_download(sfl_context *ctx, uint8_t *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
