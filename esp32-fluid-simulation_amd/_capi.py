@@ -74,6 +74,12 @@ class HistoryRecord(C.Structure):
                 ("dt", C.c_float), ("dx", C.c_float)]
 
 
+class OpenFlux(C.Structure):
+    """struct sfl_open_flux: the flux through the live open cells of one grid, 40 bytes."""
+    _fields_ = [("inflow", C.c_int64), ("outflow", C.c_int64), ("exp2", C.c_int32), ("max_abs_n", C.c_float), ("inflow_cells", C.c_uint32),
+                ("outflow_cells", C.c_uint32), ("nonfinite", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class BodyLoad(C.Structure):
     """struct sfl_body_load: the pressure load on one solid body, 48 bytes."""
     _fields_ = [("fx", C.c_int64), ("fy", C.c_int64), ("exp2", C.c_int32), ("max_abs_p", C.c_float), ("faces", C.c_uint32 * 4),
@@ -296,6 +302,14 @@ SIGNATURES = {
     "sfl_set_inflow": (_i, [_ctx, _f, _f]),
     "sfl_openings_info": (_i, [_ctx, _pi, _pf, _pf, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sfl_openings_download": (_i, [_ctx, C.POINTER(C.c_uint8), _sz]),
+    "sfl_set_inflow_profile": (_i, [_ctx, _pi, _pf, _i]),
+    "sfl_inflow_profile_info": (_i, [_ctx, _pi]),
+    "sfl_inflow_profile_download": (_i, [_ctx, _pi, _pf, _i]),
+    "sfl_openings_flux": (_i, [_ctx, C.POINTER(OpenFlux)]),
+    "sfl_batch_set_inflow_profile": (_i, [_ctx, _pi, _pi, _pf, _i]),
+    "sfl_batch_inflow_profile_info": (_i, [_ctx, _pi, C.POINTER(C.c_int64)]),
+    "sfl_batch_inflow_profile_download": (_i, [_ctx, _i, _pi, _pf, _i, _pi]),
+    "sfl_batch_openings_flux": (_i, [_ctx, _i, _i, C.POINTER(OpenFlux), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

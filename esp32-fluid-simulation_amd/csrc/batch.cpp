@@ -22,7 +22,7 @@ void release(sfl_batch *b)
                     (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
                     (void *)b->d_rec_palette, b->history.d_records, (void *)b->solids.d_codes,
                     (void *)b->loads.d_labels, b->loads.d_records, b->viscosity.d_table, (void *)b->openings.d_codes,
-                    (void *)b->openings.d_inflow})
+                    (void *)b->openings.d_inflow, b->openings.d_profile, b->openings.d_flux})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
     if (b->h_dist) (void)hipHostFree(b->h_dist);

@@ -6,6 +6,8 @@
 #pragma once
 #include "kernels.h"
 
+struct sfl_open_flux;   // include/sfl.h
+
 namespace sfl {
 
 // One step (ino:252-287) of every member.  `step` describes member 0: its arrays (the kernel adds each member's offset,
@@ -141,6 +143,25 @@ hipError_t launch_batch_open_solve_each(hipStream_t s, float *p, const float *d,
                                         int batch, const BatchMember *members, float *report);
 hipError_t launch_open_velocity_stats(hipStream_t s, FlowStatsRecord *out, const float *v, const BatchOpenings &open, int dim_x,
                                       int dim_y, int members, float two_dx_inv, const float *member_two_dx_inv);
+
+// ---- members with an inflow profile, and the flux through the openings (include/sfl.h "INFLOW PROFILES AND FLUX") ----
+// The profile as ONE CSR table on the device, formed by the host (inflow.cpp) once per change of the profile, the map or
+// the mask: member m's records are [offsets[m], offsets[m + 1]), record k the cell index cells[k] -- a FLUID inflow cell
+// of that member, unique within the row -- and its velocity (vel[2 * k], vel[2 * k + 1]).
+struct BatchProfile {
+    const int *offsets;
+    const uint32_t *cells;
+    const float *vel;
+};
+// launch_batch_open_step[_each] (batch_openings.hip) with the records of the member's row written behind the advection:
+// with empty rows, or rows that hold the uniform inflow, the same results bit for bit.
+hipError_t launch_batch_open_profile_step(hipStream_t s, const BatchStep &a, const BatchOpenings &open, const BatchProfile &profile, int batch);
+hipError_t launch_batch_open_profile_step_each(hipStream_t s, const BatchStep &a, const BatchOpenings &open, const BatchProfile &profile,
+                                               int batch, const BatchMember *members, float *report);
+// out[k] = the flux record of member first + k, k in [0, count), from the velocity at v (member 0's) and the open codes
+// (inflow.hip): one launch, one workgroup per member, ordinary stores.
+hipError_t launch_batch_open_flux(hipStream_t s, struct sfl_open_flux *out, const float *v, const BatchOpenings &open, int dim_x, int dim_y,
+                                  int first, int count);
 
 // ---- the draw task of many members in one launch (batch_render.hip) -----------------------------------------------
 // Image k of `images` (k in [0, count), member-major: image k starts at pixel k * H * W, H = scaling * (dim_x - 1) rows of

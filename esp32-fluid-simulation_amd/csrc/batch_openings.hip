@@ -13,6 +13,8 @@
 //     inflow cell the member's inflow velocity;
 //   * forces in queue order, a record on a solid cell or on an inflow cell skipped: together the same as imposing the
 //     inflow and zeroing the solids after the forces, without a pass and a barrier of their own;
+//   * with an inflow profile (the kernels named *_profile_*; include/sfl.h "INFLOW PROFILES AND FLUX"): the records of the
+//     member's row of the profile's table into the same array, beside the forces;
 //   * divergence (divergence_sum_open), solve (sor_open_in_lds: sor_solid_in_lds' loop, only the set-up of k differs),
 //     gradient (project_cell_open), dye as ever.
 //
@@ -71,9 +73,25 @@ __device__ __forceinline__ float2 member_inflow(const BatchOpenings &o, size_t m
     return make_float2(o.inflow[2 * member], o.inflow[2 * member + 1]);
 }
 
+// the row of one member in the profile's table ("INFLOW PROFILES AND FLUX"); none for a step without a profile
+struct ProfileRow {
+    const uint32_t *cells;
+    const float2 *vel;
+    int n;
+};
+__device__ __forceinline__ ProfileRow member_profile(const BatchProfile &t, size_t member)
+{
+    const int r0 = t.offsets[member], r1 = t.offsets[member + 1];   // workgroup-uniform: scalar loads
+    return ProfileRow{t.cells + r0, reinterpret_cast<const float2 *>(t.vel) + r0, r1 - r0};
+}
+
 // One whole step of the grid `a` describes, its open codes at `codes`; returns the carved LDS (p and d final, for the
-// update norm of the *_each kernel).
-__device__ __forceinline__ Lds open_step(const SmallStep &a, const uint16_t *__restrict__ codes, float2 inflow, char *lds_raw)
+// update norm of the *_each kernel).  kProfile: the records of `row` -- unique fluid inflow cells, which the force loop
+// never writes -- go into l.v by all threads behind the advection's barrier, beside the forces, and ONE barrier that every
+// workgroup reaches stands in front of the divergence instead of the forces' own.
+template <bool kProfile = false>
+__device__ __forceinline__ Lds open_step(const SmallStep &a, const uint16_t *__restrict__ codes, float2 inflow, char *lds_raw,
+                                         ProfileRow row = ProfileRow{nullptr, nullptr, 0})
 {
     const int dim_x = a.dim_x, dim_y = a.dim_y, cells = dim_x * dim_y;
     const Lds l = carve(lds_raw, cells);
@@ -93,6 +111,8 @@ __device__ __forceinline__ Lds open_step(const SmallStep &a, const uint16_t *__r
         l.v[c] = !(code & kSolidFluid) ? make_float2(0.0f, 0.0f) : is_inflow_cell(code) ? inflow : r;
     }
     __syncthreads();
+    if constexpr (kProfile)   // the profile's part of item 2a
+        for (int k = threadIdx.x; k < row.n; k += kThreads) l.v[row.cells[k]] = row.vel[k];
     // drag forces, in queue order: later entries win; a record on a solid or an inflow cell has no effect (items 2, 2a, 3)
     if (a.n_forces > 0) {
         if (threadIdx.x == 0)
@@ -103,8 +123,9 @@ __device__ __forceinline__ Lds open_step(const SmallStep &a, const uint16_t *__r
                 if (!(code & kSolidFluid) || is_inflow_cell(code)) continue;
                 l.v[gj * dim_x + i] = make_float2(a.force_vel[2 * k], a.force_vel[2 * k + 1]);
             }
-        __syncthreads();
+        if constexpr (!kProfile) __syncthreads();
     }
+    if constexpr (kProfile) __syncthreads();   // the records and the forces are visible to the divergence
     // the divergence of a fluid cell; 0.0f in a solid one (item 4)
     for (int c = threadIdx.x; c < cells; c += kThreads) {
         const int code = codes[c];
@@ -165,6 +186,32 @@ batch_open_step_each_kernel(BatchStep b, BatchOpenings open, const BatchMember *
     const uint16_t *codes = member_codes(open, member);
     const Lds l = open_step(a, codes, member_inflow(open, member), lds_raw);
     // (the step's last loop only reads l.p and l.v; l.p and l.d are final since the solve's last barrier)
+    update_norm_open_in_lds<kThreads>(l.p, l.d, codes, a.dim_x, a.dim_y, a.prm.dx, report + member);
+}
+
+// ... with an inflow profile: the same step, the member's row of the table beside its codes
+__global__ void SFL_BATCH_BOUNDS
+batch_open_profile_step_kernel(BatchStep b, BatchOpenings open, BatchProfile profile)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    const SmallStep a = member_step(b, blockIdx.x);
+    open_step<true>(a, member_codes(open, blockIdx.x), member_inflow(open, blockIdx.x), lds_raw, member_profile(profile, blockIdx.x));
+}
+
+__global__ void SFL_BATCH_BOUNDS
+batch_open_profile_step_each_kernel(BatchStep b, BatchOpenings open, BatchProfile profile, const BatchMember *__restrict__ members,
+                                    float *__restrict__ report)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    const BatchMember q = members[blockIdx.x];
+    const size_t member = (size_t)q.member;
+    SmallStep a = member_step(b, member);
+    a.dt = q.dt;
+    a.two_dx_inv = q.two_dx_inv;
+    a.iters = q.iters;
+    a.prm = q.prm;
+    const uint16_t *codes = member_codes(open, member);
+    const Lds l = open_step<true>(a, codes, member_inflow(open, member), lds_raw, member_profile(profile, member));
     update_norm_open_in_lds<kThreads>(l.p, l.d, codes, a.dim_x, a.dim_y, a.prm.dx, report + member);
 }
 
@@ -252,6 +299,17 @@ hipError_t launch_batch_open_step_each(hipStream_t s, const BatchStep &a, const 
                                        const BatchMember *members, float *report)
 {
     return launch_members<batch_open_step_each_kernel>(s, a.step.dim_x, a.step.dim_y, batch, a, open, members, report);
+}
+
+hipError_t launch_batch_open_profile_step(hipStream_t s, const BatchStep &a, const BatchOpenings &open, const BatchProfile &profile, int batch)
+{
+    return launch_members<batch_open_profile_step_kernel>(s, a.step.dim_x, a.step.dim_y, batch, a, open, profile);
+}
+
+hipError_t launch_batch_open_profile_step_each(hipStream_t s, const BatchStep &a, const BatchOpenings &open, const BatchProfile &profile,
+                                               int batch, const BatchMember *members, float *report)
+{
+    return launch_members<batch_open_profile_step_each_kernel>(s, a.step.dim_x, a.step.dim_y, batch, a, open, profile, members, report);
 }
 
 hipError_t launch_batch_open_solve(hipStream_t s, float *p, const float *d, const BatchOpenings &open, int dim_x, int dim_y,

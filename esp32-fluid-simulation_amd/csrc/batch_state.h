@@ -161,6 +161,25 @@ struct sfl_batch {
         int (*solve)(sfl_batch *b, bool each, int iters, sfl::SorParams prm) = nullptr;
         int (*stats)(sfl_batch *b, float two_dx_inv, const float *d_member_two_dx_inv) = nullptr;
         int (*restage)(sfl_batch *b) = nullptr;
+        // the inflow profile and the flux (inflow.cpp; include/sfl.h "INFLOW PROFILES AND FLUX").  The records as given,
+        // duplicates removed and in cell order: one row for all members (profile_shared) or one per member; profile_on: a
+        // profile is held (it may hold no record).  ONE CSR table on the device (batch.h BatchProfile: `batch` + 1 offsets, the
+        // cells, the velocities) that names only the cells that are fluid inflow cells at the time, and `batch` flux records;
+        // both freed where the codes are.  While a profile is held the openings' step launches through profile_step, and the
+        // staging of the codes (a new mask) forms the table again through profile_restage with the codes it has just made
+        // (member stride as in BatchOpenings).  inflow.cpp sets both; a new map and a clearing drop them with the profile.
+        struct ProfileRecord {
+            uint32_t cell;
+            float u, v;
+        };
+        bool profile_on = false, profile_shared = false;
+        std::vector<std::vector<ProfileRecord>> profile;
+        void *d_profile = nullptr;
+        size_t d_profile_bytes = 0;
+        sfl::BatchProfile profile_table{nullptr, nullptr, nullptr};
+        void *d_flux = nullptr;
+        int (*profile_step)(sfl_batch *b, bool each, const sfl::BatchStep &a) = nullptr;
+        int (*profile_restage)(sfl_batch *b, const uint16_t *codes, size_t member_stride) = nullptr;
     } openings;
 };
 

@@ -18,7 +18,9 @@
 //   context_viscous.cpp viscosity of a whole-domain context (sfl_set_viscosity, _viscosity_info, sfl_diffuse_velocity)
 //   viscous.cpp       viscosity of a batch (sfl_batch_set_viscosity, _viscosity_info, _viscosity_download)
 //   openings.cpp      inflow and outflow cells on the rim of a batch member (sfl_batch_set_openings, _set_inflow, _openings_info, ...)
-//   context_openings.cpp  the same on a whole-domain context (sfl_set_openings, _set_inflow, _openings_info, _openings_download)
+//   context_openings.cpp  the same on a whole-domain context (sfl_set_openings, _set_inflow, _openings_info, _openings_download), with its
+//                     inflow profile and flux (sfl_set_inflow_profile, _inflow_profile_info, _inflow_profile_download, sfl_openings_flux)
+//   inflow.cpp        the inflow profile of a batch and the flux through its openings (sfl_batch_set_inflow_profile, ..., sfl_batch_openings_flux)
 //
 // There is deliberately no CPU compute path in any of them: every operator ends in a kernel launch and fails with
 // SFL_ERR_HIP when no device is usable.
@@ -332,6 +334,19 @@ struct ContextOpenings {
     uint32_t *d_inflow_cells = nullptr;   // the fluid inflow cells, a compact list
     int64_t inflow_cells = 0, outflow_cells = 0;   // live ones
     int (*restage)(sfl_context *c) = nullptr;
+    // the inflow profile and the flux (include/sfl.h "INFLOW PROFILES AND FLUX"): the compact list on the host, the records as
+    // given (duplicates removed, in cell order; profile_on: a profile is held), and beside the list on the device one (u, v)
+    // per list entry -- the record's velocity where the profile has one, the uniform inflow elsewhere --, formed again when
+    // the profile, the inflow or the mask changes; the one flux record.  Freed where the list is.
+    struct ProfileRecord {
+        uint32_t cell;
+        float u, v;
+    };
+    std::vector<uint32_t> list;
+    bool profile_on = false;
+    std::vector<ProfileRecord> profile;
+    float *d_inflow_values = nullptr;
+    void *d_flux = nullptr;
 };
 
 // Viscosity of a whole-domain context (context_viscous.cpp; include/sfl.h "VISCOSITY"): what the context holds of it.  Plain

@@ -88,6 +88,7 @@ sfl::BatchOpenings openings_of(const sfl_batch *b)
 
 int step(sfl_batch *b, bool each, const sfl::BatchStep &a)
 {
+    if (b->openings.profile_step) return b->openings.profile_step(b, each, a);   // (an inflow profile is held: inflow.cpp)
     if (each)
         HIP_TRY(sfl::launch_batch_open_step_each(b->stream, a, openings_of(b), b->batch, b->d_members, b->d_report));
     else
@@ -130,8 +131,24 @@ int clear(sfl_batch *b)
     if (o.d_codes || o.d_inflow) HIP_TRY(hipStreamSynchronize(b->stream));
     if (o.d_codes) (void)hipFree(o.d_codes);
     if (o.d_inflow) (void)hipFree(o.d_inflow);
+    if (o.d_profile) (void)hipFree(o.d_profile);
+    if (o.d_flux) (void)hipFree(o.d_flux);
     o = sfl_batch::Openings{};
     return SFL_OK;
+}
+
+// a new map: the inflow profile goes ("INFLOW PROFILES AND FLUX"; the stream is idle)
+void drop_profile(sfl_batch *b)
+{
+    sfl_batch::Openings &o = b->openings;
+    if (o.d_profile) (void)hipFree(o.d_profile);
+    o.d_profile = nullptr;
+    o.d_profile_bytes = 0;
+    o.profile_table = sfl::BatchProfile{nullptr, nullptr, nullptr};
+    o.profile.clear();
+    o.profile_on = o.profile_shared = false;
+    o.profile_step = nullptr;
+    o.profile_restage = nullptr;
 }
 
 // a device allocation of the call `call`; nothing is held on failure
@@ -182,6 +199,7 @@ int stage_codes(sfl_batch *b, const char *call)
     HIP_TRY(hipMemcpyAsync(o.d_codes, codes.data(), want, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));   // (`codes` goes with this call)
     o.codes_per_member = members != 1;
+    if (o.profile_restage) SFL_TRY(o.profile_restage(b, codes.data(), members != 1 ? cells : 0));   // (the profile's table names fluid cells only)
     set_hooks(b, true);
     return SFL_OK;
 }
@@ -266,6 +284,10 @@ int sfl_batch_set_openings(sfl_batch *b, const uint8_t *open, int per_member, co
     HIP_TRY(hipSetDevice(b->device));
     if (!open) return clear(b);
     sfl_batch::Openings &o = b->openings;
+    if (o.profile_on) {   // (launches in flight may still read its table)
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        drop_profile(b);
+    }
     o.map.assign(open, open + (per_member ? (size_t)b->batch : 1) * b->cells);
     o.per_member = per_member != 0;
     keep_inflow(b, inflow, inflow_per_member);

@@ -81,6 +81,10 @@ HISTORY_DTYPE = np.dtype({"names": ["max_abs_vx", "max_abs_vy", "max_abs_div", "
 # and body).  48 bytes; the load in pressure times cell widths is fx * 2^exp2, fy * 2^exp2.
 BODY_LOAD_DTYPE = np.dtype([("fx", "<i8"), ("fy", "<i8"), ("exp2", "<i4"), ("max_abs_p", "<f4"), ("faces", "<u4", (4,)),
                             ("nonfinite", "<u4"), ("reserved", "<u4")])
+# struct sfl_open_flux: the flux through the live open cells of one grid (Solver.openings_flux: one record;
+# BatchSolver.openings_flux: one per member).  40 bytes; the flux in velocity times cell widths is inflow * 2^exp2.
+OPEN_FLUX_DTYPE = np.dtype([("inflow", "<i8"), ("outflow", "<i8"), ("exp2", "<i4"), ("max_abs_n", "<f4"), ("inflow_cells", "<u4"),
+                            ("outflow_cells", "<u4"), ("nonfinite", "<u4"), ("reserved", "<u4")])
 HISTORY_THREADS = 1024  # kHistoryThreads of csrc/history_kernels.h: threads of the sampler's workgroup (stated for the tests)
 
 
@@ -752,6 +756,29 @@ class Solver(_Tracers, _History, _Loads):
         capi.check(self._lib.sfl_openings_info(self._h, None, C.byref(x), C.byref(y), None, None))
         return m, np.array([x.value, y.value], np.float32)
 
+    def set_inflow_profile(self, cells, vel):
+        """A per-cell inflow profile (include/sfl.h "INFLOW PROFILES AND FLUX"): `cells` integers ``(n, 2)``, (i, j) per
+        record, each a cell whose map byte is OPEN_INFLOW; `vel` float32 ``(n, 2)``.  After the forces those cells hold their
+        record's velocity, every other fluid inflow cell the uniform inflow.  Of two records on one cell the later wins;
+        n == 0 (or None) clears the profile; a new map drops it, set_inflow keeps it."""
+        c, v = _profile_records([] if cells is None else cells, [] if vel is None else vel)
+        capi.check(self._lib.sfl_set_inflow_profile(self._h, c.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data_as(C.POINTER(C.c_float)), len(c)))
+
+    def inflow_profile(self):
+        """(cells int32[n, 2], vel float32[n, 2]): the records held, in cell-index order; empty without a profile."""
+        n = C.c_int(0)
+        capi.check(self._lib.sfl_inflow_profile_info(self._h, C.byref(n)))
+        c, v = np.zeros((n.value, 2), np.int32), np.zeros((n.value, 2), np.float32)
+        capi.check(self._lib.sfl_inflow_profile_download(self._h, c.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data_as(C.POINTER(C.c_float)), n.value))
+        return c, v
+
+    def openings_flux(self) -> np.ndarray:
+        """The flux through the live open cells from the velocity held: one OPEN_FLUX_DTYPE record (shape ``()``); exact
+        integers, see :func:`openings_flux_xy`.  All zeros without openings.  One launch over the rim, synchronous."""
+        out = np.zeros((), OPEN_FLUX_DTYPE)
+        capi.check(self._lib.sfl_openings_flux(self._h, out.ctypes.data_as(C.POINTER(capi.OpenFlux))))
+        return out
+
     def set_viscosity(self, nu, sweeps: int):
         """Viscosity (include/sfl.h "VISCOSITY"): step and step_n then run `sweeps` red-black sweeps of an implicit
         diffusion of the velocity between the forces and the divergence, as one unfused sequence per step.  nu == 0 or
@@ -1233,8 +1260,71 @@ class BatchSolver(_Tracers, _History, _Loads):
         capi.check(self._lib.sfl_batch_inflow_download(self._h, first, count, a.ctypes.data_as(C.POINTER(C.c_float)), a.nbytes))
         return m, a
 
+    def set_inflow_profile(self, cells, vel, members=None):
+        """A per-cell inflow profile (include/sfl.h "INFLOW PROFILES AND FLUX"): `cells` integers ``(n, 2)``, (i, j) per
+        record; `vel` float32 ``(n, 2)``; `members` None -- every record to every member -- or ``n`` member numbers, record k
+        to member members[k] (one batch is then a sweep over the profile).  Each record names a cell whose map byte is
+        OPEN_INFLOW in every member it applies to.  Of two records on one cell of one member the later wins; n == 0 (or
+        None) clears the profile; a new map drops it, set_inflow keeps it."""
+        c, v = _profile_records([] if cells is None else cells, [] if vel is None else vel)
+        who = None
+        if members is not None and len(c):
+            w = np.asarray(members)
+            if w.shape != (len(c),) or not np.issubdtype(w.dtype, np.integer):
+                raise ValueError(f"inflow profile: members of shape {w.shape} and dtype {w.dtype}, want {(len(c),)} integers")
+            w = np.ascontiguousarray(w, np.int32)
+            who = w.ctypes.data_as(C.POINTER(C.c_int))
+        capi.check(self._lib.sfl_batch_set_inflow_profile(self._h, who, c.ctypes.data_as(C.POINTER(C.c_int)),
+                                                          v.ctypes.data_as(C.POINTER(C.c_float)), len(c)))
+
+    def inflow_profile(self, member: int = 0):
+        """(cells int32[n, 2], vel float32[n, 2]): the records of one member, in cell-index order; empty without a profile."""
+        n = C.c_int(0)
+        rc = self._lib.sfl_batch_inflow_profile_download(self._h, member, None, None, 0, C.byref(n))   # (no room: the count alone)
+        if rc != capi.OK and n.value == 0:
+            capi.check(rc)
+        c, v = np.zeros((n.value, 2), np.int32), np.zeros((n.value, 2), np.float32)
+        capi.check(self._lib.sfl_batch_inflow_profile_download(self._h, member, c.ctypes.data_as(C.POINTER(C.c_int)),
+                                                               v.ctypes.data_as(C.POINTER(C.c_float)), n.value, None))
+        return c, v
+
+    def inflow_profile_info(self):
+        """(set, unique cells held over all members) as the library reports it.  Never waits."""
+        s, n = C.c_int(0), C.c_int64(0)
+        capi.check(self._lib.sfl_batch_inflow_profile_info(self._h, C.byref(s), C.byref(n)))
+        return bool(s.value), n.value
+
+    def openings_flux(self, first: int = 0, count=None) -> np.ndarray:
+        """The flux through the live open cells of members [first, first + count) from the velocity held: an
+        OPEN_FLUX_DTYPE array of shape ``(count,)``; exact integers, see :func:`openings_flux_xy`.  All zeros without
+        openings.  One launch, one workgroup per member over its rim; synchronous."""
+        count = self.batch - first if count is None else count
+        out = np.zeros((max(count, 0),), OPEN_FLUX_DTYPE)
+        capi.check(self._lib.sfl_batch_openings_flux(self._h, first, count, out.ctypes.data_as(C.POINTER(capi.OpenFlux)), out.nbytes))
+        return out
+
     def synchronize(self):
         capi.check(self._lib.sfl_batch_synchronize(self._h))
+
+
+def _profile_records(cells, vel):
+    """(cells int32[n, 2], vel float32[n, 2]) of an inflow profile, checked for shape before the library sees them."""
+    c = np.asarray(cells)
+    v = np.asarray(vel, dtype=np.float32)
+    if c.size == 0 and v.size == 0:
+        return np.zeros((0, 2), np.int32), np.zeros((0, 2), np.float32)
+    if c.ndim != 2 or c.shape[1] != 2 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"inflow profile: cells of shape {c.shape} and dtype {c.dtype}, want integers (n, 2): (i, j) per record")
+    if v.shape != c.shape:
+        raise ValueError(f"inflow profile: vel of shape {v.shape}, want {c.shape}: (u, v) per record")
+    return np.ascontiguousarray(c, np.int32), np.ascontiguousarray(v)
+
+
+def openings_flux_xy(flux) -> np.ndarray:
+    """OPEN_FLUX_DTYPE record(s) as float64 ``(..., 2)``: inflow * 2^exp2 and outflow * 2^exp2, in velocity times cell widths
+    (multiply by dx).  Exact: an integer below 2^49 times a power of two."""
+    f = np.asarray(flux)
+    return np.stack([np.ldexp(f["inflow"].astype(np.float64), f["exp2"]), np.ldexp(f["outflow"].astype(np.float64), f["exp2"])], axis=-1)
 
 
 def _fp(a):

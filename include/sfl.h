@@ -1271,8 +1271,9 @@ SFL_API int sfl_batch_viscosity_download(sfl_batch *b, int first, int count, flo
  *   A CHANGE OF THE MASK behind a map (sfl_batch_set_solids, sfl_set_solids) forms the openings' codes again.  If that fails
  * (SFL_ERR_NOMEM, SFL_ERR_HIP) the call returns the error with the mask as it asked for and the openings OFF: the one case in
  * which a failing call leaves a change behind.  Set the map again.
- *   NOT THERE: openings together with viscosity and in the viscous kernels; a per-cell inflow profile; a flux diagnostic;
- * openings on slabs and on the batches of sfl_batch_create_large.                                                          */
+ *   NOT THERE: openings together with viscosity and in the viscous kernels; openings on slabs and on the batches of
+ * sfl_batch_create_large.  (A per-cell inflow profile and a flux diagnostic, once listed here, are the calls of "INFLOW
+ * PROFILES AND FLUX" below.)                                                                                               */
 #define SFL_OPEN_INFLOW  1
 #define SFL_OPEN_OUTFLOW 2
 /* Set the openings: open = dim_y * dim_x bytes shared by all members (per_member 0) or batch * dim_y * dim_x bytes, member-
@@ -1322,6 +1323,84 @@ SFL_API int sfl_openings_info(sfl_context *ctx, int *set, float *inflow_x, float
                               int64_t *outflow_cells);
 /* The map as given (none set: zeros); bytes must be dim_y * dim_x.  Never waits.                                           */
 SFL_API int sfl_openings_download(sfl_context *ctx, uint8_t *host, size_t bytes);
+/* --- INFLOW PROFILES AND FLUX: an inflow velocity per cell instead of one per member or context -- parabolic inlets, shear
+ *     layers, jets --, and how much fluid enters and leaves through the openings, without a download.  Both extend "OPENINGS"
+ *     and "OPENINGS OF A CONTEXT" by calls of their own; with no profile set and no flux call made, every call launches exactly
+ *     what it launched before.
+ *   A PROFILE is a set of records (cell (i, j), velocity (u, v)).  It extends item 2a: after the forces, a fluid inflow cell
+ * named by a record holds that record's velocity, both components; every other fluid inflow cell holds the uniform inflow as
+ * before.  A force record on a profiled cell has no effect, as on any inflow cell.  Items 1, 3 and 4 to 7 are unchanged.
+ *     - A record must name a cell whose map byte is SFL_OPEN_INFLOW -- in a batch with per-member maps, in the map of every
+ *       member the record applies to.  Otherwise the call returns SFL_ERR_INVALID and the message names the first offending
+ *       record, and the member where there is one.  The velocity must be finite.
+ *     - Of two records on one cell of one member the later wins.  The host removes the duplicates: the device sees unique
+ *       cells, and the result does not depend on the order of execution.
+ *     - A record on an inflow cell that is solid at the time has no effect: an opening counts only where the cell is fluid.
+ *       The record is kept, and counts again when the cell is fluid again.
+ *     - A call replaces the profile that was set; n == 0 clears it.  A new map (sfl_batch_set_openings, sfl_set_openings) drops
+ *       the profile; a new uniform inflow (sfl_batch_set_inflow, sfl_set_inflow) keeps it -- with a profile set, sfl_set_inflow
+ *       forms the context's table again and waits for the stream.
+ *     - A CHANGE OF THE MASK behind a map forms the profile's device table again together with the openings' codes; the rule
+ *       for a failure there, in "OPENINGS", covers it: the openings go OFF, and the profile with them.
+ *     - ANCHOR: a profile that gives every inflow cell the uniform inflow velocity produces the bits of no profile.
+ *   A batch keeps the profile as one table on the device, staged once per change of the profile, the map or the mask, never
+ * per step, and steps through kernels of its own (sfl_batch_step_n, sfl_batch_step_n_each; one launch per step, as with
+ * openings alone); without a profile it launches what it launched before.  A context runs item 2a over its compact list with
+ * one velocity per list entry: the record's where there is one, the uniform inflow elsewhere.
+ *   THE FLUX is computed from the velocity HELD, over the LIVE OPEN CELLS: the fluid cells with a nonzero map byte.  After a
+ * step the inflow cells hold the inflow MINUS the pressure gradient of item 6: the figure is what actually enters, not what
+ * was imposed.  The quantisation is that of "LOADS", word for word:
+ *     n              the outward normal component of the cell's velocity: -v.x on the W rim, +v.x on E, -v.y on S, +v.y on N;
+ *     nonfinite      the number of live open cells whose n is NaN or +-Inf; those cells take no further part;
+ *     max_abs_n      the maximum of |n| over the remaining cells of both kinds; 0.0f when there is none;
+ *     exp2           q = floor(log2(max_abs_n)) - 32, denormals included, exactly as exp2 of "LOADS"; q = 0 when max_abs_n == 0.
+ *                    ONE q serves both sums, so that inflow - outflow is itself an exact integer;
+ *     a cell's term  t = (int64_t)trunc(ldexp((double)n, -q)), |t| < 2^33;
+ *     inflow         minus the sum of t over the live inflow cells: positive when fluid enters;
+ *     outflow        the sum of t over the live outflow cells: positive when fluid leaves;
+ *     inflow_cells, outflow_cells   the numbers of live cells of each kind.
+ *   A side of the largest context has fewer than 2^16 rim cells: the sums cannot overflow.  The flux in velocity times cell
+ * widths is inflow * 2^exp2 (outflow * 2^exp2); the caller multiplies by dx.  With no openings set, or with no live open cell,
+ * the record is all zeros and no launch is made.  Integer sums, counts and maxima over bit patterns do not depend on the order
+ * of reduction: every field is, bit for bit, what the rule computes from the downloaded velocity, map and mask, and a context
+ * and a batch member of the same shape report the same bytes.  A batch: one launch, one workgroup per member over the rim
+ * cells of the member; a context: one launch of one workgroup over the 2 (dim_x + dim_y) - 4 rim cells, never a pass over the
+ * grid.  No atomics, no float sums.
+ *   Admission as everywhere.  A call's own argument checks come first, SFL_ERR_INVALID and answered on a machine without a GPU
+ * where they need no handle: n < 0, NULL arrays with n > 0, a non-finite velocity (the message names the record), a NULL
+ * handle, a member outside the batch, a wrong size.  The state refusals come next, each with its own message: a profile on a
+ * batch of sfl_batch_create_large and a profile without openings set give SFL_ERR_STATE -- so everything that
+ * sfl_[batch_]set_openings refuses stays refused: without openings there is no profile.  Then the records against the map.  A
+ * refused call stages and launches nothing and leaves the profile as it was.                                                */
+struct sfl_open_flux {
+    int64_t  inflow, outflow;
+    int32_t  exp2;
+    float    max_abs_n;
+    uint32_t inflow_cells, outflow_cells, nonfinite, reserved;
+};                                     /* 40 bytes: offsets 0, 8, 16, 20, 24, 28, 32, 36 */
+/* Set the inflow profile of a context: record k is cell (cells_ij[2 k], cells_ij[2 k + 1]) with velocity (vel_xy[2 k],
+ * vel_xy[2 k + 1]); both arrays are read during the call only.  n == 0 clears the profile (the arrays may then be NULL).
+ * Synchronous.                                                                                                             */
+SFL_API int sfl_set_inflow_profile(sfl_context *ctx, const int *cells_ij, const float *vel_xy, int n);
+/* The number of unique cells the profile holds (0 without one).  Never waits.                                              */
+SFL_API int sfl_inflow_profile_info(sfl_context *ctx, int *records);
+/* The records held, in cell-index order (dim_x * j + i ascending); capacity counts records, and capacity < records returns
+ * SFL_ERR_INVALID.  Never waits.                                                                                           */
+SFL_API int sfl_inflow_profile_download(sfl_context *ctx, int *cells_ij, float *vel_xy, int capacity);
+/* The flux record of the velocity held.  One launch, synchronous; changes no field.                                        */
+SFL_API int sfl_openings_flux(sfl_context *ctx, struct sfl_open_flux *out);
+/* Set the inflow profile of a batch made by sfl_batch_create, in the idiom of sfl_batch_queue_forces: record k belongs to
+ * member members[k]; members == NULL gives every record to every member.  n == 0 clears the profile.  Synchronous.          */
+SFL_API int sfl_batch_set_inflow_profile(sfl_batch *b, const int *members, const int *cells_ij, const float *vel_xy, int n);
+/* Whether a profile is set, and the number of unique cells held over all members (a shared profile counts once per member).
+ * Either out pointer may be NULL.  Never waits.                                                                            */
+SFL_API int sfl_batch_inflow_profile_info(sfl_batch *b, int *set, int64_t *records);
+/* The records of one member, in cell-index order; *records (may be NULL) gets their number; capacity < that number returns
+ * SFL_ERR_INVALID with *records set.  Never waits.                                                                         */
+SFL_API int sfl_batch_inflow_profile_download(sfl_batch *b, int member, int *cells_ij, float *vel_xy, int capacity, int *records);
+/* The flux records of members [first, first + count) from the velocity held: host[m - first] is member m's; bytes must be
+ * count * 40.  One launch, synchronous; changes no field.  A batch without openings reports zero records without a launch.  */
+SFL_API int sfl_batch_openings_flux(sfl_batch *b, int first, int count, struct sfl_open_flux *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
