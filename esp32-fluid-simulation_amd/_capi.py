@@ -86,6 +86,12 @@ class BodyLoad(C.Structure):
                 ("nonfinite", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class BodyFriction(C.Structure):
+    """struct sfl_body_friction: the skin friction on one solid body, 48 bytes with the offsets of BodyLoad."""
+    _fields_ = [("fx", C.c_int64), ("fy", C.c_int64), ("exp2", C.c_int32), ("max_abs_t", C.c_float), ("faces", C.c_uint32 * 4),
+                ("nonfinite", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class FieldDistance(C.Structure):
     """struct sfl_field_distance: what sfl_distance and sfl_batch_distance report, 64 bytes."""
     _fields_ = [("max_abs_dvx", C.c_float), ("max_abs_dvy", C.c_float), ("max_abs_dp", C.c_float), ("what", C.c_uint32),
@@ -310,6 +316,16 @@ SIGNATURES = {
     "sfl_batch_inflow_profile_info": (_i, [_ctx, _pi, C.POINTER(C.c_int64)]),
     "sfl_batch_inflow_profile_download": (_i, [_ctx, _i, _pi, _pf, _i, _pi]),
     "sfl_batch_openings_flux": (_i, [_ctx, _i, _i, C.POINTER(OpenFlux), _sz]),
+    "sfl_batch_friction": (_i, [_ctx, _i, _i, C.POINTER(BodyFriction), _sz]),
+    "sfl_batch_friction_start": (_i, [_ctx, _i, _i, _i, _i]),
+    "sfl_batch_friction_stop": (_i, [_ctx]),
+    "sfl_batch_friction_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), _pi]),
+    "sfl_batch_friction_read": (_i, [_ctx, _i, _i, C.POINTER(BodyFriction), _sz]),
+    "sfl_friction": (_i, [_ctx, C.POINTER(BodyFriction), _sz]),
+    "sfl_friction_start": (_i, [_ctx, _i, _i]),
+    "sfl_friction_stop": (_i, [_ctx]),
+    "sfl_friction_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), _pi]),
+    "sfl_friction_read": (_i, [_ctx, _i, _i, C.POINTER(BodyFriction), _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

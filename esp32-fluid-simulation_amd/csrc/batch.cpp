@@ -21,7 +21,7 @@ void release(sfl_batch *b)
                     (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env,
                     (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
                     (void *)b->d_rec_palette, b->history.d_records, (void *)b->solids.d_codes,
-                    (void *)b->loads.d_labels, b->loads.d_records, b->viscosity.d_table, (void *)b->openings.d_codes,
+                    (void *)b->loads.d_labels, b->loads.d_records, b->friction.d_records, b->viscosity.d_table, (void *)b->openings.d_codes,
                     (void *)b->openings.d_inflow, b->openings.d_profile, b->openings.d_flux})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
@@ -240,6 +240,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
             SFL_TRY(sfl::host::record_step(b, steps));
             if (b->history_step) SFL_TRY(b->history_step(b, steps, kind == kEach ? b->d_members : nullptr, false, a.step));
             if (b->loads_step) SFL_TRY(b->loads_step(b, steps));   // (no solids here: the samples inside are zeros, no cut)
+            if (b->friction_step) SFL_TRY(b->friction_step(b, steps));   // (the same)
             done += steps;
         }
         consume_forces(b, n);
@@ -270,6 +271,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
         if (b->tracers_follow) SFL_TRY(b->tracers_follow(b, kind == kUniform ? nullptr : b->d_members, a.step.dt));
         if (b->history_step) SFL_TRY(b->history_step(b, 1, kind == kUniform ? nullptr : b->d_members, kind == kUntil, a.step));
         if (b->loads_step) SFL_TRY(b->loads_step(b, 1));
+        if (b->friction_step) SFL_TRY(b->friction_step(b, 1));
     }
     consume_forces(b, n);
     return SFL_OK;
@@ -595,6 +597,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
     SFL_TRY(sfl::host::history_admit(b->history, n));   // ... and a history without room for its samples
     SFL_TRY(sfl::host::loads_admit(b->loads, n));       // ... and a loads recorder without room for its
+    SFL_TRY(sfl::host::friction_admit(b->friction, n)); // ... and a friction recorder without room for its
     SFL_TRY(use_device(b));
     b->report_valid = b->counts_valid = false;   // (the uniform kernels leave no update norm)
     sfl::BatchStep a{};
@@ -633,6 +636,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
     SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
     SFL_TRY(sfl::host::history_admit(b->history, n));   // ... and a history without room for its samples
     SFL_TRY(sfl::host::loads_admit(b->loads, n));       // ... and a loads recorder without room for its
+    SFL_TRY(sfl::host::friction_admit(b->friction, n)); // ... and a friction recorder without room for its
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
     if (b->viscosity.set) SFL_TRY(b->viscosity.stage(b, 0.0f, 0.0f, params));   // every member's a and c of its own dt and dx
@@ -678,6 +682,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
     SFL_TRY(sfl::host::trail_admit_steps(b->tracers, n));   // ... and so does a trail of following tracers without room for its slots
     SFL_TRY(sfl::host::history_admit(b->history, n));   // ... and a history without room for its samples
     SFL_TRY(sfl::host::loads_admit(b->loads, n));       // ... and a loads recorder without room for its
+    SFL_TRY(sfl::host::friction_admit(b->friction, n)); // ... and a friction recorder without room for its
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params, stops));
     b->report_valid = b->counts_valid = false;   // until every launch below is queued

@@ -126,6 +126,9 @@ struct sfl_batch {
     // last, behind history_step
     sfl::host::Loads loads;
     int (*loads_step)(sfl_batch *b, int steps) = nullptr;
+    // the friction recorder (friction.cpp; context.h has Friction), by the same rule; called last, behind loads_step
+    sfl::host::Friction friction;
+    int (*friction_step)(sfl_batch *b, int steps) = nullptr;
     // viscosity (viscous.cpp; include/sfl.h "VISCOSITY"): nu of every member on the host, and one record per member on the
     // device (viscous_kernels.h BatchViscous: a, c, sweeps), indexed by the member, filled from pinned memory by the
     // two-slot rule of member_stage.  Plain data, as the solids are and for the same reason: the destroy path frees the

@@ -15,6 +15,7 @@
 //   tracers.cpp       points that move with the flow (sfl_tracers_*, sfl_batch_tracers_*): sets, advances, samples, trails
 //   context_solids.cpp solid cells of a whole-domain context (sfl_set_solids, _solids_info, _solids_download) and the masked launches
 //   loads.cpp         the pressure load on solid bodies (sfl_loads*, sfl_batch_loads*, sfl_set_bodies, sfl_batch_set_bodies)
+//   friction.cpp      the skin friction on solid bodies (sfl_friction*, sfl_batch_friction*); body_recorder.h: the calls both share
 //   context_viscous.cpp viscosity of a whole-domain context (sfl_set_viscosity, _viscosity_info, sfl_diffuse_velocity)
 //   viscous.cpp       viscosity of a batch (sfl_batch_set_viscosity, _viscosity_info, _viscosity_download)
 //   openings.cpp      inflow and outflow cells on the rim of a batch member (sfl_batch_set_openings, _set_inflow, _openings_info, ...)
@@ -286,6 +287,29 @@ inline int loads_admit(const Loads &l, int64_t n)
     return SFL_OK;
 }
 
+// Friction (friction.cpp; include/sfl.h "FRICTION"): the second recorder of 48-byte records per body, beside the loads' and
+// independent of it.  The labels and `bodies` are Loads'; this is the recorder alone, with the field names of Loads so
+// that body_recorder.h serves both.  Plain data for the same reason; the sample is launched through `friction_step`.
+struct Friction {
+    bool on = false;
+    int every = 0, first = 0, count = 0, capacity = 0, written = 0;   // members [first, first + count) (a context: [0, 1))
+    int64_t steps = 0;            // counted since friction_start
+    void *d_records = nullptr;    // laid out as Loads::d_records; freed by friction_stop and the destroy paths
+    size_t d_bytes = 0;
+};
+
+// SFL_ERR_STATE if the n steps of a call would complete more samples than are free: loads_admit's rule
+inline int friction_admit(const Friction &f, int64_t n)
+{
+    if (!f.on) return SFL_OK;
+    const int64_t due = (f.steps + n) / f.every - f.steps / f.every, room = f.capacity - f.written;
+    if (due > room)
+        return fail(SFL_ERR_STATE, "the friction recorder has room for %lld more samples (%d of %d written) and %lld steps would complete %lld: "
+                    "nothing stepped; read the samples (sfl_friction_read, sfl_batch_friction_read) and start the recorder again to make room",
+                    (long long)room, f.written, f.capacity, (long long)n, (long long)due);
+    return SFL_OK;
+}
+
 // What the view calls (views.cpp; include/sfl.h "VIEWS") keep on the device for a context or a batch: the staged palette
 // of the call (kViewPaletteWords words, allocated at the first call) and the call's result, which only grows.  Plain
 // data, freed by the two destroy paths, so that they need no symbol of views.cpp.
@@ -486,6 +510,9 @@ struct sfl_context {
     // sample is due, launch it on the context's stream); called last, behind history_step
     sfl::host::Loads loads;
     int (*loads_step)(sfl_context *c) = nullptr;
+    // the friction recorder (friction.cpp), by the same rule; called last, behind loads_step
+    sfl::host::Friction friction;
+    int (*friction_step)(sfl_context *c) = nullptr;
     sfl::host::ContextViscosity viscosity;   // item 3a of a step (context_viscous.cpp)
     sfl::host::ContextOpenings openings;     // inflow and outflow cells on the rim (context_openings.cpp)
 

@@ -329,6 +329,7 @@ int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
     SFL_TRY(trail_admit_steps(ctx->tracers, 1));   // a trail of following tracers without a free slot refuses the step
     SFL_TRY(history_admit(ctx->history, 1));       // ... and so does a history without a free sample
     SFL_TRY(loads_admit(ctx->loads, 1));           // ... and a loads recorder without one
+    SFL_TRY(friction_admit(ctx->friction, 1));     // ... and a friction recorder without one
     if (ctx->nranks > 1 && ctx->opt.advect_halo == 0 && ctx->color_unsettled && ctx->unsettled_dt == dt && ctx->force_cells.empty())
         SFL_TRY(advect_interior_early(ctx, dt));
     SFL_TRY(settle_color(ctx, true));
@@ -338,6 +339,7 @@ int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
     if (ctx->tracers_follow) SFL_TRY(ctx->tracers_follow(ctx, dt));   // a following set moves with this step's projected velocity
     if (ctx->history_step) SFL_TRY(ctx->history_step(ctx, dt, dx, iters));   // a history counts the step and samples what it left
     if (ctx->loads_step) SFL_TRY(ctx->loads_step(ctx));   // ... and so does a loads recorder
+    if (ctx->friction_step) SFL_TRY(ctx->friction_step(ctx));   // ... and a friction recorder, last
     return SFL_OK;
 }
 
@@ -353,6 +355,7 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
     SFL_TRY(trail_admit_steps(ctx->tracers, n));   // a trail without room for the slots of n advances refuses the call whole
     SFL_TRY(history_admit(ctx->history, n));       // ... and so does a history without room for the call's samples
     SFL_TRY(loads_admit(ctx->loads, n));           // ... and a loads recorder without room for its
+    SFL_TRY(friction_admit(ctx->friction, n));     // ... and a friction recorder without room for its
     SFL_TRY(settle_color(ctx, true));
     SFL_TRY(check_wait_error(ctx));
     const int64_t cells = (int64_t)ctx->dim_x * ctx->gdim_y;
@@ -389,6 +392,7 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
             SFL_TRY(project_and_advect_color(ctx, dt, dx, ctx->opt.advect_halo, false));          // ino:276 + ino:281-287
         // (a loads recorder keeps the seams: they only run without solids, where a sample is zero records and reads no field)
         if (ctx->loads_step) SFL_TRY(ctx->loads_step(ctx));
+        if (ctx->friction_step) SFL_TRY(ctx->friction_step(ctx));   // (the same)
     }
     return SFL_OK;
 }

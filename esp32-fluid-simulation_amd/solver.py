@@ -81,6 +81,10 @@ HISTORY_DTYPE = np.dtype({"names": ["max_abs_vx", "max_abs_vy", "max_abs_div", "
 # and body).  48 bytes; the load in pressure times cell widths is fx * 2^exp2, fy * 2^exp2.
 BODY_LOAD_DTYPE = np.dtype([("fx", "<i8"), ("fy", "<i8"), ("exp2", "<i4"), ("max_abs_p", "<f4"), ("faces", "<u4", (4,)),
                             ("nonfinite", "<u4"), ("reserved", "<u4")])
+# struct sfl_body_friction: the skin friction on one solid body (Solver.friction, BatchSolver.friction), laid out as the load.
+# 48 bytes; the force per unit depth and density is nu * fx * 2^exp2 (no dx): friction_xy() does that arithmetic in float64.
+BODY_FRICTION_DTYPE = np.dtype([("fx", "<i8"), ("fy", "<i8"), ("exp2", "<i4"), ("max_abs_t", "<f4"), ("faces", "<u4", (4,)),
+                                ("nonfinite", "<u4"), ("reserved", "<u4")])
 # struct sfl_open_flux: the flux through the live open cells of one grid (Solver.openings_flux: one record;
 # BatchSolver.openings_flux: one per member).  40 bytes; the flux in velocity times cell widths is inflow * 2^exp2.
 OPEN_FLUX_DTYPE = np.dtype([("inflow", "<i8"), ("outflow", "<i8"), ("exp2", "<i4"), ("max_abs_n", "<f4"), ("inflow_cells", "<u4"),
@@ -464,7 +468,96 @@ class _Loads:
         capi.check(self._loads_call("loads_stop")(self._h))
 
 
-class Solver(_Tracers, _History, _Loads):
+class _Friction:
+    """Friction: the skin friction on solid bodies, beside the pressure load of :class:`_Loads` and with its bodies, as
+    figures and as curves recorded while stepping (include/sfl.h "FRICTION").  Shared by :class:`Solver` (``[1, bodies]``
+    records per sample) and :class:`BatchSolver` (``[count, bodies]``)."""
+
+    _friction_rec = (0, 1)   # the recorded members (first, count)
+
+    def _friction_ptr(self, a):
+        return a.ctypes.data_as(C.POINTER(capi.BodyFriction))
+
+    def friction(self, first: int = 0, count=None) -> np.ndarray:
+        """The friction on every body from the velocity held: a BODY_FRICTION_DTYPE array of shape ``(count, bodies)`` --
+        a context: ``(1, bodies)`` --, every field bit for bit what the rule of include/sfl.h "FRICTION" gives on the
+        downloaded velocity, mask and labels.  All zeros without solids.  Synchronous; changes no field."""
+        n_bodies = self.bodies_info()[0]
+        if not self._loads_batch:
+            if first != 0 or count not in (None, 1):
+                raise ValueError("a context has one set of records: first = 0, count = None")
+            out = np.zeros((1, n_bodies), BODY_FRICTION_DTYPE)
+            capi.check(self._lib.sfl_friction(self._h, self._friction_ptr(out), out.nbytes))
+            return out
+        count = self.batch - first if count is None else count
+        out = np.zeros((count, n_bodies), BODY_FRICTION_DTYPE)
+        capi.check(self._lib.sfl_batch_friction(self._h, first, count, self._friction_ptr(out), out.nbytes))
+        return out
+
+    def _friction_nu(self, nu, first, count):
+        """nu as float64 that broadcasts against ``(..., count, bodies, 2)``: a scalar, one value per member of the range,
+        or None for the viscosity that is set (per member in a batch; zeros when none is set)."""
+        if nu is None:
+            nu = self.viscosity()[0]
+            if self._loads_batch:
+                nu = nu[first:first + count]
+        a = np.asarray(nu, dtype=np.float64)
+        if a.ndim == 0:
+            return a
+        if a.shape != (count,):
+            raise ValueError(f"friction: nu of shape {a.shape}, want a number or {(count,)}")
+        return a[:, None, None]
+
+    def friction_xy(self, nu=None, first: int = 0, count=None) -> np.ndarray:
+        """:meth:`friction` as float64 ``(count, bodies, 2)``: nu * fx * 2^exp2, nu * fy * 2^exp2 -- the force per unit
+        depth and density, with NO factor dx.  `nu`: a number, one value per member, or None for the viscosity that is
+        set (zeros when none is)."""
+        rec = self.friction(first, count)
+        return self._friction_nu(nu, first, rec.shape[0]) * _Loads._xy(rec)
+
+    def friction_start(self, every: int, capacity: int, first: int = 0, count=None):
+        """Start the friction recorder, by the rules of :meth:`loads_start` and independent of it: after every
+        `every`-th step of any step call one launch on the stream writes the records of members [first, first + count)
+        from the velocity that step left; `capacity` samples fit.  A step call that would complete more samples than are
+        free raises SflError with ERR_STATE and steps nothing.  A sample taken without solids set is zeros."""
+        if not self._loads_batch:
+            if first != 0 or count not in (None, 1):
+                raise ValueError("a context has one set of records per sample: first = 0, count = None")
+            rc = self._lib.sfl_friction_start(self._h, every, capacity)
+            rec = (0, 1)
+        else:
+            count = self.batch - first if count is None else count
+            rc = self._lib.sfl_batch_friction_start(self._h, every, first, count, capacity)
+            rec = (first, count)
+        if rc == capi.OK:
+            self._friction_rec = rec
+        capi.check(rc)
+
+    def friction_info(self):
+        """(samples written, capacity, steps counted since friction_start, bodies).  Never waits."""
+        samples, capacity, steps, n = C.c_int(), C.c_int(), C.c_int64(), C.c_int()
+        capi.check(self._loads_call("friction_info")(self._h, C.byref(samples), C.byref(capacity), C.byref(steps), C.byref(n)))
+        return samples.value, capacity.value, steps.value, n.value
+
+    def friction_history(self) -> np.ndarray:
+        """The samples written so far, BODY_FRICTION_DTYPE of shape ``(samples, count, bodies)`` (a context: count = 1);
+        sample s belongs to step (s + 1) * every since friction_start.  Not consumed.  Synchronous."""
+        samples, _, _, n_bodies = self.friction_info()
+        out = np.zeros((samples, self._friction_rec[1], n_bodies), BODY_FRICTION_DTYPE)
+        capi.check(self._loads_call("friction_read")(self._h, 0, samples, self._friction_ptr(out), out.nbytes))
+        return out
+
+    def friction_history_xy(self, nu=None) -> np.ndarray:
+        """:meth:`friction_history` as float64 ``(samples, count, bodies, 2)``, scaled by `nu` as :meth:`friction_xy`."""
+        rec = self.friction_history()
+        return self._friction_nu(nu, self._friction_rec[0], rec.shape[1]) * _Loads._xy(rec)
+
+    def friction_stop(self):
+        """Stop the friction recorder and free its samples."""
+        capi.check(self._loads_call("friction_stop")(self._h))
+
+
+class Solver(_Tracers, _History, _Loads, _Friction):
     """One solver context: rows [row_begin, row_end) of a dim_x * dim_y domain on one device."""
 
     def __init__(self, dim_x: int, dim_y: int, device: int = 0, rank: int = 0, nranks: int = 1):
@@ -812,7 +905,7 @@ class Solver(_Tracers, _History, _Loads):
         return {"launches": a.value, "exchanges": b.value, "fuse": c.value, "halo": self.get_option(capi.OPT_LAST_HALO)}
 
 
-class BatchSolver(_Tracers, _History, _Loads):
+class BatchSolver(_Tracers, _History, _Loads, _Friction):
     """A batch (sfl_batch_*): `batch` independent whole-domain simulations of one dim_x * dim_y grid on one device,
     every member stepped by the same launch.  Member m holds, bit for bit, what a :class:`Solver` of the same shape
     holds after the same calls made with member m's data and forces.  Arrays of members are shaped

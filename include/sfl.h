@@ -1129,7 +1129,7 @@ SFL_API int sfl_solids_download(sfl_context *ctx, uint8_t *host, size_t bytes);
  * without solids: the samples that fall inside it are zeros).  A loads recorder changes no result and, unlike a history, not
  * even which step launches a call makes; with none on, every call launches exactly what it launched before there were loads.
  *   Admission as everywhere: a call's own argument checks come first, then the state refusals, each with its own message;
- * a refused call stages and launches nothing.                                                                              */
+ * a refused call stages and launches nothing.  (The tangential viscous force on the same bodies: "FRICTION", below.)        */
 #define SFL_MAX_BODIES 16
 struct sfl_body_load {
     int64_t  fx, fy;
@@ -1401,6 +1401,73 @@ SFL_API int sfl_batch_inflow_profile_download(sfl_batch *b, int member, int *cel
 /* The flux records of members [first, first + count) from the velocity held: host[m - first] is member m's; bytes must be
  * count * 40.  One launch, synchronous; changes no field.  A batch without openings reports zero records without a launch.  */
 SFL_API int sfl_batch_openings_flux(sfl_batch *b, int first, int count, struct sfl_open_flux *host, size_t bytes);
+/* --- FRICTION: how hard the flow DRAGS solid bodies along -- the skin friction on every body, beside the pressure load of
+ *     "LOADS": as figures (sfl_batch_friction, sfl_friction) and as curves recorded while stepping (sfl_batch_friction_start,
+ *     sfl_friction_start), without a download.  The rule below is a definition stated here, like the loads': the reference
+ *     knows no bodies.  It is the TANGENTIAL viscous force only: the normal viscous stress 2 nu dv_n/dn is left out -- it
+ *     vanishes at a no-slip wall of a divergence-free flow -- and there is no torque.
+ *   FACES AND BODIES are those of "LOADS", word for word: a wet face is a pair (fluid cell F, solid cell S) where S is one of
+ * F's four neighbours, S is INSIDE THE DOMAIN and S belongs to a body; the rim has no faces; labels, `bodies` and
+ * SFL_MAX_BODIES come from sfl_batch_set_bodies / sfl_set_bodies; a label counts only where the cell is solid at the time of
+ * the sample.  For the same mask and labels, faces[4] of a friction record equals faces[4] of the load record.
+ *   THE WALL IS AT REST AND LIES AT NODE S, the node-based wall of items 1 and 3a.  The shear on the face is
+ * nu * (tangential velocity of F) / dx; over a face of length dx the force is nu * (tangential velocity of F): the face's
+ * term is F's tangential component alone.
+ *     F lies W or E of S (directions 0 and 1): the term is v.y and goes into fy;
+ *     F lies S or N of S (directions 2 and 3): the term is v.x and goes into fx.
+ * The sign is plain -- the fluid drags the body along with it: no subtraction between sides.  A fluid cell with several
+ * faces contributes once per face, possibly to different bodies.
+ *   THE RECORD, per body, over its wet faces, from the velocity held, with the quantisation of "LOADS" unchanged:
+ *     nonfinite   the number of faces whose TANGENTIAL component is NaN or +-Inf; the normal component is not looked at;
+ *                 those faces take no further part;
+ *     max_abs_t   the maximum of |tangential component| over the remaining faces; 0.0f when there is none;
+ *     exp2        q = floor(log2(max_abs_t)) - 32, denormals included, exactly as exp2 of "LOADS"; q = 0 when max_abs_t == 0.
+ *                 ONE q serves both fx and fy;
+ *     a face's term  t = (int64_t)trunc(ldexp((double)v_t, -q)), |t| < 2^33;
+ *     fx          the sum of t over the faces whose fluid cell lies SOUTH or NORTH of its solid cell;
+ *     fy          the sum of t over the faces whose fluid cell lies WEST or EAST of it;
+ *     faces[4]    as in "LOADS": the numbers of faces whose fluid cell lies W, E, S, N of the solid cell.
+ *   Fewer than 2^30 faces: the sums cannot overflow.
+ *   The friction force on the body per unit depth is rho * nu * fx * 2^exp2 (rho * nu * fy * 2^exp2): there is NO FACTOR dx,
+ * unlike the pressure load.  The library does not multiply by nu: the record is defined with or without a viscosity set, and
+ * the caller supplies nu.  All zeros mean a body without a face, or no solids set.  Integer sums, maxima over bit patterns
+ * and counts do not depend on the order of reduction: every field of every record is, bit for bit, what the rule computes
+ * from the downloaded velocity, mask and labels, and a context and a batch member of the same shape, mask, labels and
+ * velocity report the same bytes.  The pressure plays no part.
+ *   THE FRICTION RECORDER follows the loads recorder's rules unchanged: steps count across calls; sample s belongs to step
+ * (s + 1) * every; a step call without room for its samples is refused WHOLE with SFL_ERR_STATE before anything is staged or
+ * launched, with a message that names the friction recorder; a restart keeps the buffer; a sample taken without solids is
+ * zero records; a batch's one-launch replay of a timeline and the fused seams of sfl_step_n are NOT cut.  It is independent
+ * of the loads recorder and of the history: any of the three may be on together, and behind a step the order is history,
+ * loads, friction.  With no friction recorder on, every call launches exactly what it launched before there was one.
+ * sfl_batch_set_bodies / sfl_set_bodies are refused with SFL_ERR_STATE while the friction recorder is on, with a message of
+ * their own: the layout of its samples depends on `bodies` too.
+ *   Admission as everywhere: the argument checks and their order are those of the loads' calls, one for one.               */
+struct sfl_body_friction {
+    int64_t  fx, fy;
+    int32_t  exp2;
+    float    max_abs_t;
+    uint32_t faces[4];
+    uint32_t nonfinite, reserved;
+};                                     /* 48 bytes: offsets 0, 8, 16, 20, 24, 40, 44 -- those of sfl_body_load */
+/* The friction records of members [first, first + count) from the velocity held: count * bodies records, member-major, as
+ * sfl_batch_loads; bytes must be count * bodies * 48.  One launch, synchronous; changes no field.  A batch without solids set
+ * reports zero records without a launch.  Batches of either kind.                                                          */
+SFL_API int sfl_batch_friction(sfl_batch *b, int first, int count, struct sfl_body_friction *host, size_t bytes);
+/* The friction recorder of a batch: the calls of the loads recorder, one for one (sfl_batch_loads_start, _stop, _info,
+ * _read), with a buffer, a step count and samples of their own.                                                            */
+SFL_API int sfl_batch_friction_start(sfl_batch *b, int every, int first, int count, int capacity);
+SFL_API int sfl_batch_friction_stop(sfl_batch *b);
+SFL_API int sfl_batch_friction_info(sfl_batch *b, int *samples, int *capacity, int64_t *steps, int *bodies);
+SFL_API int sfl_batch_friction_read(sfl_batch *b, int first_sample, int samples, struct sfl_body_friction *host, size_t bytes);
+/* The same for a whole-domain context: `bodies` records per sample.  A slab and a context with a transport attached get
+ * SFL_ERR_STATE, as from sfl_loads.  A sample is two streaming passes over the code bytes, the maxima and then the sums,
+ * behind a memset of the sample's records, all on the context's stream.                                                    */
+SFL_API int sfl_friction(sfl_context *ctx, struct sfl_body_friction *host, size_t bytes);
+SFL_API int sfl_friction_start(sfl_context *ctx, int every, int capacity);
+SFL_API int sfl_friction_stop(sfl_context *ctx);
+SFL_API int sfl_friction_info(sfl_context *ctx, int *samples, int *capacity, int64_t *steps, int *bodies);
+SFL_API int sfl_friction_read(sfl_context *ctx, int first_sample, int samples, struct sfl_body_friction *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 

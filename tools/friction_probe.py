@@ -1,0 +1,209 @@
+#!/usr/bin/env python3
+"""What the friction costs: the numbers of profiles/friction.txt, with the loads sampler of the same job as the yardstick.
+
+The two workloads of tools/loads_probe.py, each in one process, warmed, its configurations alternating, host clock around the
+call and the synchronise that ends it:
+
+  batch    61 x 81 x 1024 members at 20 iterations, one shared disc of radius 8 in every member
+  context  2048 x 2048 at 40 iterations, a disc of radius 256
+
+and for each
+
+  (a) step, no recorder          step_n(n) as it ran before there was friction: the new code in this path is one null-pointer
+                                 test and one admission check per call
+  (b) step, a friction sample    the same call with the friction recorder on, every = 1
+  (c) step, a loads sample       ... with the loads recorder on instead: the yardstick
+  (d) step, both samples         ... with both on
+  (e) friction() alone           the sampler n times through the synchronous call, its copy and wait included; on the stream it
+                                 costs (b) - (a)
+
+With --parent PATH (the library of the parent commit, built from a scratch worktree) (a) is also run on that library, the two
+alternating in the same rounds through the same raw ctypes calls, on --objects batches (contexts) of each made in turn: where
+an object's fields lie moves a step by more than the rounds of one object differ.  The ONE condition: (a) on this library
+agrees with (a) on the parent's inside the spread the probe itself reports for the PARENT's rounds and objects, max - min.
+Everything else is written down as measured.
+
+usage: python3 tools/friction_probe.py [--parent libsfl_parent.so] [--objects K] [--reps R] [--steps N] [--out profiles/friction.txt]"""
+import argparse
+import ctypes as C
+import importlib
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sfl = importlib.import_module("esp32-fluid-simulation_amd")
+capi = sfl.capi
+
+OUT = []
+DT, DX, OMEGA = 0.05, 1.0, 1.9
+
+
+def say(text=""):
+    print(text)
+    sys.stdout.flush()
+    OUT.append(text)
+
+
+def timed(call, sync):
+    sync()
+    t = time.perf_counter()
+    call()
+    sync()
+    return (time.perf_counter() - t) * 1e6
+
+
+def disc(dim_x, dim_y, r):
+    j, i = np.mgrid[0:dim_y, 0:dim_x]
+    return ((i - dim_x // 2) ** 2 + (j - dim_y // 2) ** 2 <= r * r).astype(np.uint8)
+
+
+class Raw:
+    """The few calls of the C ABI the comparison with the parent's library needs, on either library, through the same code."""
+
+    def __init__(self, path, batch, dim_x, dim_y, members, mask):
+        self.lib = C.CDLL(path)
+        for name, (res, args) in capi.SIGNATURES.items():
+            if hasattr(self.lib, name):
+                fn = getattr(self.lib, name)
+                fn.restype, fn.argtypes = res, args
+        self.batch, self.h = batch, C.c_void_p()
+        ptr = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        if batch:
+            self.ok(self.lib.sfl_batch_create(C.byref(self.h), 0, dim_x, dim_y, members))
+            self.ok(self.lib.sfl_batch_setup_sketch_fields(self.h))
+            self.ok(self.lib.sfl_batch_set_solids(self.h, ptr, 0))
+        else:
+            self.ok(self.lib.sfl_create(C.byref(self.h), 0, dim_x, dim_y))
+            self.ok(self.lib.sfl_setup_sketch_fields(self.h))
+            self.ok(self.lib.sfl_set_solids(self.h, ptr))
+
+    def ok(self, rc):
+        if rc != capi.OK:
+            raise SystemExit(f"{self.lib._name}: {self.lib.sfl_last_error().decode()}")
+
+    def step_n(self, n, iters):
+        self.ok((self.lib.sfl_batch_step_n if self.batch else self.lib.sfl_step_n)(self.h, n, DT, DX, iters, OMEGA))
+
+    def synchronize(self):
+        self.ok((self.lib.sfl_batch_synchronize if self.batch else self.lib.sfl_synchronize)(self.h))
+
+    def close(self):
+        (self.lib.sfl_batch_destroy if self.batch else self.lib.sfl_destroy)(self.h)
+
+
+def report(us, n, base):
+    med = {name: statistics.median(u) for name, u in us.items()}
+    for name, u in us.items():
+        mad = statistics.median(abs(x - med[name]) for x in u)
+        say(f"  {name:<32} median {med[name] / n:9.2f} us per step   min {min(u) / n:9.2f}   max {max(u) / n:9.2f}   MAD {mad / n:7.2f}   "
+            f"vs {base} {100 * (med[name] - med[base]) / med[base]:+6.2f} %")
+    return med
+
+
+def workload(a, batch, dim_x, dim_y, members, iters, radius):
+    n = a.steps
+    mask = disc(dim_x, dim_y, radius)
+    what = f"batch of {members} x ({dim_x} x {dim_y})" if batch else f"context of {dim_x} x {dim_y}"
+    say(f"{what}, a disc of radius {radius}, step_n({n}) of {iters} iterations, {a.warmup} warm-up and {a.reps} timed rounds, the configurations "
+        f"alternating, host clock around call + synchronize:")
+    # ---- the parent's library against this one, no recorder: --objects batches (contexts) of each, made in turn
+    libs = {"this": capi.LIB_PATH}
+    if a.parent:
+        libs["parent"] = os.path.abspath(a.parent)
+    raws = [(name, k, Raw(path, batch, dim_x, dim_y, members, mask)) for k in range(a.objects) for name, path in libs.items()]
+    for _, _, r in raws:
+        r.step_n(2, iters)
+    us = {(name, k): [] for name, k, _ in raws}
+    for rnd in range(a.warmup + a.reps):
+        for name, k, r in (raws if rnd % 2 == 0 else raws[::-1]):   # (either end first in turn)
+            t = timed(lambda: r.step_n(n, iters), r.synchronize)
+            if rnd >= a.warmup:
+                us[(name, k)].append(t / n)
+    per_lib = {}
+    for name in libs:
+        meds = [statistics.median(us[(name, k)]) for k in range(a.objects)]
+        every = [t for k in range(a.objects) for t in us[(name, k)]]
+        per_lib[name] = (statistics.median(every), min(every), max(every), meds)
+        say(f"  (a) {name:<7} no recorder, {a.objects} objects: median {per_lib[name][0]:9.2f} us per step   min {min(every):9.2f}   max {max(every):9.2f}   "
+            f"medians of the objects {', '.join(f'{m:.2f}' for m in meds)}")
+    if a.parent:
+        med, lo, hi, meds = per_lib["parent"]
+        say(f"  spread of (a) parent: over the objects' medians {max(meds) - min(meds):.2f} us per step, over its rounds and objects max - min = {hi - lo:.2f}")
+        gap = per_lib["this"][0] - med
+        verdict = "inside" if abs(gap) <= hi - lo else "OUTSIDE"
+        say(f"  this - parent = {gap:+.2f} us per step ({100 * gap / med:+.2f} %): {verdict} the parent's max - min of {hi - lo:.2f}")
+    else:
+        say("  the parent's library: not measured (no --parent)")
+    for _, _, r in raws:
+        r.close()
+    # ---- the recorders and the sampler alone
+    def make():
+        s = sfl.BatchSolver(dim_x, dim_y, members) if batch else sfl.Solver(dim_x, dim_y)
+        s.setup_sketch_fields()
+        s.set_solids(mask)
+        s.step_n(2, DT, DX, iters, OMEGA)
+        return s
+
+    plain, fr, lo_, both = make(), make(), make(), make()
+
+    def friction_recorded():
+        fr.friction_start(1, n)
+        fr.step_n(n, DT, DX, iters, OMEGA)
+
+    def loads_recorded():
+        lo_.loads_start(1, n)
+        lo_.step_n(n, DT, DX, iters, OMEGA)
+
+    def both_recorded():
+        both.loads_start(1, n)
+        both.friction_start(1, n)
+        both.step_n(n, DT, DX, iters, OMEGA)
+
+    def sampled():
+        for _ in range(n):
+            plain.friction()
+
+    A, Bf, Cl, D, E = "(a) step, no recorder", "(b) step, a friction sample", "(c) step, a loads sample", "(d) step, both samples", "(e) friction() alone, synchronous"
+    runs = {A: (lambda: plain.step_n(n, DT, DX, iters, OMEGA), plain.synchronize), Bf: (friction_recorded, fr.synchronize),
+            Cl: (loads_recorded, lo_.synchronize), D: (both_recorded, both.synchronize), E: (sampled, plain.synchronize)}
+    us = {name: [] for name in runs}
+    for k in range(a.warmup + a.reps):
+        for name, (call, sync) in runs.items():
+            t = timed(call, sync)
+            if k >= a.warmup:
+                us[name].append(t)
+    med = report(us, n, A)
+    say(f"  on the stream a friction sample costs (b) - (a) = {(med[Bf] - med[A]) / n:+.2f} us per step, a loads sample (c) - (a) = {(med[Cl] - med[A]) / n:+.2f}, "
+        f"both (d) - (a) = {(med[D] - med[A]) / n:+.2f} against (b) + (c) - 2 (a) = {(med[Bf] + med[Cl] - 2 * med[A]) / n:+.2f}")
+    recs = fr.friction_history()
+    say(f"  (the last sample: faces {recs[-1, 0, 0]['faces'].tolist()}, fx, fy * 2^exp2 = {fr.friction_history_xy(nu=1.0)[-1, 0, 0].tolist()})")
+    for s in (plain, fr, lo_, both):
+        s.close()
+    say()
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", default=None, help="libsfl_hip.so of the parent commit: (a) is run on it too")
+    ap.add_argument("--reps", type=int, default=16)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=16)
+    ap.add_argument("--objects", type=int, default=4, help="batches (contexts) per library in the comparison with the parent")
+    ap.add_argument("--only", choices=["batch", "context"], default=None)
+    ap.add_argument("--out", default=None, help="also write the lines to this file")
+    a = ap.parse_args()
+    if sfl.device_count() < 1:
+        raise SystemExit("needs a GPU: nothing here is measured without one")
+    say("# tools/friction_probe.py " + " ".join(sys.argv[1:]))
+    say(f"# device: {sfl.device_info(0)[0]}")
+    if a.only != "context":
+        workload(a, True, 61, 81, 1024, 20, 8)
+    if a.only != "batch":
+        workload(a, False, 2048, 2048, 1, 40, 256)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(OUT) + "\n")
