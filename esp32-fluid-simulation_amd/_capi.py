@@ -36,6 +36,10 @@ VIEW_MAX_STOPS = 256
 VIEW_MAX_COLOUR = 0xFC000000
 MAX_BODIES = 16   # SFL_MAX_BODIES
 OPEN_INFLOW, OPEN_OUTFLOW = 1, 2   # SFL_OPEN_*: the bytes of an openings map
+MEAN_VELOCITY, MEAN_STRESS, MEAN_PRESSURE, MEAN_DYE, MEAN_ALL = 1, 2, 4, 8, 15   # SFL_MEAN_*: the groups of the averages
+(MEAN_PLANE_U, MEAN_PLANE_V, MEAN_PLANE_UU, MEAN_PLANE_VV, MEAN_PLANE_UV, MEAN_PLANE_P, MEAN_PLANE_PP, MEAN_PLANE_R, MEAN_PLANE_G,
+ MEAN_PLANE_B) = range(10)   # SFL_MEAN_PLANE_*
+MEAN_PLANES = 10
 UNIQUE_ID_BYTES = 128
 TRACER_THREADS = 256   # kTracerThreads of csrc/tracer_kernels.h: tracers per workgroup (stated for the tests)
 BATCH_LARGE_MAX_CELLS = 20224   # SFL_BATCH_LARGE_MAX_CELLS: cells of one member of sfl_batch_create_large
@@ -326,6 +330,16 @@ SIGNATURES = {
     "sfl_friction_stop": (_i, [_ctx]),
     "sfl_friction_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), _pi]),
     "sfl_friction_read": (_i, [_ctx, _i, _i, C.POINTER(BodyFriction), _sz]),
+    "sfl_mean_start": (_i, [_ctx, _i, _i]),
+    "sfl_mean_stop": (_i, [_ctx]),
+    "sfl_mean_sample": (_i, [_ctx]),
+    "sfl_mean_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sfl_mean_download": (_i, [_ctx, _i, C.c_void_p, _sz]),
+    "sfl_batch_mean_start": (_i, [_ctx, _i, _i, _i, _i]),
+    "sfl_batch_mean_stop": (_i, [_ctx]),
+    "sfl_batch_mean_sample": (_i, [_ctx]),
+    "sfl_batch_mean_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sfl_batch_mean_download": (_i, [_ctx, _i, _i, _i, C.c_void_p, _sz]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

@@ -21,7 +21,7 @@ void release(sfl_batch *b)
                     (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env,
                     (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
                     (void *)b->d_rec_palette, b->history.d_records, (void *)b->solids.d_codes,
-                    (void *)b->loads.d_labels, b->loads.d_records, b->friction.d_records, b->viscosity.d_table, (void *)b->openings.d_codes,
+                    (void *)b->loads.d_labels, b->loads.d_records, b->friction.d_records, b->means.d_planes, b->viscosity.d_table, (void *)b->openings.d_codes,
                     (void *)b->openings.d_inflow, b->openings.d_profile, b->openings.d_flux})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
@@ -216,7 +216,7 @@ enum StepKind { kUniform, kEach, kUntil };
 // recorder on, such a call is cut into launches that end at the steps whose frame is due, the render between them.
 // With a following set of tracers (tracers_follow) every step is a launch of its own, the advance behind it: the tracers
 // read each step's projected velocity, which the launch of several steps never stores.  A history (history_step) cuts
-// the call as the recorder does: its sample reads the fields of the step it is due after.  With solid cells set
+// the call as the recorder does: its sample reads the fields of the step it is due after, and so do the averages (mean_step).  With solid cells set
 // (b->solids; solids.cpp) every step is a launch of its own too, made through the batch's pointer, and so it is with a
 // viscosity set (b->viscosity; viscous.cpp), whose pointer picks the kernel with or without solids itself.
 int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
@@ -224,7 +224,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
     SFL_TRY(stage_timeline(b, n));
     if (kind != kUntil && !b->large && n >= 2 && !b->tracers_follow && !b->solids.set && !b->viscosity.set && !b->openings.set && staged_has(b, 1, n)) {
         for (int done = 0; done < n;) {
-            const int steps = sfl::host::history_run(b->history, sfl::host::record_run(b, n - done));   // (cut at either's due steps)
+            const int steps = sfl::host::mean_run(b->means, sfl::host::history_run(b->history, sfl::host::record_run(b, n - done)));   // (cut at any's due steps)
             sfl::BatchPlay play{};
             play.step = a.step;
             play.force_rows = staged_rows_from(b, done, &play.rows, &play.step.force_cells, &play.step.force_vel);
@@ -241,6 +241,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
             if (b->history_step) SFL_TRY(b->history_step(b, steps, kind == kEach ? b->d_members : nullptr, false, a.step));
             if (b->loads_step) SFL_TRY(b->loads_step(b, steps));   // (no solids here: the samples inside are zeros, no cut)
             if (b->friction_step) SFL_TRY(b->friction_step(b, steps));   // (the same)
+            if (b->mean_step) SFL_TRY(b->mean_step(b, steps));   // (the averages read the fields: mean_run has cut at their due steps)
             done += steps;
         }
         consume_forces(b, n);
@@ -272,6 +273,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
         if (b->history_step) SFL_TRY(b->history_step(b, 1, kind == kUniform ? nullptr : b->d_members, kind == kUntil, a.step));
         if (b->loads_step) SFL_TRY(b->loads_step(b, 1));
         if (b->friction_step) SFL_TRY(b->friction_step(b, 1));
+        if (b->mean_step) SFL_TRY(b->mean_step(b, 1));
     }
     consume_forces(b, n);
     return SFL_OK;

@@ -129,6 +129,11 @@ struct sfl_batch {
     // the friction recorder (friction.cpp; context.h has Friction), by the same rule; called last, behind loads_step
     sfl::host::Friction friction;
     int (*friction_step)(sfl_batch *b, int steps) = nullptr;
+    // the averages (means.cpp; context.h has Means): mean_step: `steps` steps have been launched (one launch: mean_run saw to
+    // it that no sample falls inside them) and the ping-pong swapped -- count them and, when a sample is due, launch it on
+    // the batch's stream behind them; called last, behind friction_step
+    sfl::host::Means means;
+    int (*mean_step)(sfl_batch *b, int steps) = nullptr;
     // viscosity (viscous.cpp; include/sfl.h "VISCOSITY"): nu of every member on the host, and one record per member on the
     // device (viscous_kernels.h BatchViscous: a, c, sweeps), indexed by the member, filled from pinned memory by the
     // two-slot rule of member_stage.  Plain data, as the solids are and for the same reason: the destroy path frees the

@@ -16,6 +16,7 @@
 //   context_solids.cpp solid cells of a whole-domain context (sfl_set_solids, _solids_info, _solids_download) and the masked launches
 //   loads.cpp         the pressure load on solid bodies (sfl_loads*, sfl_batch_loads*, sfl_set_bodies, sfl_batch_set_bodies)
 //   friction.cpp      the skin friction on solid bodies (sfl_friction*, sfl_batch_friction*); body_recorder.h: the calls both share
+//   means.cpp         per-cell sums over time of a context or a batch, added while stepping (sfl_mean_*, sfl_batch_mean_*)
 //   context_viscous.cpp viscosity of a whole-domain context (sfl_set_viscosity, _viscosity_info, sfl_diffuse_velocity)
 //   viscous.cpp       viscosity of a batch (sfl_batch_set_viscosity, _viscosity_info, _viscosity_download)
 //   openings.cpp      inflow and outflow cells on the rim of a batch member (sfl_batch_set_openings, _set_inflow, _openings_info, ...)
@@ -310,6 +311,24 @@ inline int friction_admit(const Friction &f, int64_t n)
     return SFL_OK;
 }
 
+// Averages (means.cpp; include/sfl.h "AVERAGES"): the per-cell sums over time that a context or a batch holds.  Plain data,
+// as History and for the same reason: the destroy paths free the planes and batch.cpp finds the cut points of a replay
+// (mean_run) without a symbol of means.cpp; the sample is launched through the `mean_step` pointer of the two structs, which
+// means.cpp sets while averages are on with every >= 1 (null: the step calls launch what they launched before there were
+// averages).  There is no capacity and so no admission.
+struct Means {
+    bool on = false;
+    unsigned what = 0;            // the mask of SFL_MEAN_* groups whose planes exist
+    int every = 0, first = 0, count = 0;   // members [first, first + count) (a context: [0, 1)); every == 0: manual samples only
+    int64_t steps = 0, samples = 0;        // counted since mean_start
+    // the live planes, in the order of their ids, each `count` members of `member_stride` values of 8 bytes (the cells of a
+    // member rounded up to an even number: every member's plane starts on 16 bytes); freed by mean_stop and the destroy paths
+    void *d_planes = nullptr;
+    size_t member_stride = 0, d_bytes = 0;
+};
+// how many of the next n steps may run in one launch before a sample is due (n with no averages behind the steps): history_run's rule
+inline int mean_run(const Means &m, int n) { return m.on && m.every > 0 ? (int)std::min<int64_t>(n, m.every - m.steps % m.every) : n; }
+
 // What the view calls (views.cpp; include/sfl.h "VIEWS") keep on the device for a context or a batch: the staged palette
 // of the call (kViewPaletteWords words, allocated at the first call) and the call's result, which only grows.  Plain
 // data, freed by the two destroy paths, so that they need no symbol of views.cpp.
@@ -513,7 +532,11 @@ struct sfl_context {
     // the friction recorder (friction.cpp), by the same rule; called last, behind loads_step
     sfl::host::Friction friction;
     int (*friction_step)(sfl_context *c) = nullptr;
-    sfl::host::ContextViscosity viscosity;   // item 3a of a step (context_viscous.cpp)
+    // the averages (means.cpp), and their sample behind every step while they are on with every >= 1 (one step has run: count
+    // it and, when a sample is due, launch it on the context's stream); called last, behind friction_step
+    sfl::host::Means means;
+    int (*mean_step)(sfl_context *c) = nullptr;
+    sfl::host::ContextViscosity viscosity;  // item 3a of a step (context_viscous.cpp)
     sfl::host::ContextOpenings openings;     // inflow and outflow cells on the rim (context_openings.cpp)
 
     sfl::host::Options opt;  // what sfl_set_option stores (kOptions above: one row per option)

@@ -339,7 +339,8 @@ int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
     if (ctx->tracers_follow) SFL_TRY(ctx->tracers_follow(ctx, dt));   // a following set moves with this step's projected velocity
     if (ctx->history_step) SFL_TRY(ctx->history_step(ctx, dt, dx, iters));   // a history counts the step and samples what it left
     if (ctx->loads_step) SFL_TRY(ctx->loads_step(ctx));   // ... and so does a loads recorder
-    if (ctx->friction_step) SFL_TRY(ctx->friction_step(ctx));   // ... and a friction recorder, last
+    if (ctx->friction_step) SFL_TRY(ctx->friction_step(ctx));   // ... and a friction recorder
+    if (ctx->mean_step) SFL_TRY(ctx->mean_step(ctx));   // ... and the averages, last
     return SFL_OK;
 }
 
@@ -361,9 +362,10 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
     const int64_t cells = (int64_t)ctx->dim_x * ctx->gdim_y;
     const bool tiled = ctx->opt.advect_kernel == 2 || (ctx->opt.advect_kernel == 0 && cells >= sfl::kAdvectTiledMinCells);
     // (a following set of tracers reads every step's projected velocity, which a seam never stores: no seams then; nor with
-    // a history on, whose samples read it too; nor with solid cells or a viscosity set, whose step is an unfused sequence of its own)
+    // a history on, whose samples read it too, or averages behind the steps (mean_step); nor with solid cells or a viscosity set, whose step
+    // is an unfused sequence of its own)
     const bool seams = n > 1 && ctx->opt.step_seams && ctx->nranks == 1 && !ctx->transport && !small_grid(ctx) && tiled &&
-                       ctx->opt.fuse_projection && ctx->opt.fuse_divergence && !ctx->tracers_follow && !ctx->history_step &&
+                       ctx->opt.fuse_projection && ctx->opt.fuse_divergence && !ctx->tracers_follow && !ctx->history_step && !ctx->mean_step &&
                        !ctx->solids.step && !ctx->viscosity.step;
     if (!seams) {
         for (int k = 0; k < n; ++k) SFL_TRY(sfl_step(ctx, dt, dx, iters, omega));

@@ -557,7 +557,83 @@ class _Friction:
         capi.check(self._loads_call("friction_stop")(self._h))
 
 
-class Solver(_Tracers, _History, _Loads, _Friction):
+MEAN_PLANE_NAMES = ("U", "V", "UU", "VV", "UV", "P", "PP", "R", "G", "B")   # plane ids 0..9 of include/sfl.h "AVERAGES"
+_MEAN_GROUP_OF = (1, 1, 2, 2, 2, 4, 4, 8, 8, 8)                           # ... and the SFL_MEAN_* group of each
+
+
+class _Means:
+    """Averages: per-cell sums over time of the velocity, its second moments, the pressure and the dye, added on the device
+    while stepping (include/sfl.h "AVERAGES").  The library reports SUMS and the number of samples; the means and the
+    central moments are formed here, in float64.  Shared by :class:`Solver` (planes of shape ``(1, dim_y, dim_x)``) and
+    :class:`BatchSolver` (``(count, dim_y, dim_x)``)."""
+
+    _mean_rec = (0, 1)   # the recorded members (first, count)
+
+    def mean_start(self, what: int, every: int, first: int = 0, count=None):
+        """Allocate and zero the planes of the groups in `what` (a mask of ``capi.MEAN_*``) for members [first, first +
+        count) and, for every >= 1, add one sample behind every `every`-th step of any step call from now on -- counted
+        across calls; the step calls stay asynchronous.  every = 0: only :meth:`mean_sample` adds, and the step calls keep
+        their fusion.  A start while on begins anew from zero."""
+        if not self._loads_batch:
+            if first != 0 or count not in (None, 1):
+                raise ValueError("a context has one set of planes: first = 0, count = None")
+            capi.check(self._lib.sfl_mean_start(self._h, what, every))
+        else:
+            count = self.batch - first if count is None else count
+            capi.check(self._lib.sfl_batch_mean_start(self._h, what, every, first, count))
+            self._mean_rec = (first, count)
+
+    def mean_stop(self):
+        """Drain the stream and free the planes."""
+        capi.check(self._loads_call("mean_stop")(self._h))
+
+    def mean_sample(self):
+        """Add the fields held now as one more sample, asynchronously, whatever `every` is."""
+        capi.check(self._loads_call("mean_sample")(self._h))
+
+    def mean_info(self):
+        """(what, every, samples added, steps counted since mean_start); zeros without averages on.  Never waits."""
+        what, every, samples, steps = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
+        capi.check(self._loads_call("mean_info")(self._h, C.byref(what), C.byref(every), C.byref(samples), C.byref(steps)))
+        return what.value, every.value, samples.value, steps.value
+
+    def mean_sums(self, plane: int, first=None, count=None) -> np.ndarray:
+        """The raw plane `plane` (``capi.MEAN_PLANE_*``) of members [first, first + count) -- default: the recorded range;
+        any other must lie inside it --: float64, uint64 for the dye planes, of
+        shape ``(count, dim_y, dim_x)``, bit for bit what the rule gives on the downloaded fields.  Synchronous."""
+        dtype = np.uint64 if 0 <= plane < len(_MEAN_GROUP_OF) and _MEAN_GROUP_OF[plane] == capi.MEAN_DYE else np.float64
+        if not self._loads_batch:
+            if first not in (None, 0) or count not in (None, 1):
+                raise ValueError("a context has one set of planes: first = None, count = None")
+            out = np.empty((1, self.dim_y, self.dim_x), dtype)
+            capi.check(self._lib.sfl_mean_download(self._h, plane, out.ctypes.data_as(C.c_void_p), out.nbytes))
+            return out
+        first = self._mean_rec[0] if first is None else first
+        count = self._mean_rec[0] + self._mean_rec[1] - first if count is None else count
+        out = np.empty((max(count, 0), self.dim_y, self.dim_x), dtype)
+        capi.check(self._lib.sfl_batch_mean_download(self._h, plane, first, count, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def means(self, first=None, count=None) -> dict:
+        """The means of the live groups as float64 arrays by plane name ("U", "V", "UU", ..., "B"): sum / samples; the dye
+        in units of the raw UQ32 value.  NaN everywhere while no sample has been added."""
+        what, _, samples, _ = self.mean_info()
+        n = np.float64(samples) if samples else np.float64("nan")
+        return {name: self.mean_sums(k, first, count).astype(np.float64) / n
+                for k, name in enumerate(MEAN_PLANE_NAMES) if what & _MEAN_GROUP_OF[k]}
+
+    def reynolds_stress(self, first=None, count=None) -> dict:
+        """The central second moments of the velocity, float64: ``uu`` = <u'u'> = UU/n - (U/n)^2, ``vv``, ``uv`` = UV/n -
+        (U/n)(V/n), and ``tke`` = (uu + vv) / 2.  Needs the groups MEAN_VELOCITY and MEAN_STRESS."""
+        what = self.mean_info()[0]
+        if what & 3 != 3:
+            raise ValueError(f"reynolds_stress: the averages hold the groups {what}; MEAN_VELOCITY | MEAN_STRESS are needed")
+        m = self.means(first, count)
+        uu, vv, uv = m["UU"] - m["U"] * m["U"], m["VV"] - m["V"] * m["V"], m["UV"] - m["U"] * m["V"]
+        return {"uu": uu, "vv": vv, "uv": uv, "tke": 0.5 * (uu + vv)}
+
+
+class Solver(_Tracers, _History, _Loads, _Friction, _Means):
     """One solver context: rows [row_begin, row_end) of a dim_x * dim_y domain on one device."""
 
     def __init__(self, dim_x: int, dim_y: int, device: int = 0, rank: int = 0, nranks: int = 1):
@@ -905,7 +981,7 @@ class Solver(_Tracers, _History, _Loads, _Friction):
         return {"launches": a.value, "exchanges": b.value, "fuse": c.value, "halo": self.get_option(capi.OPT_LAST_HALO)}
 
 
-class BatchSolver(_Tracers, _History, _Loads, _Friction):
+class BatchSolver(_Tracers, _History, _Loads, _Friction, _Means):
     """A batch (sfl_batch_*): `batch` independent whole-domain simulations of one dim_x * dim_y grid on one device,
     every member stepped by the same launch.  Member m holds, bit for bit, what a :class:`Solver` of the same shape
     holds after the same calls made with member m's data and forces.  Arrays of members are shaped

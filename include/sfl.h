@@ -1468,6 +1468,82 @@ SFL_API int sfl_friction_start(sfl_context *ctx, int every, int capacity);
 SFL_API int sfl_friction_stop(sfl_context *ctx);
 SFL_API int sfl_friction_info(sfl_context *ctx, int *samples, int *capacity, int64_t *steps, int *bodies);
 SFL_API int sfl_friction_read(sfl_context *ctx, int first_sample, int samples, struct sfl_body_friction *host, size_t bytes);
+/* --- AVERAGES: the time-averaged flow -- per-cell sums over time of the velocity, its second moments, the pressure and the
+ *     dye, added on the device while stepping, without a download per sample.  Every other record of this library reports one
+ *     instant; a wake or drag study is read through the mean velocity field, the mean pressure, the Reynolds stresses and
+ *     the long exposure of the dye.  The accumulators live in device memory, one PLANE per quantity, one value per cell.
+ *     After every `every`-th step of any step call ONE launch on the stream adds that step's fields to them; the step calls
+ *     stay asynchronous, the host never waits, and the sums are downloaded afterwards.  The rule below is a definition stated
+ *     here: the reference keeps no averages.
+ *   `what` is a mask of four groups; only the planes of the chosen groups exist:
+ *     SFL_MEAN_VELOCITY (1)   planes U (0), V (1)            float64   a sample adds (double)v.x, (double)v.y
+ *     SFL_MEAN_STRESS   (2)   planes UU (2), VV (3), UV (4)  float64   (double)v.x * (double)v.x, (double)v.y * (double)v.y,
+ *                                                                      (double)v.x * (double)v.y
+ *     SFL_MEAN_PRESSURE (4)   planes P (5), PP (6)           float64   (double)p, (double)p * (double)p
+ *     SFL_MEAN_DYE      (8)   planes R (7), G (8), B (9)     uint64    the raw UQ32 value of each channel
+ *   Every plane STARTS AT +0.0 (0 for the dye planes).  A sample adds THE FIELDS HELD, exactly as the table says: the projected
+ * velocity of the step it follows, the pressure of that step's solve (SFL_FIELD_PRESSURE as held) and that step's dye.  Every
+ * cell takes part as it is, SOLID CELLS INCLUDED.
+ *   A sample is ONE IEEE-754 DOUBLE ADDITION PER PLANE AND CELL, in sample order.  The product of two float32 values is exact
+ * in a double (48 <= 53 bits), so a fused multiply-add gives the same bits as multiply-then-add and the rule needs no word
+ * about contraction.  Special values are PLAIN IEEE: a NaN or +-Inf in a cell goes into that cell's sums as IEEE says and
+ * into NO OTHER CELL'S; a float32 denormal converts exactly and is NEVER FLUSHED; +0.0 + (-0.0) is +0.0.
+ *   Each cell's sum is sequential in time and integer sums do not depend on any order: every plane is, BIT FOR BIT, what the
+ * rule computes from the downloaded fields.  That is the whole contract; there is NO TOLERANCE anywhere.  The dye sums cannot
+ * wrap below 2^32 samples.
+ *   THE MEANS ARE NOT THE LIBRARY'S: it reports SUMS and the number of samples.  The mean is sum / samples, and the central
+ * moment <u'u'> = UU / n - (U / n)^2; the caller forms both (the Python binding does, in float64).  There is no division on
+ * the device.
+ *   `every` >= 1: steps count across calls, as the histories' do, and a sample is due after step (s + 1) * every.  While such
+ * averages are on, a batch's one-launch replay of a timeline IS CUT at the steps whose sample is due, and sfl_step_n of a
+ * context runs WITHOUT ITS FUSED STEP BOUNDARIES, every step as sfl_step runs it, exactly as with a history on: the sample
+ * reads the projected velocity, which a fused boundary never stores.  `every` == 0: nothing is added behind the steps and no
+ * hook is set -- the step calls keep their fusion and their one-launch replay -- and only sfl_mean_sample /
+ * sfl_batch_mean_sample add.  Behind a step the order is tracers, history, loads, friction, averages.
+ *   There is NO CAPACITY and so no admission rule: a step call is never refused for the averages.  With no averages on, every
+ * call launches exactly what it launched before there were any.
+ *   MEMORY: a plane is 8 bytes per cell and recorded member (a member's cells rounded up to an even number on the device).
+ * Ten planes at 8192 x 8192 are 5.4 GB; choose the groups that are needed.  Out of memory is SFL_ERR_NOMEM with nothing set.
+ *   Whole-domain contexts and batches of either kind; a slab and a context with a transport attached get SFL_ERR_STATE, each
+ * with its own message.  Admission as everywhere: argument checks come first.                                              */
+#define SFL_MEAN_VELOCITY 1
+#define SFL_MEAN_STRESS   2
+#define SFL_MEAN_PRESSURE 4
+#define SFL_MEAN_DYE      8
+#define SFL_MEAN_ALL      15
+#define SFL_MEAN_PLANE_U  0
+#define SFL_MEAN_PLANE_V  1
+#define SFL_MEAN_PLANE_UU 2
+#define SFL_MEAN_PLANE_VV 3
+#define SFL_MEAN_PLANE_UV 4
+#define SFL_MEAN_PLANE_P  5
+#define SFL_MEAN_PLANE_PP 6
+#define SFL_MEAN_PLANE_R  7
+#define SFL_MEAN_PLANE_G  8
+#define SFL_MEAN_PLANE_B  9
+#define SFL_MEAN_PLANES   10
+/* Start the averages of a whole-domain context: allocate the planes of `what` (1..15), zero them on the stream, and, for
+ * every >= 1, add a sample behind every `every`-th step from now on.  A start while on begins anew from zero.              */
+SFL_API int sfl_mean_start(sfl_context *ctx, int what, int every);
+/* Drains the stream, frees the planes and takes the hook away.  Without averages on it does nothing.                       */
+SFL_API int sfl_mean_stop(sfl_context *ctx);
+/* Adds the fields held now as one more sample, asynchronously on the stream, whatever `every` is.                          */
+SFL_API int sfl_mean_sample(sfl_context *ctx);
+/* The mask, `every`, the samples added and the steps counted since the start; all zero without averages on.  Any pointer
+ * may be NULL.                                                                                                             */
+SFL_API int sfl_mean_info(sfl_context *ctx, int *what, int *every, int64_t *samples, int64_t *steps);
+/* One plane (SFL_MEAN_PLANE_*) to the host, synchronously: dim_y x dim_x values of 8 bytes, densely packed, whatever the
+ * padding on the device; float64, uint64 for the dye planes.  bytes must be exactly that.  Refused: a plane outside `what`,
+ * another byte count, averages that are not on.                                                                            */
+SFL_API int sfl_mean_download(sfl_context *ctx, int plane, void *host, size_t bytes);
+/* The same for members [first, first + count) of a batch of either kind: the planes hold those members only.  A download
+ * takes members [first_member, first_member + members), which must lie inside the recorded range: members x dim_y x dim_x
+ * values, members in order.                                                                                                */
+SFL_API int sfl_batch_mean_start(sfl_batch *b, int what, int every, int first, int count);
+SFL_API int sfl_batch_mean_stop(sfl_batch *b);
+SFL_API int sfl_batch_mean_sample(sfl_batch *b);
+SFL_API int sfl_batch_mean_info(sfl_batch *b, int *what, int *every, int64_t *samples, int64_t *steps);
+SFL_API int sfl_batch_mean_download(sfl_batch *b, int plane, int first_member, int members, void *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
