@@ -96,6 +96,13 @@ class BodyFriction(C.Structure):
                 ("nonfinite", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class BodyTorque(C.Structure):
+    """struct sfl_body_torque: the moment of pressure and friction on one solid body about its pivot, 64 bytes."""
+    _fields_ = [("mp", C.c_int64), ("mf", C.c_int64), ("exp2_p", C.c_int32), ("exp2_f", C.c_int32), ("max_abs_p", C.c_float),
+                ("max_abs_t", C.c_float), ("faces", C.c_uint32), ("max_arm2", C.c_uint32), ("nonfinite_p", C.c_uint32),
+                ("nonfinite_t", C.c_uint32), ("pivot2", C.c_int32 * 2), ("reserved", C.c_uint32 * 2)]
+
+
 class FieldDistance(C.Structure):
     """struct sfl_field_distance: what sfl_distance and sfl_batch_distance report, 64 bytes."""
     _fields_ = [("max_abs_dvx", C.c_float), ("max_abs_dvy", C.c_float), ("max_abs_dp", C.c_float), ("what", C.c_uint32),
@@ -330,6 +337,20 @@ SIGNATURES = {
     "sfl_friction_stop": (_i, [_ctx]),
     "sfl_friction_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), _pi]),
     "sfl_friction_read": (_i, [_ctx, _i, _i, C.POINTER(BodyFriction), _sz]),
+    "sfl_batch_set_body_pivots": (_i, [_ctx, C.POINTER(C.c_int32), _i, _i]),
+    "sfl_batch_body_pivots_download": (_i, [_ctx, _i, _i, C.POINTER(C.c_int32), _sz]),
+    "sfl_batch_torque": (_i, [_ctx, _i, _i, C.POINTER(BodyTorque), _sz]),
+    "sfl_batch_torque_start": (_i, [_ctx, _i, _i, _i, _i]),
+    "sfl_batch_torque_stop": (_i, [_ctx]),
+    "sfl_batch_torque_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), _pi]),
+    "sfl_batch_torque_read": (_i, [_ctx, _i, _i, C.POINTER(BodyTorque), _sz]),
+    "sfl_set_body_pivots": (_i, [_ctx, C.POINTER(C.c_int32), _i]),
+    "sfl_body_pivots_download": (_i, [_ctx, C.POINTER(C.c_int32), _sz]),
+    "sfl_torque": (_i, [_ctx, C.POINTER(BodyTorque), _sz]),
+    "sfl_torque_start": (_i, [_ctx, _i, _i]),
+    "sfl_torque_stop": (_i, [_ctx]),
+    "sfl_torque_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), _pi]),
+    "sfl_torque_read": (_i, [_ctx, _i, _i, C.POINTER(BodyTorque), _sz]),
     "sfl_mean_start": (_i, [_ctx, _i, _i]),
     "sfl_mean_stop": (_i, [_ctx]),
     "sfl_mean_sample": (_i, [_ctx]),

@@ -21,7 +21,7 @@ void release(sfl_batch *b)
                     (void *)b->d_stats, (void *)b->d_images, (void *)b->d_frames, (void *)b->d_dist, (void *)b->d_env,
                     (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
                     (void *)b->d_rec_palette, b->history.d_records, (void *)b->solids.d_codes,
-                    (void *)b->loads.d_labels, b->loads.d_records, b->friction.d_records, b->means.d_planes, b->viscosity.d_table, (void *)b->openings.d_codes,
+                    (void *)b->loads.d_labels, b->loads.d_records, b->friction.d_records, b->torque.d_records, (void *)b->torque.d_pivot2, b->means.d_planes, b->viscosity.d_table, (void *)b->openings.d_codes,
                     (void *)b->openings.d_inflow, b->openings.d_profile, b->openings.d_flux})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
@@ -241,6 +241,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
             if (b->history_step) SFL_TRY(b->history_step(b, steps, kind == kEach ? b->d_members : nullptr, false, a.step));
             if (b->loads_step) SFL_TRY(b->loads_step(b, steps));   // (no solids here: the samples inside are zeros, no cut)
             if (b->friction_step) SFL_TRY(b->friction_step(b, steps));   // (the same)
+            if (b->torque_step) SFL_TRY(b->torque_step(b, steps));       // (the same)
             if (b->mean_step) SFL_TRY(b->mean_step(b, steps));   // (the averages read the fields: mean_run has cut at their due steps)
             done += steps;
         }
@@ -273,6 +274,7 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
         if (b->history_step) SFL_TRY(b->history_step(b, 1, kind == kUniform ? nullptr : b->d_members, kind == kUntil, a.step));
         if (b->loads_step) SFL_TRY(b->loads_step(b, 1));
         if (b->friction_step) SFL_TRY(b->friction_step(b, 1));
+        if (b->torque_step) SFL_TRY(b->torque_step(b, 1));
         if (b->mean_step) SFL_TRY(b->mean_step(b, 1));
     }
     consume_forces(b, n);
@@ -600,6 +602,7 @@ int sfl_batch_step_n(sfl_batch *b, int n, float dt, float dx, int iters, float o
     SFL_TRY(sfl::host::history_admit(b->history, n));   // ... and a history without room for its samples
     SFL_TRY(sfl::host::loads_admit(b->loads, n));       // ... and a loads recorder without room for its
     SFL_TRY(sfl::host::friction_admit(b->friction, n)); // ... and a friction recorder without room for its
+    SFL_TRY(sfl::host::torque_admit(b->torque, n));     // ... and a torque recorder without room for its
     SFL_TRY(use_device(b));
     b->report_valid = b->counts_valid = false;   // (the uniform kernels leave no update norm)
     sfl::BatchStep a{};
@@ -639,6 +642,7 @@ int sfl_batch_step_n_each(sfl_batch *b, int n, const sfl_member_params *params)
     SFL_TRY(sfl::host::history_admit(b->history, n));   // ... and a history without room for its samples
     SFL_TRY(sfl::host::loads_admit(b->loads, n));       // ... and a loads recorder without room for its
     SFL_TRY(sfl::host::friction_admit(b->friction, n)); // ... and a friction recorder without room for its
+    SFL_TRY(sfl::host::torque_admit(b->torque, n));     // ... and a torque recorder without room for its
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params));
     if (b->viscosity.set) SFL_TRY(b->viscosity.stage(b, 0.0f, 0.0f, params));   // every member's a and c of its own dt and dx
@@ -685,6 +689,7 @@ int sfl_batch_step_n_until(sfl_batch *b, int n, const sfl_member_params *params,
     SFL_TRY(sfl::host::history_admit(b->history, n));   // ... and a history without room for its samples
     SFL_TRY(sfl::host::loads_admit(b->loads, n));       // ... and a loads recorder without room for its
     SFL_TRY(sfl::host::friction_admit(b->friction, n)); // ... and a friction recorder without room for its
+    SFL_TRY(sfl::host::torque_admit(b->torque, n));     // ... and a torque recorder without room for its
     SFL_TRY(use_device(b));
     SFL_TRY(stage_members(b, params, stops));
     b->report_valid = b->counts_valid = false;   // until every launch below is queued

@@ -129,6 +129,9 @@ struct sfl_batch {
     // the friction recorder (friction.cpp; context.h has Friction), by the same rule; called last, behind loads_step
     sfl::host::Friction friction;
     int (*friction_step)(sfl_batch *b, int steps) = nullptr;
+    // the pivots and the torque recorder (torque.cpp; context.h has Torque), by the same rule; called behind friction_step
+    sfl::host::Torque torque;
+    int (*torque_step)(sfl_batch *b, int steps) = nullptr;
     // the averages (means.cpp; context.h has Means): mean_step: `steps` steps have been launched (one launch: mean_run saw to
     // it that no sample falls inside them) and the ping-pong swapped -- count them and, when a sample is due, launch it on
     // the batch's stream behind them; called last, behind friction_step

@@ -1,11 +1,14 @@
-// body_recorder.h -- the calls that report one 48-byte record per solid body, at once and as samples recorded behind the steps,
-// written once for the two kinds that exist: the loads (loads.cpp; include/sfl.h "LOADS") and the friction (friction.cpp;
-// "FRICTION").  Host C++ only.  Generic over the holder H (sfl_context, sfl_batch) and over the kind K, a struct of statics:
-//     Record                        the record type (48 bytes)
+// body_recorder.h -- the calls that report one record per solid body, at once and as samples recorded behind the steps,
+// written once for the three kinds that exist: the loads (loads.cpp; include/sfl.h "LOADS"), the friction (friction.cpp;
+// "FRICTION") and the torque (torque.cpp; "TORQUE").  Host C++ only.  Generic over the holder H (sfl_context, sfl_batch) and
+// over the kind K, a struct of statics:
+//     Record                        the record type (48 bytes; the torque's 64)
 //     state(H *)                    the recorder's plain data on the holder (context.h Loads, Friction): on, every, first, count,
 //                                   capacity, written, steps, d_records, d_bytes
 //     launch_sample(H *, first, count, Record *out)   the sampler's launches on the holder's stream (solids are set)
 //     set_hook(H *)                 sets the holder's step pointer from state(x).on
+//     zero_sample(H *, first, count, Record *out)     the records of a sample taken while no solids are set, on the stream, and
+//     zero_host(H *, first, count, Record *host)      the same on the host, without a launch (ZeroRecords: all bytes zero)
 //     kNoun, kRecorder, kStartCalls the words of the messages ("loads", "loads recorder", "sfl_loads_start (sfl_batch_loads_start)")
 // The labels and the number of bodies are the loads' (Loads::d_labels, ::bodies) for every kind.
 #pragma once
@@ -39,7 +42,19 @@ inline int check_handle(sfl_batch *b, const char *call, const char *, bool = tru
     return SFL_OK;
 }
 
-constexpr size_t kRecord = 48;
+// what the kinds whose records are all zeros without solids inherit
+template <class R>
+struct ZeroRecords {
+    template <class H>
+    static int zero_sample(H *x, int, int count, R *out)
+    {
+        const Holder o = holder_of(x);
+        HIP_TRY(hipMemsetAsync(out, 0, (size_t)count * o.bodies * sizeof(R), o.stream));
+        return SFL_OK;
+    }
+    template <class H>
+    static void zero_host(H *x, int, int count, R *host) { memset(host, 0, (size_t)count * holder_of(x).bodies * sizeof(R)); }
+};
 
 inline size_t scratch_records(const Holder &o) { return (size_t)o.members * o.bodies; }
 // sample `sample` of a recorder over `count` members: behind the records of one sample of every member
@@ -86,7 +101,7 @@ int step(H *x, int steps)
         if (o.solids)
             SFL_TRY(K::launch_sample(x, l.first, l.count, out));
         else
-            HIP_TRY(hipMemsetAsync(out, 0, (size_t)l.count * o.bodies * kRecord, o.stream));
+            SFL_TRY(K::zero_sample(x, l.first, l.count, out));
         l.written = (int)s + 1;
     }
     return SFL_OK;
@@ -104,7 +119,7 @@ void stop_recorder(S &l)
 template <class K, class H>
 int now(H *x, int first, int count, typename K::Record *host, size_t bytes, const char *call)
 {
-    static_assert(sizeof(typename K::Record) == kRecord, "a record per body is 48 bytes");
+    constexpr size_t kRecord = sizeof(typename K::Record);
     SFL_TRY(check_handle(x, call, K::kNoun));
     const Holder o = holder_of(x);
     auto &l = K::state(x);
@@ -112,13 +127,13 @@ int now(H *x, int first, int count, typename K::Record *host, size_t bytes, cons
         return fail(SFL_ERR_INVALID, "%s: members [%d, %d + %d) are not inside the batch's [0, %d)", call, first, first, count, o.members);
     const size_t want = (size_t)count * o.bodies * kRecord;
     if (bytes != want && o.batch)
-        return fail(SFL_ERR_INVALID, "%s: %d members of %d records of 48 bytes are %zu bytes, got %zu", call, count, o.bodies, want, bytes);
+        return fail(SFL_ERR_INVALID, "%s: %d members of %d records of %zu bytes are %zu bytes, got %zu", call, count, o.bodies, kRecord, want, bytes);
     if (bytes != want)
-        return fail(SFL_ERR_INVALID, "%s: the records of %d bodies of 48 bytes each are %zu bytes, got %zu", call, o.bodies, want, bytes);
+        return fail(SFL_ERR_INVALID, "%s: the records of %d bodies of %zu bytes each are %zu bytes, got %zu", call, o.bodies, kRecord, want, bytes);
     if (count == 0) return SFL_OK;
     if (!host) return fail(SFL_ERR_INVALID, "%s: host is NULL", call);
     if (!o.solids) {   // no body anywhere: no launch
-        memset(host, 0, bytes);
+        K::zero_host(x, first, count, host);
         return SFL_OK;
     }
     HIP_TRY(hipSetDevice(o.device));
@@ -133,6 +148,7 @@ int now(H *x, int first, int count, typename K::Record *host, size_t bytes, cons
 template <class K, class H>
 int start(H *x, int every, int first, int count, int capacity, const char *call)
 {
+    constexpr size_t kRecord = sizeof(typename K::Record);
     if (every < 1) return fail(SFL_ERR_INVALID, "%s: every must be >= 1 (got %d)", call, every);
     if (capacity < 1) return fail(SFL_ERR_INVALID, "%s: capacity must be >= 1 (got %d)", call, capacity);
     if (count < 1) return fail(SFL_ERR_INVALID, "%s: count must be >= 1 (got %d)", call, count);
@@ -191,6 +207,7 @@ int info(H *x, int *samples, int *capacity, int64_t *steps, int *bodies, const c
 template <class K, class H>
 int read(H *x, int first_sample, int samples, typename K::Record *host, size_t bytes, const char *call)
 {
+    constexpr size_t kRecord = sizeof(typename K::Record);
     if (first_sample < 0 || samples < 0)
         return fail(SFL_ERR_INVALID, "%s: samples [%d, %d + %d): first_sample and samples must be >= 0", call, first_sample, first_sample, samples);
     SFL_TRY(check_handle(x, call, K::kNoun));
@@ -199,8 +216,8 @@ int read(H *x, int first_sample, int samples, typename K::Record *host, size_t b
     if (!l.on) return fail(SFL_ERR_STATE, "%s: no %s to read: call %s first", call, K::kRecorder, K::kStartCalls);
     const size_t per_sample = (size_t)l.count * o.bodies, want = (size_t)samples * per_sample * kRecord;
     if (bytes != want)
-        return fail(SFL_ERR_INVALID, "%s: %d samples of %zu records of 48 bytes (%d %s %d bodies) are %zu bytes, got %zu", call, samples, per_sample,
-                    l.count, o.batch ? "members of" : "context of", o.bodies, want, bytes);
+        return fail(SFL_ERR_INVALID, "%s: %d samples of %zu records of %zu bytes (%d %s %d bodies) are %zu bytes, got %zu", call, samples, per_sample,
+                    kRecord, l.count, o.batch ? "members of" : "context of", o.bodies, want, bytes);
     if ((int64_t)first_sample + samples > l.written)
         return fail(SFL_ERR_INVALID, "%s: samples [%d, %d + %d) are not inside the %d samples written so far, [0, %d)", call, first_sample,
                     first_sample, samples, l.written, l.written);

@@ -16,6 +16,7 @@
 //   context_solids.cpp solid cells of a whole-domain context (sfl_set_solids, _solids_info, _solids_download) and the masked launches
 //   loads.cpp         the pressure load on solid bodies (sfl_loads*, sfl_batch_loads*, sfl_set_bodies, sfl_batch_set_bodies)
 //   friction.cpp      the skin friction on solid bodies (sfl_friction*, sfl_batch_friction*); body_recorder.h: the calls both share
+//   torque.cpp        the torque on solid bodies and their pivots (sfl_torque*, sfl_batch_torque*, sfl_[batch_]set_body_pivots)
 //   means.cpp         per-cell sums over time of a context or a batch, added while stepping (sfl_mean_*, sfl_batch_mean_*)
 //   context_viscous.cpp viscosity of a whole-domain context (sfl_set_viscosity, _viscosity_info, sfl_diffuse_velocity)
 //   viscous.cpp       viscosity of a batch (sfl_batch_set_viscosity, _viscosity_info, _viscosity_download)
@@ -311,6 +312,36 @@ inline int friction_admit(const Friction &f, int64_t n)
     return SFL_OK;
 }
 
+// Torque (torque.cpp; include/sfl.h "TORQUE"): the pivots of the bodies and the third recorder of records per body (64 bytes
+// each), beside the loads' and the friction's and independent of both.  The labels and `bodies` are Loads'; the recorder has
+// the field names of Loads so that body_recorder.h serves it too.  Plain data for the same reason; the sample is launched
+// through `torque_step`.  The pivots live twice: on the host, for the records that need no launch (no solids set) and for the
+// download, and in a small device table that the samplers read.
+struct Torque {
+    bool on = false;
+    int every = 0, first = 0, count = 0, capacity = 0, written = 0;   // members [first, first + count) (a context: [0, 1))
+    int64_t steps = 0;            // counted since torque_start
+    void *d_records = nullptr;    // laid out as Loads::d_records; freed by torque_stop and the destroy paths
+    size_t d_bytes = 0;
+    // (x2, y2) per body, of every member when pivots_per_member; null / empty: every pivot is (0, 0)
+    int32_t *d_pivot2 = nullptr;  //   freed by set_body_pivots(NULL), by a set_bodies that changes `bodies` and by the destroy paths
+    size_t d_pivot_bytes = 0;
+    bool pivots_per_member = false;
+    std::vector<int32_t> h_pivot2;
+};
+
+// SFL_ERR_STATE if the n steps of a call would complete more samples than are free: loads_admit's rule
+inline int torque_admit(const Torque &t, int64_t n)
+{
+    if (!t.on) return SFL_OK;
+    const int64_t due = (t.steps + n) / t.every - t.steps / t.every, room = t.capacity - t.written;
+    if (due > room)
+        return fail(SFL_ERR_STATE, "the torque recorder has room for %lld more samples (%d of %d written) and %lld steps would complete %lld: "
+                    "nothing stepped; read the samples (sfl_torque_read, sfl_batch_torque_read) and start the recorder again to make room",
+                    (long long)room, t.written, t.capacity, (long long)n, (long long)due);
+    return SFL_OK;
+}
+
 // Averages (means.cpp; include/sfl.h "AVERAGES"): the per-cell sums over time that a context or a batch holds.  Plain data,
 // as History and for the same reason: the destroy paths free the planes and batch.cpp finds the cut points of a replay
 // (mean_run) without a symbol of means.cpp; the sample is launched through the `mean_step` pointer of the two structs, which
@@ -532,6 +563,9 @@ struct sfl_context {
     // the friction recorder (friction.cpp), by the same rule; called last, behind loads_step
     sfl::host::Friction friction;
     int (*friction_step)(sfl_context *c) = nullptr;
+    // the pivots and the torque recorder (torque.cpp), by the same rule; called behind friction_step
+    sfl::host::Torque torque;
+    int (*torque_step)(sfl_context *c) = nullptr;
     // the averages (means.cpp), and their sample behind every step while they are on with every >= 1 (one step has run: count
     // it and, when a sample is due, launch it on the context's stream); called last, behind friction_step
     sfl::host::Means means;

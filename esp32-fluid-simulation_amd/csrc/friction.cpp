@@ -25,7 +25,7 @@ namespace {
 int step_batch(sfl_batch *b, int steps);
 int step_context(sfl_context *c);
 
-struct FrictionKind {
+struct FrictionKind : ZeroRecords<struct sfl_body_friction> {
     typedef struct sfl_body_friction Record;
     static constexpr const char *kNoun = "friction", *kRecorder = "friction recorder",
                                 *kStartCalls = "sfl_friction_start (sfl_batch_friction_start)";

@@ -26,7 +26,7 @@ int step_batch(sfl_batch *b, int steps);
 int step_context(sfl_context *c);
 
 // the loads as a kind of body_recorder.h: the calls themselves (start, stop, info, read, the figures at once) live there
-struct LoadsKind {
+struct LoadsKind : ZeroRecords<struct sfl_body_load> {
     typedef struct sfl_body_load Record;
     static constexpr const char *kNoun = "loads", *kRecorder = "loads recorder", *kStartCalls = "sfl_loads_start (sfl_batch_loads_start)";
     static Loads &state(sfl_context *c) { return c->loads; }
@@ -76,6 +76,8 @@ int step_context(sfl_context *c) { return step<K>(c, 1); }
 
 bool friction_on(const sfl_context *c) { return c->friction.on; }
 bool friction_on(const sfl_batch *b) { return b->friction.on; }
+Torque &torque_of(sfl_context *c) { return c->torque; }
+Torque &torque_of(sfl_batch *b) { return b->torque; }
 
 template <class H>
 int set_bodies(H *x, const uint8_t *labels, int per_member, int bodies, const char *call)
@@ -100,8 +102,19 @@ int set_bodies(H *x, const uint8_t *labels, int per_member, int bodies, const ch
     if (friction_on(x))
         return fail(SFL_ERR_STATE, "%s: the friction recorder is on and the layout of its samples depends on the number of bodies: nothing set; "
                     "stop it first (sfl_friction_stop, sfl_batch_friction_stop)", call);
+    if (torque_of(x).on)
+        return fail(SFL_ERR_STATE, "%s: the torque recorder is on and the layout of its samples depends on the number of bodies: nothing set; "
+                    "stop it first (sfl_torque_stop, sfl_batch_torque_stop)", call);
     HIP_TRY(hipSetDevice(o.device));
     HIP_TRY(hipStreamSynchronize(o.stream));   // a sample in flight may still read the bytes this call replaces
+    if ((labels ? bodies : 1) != l.bodies) {   // the pivots are per body: another number of bodies puts them back to (0, 0)
+        Torque &t = torque_of(x);
+        if (t.d_pivot2) (void)hipFree(t.d_pivot2);
+        t.d_pivot2 = nullptr;
+        t.d_pivot_bytes = 0;
+        t.pivots_per_member = false;
+        t.h_pivot2.clear();
+    }
     if (!labels || bytes > l.d_label_bytes) {
         if (l.d_labels) (void)hipFree(l.d_labels);
         l.d_labels = nullptr;

@@ -330,6 +330,7 @@ int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
     SFL_TRY(history_admit(ctx->history, 1));       // ... and so does a history without a free sample
     SFL_TRY(loads_admit(ctx->loads, 1));           // ... and a loads recorder without one
     SFL_TRY(friction_admit(ctx->friction, 1));     // ... and a friction recorder without one
+    SFL_TRY(torque_admit(ctx->torque, 1));         // ... and a torque recorder without one
     if (ctx->nranks > 1 && ctx->opt.advect_halo == 0 && ctx->color_unsettled && ctx->unsettled_dt == dt && ctx->force_cells.empty())
         SFL_TRY(advect_interior_early(ctx, dt));
     SFL_TRY(settle_color(ctx, true));
@@ -340,6 +341,7 @@ int sfl_step(sfl_context *ctx, float dt, float dx, int iters, float omega)
     if (ctx->history_step) SFL_TRY(ctx->history_step(ctx, dt, dx, iters));   // a history counts the step and samples what it left
     if (ctx->loads_step) SFL_TRY(ctx->loads_step(ctx));   // ... and so does a loads recorder
     if (ctx->friction_step) SFL_TRY(ctx->friction_step(ctx));   // ... and a friction recorder
+    if (ctx->torque_step) SFL_TRY(ctx->torque_step(ctx));   // ... and a torque recorder
     if (ctx->mean_step) SFL_TRY(ctx->mean_step(ctx));   // ... and the averages, last
     return SFL_OK;
 }
@@ -357,6 +359,7 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
     SFL_TRY(history_admit(ctx->history, n));       // ... and so does a history without room for the call's samples
     SFL_TRY(loads_admit(ctx->loads, n));           // ... and a loads recorder without room for its
     SFL_TRY(friction_admit(ctx->friction, n));     // ... and a friction recorder without room for its
+    SFL_TRY(torque_admit(ctx->torque, n));         // ... and a torque recorder without room for its
     SFL_TRY(settle_color(ctx, true));
     SFL_TRY(check_wait_error(ctx));
     const int64_t cells = (int64_t)ctx->dim_x * ctx->gdim_y;
@@ -395,6 +398,7 @@ int sfl_step_n(sfl_context *ctx, int n, float dt, float dx, int iters, float ome
         // (a loads recorder keeps the seams: they only run without solids, where a sample is zero records and reads no field)
         if (ctx->loads_step) SFL_TRY(ctx->loads_step(ctx));
         if (ctx->friction_step) SFL_TRY(ctx->friction_step(ctx));   // (the same)
+        if (ctx->torque_step) SFL_TRY(ctx->torque_step(ctx));   // (the same)
     }
     return SFL_OK;
 }

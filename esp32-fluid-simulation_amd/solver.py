@@ -85,6 +85,12 @@ BODY_LOAD_DTYPE = np.dtype([("fx", "<i8"), ("fy", "<i8"), ("exp2", "<i4"), ("max
 # 48 bytes; the force per unit depth and density is nu * fx * 2^exp2 (no dx): friction_xy() does that arithmetic in float64.
 BODY_FRICTION_DTYPE = np.dtype([("fx", "<i8"), ("fy", "<i8"), ("exp2", "<i4"), ("max_abs_t", "<f4"), ("faces", "<u4", (4,)),
                                 ("nonfinite", "<u4"), ("reserved", "<u4")])
+# struct sfl_body_torque: the moment of pressure and friction on one solid body about its pivot (Solver.torque,
+# BatchSolver.torque).  64 bytes; the pressure torque in pressure times cell widths^2 is mp * 2^(exp2_p - 1), the friction
+# torque per unit depth rho * nu * mf * 2^(exp2_f - 1) * dx: torque_xy() does that arithmetic in float64.
+BODY_TORQUE_DTYPE = np.dtype([("mp", "<i8"), ("mf", "<i8"), ("exp2_p", "<i4"), ("exp2_f", "<i4"), ("max_abs_p", "<f4"), ("max_abs_t", "<f4"),
+                              ("faces", "<u4"), ("max_arm2", "<u4"), ("nonfinite_p", "<u4"), ("nonfinite_t", "<u4"), ("pivot2", "<i4", (2,)),
+                              ("reserved", "<u4", (2,))])
 # struct sfl_open_flux: the flux through the live open cells of one grid (Solver.openings_flux: one record;
 # BatchSolver.openings_flux: one per member).  40 bytes; the flux in velocity times cell widths is inflow * 2^exp2.
 OPEN_FLUX_DTYPE = np.dtype([("inflow", "<i8"), ("outflow", "<i8"), ("exp2", "<i4"), ("max_abs_n", "<f4"), ("inflow_cells", "<u4"),
@@ -633,7 +639,121 @@ class _Means:
         return {"uu": uu, "vv": vv, "uv": uv, "tke": 0.5 * (uu + vv)}
 
 
-class Solver(_Tracers, _History, _Loads, _Friction, _Means):
+class _Torque:
+    """Torque: the moment about z of the pressure load and of the skin friction on solid bodies about a pivot per body, as
+    figures and as curves recorded while stepping (include/sfl.h "TORQUE").  Shared by :class:`Solver` (``[1, bodies]``
+    records per sample) and :class:`BatchSolver` (``[count, bodies]``)."""
+
+    _torque_rec = (0, 1)   # the recorded members (first, count)
+
+    def _torque_ptr(self, a):
+        return a.ctypes.data_as(C.POINTER(capi.BodyTorque))
+
+    def set_body_pivots(self, xy):
+        """The pivots in cells: floats of shape ``(bodies, 2)`` (a batch: also ``(batch, bodies, 2)``), (x, y) last, every
+        value a multiple of 0.5 (ValueError otherwise) -- the library takes half cells.  None goes back to (0, 0) for every
+        body.  Allowed while the recorder is on: the new pivots hold from the next sample."""
+        ptr = C.POINTER(C.c_int32)
+        if xy is None:
+            args = (None, 0, 1) if self._loads_batch else (None, 1)
+            capi.check(self._loads_call("set_body_pivots")(self._h, *args))
+            return
+        a = np.asarray(xy, dtype=np.float64)
+        n_bodies = self.bodies_info()[0]
+        shapes = [(n_bodies, 2)] + ([(self.batch, n_bodies, 2)] if self._loads_batch else [])
+        if a.shape not in shapes:
+            raise ValueError(f"pivots: shape {a.shape}, want one of {shapes}")
+        twice = a * 2.0
+        if not (np.isfinite(twice).all() and (twice == np.round(twice)).all() and (np.abs(twice) < 2.0 ** 31).all()):
+            raise ValueError("pivots: every coordinate must be a multiple of 0.5 cells")
+        p2 = np.ascontiguousarray(twice.astype(np.int32))
+        args = (int(a.ndim == 3), n_bodies) if self._loads_batch else (n_bodies,)
+        capi.check(self._loads_call("set_body_pivots")(self._h, p2.ctypes.data_as(ptr), *args))
+
+    def body_pivots(self, first: int = 0, count=None) -> np.ndarray:
+        """The pivots in cells, float64 ``(bodies, 2)`` (a batch: ``(count, bodies, 2)`` of members [first, first + count));
+        zeros when none are set."""
+        ptr = C.POINTER(C.c_int32)
+        n_bodies = self.bodies_info()[0]
+        if not self._loads_batch:
+            a = np.zeros((n_bodies, 2), np.int32)
+            capi.check(self._lib.sfl_body_pivots_download(self._h, a.ctypes.data_as(ptr), a.nbytes))
+            return a / 2.0
+        count = self.batch - first if count is None else count
+        a = np.zeros((count, n_bodies, 2), np.int32)
+        capi.check(self._lib.sfl_batch_body_pivots_download(self._h, first, count, a.ctypes.data_as(ptr), a.nbytes))
+        return a / 2.0
+
+    def torque(self, first: int = 0, count=None) -> np.ndarray:
+        """The torque on every body from the pressure and the velocity held: a BODY_TORQUE_DTYPE array of shape
+        ``(count, bodies)`` -- a context: ``(1, bodies)`` --, every field bit for bit what the rule of include/sfl.h "TORQUE"
+        gives on the downloaded fields, mask, labels and pivots.  Zeros but for pivot2 without solids.  Synchronous."""
+        n_bodies = self.bodies_info()[0]
+        if not self._loads_batch:
+            if first != 0 or count not in (None, 1):
+                raise ValueError("a context has one set of records: first = 0, count = None")
+            out = np.zeros((1, n_bodies), BODY_TORQUE_DTYPE)
+            capi.check(self._lib.sfl_torque(self._h, self._torque_ptr(out), out.nbytes))
+            return out
+        count = self.batch - first if count is None else count
+        out = np.zeros((count, n_bodies), BODY_TORQUE_DTYPE)
+        capi.check(self._lib.sfl_batch_torque(self._h, first, count, self._torque_ptr(out), out.nbytes))
+        return out
+
+    def _torque_xy(self, rec, first, dx, rho):
+        """float64 ``(..., count, bodies, 2)`` of records ``(..., count, bodies)``: the pressure torque mp * 2^(exp2_p - 1) *
+        dx^2 and the friction torque rho * nu * mf * 2^(exp2_f - 1) * dx, nu the viscosity that is set (per member)."""
+        nu = self._friction_nu(None, first, rec.shape[-2])
+        nu = nu if nu.ndim == 0 else nu[:, :, 0]   # (count, 1) against (..., count, bodies)
+        mp = rec["mp"].astype(np.float64) * np.ldexp(1.0, rec["exp2_p"].astype(np.int64) - 1) * (float(dx) * float(dx))
+        mf = rec["mf"].astype(np.float64) * np.ldexp(1.0, rec["exp2_f"].astype(np.int64) - 1) * nu * (float(rho) * float(dx))
+        return np.stack([mp, mf], axis=-1)
+
+    def torque_xy(self, dx: float = 1.0, rho: float = 1.0, first: int = 0, count=None) -> np.ndarray:
+        """:meth:`torque` as float64 ``(count, bodies, 2)``: [..., 0] the pressure torque in pressure x length^2, [..., 1] the
+        friction torque per unit depth, with the viscosity that is set (zeros when none is).  Counter-clockwise positive."""
+        return self._torque_xy(self.torque(first, count), first, dx, rho)
+
+    def torque_start(self, every: int, capacity: int, first: int = 0, count=None):
+        """Start the torque recorder, by the rules of :meth:`loads_start` and independent of the other recorders; behind a
+        step the order is history, loads, friction, torque."""
+        if not self._loads_batch:
+            if first != 0 or count not in (None, 1):
+                raise ValueError("a context has one set of records per sample: first = 0, count = None")
+            rc = self._lib.sfl_torque_start(self._h, every, capacity)
+            rec = (0, 1)
+        else:
+            count = self.batch - first if count is None else count
+            rc = self._lib.sfl_batch_torque_start(self._h, every, first, count, capacity)
+            rec = (first, count)
+        if rc == capi.OK:
+            self._torque_rec = rec
+        capi.check(rc)
+
+    def torque_info(self):
+        """(samples written, capacity, steps counted since torque_start, bodies).  Never waits."""
+        samples, capacity, steps, n = C.c_int(), C.c_int(), C.c_int64(), C.c_int()
+        capi.check(self._loads_call("torque_info")(self._h, C.byref(samples), C.byref(capacity), C.byref(steps), C.byref(n)))
+        return samples.value, capacity.value, steps.value, n.value
+
+    def torque_history(self) -> np.ndarray:
+        """The samples written so far, BODY_TORQUE_DTYPE of shape ``(samples, count, bodies)`` (a context: count = 1); sample
+        s belongs to step (s + 1) * every since torque_start.  Not consumed.  Synchronous."""
+        samples, _, _, n_bodies = self.torque_info()
+        out = np.zeros((samples, self._torque_rec[1], n_bodies), BODY_TORQUE_DTYPE)
+        capi.check(self._loads_call("torque_read")(self._h, 0, samples, self._torque_ptr(out), out.nbytes))
+        return out
+
+    def torque_history_xy(self, dx: float = 1.0, rho: float = 1.0) -> np.ndarray:
+        """:meth:`torque_history` as float64 ``(samples, count, bodies, 2)``, scaled as :meth:`torque_xy`."""
+        return self._torque_xy(self.torque_history(), self._torque_rec[0], dx, rho)
+
+    def torque_stop(self):
+        """Stop the torque recorder and free its samples."""
+        capi.check(self._loads_call("torque_stop")(self._h))
+
+
+class Solver(_Tracers, _History, _Loads, _Friction, _Torque, _Means):
     """One solver context: rows [row_begin, row_end) of a dim_x * dim_y domain on one device."""
 
     def __init__(self, dim_x: int, dim_y: int, device: int = 0, rank: int = 0, nranks: int = 1):
@@ -981,7 +1101,7 @@ class Solver(_Tracers, _History, _Loads, _Friction, _Means):
         return {"launches": a.value, "exchanges": b.value, "fuse": c.value, "halo": self.get_option(capi.OPT_LAST_HALO)}
 
 
-class BatchSolver(_Tracers, _History, _Loads, _Friction, _Means):
+class BatchSolver(_Tracers, _History, _Loads, _Friction, _Torque, _Means):
     """A batch (sfl_batch_*): `batch` independent whole-domain simulations of one dim_x * dim_y grid on one device,
     every member stepped by the same launch.  Member m holds, bit for bit, what a :class:`Solver` of the same shape
     holds after the same calls made with member m's data and forces.  Arrays of members are shaped

@@ -1442,7 +1442,8 @@ SFL_API int sfl_batch_openings_flux(sfl_batch *b, int first, int count, struct s
  * loads, friction.  With no friction recorder on, every call launches exactly what it launched before there was one.
  * sfl_batch_set_bodies / sfl_set_bodies are refused with SFL_ERR_STATE while the friction recorder is on, with a message of
  * their own: the layout of its samples depends on `bodies` too.
- *   Admission as everywhere: the argument checks and their order are those of the loads' calls, one for one.               */
+ *   Admission as everywhere: the argument checks and their order are those of the loads' calls, one for one.  (The moment
+ * of both forces about a pivot per body: "TORQUE", below.)                                                                  */
 struct sfl_body_friction {
     int64_t  fx, fy;
     int32_t  exp2;
@@ -1544,6 +1545,98 @@ SFL_API int sfl_batch_mean_stop(sfl_batch *b);
 SFL_API int sfl_batch_mean_sample(sfl_batch *b);
 SFL_API int sfl_batch_mean_info(sfl_batch *b, int *what, int *every, int64_t *samples, int64_t *steps);
 SFL_API int sfl_batch_mean_download(sfl_batch *b, int plane, int first_member, int members, void *host, size_t bytes);
+/* --- TORQUE: how hard the flow TURNS solid bodies -- the moment about z of the pressure load of "LOADS" and of the skin
+ *     friction of "FRICTION" on every body, about a pivot per body: as figures (sfl_batch_torque, sfl_torque) and as curves
+ *     recorded while stepping (sfl_batch_torque_start, sfl_torque_start), without a download.  It is the pitching moment of a
+ *     plate or a foil, with the loads the centre of pressure, and the torque that spins a disc.  The rule below is a definition
+ *     stated here, like the loads' and the friction's: the reference knows no bodies.  ONE walk over the faces reads both
+ *     fields.  The normal viscous stress has no part, as in "FRICTION"; the bodies are at rest.
+ *   FACES, BODIES AND LABELS are those of "LOADS", word for word: a wet face is a pair (fluid cell F, solid cell S) where S is
+ * one of F's four neighbours, S is INSIDE THE DOMAIN and S belongs to a body; the rim has no faces; labels and `bodies` come
+ * from sfl_batch_set_bodies / sfl_set_bodies; a label counts only where the cell is solid at the time of the sample.
+ *   AXES AND ARMS.  x grows with i (towards E) and y with j (towards N); the moment is about z, COUNTER-CLOCKWISE POSITIVE.  The
+ * wall lies at node S, as in "FRICTION": both the pressure and the shear of a face ACT AT NODE S = (iS, jS).  A body's PIVOT
+ * is given in HALF cell widths, int32_t pivot2[2]: the pivot is (pivot2[0] / 2, pivot2[1] / 2), so that the centre of a body
+ * of even width is exact.  Every component satisfies |pivot2| <= SFL_TORQUE_MAX_PIVOT2 = 2^24.  Without pivots every pivot is
+ * (0, 0).  The DOUBLED ARMS of a face are rx2 = 2 * iS - pivot2[0] and ry2 = 2 * jS - pivot2[1], in int32.
+ *   PER BODY, FROM PASS 1 over its wet faces:
+ *     max_abs_p   the load record's: the maximum of |p| over the finite pressures of the fluid cells of its faces;
+ *     max_abs_t   the friction record's: the maximum over the finite tangential components (v.y for a fluid cell W or E of
+ *                 its solid cell, v.x for one S or N of it);
+ *     faces       the number of ALL of its wet faces, non-finite ones included;
+ *     max_arm2    the maximum over its faces of max(|rx2|, |ry2|);
+ *     s           with L(x) the bit length of x (0 for 0): s = max(0, L(faces) + L(max_arm2) - 30);
+ *     exp2_p, exp2_f   q_p + s and q_f + s, where q_p and q_f are the exp2 of "LOADS" and of "FRICTION".
+ *   A FACE'S TERMS.  tp = (int64_t)trunc(ldexp((double)p, -exp2_p)), and tf the same from the tangential component with exp2_f;
+ * both satisfy |t| < 2^(33 - s).  A non-finite p (tangential component) takes that face out of mp (mf) and into nonfinite_p
+ * (nonfinite_t); the other sum still takes it.
+ *   THE SUMS, with dir as everywhere: the FLUID cell lies 0 = W, 1 = E, 2 = S, 3 = N of the solid one.
+ *     mp (pressure)   adds -ry2 * tp for dir 0, +ry2 * tp for dir 1, +rx2 * tp for dir 2 and -rx2 * tp for dir 3;
+ *     mf (friction)   adds +rx2 * tf for dir 0 and 1 (tf from v.y) and -ry2 * tf for dir 2 and 3 (tf from v.x).
+ * These are rx * Fy - ry * Fx with the signs of fx and fy of the two existing records.
+ *   NO OVERFLOW.  |arm| < 2^L(max_arm2) and |t| < 2^(33 - s), so a product is below 2^(33 - s + L(max_arm2)) and the sum of
+ * `faces` < 2^L(faces) of them satisfies |sum| < 2^(33 - s + L(max_arm2) + L(faces)) <= 2^63: for s = 0 because then
+ * L(faces) + L(max_arm2) <= 30, else because s makes up the difference exactly.  mp and mf never overflow.
+ *   UNITS.  The pressure torque is mp * 2^(exp2_p - 1) in pressure x cell widths^2 (the arms are doubled); the caller
+ * multiplies by dx^2.  The friction torque per unit depth is rho * nu * mf * 2^(exp2_f - 1) * dx.
+ *   IDENTITY WITH THE EXISTING RECORDS.  For every real body s = 0 -- s > 0 needs L(faces) + L(max_arm2) > 30, more than 2^14
+ * faces at arms beyond 2^16 half cells.  Then tp and tf ARE the terms of the load and of the friction record, and moving the
+ * pivot by (a2, b2) half cells changes mp by exactly -(a2 * fy - b2 * fx) of the load record, and mf in the same way with the
+ * friction record: the centre of pressure follows from the three records without a second sample.
+ *   A body without a face reports all zeros, and so does every body while no solids are set; in both cases pivot2 is still
+ * filled in.  Integer sums, maxima and counts do not depend on the order of reduction: every field of every record is, bit
+ * for bit, what the rule computes from the downloaded pressure, velocity, mask, labels and pivots, and a context and a batch
+ * member of the same shape, mask, labels, pivots and fields report the same bytes.
+ *   THE TORQUE RECORDER follows the loads recorder's rules unchanged, with a buffer, a step count and samples of its own:
+ * steps count across calls; sample s belongs to step (s + 1) * every; a step call without room for its samples is refused
+ * WHOLE with SFL_ERR_STATE before anything is staged or launched, with a message that names the torque recorder; a restart
+ * keeps the buffer; a batch's one-launch replay of a timeline and the fused seams of sfl_step_n are NOT cut (they only run
+ * without solids, where a sample reads no field).  It is independent of the history, of the loads recorder and of the
+ * friction recorder: any of the four may be on together, and behind a step the order is history, loads, friction, torque.
+ * With no torque recorder on, every call launches exactly what it launched before there was one.  sfl_batch_set_bodies /
+ * sfl_set_bodies are refused with SFL_ERR_STATE while the torque recorder is on, with a message of their own; a call of
+ * theirs that changes the number of bodies puts every pivot back to (0, 0).
+ *   Admission as everywhere: the argument checks and their order are those of the loads' calls, one for one; the state
+ * refusals follow; a slab and a context with a transport attached are refused as from sfl_loads.                            */
+#define SFL_TORQUE_MAX_PIVOT2 16777216
+struct sfl_body_torque {
+    int64_t  mp, mf;
+    int32_t  exp2_p, exp2_f;
+    float    max_abs_p, max_abs_t;
+    uint32_t faces, max_arm2;
+    uint32_t nonfinite_p, nonfinite_t;
+    int32_t  pivot2[2];
+    uint32_t reserved[2];
+};                                     /* 64 bytes: offsets 0, 8, 16, 20, 24, 28, 32, 36, 40, 44, 48, 56 */
+/* The pivots: pivot2 = bodies pairs (x2, y2) shared by all members (per_member 0) or batch * bodies pairs, member-major
+ * (per_member 1), the pair of body k of member m at pivot2[2 * (m * bodies + k - 1)]; read during the call only.  pivot2 NULL
+ * goes back to (0, 0) for every body (bodies and per_member are then not looked at).  `bodies` must equal what
+ * sfl_batch_bodies_info reports.  b NULL, per_member outside 0..1, another `bodies` and a component beyond
+ * SFL_TORQUE_MAX_PIVOT2 (the message names the body) return SFL_ERR_INVALID.  Allowed while a recorder is on: the new pivots
+ * hold from the next sample.  Batches of either kind.                                                                      */
+SFL_API int sfl_batch_set_body_pivots(sfl_batch *b, const int32_t *pivot2, int per_member, int bodies);
+/* The pivots of members [first, first + count), member-major (shared pivots: repeated; none set: zeros); bytes must be
+ * count * bodies * 8.                                                                                                       */
+SFL_API int sfl_batch_body_pivots_download(sfl_batch *b, int first, int count, int32_t *host, size_t bytes);
+/* The torque records of members [first, first + count) from the pressure and the velocity held: count * bodies records,
+ * member-major, as sfl_batch_loads; bytes must be count * bodies * 64.  One launch, synchronous; changes no field.  A batch
+ * without solids set reports records that are zero but for pivot2, without a launch.                                        */
+SFL_API int sfl_batch_torque(sfl_batch *b, int first, int count, struct sfl_body_torque *host, size_t bytes);
+/* The torque recorder of a batch: the calls of the loads recorder, one for one (sfl_batch_loads_start, _stop, _info, _read). */
+SFL_API int sfl_batch_torque_start(sfl_batch *b, int every, int first, int count, int capacity);
+SFL_API int sfl_batch_torque_stop(sfl_batch *b);
+SFL_API int sfl_batch_torque_info(sfl_batch *b, int *samples, int *capacity, int64_t *steps, int *bodies);
+SFL_API int sfl_batch_torque_read(sfl_batch *b, int first_sample, int samples, struct sfl_body_torque *host, size_t bytes);
+/* The same for a whole-domain context: `bodies` pairs, `bodies` records per sample.  A slab and a context with a transport
+ * attached get SFL_ERR_STATE, as from sfl_loads.  A sample is two streaming passes over the code bytes, pass 1 and then the
+ * sums, behind a memset of the sample's records, all on the context's stream.                                              */
+SFL_API int sfl_set_body_pivots(sfl_context *ctx, const int32_t *pivot2, int bodies);
+SFL_API int sfl_body_pivots_download(sfl_context *ctx, int32_t *host, size_t bytes);
+SFL_API int sfl_torque(sfl_context *ctx, struct sfl_body_torque *host, size_t bytes);
+SFL_API int sfl_torque_start(sfl_context *ctx, int every, int capacity);
+SFL_API int sfl_torque_stop(sfl_context *ctx);
+SFL_API int sfl_torque_info(sfl_context *ctx, int *samples, int *capacity, int64_t *steps, int *bodies);
+SFL_API int sfl_torque_read(sfl_context *ctx, int first_sample, int samples, struct sfl_body_torque *host, size_t bytes);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
