@@ -24,13 +24,29 @@ where one is held), diffuse_velocity is that function alone, a load is tests/loa
 and labels, compared as the raw bytes of its records, and the loads recorder counts as a history does and appends zero records
 while no mask is held.  The refusals the two features add -- set_bodies while the recorder is on, a batch's step_n_until while a
 viscosity is set, a step call that a full loads recorder has no room for, loads_history without a recorder -- are in the models
-and in the Gate, from the header."""
+and in the Gate, from the header.
+
+Four more subjects walk what came after.  Subject(records=True), on top of the viscous deck: the friction and the torque recorder
+count as the loads recorder does, each for itself, and sample tests/friction_rule.py and tests/torque_rule.py behind the loads
+(zero records without a mask, the torque's but for pivot2); the pivots follow the number of bodies; the averages add
+tests/mean_rule.py's terms behind the torque's sample, count only while every >= 1, have no capacity and never refuse a step call;
+float64 planes are compared as their uint64 bit patterns.  Subject(opens=True), on top of the solids' deck: while a map is set a
+step is tests/inflow_rule.py's (item 2a behind the forces, items 4 to 6 of tests/opening_rule.py), the operators of a context
+follow items 4, 5, 5 and 6 and never impose the inflow, and the whole-domain queries use the openings' divergence and update
+norm; the flux is compared as the raw bytes of its record.  A refusal carries its code: SFL_ERR_STATE, or SFL_ERR_INVALID for a
+profile record off the inflow cells, pivots of another number of bodies and a plane outside `what` (csrc/means.cpp download():
+"plane %d belongs to group %u, which is not in the mask")."""
 import ctypes
 
 import numpy as np
 
+import friction_rule
+import inflow_rule
 import load_rule
+import mean_rule
+import opening_rule
 import solid_rule
+import torque_rule
 import tracer_rule
 import view_rule
 import viscosity_rule
@@ -79,7 +95,14 @@ SOLID_QUERIES = ("solids", "history")
 VISCOUS_WRITERS = ("set_viscosity", "clear_viscosity", "diffuse_velocity", "set_bodies", "clear_bodies", "loads_start", "loads_stop")
 VISCOUS_QUERIES = ("viscosity", "bodies", "loads", "loads_history")
 BATCH_VISCOUS_WRITERS = tuple(k for k in VISCOUS_WRITERS if k != "diffuse_velocity")      # (a batch has no operator of its own)
-QUERIES = set(CONTEXT_QUERIES) | set(BATCH_QUERIES) | set(SOLID_QUERIES) | set(VISCOUS_QUERIES)
+# the friction's, the torque's and the averages' calls, dealt only to the subjects made with record=True (on top of the viscous deck)
+RECORD_WRITERS = ("friction_start", "friction_stop", "torque_start", "torque_stop", "set_body_pivots", "mean_start", "mean_stop", "mean_sample")
+RECORD_QUERIES = ("friction", "friction_history", "torque", "torque_history", "body_pivots", "mean_info", "mean_sums")
+# the openings', the profiles' and the flux's calls, dealt only to the subjects made with opens=True (on top of the solids' deck;
+# set_viscosity and clear_viscosity are there to plant the refusals: openings and a viscosity refuse each other)
+OPEN_WRITERS = ("set_openings", "clear_openings", "set_inflow", "set_inflow_profile", "set_viscosity", "clear_viscosity")
+OPEN_QUERIES = ("openings", "inflow_profile", "openings_flux")
+QUERIES = set(CONTEXT_QUERIES) | set(BATCH_QUERIES) | set(SOLID_QUERIES) | set(VISCOUS_QUERIES) | set(RECORD_QUERIES) | set(OPEN_QUERIES)
 NUS, CONTEXT_SWEEPS, BATCH_SWEEPS = (0.0, 0.05, 0.3, 2.5), (0, 1, 3, 8, 9, 17), (0, 1, 3, 10)
 D_DIFFUSE = 8                                           # sweeps of one launch of a context's diffusion (kD of csrc/diffuse_tile.h)
 LABEL_KINDS = {"all one": 1, "halves": 2, "with zeros": 3, "sixteen": 16}     # kind -> bodies
@@ -89,7 +112,15 @@ SOLID_LEFT_OUT = ("queue_drags", "trail_stop", "last_solve_info")
 MASK_KINDS = ("one", "disc", "plate", "channel", "isolated", "all", "seeded", "empty")     # mask_of of tests/test_solids_gpu.py
 MIXED_KINDS = tuple(k for k in MASK_KINDS if k not in ("all", "empty"))                     # at least one solid and one fluid cell
 ERR_STATE, VIEW_DIVERGENCE, D_SOLID = -5, 3, 8      # SFL_ERR_STATE; SFL_VIEW_DIVERGENCE; iterations of one launch of the masked solve
+ERR_INVALID = -1                                    # SFL_ERR_INVALID: a profile record off the inflow cells, pivots of another `bodies`, a plane outside `what`
 REFUSED = {"refused": np.int32(ERR_STATE)}
+
+
+def refusal(code):
+    """What a refused call returns: refuses() of a model says True (SFL_ERR_STATE) or the code itself."""
+    return {"refused": np.int32(ERR_STATE if code is True else code)}
+
+
 # struct sfl_history_record (HISTORY_DTYPE of the package): field -> dtype
 HISTORY_FIELDS = {"max_abs_vx": np.float32, "max_abs_vy": np.float32, "max_abs_div": np.float32, "what": np.uint32, "dye_sum": np.uint64,
                   "update_norm": np.float32, "iterations": np.int32, "step": np.int64, "dt": np.float32, "dx": np.float32}
@@ -125,6 +156,73 @@ def load_bytes(records):
     return records.view(np.uint8).reshape(records.shape + (LOAD_BYTES,))
 
 
+def raw_bytes(records):
+    """Records of any of the structs (48, 64 or 40 bytes each) as their raw bytes, uint8[..., itemsize]."""
+    records = np.asarray(records)
+    return np.ascontiguousarray(records).reshape(-1).view(np.uint8).reshape(records.shape + (records.dtype.itemsize,))
+
+
+PIVOT_KINDS = ("centre", "seeded")
+MEAN_WHATS = (1, 2, 4, 8, 3, 6, 9, 12, 7, 15)          # masks of one group, of several and of all four
+OPEN_KINDS = ("channel", "inflow only", "outflow only", "every rim cell", "seeded", "single inflow", "none")
+LIVE_OPEN_KINDS = ("channel", "every rim cell", "seeded")       # an inflow and an outflow cell, whatever the seed
+INFLOWS = ((12.5, 0.0), (-3.0, 2.5), (0.0, 0.0), (40.0, -7.25))   # the uniform inflow velocities the generator draws from
+FLUX_BYTES = inflow_rule.FLUX_DTYPE.itemsize            # struct sfl_open_flux
+
+
+def body_pivots_of(kind, bodies, dim_x, dim_y, seed, member=None):
+    """The pivots a set_body_pivots op sets, int32[bodies, 2] in HALF cells, none of them (0, 0): the centre of the grid (a half
+    cell where the side is even) or seeded ones, inside the grid and outside it, odd and negative.  Per member: its own."""
+    k = member or 0
+    if kind == "centre":
+        return np.tile(np.array([dim_x - 1 + 2 * k, dim_y - 1], np.int32), (bodies, 1))
+    p = np.random.default_rng([seed, k, 9]).integers(-2 * dim_x, 4 * dim_x, (bodies, 2))
+    p[(p == 0).all(axis=1)] = (1, -3)
+    return p.astype(np.int32)
+
+
+def open_map(kind, dim_x, dim_y, seed, member=None):
+    """The map a set_openings op sets, uint8[dim_y, dim_x] of 0, INFLOW and OUTFLOW, nonzero only on rim cells that are no corners:
+    a channel (the W rim in, the E rim out), inflow only (the incompatible Neumann problem), outflow only (the E and the N rim),
+    every non-corner rim cell open with the bytes alternating, a seeded third of the rim cells each way, one inflow cell in the
+    middle of the W rim, and no opening at all (the solids' bits).  Per member: member k takes the k-th kind behind `kind` and
+    its own seed."""
+    if member is not None:
+        kind, seed = OPEN_KINDS[(OPEN_KINDS.index(kind) + member) % len(OPEN_KINDS)], seed + member
+    m = np.zeros((dim_y, dim_x), np.uint8)
+    j, i = np.mgrid[0:dim_y, 0:dim_x]
+    rim = ((i == 0).astype(int) + (i == dim_x - 1) + (j == 0) + (j == dim_y - 1)) == 1
+    if kind == "channel":
+        m[rim & (i == 0)], m[rim & (i == dim_x - 1)] = opening_rule.INFLOW, opening_rule.OUTFLOW
+    elif kind == "inflow only":
+        m[rim & (i == 0)] = opening_rule.INFLOW
+    elif kind == "outflow only":
+        m[rim & ((i == dim_x - 1) | (j == dim_y - 1))] = opening_rule.OUTFLOW
+    elif kind == "every rim cell":
+        m[rim] = (1 + (i + j + seed) % 2)[rim]
+    elif kind == "seeded":
+        m[rim] = np.random.default_rng([seed, 17]).integers(0, 3, int(rim.sum()))
+        m[dim_y // 2, 0], m[dim_y // 2, dim_x - 1] = opening_rule.INFLOW, opening_rule.OUTFLOW      # (never without a cell of each kind)
+    elif kind == "single inflow":
+        m[dim_y // 2, 0] = opening_rule.INFLOW
+    else:
+        assert kind == "none"
+    assert opening_rule.check_map(m) is None
+    return m
+
+
+def live_cells(open, mask):
+    """(live inflow cells, live outflow cells) of one grid: an opening counts only where the cell is fluid."""
+    fluid = np.ones(open.shape, bool) if mask is None else ~mask
+    return int(((open == opening_rule.INFLOW) & fluid).sum()), int(((open == opening_rule.OUTFLOW) & fluid).sum())
+
+
+def profile_arrays(profile):
+    """The records held as inflow_profile returns them: cells int32[n, 2] (i, j) and vel float32[n, 2], in cell-index order."""
+    rows = inflow_rule.unique(profile or [])
+    return (np.array([c for c, _ in rows], np.int32).reshape(-1, 2), np.array([uv for _, uv in rows], np.float32).reshape(-1, 2))
+
+
 def launches_of(nu, sweeps):
     """The launches of a context's diffusion: none where it is skipped, else ceil(sweeps / 8)."""
     return 0 if np.float32(nu) == 0 or sweeps == 0 else -(-sweeps // D_DIFFUSE)
@@ -145,6 +243,19 @@ def masked_rule(d, solid, dx, cap, omega, tol, every):
         p = solid_rule.iterate(p, d, solid, dx, 1, omega)
         k += 1
     return k, p, np.float32(solid_rule.update_norm(p, d, solid, dx))
+
+
+def open_rule_until(d, solid, open, dx, cap, omega, tol, every):
+    """masked_rule with the openings' iterations and their update norm (the k of item 5 of "OPENINGS")."""
+    tol, p, k = np.float32(tol), np.zeros_like(d), 0
+    while k < cap:
+        if k % every == 0:
+            u = np.float32(opening_rule.update_norm(p, d, solid, open, dx))
+            if tol >= 0 and (u <= tol or np.isnan(u)):
+                return k, p, u
+        p = opening_rule.iterate(p, d, solid, open, dx, 1, omega)
+        k += 1
+    return k, p, np.float32(opening_rule.update_norm(p, d, solid, open, dx))
 
 
 def samples_due(hist, n):
@@ -188,6 +299,12 @@ def compare(got, want, what):
         g, w = np.asarray(got[name]), np.asarray(want[name])
         if w.dtype in (np.float32, np.uint32):
             assert_bit_equal(np.ascontiguousarray(g, w.dtype), np.ascontiguousarray(w), f"{what}: {name}")
+        elif w.dtype == np.float64:          # as the uint64 bit patterns: a NaN equals itself, +0.0 is not -0.0; no cast on either side
+            assert g.dtype == np.float64 and g.shape == w.shape, f"{what}: {name}: got {g.dtype}{g.shape}, want float64{w.shape}"
+            gb, wb = np.ascontiguousarray(g).view(np.uint64), np.ascontiguousarray(w).view(np.uint64)
+            bad = np.argwhere(gb != wb)
+            assert not len(bad), (f"{what}: {name}: {len(bad)} of {gb.size} doubles differ bitwise; first at {tuple(bad[0])}: got {g[tuple(bad[0])]!r} "
+                                  f"(0x{int(gb[tuple(bad[0])]):016x}) want {w[tuple(bad[0])]!r} (0x{int(wb[tuple(bad[0])]):016x})")
         else:
             assert g.shape == w.shape and np.array_equal(g, w.astype(g.dtype)), f"{what}: {name}: got {g!r}, want {w!r}"
 
@@ -230,28 +347,57 @@ class ContextModel:
         self.visc = None                         # the viscosity: None or (nu, sweeps) with nu > 0 and sweeps > 0
         self.labels, self.bodies = None, 1       # the bodies: None (every solid cell is body 1) or uint8[dim_y, dim_x]
         self.loads = None                        # the loads recorder: {"every", "capacity", "steps", "records"}
+        self.records = False                     # (the friction's, the torque's and the averages' queries are among those of queries())
+        self.pivots = None                       # the pivots: None (every pivot (0, 0)) or int32[bodies, 2] in half cells
+        self.friction = self.torque = None       # the friction and the torque recorder, each as the loads recorder
+        self.means = None                        # the averages: {"what", "every", "steps", "samples", "sums": {plane: [1, dim_y, dim_x]}}
+        self.opens = False                       # (the openings' queries are among those of queries())
+        self.open = None                         # the openings: None or uint8[dim_y, dim_x]
+        self.inflow = (0.0, 0.0)                 # the uniform inflow velocity
+        self.profile = None                      # the inflow profile: None or [((i, j), (u, v))] as given, the later record wins
 
     # -- plumbing
     def apply(self, op):
         kind, args = op
         self.reach = 0.0
-        if self.refuses(kind, args):             # refused whole: nothing changes
-            return dict(REFUSED)
+        code = self.refuses(kind, args)
+        if code:                                 # refused whole: nothing changes
+            return refusal(code)
         return getattr(self, ("q_" if kind in QUERIES else "do_") + kind)(**args)
 
     def refuses(self, kind, a):
-        """Whether include/sfl.h refuses the call with SFL_ERR_STATE in the state the model is in."""
-        if self.mask is not None and kind in ("view_scalar", "view_texels") and a["what"] == VIEW_DIVERGENCE:
+        """Whether include/sfl.h refuses the call in the state the model is in: False, True for SFL_ERR_STATE, or the code
+        itself where it is another (ERR_INVALID: the records of a profile against the map, pivots of another `bodies`, a plane
+        outside `what`; the library checks those behind the state)."""
+        if (self.mask is not None or self.open is not None) and kind in ("view_scalar", "view_texels") and a["what"] == VIEW_DIVERGENCE:
             return True
-        if kind in ("set_bodies", "clear_bodies") and self.loads is not None:
+        if kind in ("set_bodies", "clear_bodies") and not (self.loads is None and self.friction is None and self.torque is None):
             return True
-        if kind == "loads_history" and self.loads is None:
+        if kind in ("loads_history", "friction_history", "torque_history") and getattr(self, kind[:-len("_history")]) is None:
             return True
-        for recorder in (self.hist, self.loads):
+        for recorder in (self.hist, self.loads, self.friction, self.torque):       # (the averages have no capacity: they never refuse)
             if recorder is not None and kind in ("step", "step_n"):
                 due, free = samples_due(recorder, a.get("n", 1))
                 if due > free:
                     return True
+        if kind == "set_body_pivots" and a["pivot_kind"] is not None and a["bodies"] != self.bodies:
+            return ERR_INVALID
+        if kind in ("mean_sample", "mean_sums") and self.means is None:
+            return True
+        if kind == "mean_sums" and not self.means["what"] & mean_rule.GROUP_OF[a["plane"]]:
+            return ERR_INVALID                   # csrc/means.cpp download(): "plane %d belongs to group %u, which is not in the mask"
+        # "OPENINGS OF A CONTEXT": openings and a viscosity refuse each other; without openings no inflow and no profile
+        if kind == "set_openings" and self.visc is not None:
+            return True
+        if kind == "set_viscosity" and self.open is not None and not (np.float32(a["nu"]) == 0 or a["sweeps"] == 0):
+            return True
+        if kind == "set_inflow" and self.open is None:
+            return True
+        if kind == "set_inflow_profile" and a["cells"]:
+            if self.open is None:
+                return True
+            if inflow_rule.check_profile(list(zip(map(tuple, a["cells"]), a["vels"])), self.open) is not None:
+                return ERR_INVALID
         return False
 
     def close(self):
@@ -291,10 +437,16 @@ class ContextModel:
             if 0 <= i < self.dim_x and 0 <= j < self.dim_y:
                 va[j, i] = u
         k, u = iters, None
+        if self.open is not None:                # item 2a of "OPENINGS" and of "INFLOW PROFILES": behind the forces, on the fluid inflow cells
+            inflow_rule.impose(va, self.mask, self.open, self.inflow, self.profile or [])
         if self.mask is not None:                # items 3 to 6 of "SOLIDS"; the records above stand between items 1 and 3
             va[self.mask] = 0.0
         va = self._diffuse(va, dt, dx)           # item 3a of "VISCOSITY": between the forces (the solids zeroed) and the divergence
-        if self.mask is not None:
+        if self.open is not None:                # items 4 to 6 of "OPENINGS", with and without a mask (no viscosity and no _until under a map)
+            self.d = opening_rule.divergence(va, self.mask, self.open, dx)
+            self.p = opening_rule.solve(self.d, self.mask, self.open, dx, k, omega)
+            self.v = np.ascontiguousarray(opening_rule.gradient(va, self.p, self.mask, self.open, dx))
+        elif self.mask is not None:
             self.d = solid_rule.divergence(va, self.mask, dx)
             if until is not None:
                 k, _, u = masked_rule(self.d, self.mask, dx, iters, omega, until[0], until[1])
@@ -336,19 +488,27 @@ class ContextModel:
     def do_advect_color(self, dt, no_slip):
         self.c = self._advect(self.c, dt, no_slip)
 
+    # The operators of a context under a map follow items 4, 5, 5 and 6 of "OPENINGS" and never impose the inflow.
     def do_calculate_divergence(self, dx):
-        if self.mask is not None:                # 0 in solid cells; the velocity is not touched
+        if self.open is not None:
+            self.d = opening_rule.divergence(self.v, self.mask, self.open, dx)
+        elif self.mask is not None:              # 0 in solid cells; the velocity is not touched
             self.d = solid_rule.divergence(self.v, self.mask, dx)
         else:
             self.d = self.o.divergence(self.v, dx)
 
     def do_poisson_solve(self, dx, iters, omega):
-        if self.mask is not None:                # from p = 0
+        if self.open is not None:
+            self.p = opening_rule.solve(self.d, self.mask, self.open, dx, iters, omega)
+        elif self.mask is not None:              # from p = 0
             self.p = solid_rule.solve(self.d, self.mask, dx, iters, omega)
         else:
             self.p = self.o.poisson_solve(self.d, dx, iters, omega)
 
     def do_poisson_continue(self, dx, iters, omega):
+        if self.open is not None:
+            self.p = opening_rule.iterate(self.p, self.d, self.mask, self.open, dx, iters, omega)
+            return
         if self.mask is not None:                # solid cells keep what they hold
             self.p = solid_rule.iterate(self.p, self.d, self.mask, dx, iters, omega)
             return
@@ -356,7 +516,10 @@ class ContextModel:
             self.p = sor_iteration(self.p, self.d, dx, omega)
 
     def do_poisson_solve_until(self, dx, iters, omega, tol, every):
-        if self.mask is not None:
+        if self.open is not None:
+            k, _, u = open_rule_until(self.d, self.mask, self.open, dx, iters, omega, tol, every)
+            self.p = opening_rule.solve(self.d, self.mask, self.open, dx, k, omega)
+        elif self.mask is not None:
             k, _, u = masked_rule(self.d, self.mask, dx, iters, omega, tol, every)
             self.p = solid_rule.solve(self.d, self.mask, dx, k, omega)
         else:
@@ -365,7 +528,9 @@ class ContextModel:
         return as_result(iterations=np.int32(k), norm=np.float32(u))
 
     def do_subtract_gradient(self, dx):
-        if self.mask is not None:                # (0, 0) in solid cells
+        if self.open is not None:
+            self.v = np.ascontiguousarray(opening_rule.gradient(self.v, self.p, self.mask, self.open, dx))
+        elif self.mask is not None:              # (0, 0) in solid cells
             self.v = np.ascontiguousarray(solid_rule.gradient(self.v, self.p, self.mask, dx))
         else:
             self.v = self.o.subtract_gradient(self.v, self.p, dx)
@@ -386,6 +551,42 @@ class ContextModel:
             self.loads["steps"] += 1
             if self.loads["steps"] % self.loads["every"] == 0:
                 self.loads["records"].append(self.load_records()[None])
+        # behind a step the order is history, loads, friction, torque, averages; every recorder counts for itself
+        for recorder, records_of in ((self.friction, self.friction_records), (self.torque, self.torque_records)):
+            if recorder is not None:
+                recorder["steps"] += 1
+                if recorder["steps"] % recorder["every"] == 0:
+                    recorder["records"].append(records_of()[None])
+        self.mean_step()
+
+    def friction_records(self):
+        """The `bodies` records of "FRICTION" from the velocity, the mask and the labels held; zeros while no mask is."""
+        if self.mask is None:
+            return np.zeros(self.bodies, friction_rule.DTYPE)
+        return friction_rule.friction(self.v, self.mask, self.labels, self.bodies)
+
+    def torque_records(self):
+        """The `bodies` records of "TORQUE" about the pivots held; zeros but for pivot2 while no mask is."""
+        if self.mask is None:
+            out = np.zeros(self.bodies, torque_rule.DTYPE)
+            if self.pivots is not None:
+                out["pivot2"] = self.pivots
+            return out
+        return torque_rule.torque(self.p, self.v, self.mask, self.labels, self.bodies, self.pivots)
+
+    def mean_step(self):
+        """"AVERAGES": with every >= 1 steps count across calls and a sample is due behind step (s + 1) * every; with every == 0
+        no hook is set and nothing counts."""
+        m = self.means
+        if m is not None and m["every"] >= 1:
+            m["steps"] += 1
+            if m["steps"] % m["every"] == 0:
+                self.mean_add()
+
+    def mean_add(self):
+        m = self.means
+        mean_rule.add(m["sums"], m["what"], self.v[None], self.p[None], self.c[None])
+        m["samples"] += 1
 
     def do_step(self, dt, dx, iters, omega):
         self._counted_step(dt, dx, iters, omega)
@@ -419,17 +620,61 @@ class ContextModel:
 
     # "LOADS": labels and masks are independent of each other; a restart of the recorder starts afresh
     def do_set_bodies(self, label_kind, bodies, seed):
+        before = self.bodies
         self.labels = body_labels(label_kind, self.dim_x, self.dim_y, seed)
         self.bodies = 1 if self.labels is None else bodies
+        if self.bodies != before:                # "TORQUE": the pivots are per body; the same number keeps them
+            self.pivots = None
 
     def do_clear_bodies(self):
-        self.labels, self.bodies = None, 1
+        self.do_set_bodies("all one", 1, 0)
 
     def do_loads_start(self, every, capacity):
         self.loads = {"every": every, "capacity": capacity, "steps": 0, "records": []}
 
     def do_loads_stop(self):
         self.loads = None
+
+    # "FRICTION", "TORQUE": recorders of their own beside the loads'; a restart starts afresh.  A set_bodies that changes the
+    # number of bodies puts every pivot back to (0, 0) (do_set_bodies below goes through _bodies_changed).
+    def do_friction_start(self, every, capacity):
+        self.friction = {"every": every, "capacity": capacity, "steps": 0, "records": []}
+
+    def do_friction_stop(self):
+        self.friction = None
+
+    def do_torque_start(self, every, capacity):
+        self.torque = {"every": every, "capacity": capacity, "steps": 0, "records": []}
+
+    def do_torque_stop(self):
+        self.torque = None
+
+    def do_set_body_pivots(self, pivot_kind, bodies, seed):
+        self.pivots = None if pivot_kind is None else body_pivots_of(pivot_kind, bodies, self.dim_x, self.dim_y, seed)
+
+    # "AVERAGES": a start while on begins anew from zero; a sample adds the fields held, every cell as it is
+    def do_mean_start(self, what, every):
+        self.means = {"what": what, "every": every, "steps": 0, "samples": 0, "sums": mean_rule.start(what, (1, self.dim_y, self.dim_x))}
+
+    def do_mean_stop(self):
+        self.means = None
+
+    def do_mean_sample(self):
+        self.mean_add()
+
+    # "OPENINGS OF A CONTEXT", "INFLOW PROFILES AND FLUX": no field is touched; a new map drops the profile, a new uniform inflow
+    # keeps it, a cleared map takes the profile with it; a record on a solid inflow cell is kept (step_once looks at the mask held)
+    def do_set_openings(self, open_kind, seed, inflow):
+        self.open, self.inflow, self.profile = open_map(open_kind, self.dim_x, self.dim_y, seed), tuple(inflow), None
+
+    def do_clear_openings(self):
+        self.open, self.inflow, self.profile = None, (0.0, 0.0), None
+
+    def do_set_inflow(self, inflow):
+        self.inflow = tuple(inflow)
+
+    def do_set_inflow_profile(self, cells, vels):
+        self.profile = [(tuple(c), tuple(u)) for c, u in zip(cells, vels)] or None
 
     # The timeline rule of include/sfl.h: "A step call of n steps consumes the records of steps [0, n).  Later records move down
     # by n.  This applies to sfl_step (n = 1), sfl_step_n, ..." and "Solves, uploads, setup and render calls neither consume nor
@@ -463,13 +708,18 @@ class ContextModel:
         return as_result(field=self.fields()[FIELDS[field]])
 
     def q_residual(self, dx):
+        if self.open is not None:                # the whole-domain queries use the openings' update norm and divergence while a map is set
+            return as_result(norm=np.float32(opening_rule.update_norm(self.p, self.d, self.mask, self.open, dx)))
         if self.mask is not None:                # over the fluid cells; 0.0f without one
             return as_result(norm=np.float32(solid_rule.update_norm(self.p, self.d, self.mask, dx)))
         return as_result(norm=np.float32(update_norm(self.p, self.d, dx)))
 
     def q_flow_stats(self, dx):
         out = stats_record(self.o, self.v, self.c, dx)
-        if self.mask is not None:
+        if self.open is not None:
+            with np.errstate(all="ignore"):
+                out["max_abs_div"] = np.asarray(np.max(np.abs(opening_rule.divergence(self.v, self.mask, self.open, dx))))
+        elif self.mask is not None:
             with np.errstate(all="ignore"):
                 out["max_abs_div"] = np.asarray(np.max(np.abs(solid_rule.divergence(self.v, self.mask, dx))))
         return out
@@ -496,6 +746,48 @@ class ContextModel:
         recs = self.loads["records"]
         stacked = np.stack(recs) if recs else np.zeros((0, 1, self.bodies), load_rule.DTYPE)
         return as_result(records=load_bytes(stacked), info=np.array([len(recs), self.loads["capacity"], self.loads["steps"], self.bodies], np.int64))
+
+    def _recorded(self, recorder, dtype):
+        recs = recorder["records"]
+        stacked = np.stack(recs) if recs else np.zeros((0, 1, self.bodies), dtype)
+        return as_result(records=raw_bytes(stacked), info=np.array([len(recs), recorder["capacity"], recorder["steps"], self.bodies], np.int64))
+
+    def q_friction(self):
+        return as_result(records=raw_bytes(self.friction_records()[None]))
+
+    def q_friction_history(self):
+        return self._recorded(self.friction, friction_rule.DTYPE)
+
+    def q_torque(self):
+        return as_result(records=raw_bytes(self.torque_records()[None]))
+
+    def q_torque_history(self):
+        return self._recorded(self.torque, torque_rule.DTYPE)
+
+    def q_body_pivots(self):
+        return as_result(pivot2=np.zeros((self.bodies, 2), np.int32) if self.pivots is None else self.pivots)
+
+    def q_mean_info(self):
+        m = self.means
+        return as_result(info=np.array([0, 0, 0, 0] if m is None else [m["what"], m["every"], m["samples"], m["steps"]], np.int64))
+
+    def q_mean_sums(self, plane):
+        return as_result(plane=self.means["sums"][plane].copy())
+
+    def q_openings(self):
+        on = self.open is not None
+        live = live_cells(self.open, self.mask) if on else (0, 0)
+        return as_result(map=self.open if on else np.zeros((self.dim_y, self.dim_x), np.uint8), inflow=np.array(self.inflow, np.float32), set=on,
+                         live=np.array(live, np.int64))
+
+    def q_inflow_profile(self):
+        cells, vel = profile_arrays(self.profile)
+        return as_result(cells=cells, vel=vel)
+
+    def q_openings_flux(self):
+        if self.open is None:
+            return as_result(record=np.zeros(FLUX_BYTES, np.uint8))
+        return as_result(record=raw_bytes(inflow_rule.flux(self.v, self.open, self.mask)))
 
     def q_view_scalar(self, what, dx):
         return as_result(scalar=view_rule.scalar(what, self.v, self.p, dx))
@@ -548,6 +840,17 @@ class ContextModel:
             out += [("viscosity", {}), ("bodies", {}), ("loads", {})]
             if self.loads is not None:
                 out.append(("loads_history", {}))
+        if self.records:
+            out += [("friction", {}), ("torque", {}), ("body_pivots", {}), ("mean_info", {})]
+            if self.friction is not None:
+                out.append(("friction_history", {}))
+            if self.torque is not None:
+                out.append(("torque_history", {}))
+            if self.means is not None:
+                planes = mean_rule.planes_of(self.means["what"])
+                out.append(("mean_sums", {"plane": int(planes[int(rng.integers(len(planes)))])}))
+        if self.opens:
+            out += [("openings", {}), ("inflow_profile", {}), ("openings_flux", {})]
         return out
 
 
@@ -571,12 +874,23 @@ class BatchModel:
         self.visc = None                         # the viscosity: {"nu": [one per member], "sweeps", "per_member"}; the members hold (nu, sweeps)
         self.bodies, self.labels_per_member = 1, False     # the bodies: every member's model holds its labels (or None)
         self.loads = None                        # the loads recorder: {"every", "first", "count", "capacity", "steps", "records"}
+        self.records = False                     # (the friction's, the torque's and the averages' queries are among those of queries())
+        self.pivots_per_member = False           # the pivots: every member's model holds its own (or None)
+        self.friction = self.torque = None       # the friction and the torque recorder, each as the loads recorder
+        self.means = None                        # the averages: {"what", "every", "first", "count", "steps", "samples", "sums": {plane: [count, dim_y, dim_x]}}
+        self.opens = False                       # (the openings' queries are among those of queries())
+        self.open_per_member = self.inflow_per_member = False      # the openings: every member's model holds its map and its inflow
+        self.profile_set = False                 # the profile: every member's model holds its records
 
     def apply(self, op):
         kind, args = op
-        if self.refuses(kind, args):             # refused whole: nothing changes
-            return dict(REFUSED)
+        code = self.refuses(kind, args)
+        if code:                                 # refused whole: nothing changes
+            return refusal(code)
         return getattr(self, ("q_" if kind in QUERIES else "do_") + kind)(**args)
+
+    def openings_set(self):
+        return self.m[0].open is not None
 
     def solids_set(self):
         return self.m[0].mask is not None
@@ -592,15 +906,41 @@ class BatchModel:
             return True
         if kind == "step_n_until" and self.visc is not None:      # "VISCOSITY": refused while one is set, whatever its nu
             return True
-        if kind in ("set_bodies", "clear_bodies") and self.loads is not None:
+        if kind in ("set_bodies", "clear_bodies") and not (self.loads is None and self.friction is None and self.torque is None):
             return True
-        if kind == "loads_history" and self.loads is None:
+        if kind in ("loads_history", "friction_history", "torque_history") and getattr(self, kind[:-len("_history")]) is None:
             return True
-        for recorder in (self.hist, self.loads):
+        # "OPENINGS": what a batch refuses while a map is set, and what refuses the map
+        if self.openings_set():
+            if kind in ("step_n_until", "poisson_solve_until", "history_start", "set_viscosity"):
+                return True
+            if kind in ("record_view", "view_render_members") and a["what"] == VIEW_DIVERGENCE:
+                return True
+        if kind == "set_openings" and (self.hist is not None or (self.rec is not None and self.rec["view"] == VIEW_DIVERGENCE) or self.visc is not None):
+            return True
+        for recorder in (self.hist, self.loads, self.friction, self.torque):       # (the averages have no capacity: they never refuse)
             if recorder is not None and kind in ("step_n", "step_n_each", "step_n_until"):
                 due, free = samples_due(recorder, a["n"])
                 if due > free:
                     return True
+        if kind == "set_body_pivots" and a["pivot_kind"] is not None and a["bodies"] != self.bodies:
+            return ERR_INVALID
+        if kind in ("mean_sample", "mean_sums") and self.means is None:
+            return True
+        if kind == "mean_sums":
+            if not self.means["what"] & mean_rule.GROUP_OF[a["plane"]]:
+                return ERR_INVALID               # csrc/means.cpp download(): a plane outside `what`, then a range outside the recorded one
+            if a["first"] < self.means["first"] or a["first"] + a["count"] > self.means["first"] + self.means["count"]:
+                return ERR_INVALID
+        if kind == "set_inflow" and not self.openings_set():
+            return True
+        if kind == "set_inflow_profile" and a["cells"]:
+            if not self.openings_set():
+                return True
+            for k, (cell, u) in enumerate(zip(a["cells"], a["vels"])):      # INFLOW in the map of every member the record applies to
+                for m in (self.m if a["members"] is None else [self.m[a["members"][k]]]):
+                    if inflow_rule.check_profile([(tuple(cell), u)], m.open) is not None:
+                        return ERR_INVALID
         return False
 
     def close(self):
@@ -653,10 +993,35 @@ class BatchModel:
                 l["steps"] += 1
                 if l["steps"] % l["every"] == 0:
                     l["records"].append(self._load_records(l["first"], l["count"]))
+            for r, records_of in ((self.friction, self._friction_records), (self.torque, self._torque_records)):
+                if r is not None:            # behind a step the order is history, loads, friction, torque, averages
+                    r["steps"] += 1
+                    if r["steps"] % r["every"] == 0:
+                        r["records"].append(records_of(r["first"], r["count"]))
+            self.mean_step()
         return dx, np.stack([last, total], axis=1)
 
     def _load_records(self, first, count):
         return np.stack([m.load_records() for m in self.m[first:first + count]])
+
+    def _friction_records(self, first, count):
+        return np.stack([m.friction_records() for m in self.m[first:first + count]])
+
+    def _torque_records(self, first, count):
+        return np.stack([m.torque_records() for m in self.m[first:first + count]])
+
+    def mean_step(self):
+        m = self.means
+        if m is not None and m["every"] >= 1:
+            m["steps"] += 1
+            if m["steps"] % m["every"] == 0:
+                self.mean_add()
+
+    def mean_add(self):
+        m = self.means
+        mine = self.m[m["first"]:m["first"] + m["count"]]
+        mean_rule.add(m["sums"], m["what"], np.stack([x.v for x in mine]), np.stack([x.p for x in mine]), np.stack([x.c for x in mine]))
+        m["samples"] += 1
 
     def _norms(self, dx):                        # (a member with a mask: over its fluid cells)
         self.norms = np.array([m.q_residual(dx[k])["norm"] for k, m in enumerate(self.m)], np.float32)
@@ -749,10 +1114,65 @@ class BatchModel:
             m.visc = None
 
     def do_set_bodies(self, label_kind, bodies, seed, per_member):
+        before = self.bodies
         for k, m in enumerate(self.m):
             m.labels = body_labels(label_kind, self.dim_x, self.dim_y, seed, k if per_member else None)
             m.bodies = 1 if m.labels is None else bodies
         self.bodies, self.labels_per_member = self.m[0].bodies, bool(per_member) and self.m[0].labels is not None
+        if self.bodies != before:                # "TORQUE": another number of bodies puts every pivot back to (0, 0)
+            self.pivots_per_member = False
+            for m in self.m:
+                m.pivots = None
+
+    def do_friction_start(self, every, capacity, first, count):
+        self.friction = {"every": every, "first": first, "count": count, "capacity": capacity, "steps": 0, "records": []}
+
+    def do_friction_stop(self):
+        self.friction = None
+
+    def do_torque_start(self, every, capacity, first, count):
+        self.torque = {"every": every, "first": first, "count": count, "capacity": capacity, "steps": 0, "records": []}
+
+    def do_torque_stop(self):
+        self.torque = None
+
+    def do_set_body_pivots(self, pivot_kind, bodies, seed, per_member):
+        self.pivots_per_member = bool(per_member) and pivot_kind is not None
+        for k, m in enumerate(self.m):
+            m.pivots = None if pivot_kind is None else body_pivots_of(pivot_kind, bodies, self.dim_x, self.dim_y, seed, k if per_member else None)
+
+    def do_mean_start(self, what, every, first, count):
+        self.means = {"what": what, "every": every, "first": first, "count": count, "steps": 0, "samples": 0,
+                      "sums": mean_rule.start(what, (count, self.dim_y, self.dim_x))}
+
+    def do_mean_stop(self):
+        self.means = None
+
+    def do_mean_sample(self):
+        self.mean_add()
+
+    # "OPENINGS": the map and the inflow shared or per member; the profile with `members` None (every record to every member) or per record
+    def do_set_openings(self, open_kind, seed, per_member, inflow, inflow_per_member):
+        self.open_per_member, self.inflow_per_member, self.profile_set = bool(per_member), bool(inflow_per_member), False
+        for k, m in enumerate(self.m):
+            m.open = open_map(open_kind, self.dim_x, self.dim_y, seed, k if per_member else None)
+            m.inflow, m.profile = tuple(inflow[k] if inflow_per_member else inflow), None
+
+    def do_clear_openings(self):
+        self.open_per_member = self.inflow_per_member = self.profile_set = False
+        for m in self.m:
+            m.do_clear_openings()
+
+    def do_set_inflow(self, inflow, per_member):
+        self.inflow_per_member = bool(per_member)
+        for k, m in enumerate(self.m):
+            m.inflow = tuple(inflow[k] if per_member else inflow)
+
+    def do_set_inflow_profile(self, members, cells, vels):
+        self.profile_set = bool(cells)
+        for k, m in enumerate(self.m):
+            rows = [(tuple(c), tuple(u)) for at, (c, u) in enumerate(zip(cells, vels)) if members is None or members[at] == k]
+            m.profile = rows or None
 
     def do_clear_bodies(self):
         self.do_set_bodies("all one", 1, 0, False)
@@ -780,6 +1200,46 @@ class BatchModel:
         l = self.loads
         stacked = np.stack(l["records"]) if l["records"] else np.zeros((0, l["count"], self.bodies), load_rule.DTYPE)
         return as_result(records=load_bytes(stacked), info=np.array([len(l["records"]), l["capacity"], l["steps"], self.bodies], np.int64))
+
+    def _recorded(self, r, dtype):
+        stacked = np.stack(r["records"]) if r["records"] else np.zeros((0, r["count"], self.bodies), dtype)
+        return as_result(records=raw_bytes(stacked), info=np.array([len(r["records"]), r["capacity"], r["steps"], self.bodies], np.int64))
+
+    def q_friction(self, first, count):
+        return as_result(records=raw_bytes(self._friction_records(first, count)))
+
+    def q_friction_history(self):
+        return self._recorded(self.friction, friction_rule.DTYPE)
+
+    def q_torque(self, first, count):
+        return as_result(records=raw_bytes(self._torque_records(first, count)))
+
+    def q_torque_history(self):
+        return self._recorded(self.torque, torque_rule.DTYPE)
+
+    def q_body_pivots(self):
+        return as_result(pivot2=np.stack([m.q_body_pivots()["pivot2"] for m in self.m]))
+
+    def q_mean_info(self):
+        m = self.means
+        return as_result(info=np.array([0, 0, 0, 0] if m is None else [m["what"], m["every"], m["samples"], m["steps"]], np.int64))
+
+    def q_mean_sums(self, plane, first, count):
+        at = first - self.means["first"]
+        return as_result(plane=self.means["sums"][plane][at:at + count].copy())
+
+    def q_openings(self):
+        live = np.sum([live_cells(m.open, m.mask) for m in self.m], axis=0) if self.openings_set() else (0, 0)
+        return as_result(map=np.stack([m.q_openings()["map"] for m in self.m]), inflow=np.array([m.inflow for m in self.m], np.float32), set=self.openings_set(),
+                         per_member=self.open_per_member, inflow_per_member=self.inflow_per_member, live=np.array(live, np.int64))
+
+    def q_inflow_profile(self, member):
+        cells, vel = profile_arrays(self.m[member].profile)
+        held = sum(len(profile_arrays(m.profile)[0]) for m in self.m)
+        return as_result(cells=cells, vel=vel, set=self.profile_set, held=held)
+
+    def q_openings_flux(self, first, count):
+        return as_result(records=np.stack([m.q_openings_flux()["record"] for m in self.m[first:first + count]]))
 
     def q_download(self, field):
         return as_result(field=self._stack(FIELDS[field]))
@@ -843,6 +1303,19 @@ class BatchModel:
             first = int(rng.integers(self.batch))
             out += [("viscosity", {}), ("bodies", {}), ("loads", {"first": first, "count": int(rng.integers(1, self.batch - first + 1))})]
             if self.loads is not None: out.append(("loads_history", {}))
+        if self.records:
+            first = int(rng.integers(self.batch))
+            some = {"first": first, "count": int(rng.integers(1, self.batch - first + 1))}
+            out += [("friction", dict(some)), ("torque", dict(some)), ("body_pivots", {}), ("mean_info", {})]
+            if self.friction is not None: out.append(("friction_history", {}))
+            if self.torque is not None: out.append(("torque_history", {}))
+            if self.means is not None:
+                planes = mean_rule.planes_of(self.means["what"])
+                out.append(("mean_sums", {"plane": int(planes[int(rng.integers(len(planes)))]), "first": self.means["first"], "count": self.means["count"]}))
+        if self.opens:
+            first = int(rng.integers(self.batch))
+            out += [("openings", {}), ("inflow_profile", {"member": int(rng.integers(self.batch))}),
+                    ("openings_flux", {"first": first, "count": int(rng.integers(1, self.batch - first + 1))})]
         return out
 
 
@@ -925,6 +1398,48 @@ class LibraryContext:
 
     def g_set_bodies(self, label_kind, bodies, seed):
         self.s.set_bodies(body_labels(label_kind, self.dim_x, self.dim_y, seed), bodies)
+
+    def g_friction_start(self, every, capacity): self.s.friction_start(every, capacity)
+    def g_friction_stop(self): self.s.friction_stop()
+    def g_torque_start(self, every, capacity): self.s.torque_start(every, capacity)
+    def g_torque_stop(self): self.s.torque_stop()
+    def g_mean_start(self, what, every): self.s.mean_start(what, every)
+    def g_mean_stop(self): self.s.mean_stop()
+    def g_mean_sample(self): self.s.mean_sample()
+    def g_clear_openings(self): self.s.set_openings(None)
+    def g_set_inflow(self, inflow): self.s.set_inflow(inflow)
+    def g_set_inflow_profile(self, cells, vels): self.s.set_inflow_profile(cells, vels)
+
+    def g_set_body_pivots(self, pivot_kind, bodies, seed):
+        """(straight to the C call: the package's method takes `bodies` from the handle, and the op may name another)"""
+        if pivot_kind is None:
+            return self.s.set_body_pivots(None)
+        p2 = np.ascontiguousarray(body_pivots_of(pivot_kind, bodies, self.dim_x, self.dim_y, seed), np.int32)
+        self.sfl.capi.check(self.s._lib.sfl_set_body_pivots(self.s._h, p2.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), bodies))
+
+    def g_set_openings(self, open_kind, seed, inflow):
+        self.s.set_openings(open_map(open_kind, self.dim_x, self.dim_y, seed), inflow)
+
+    def g_friction(self): return as_result(records=raw_bytes(self.s.friction()))
+    def g_torque(self): return as_result(records=raw_bytes(self.s.torque()))
+    def g_body_pivots(self): return as_result(pivot2=np.round(self.s.body_pivots() * 2).astype(np.int32))
+    def g_mean_info(self): return as_result(info=np.array(self.s.mean_info(), np.int64))
+    def g_mean_sums(self, plane): return as_result(plane=self.s.mean_sums(plane))
+    def g_openings_flux(self): return as_result(record=raw_bytes(self.s.openings_flux()))
+
+    def g_friction_history(self):
+        return as_result(records=raw_bytes(self.s.friction_history()), info=np.array(self.s.friction_info(), np.int64))
+
+    def g_torque_history(self):
+        return as_result(records=raw_bytes(self.s.torque_history()), info=np.array(self.s.torque_info(), np.int64))
+
+    def g_openings(self):
+        (on, live_in, live_out), (held, inflow) = self.s.openings_info(), self.s.openings()
+        return as_result(map=held, inflow=inflow, set=on, live=np.array([live_in, live_out], np.int64))
+
+    def g_inflow_profile(self):
+        cells, vel = self.s.inflow_profile()
+        return as_result(cells=cells, vel=vel)
 
     def g_viscosity(self):
         nu, sweeps = self.s.viscosity()
@@ -1042,6 +1557,50 @@ class LibraryBatch:
         labels = [body_labels(label_kind, self.dim_x, self.dim_y, seed, k) for k in (range(self.batch) if per_member else [None])]
         self.b.set_bodies(np.stack(labels) if per_member else labels[0], bodies)
 
+    def g_friction_start(self, every, capacity, first, count): self.b.friction_start(every, capacity, first, count)
+    def g_friction_stop(self): self.b.friction_stop()
+    def g_torque_start(self, every, capacity, first, count): self.b.torque_start(every, capacity, first, count)
+    def g_torque_stop(self): self.b.torque_stop()
+    def g_mean_start(self, what, every, first, count): self.b.mean_start(what, every, first, count)
+    def g_mean_stop(self): self.b.mean_stop()
+    def g_mean_sample(self): self.b.mean_sample()
+    def g_clear_openings(self): self.b.set_openings(None)
+    def g_set_inflow(self, inflow, per_member): self.b.set_inflow(np.array(inflow, np.float32))
+    def g_set_inflow_profile(self, members, cells, vels): self.b.set_inflow_profile(cells, vels, members)
+
+    def g_set_body_pivots(self, pivot_kind, bodies, seed, per_member):
+        """(straight to the C call: the package's method takes `bodies` from the handle, and the op may name another)"""
+        if pivot_kind is None:
+            return self.b.set_body_pivots(None)
+        members = range(self.batch) if per_member else [None]
+        p2 = np.ascontiguousarray(np.stack([body_pivots_of(pivot_kind, bodies, self.dim_x, self.dim_y, seed, k) for k in members]), np.int32)
+        self.sfl.capi.check(self.b._lib.sfl_batch_set_body_pivots(self.b._h, p2.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(bool(per_member)), bodies))
+
+    def g_set_openings(self, open_kind, seed, per_member, inflow, inflow_per_member):
+        maps = [open_map(open_kind, self.dim_x, self.dim_y, seed, k) for k in (range(self.batch) if per_member else [None])]
+        self.b.set_openings(np.stack(maps) if per_member else maps[0], np.array(inflow, np.float32))
+
+    def g_friction(self, first, count): return as_result(records=raw_bytes(self.b.friction(first, count)))
+    def g_torque(self, first, count): return as_result(records=raw_bytes(self.b.torque(first, count)))
+    def g_body_pivots(self): return as_result(pivot2=np.round(self.b.body_pivots() * 2).astype(np.int32))
+    def g_mean_info(self): return as_result(info=np.array(self.b.mean_info(), np.int64))
+    def g_mean_sums(self, plane, first, count): return as_result(plane=self.b.mean_sums(plane, first, count))
+    def g_openings_flux(self, first, count): return as_result(records=raw_bytes(self.b.openings_flux(first, count)))
+
+    def g_friction_history(self):
+        return as_result(records=raw_bytes(self.b.friction_history()), info=np.array(self.b.friction_info(), np.int64))
+
+    def g_torque_history(self):
+        return as_result(records=raw_bytes(self.b.torque_history()), info=np.array(self.b.torque_info(), np.int64))
+
+    def g_openings(self):
+        (on, per_member, inflow_per_member, live_in, live_out), (held, inflow) = self.b.openings_info(), self.b.openings()
+        return as_result(map=held, inflow=inflow, set=on, per_member=per_member, inflow_per_member=inflow_per_member, live=np.array([live_in, live_out], np.int64))
+
+    def g_inflow_profile(self, member):
+        (on, held), (cells, vel) = self.b.inflow_profile_info(), self.b.inflow_profile(member)
+        return as_result(cells=cells, vel=vel, set=on, held=held)
+
     def g_viscosity(self):
         nu, sweeps = self.b.viscosity()
         on, per_member = ctypes.c_int(0), ctypes.c_int(0)
@@ -1096,11 +1655,14 @@ class LibraryBatch:
 class Subject:
     """What a set of sequences runs on: `cases` = [(dim_x, dim_y, seed)], one sequence each."""
 
-    def __init__(self, name, kind, cases, options=(), nranks=1, batch=0, large=False, still_solves=False, length=30, solids=False, viscous=False):
+    def __init__(self, name, kind, cases, options=(), nranks=1, batch=0, large=False, still_solves=False, length=30, solids=False, viscous=False,
+                 records=False, opens=False):
         self.name, self.kind, self.cases, self.options, self.nranks, self.batch, self.large = name, kind, cases, tuple(options), nranks, batch, large
         self.still_solves, self.length = still_solves, length   # still_solves: steps on a lattice velocity run iters = 0 (it stays on the lattice)
         self.solids = solids                                    # the solids' and the histories' calls are in the vocabulary
         self.viscous = viscous                                  # ... and the viscosity's and the loads' (on top of the solids')
+        self.records = records                                  # ... and the friction's, the torque's and the averages' (on top of the viscous deck)
+        self.opens = opens                                      # the openings', the profiles' and the flux's (on top of the solids' deck)
 
     def model(self, oracle, case):
         dim_x, dim_y, _ = case
@@ -1108,7 +1670,7 @@ class Subject:
             model = BatchModel(oracle, dim_x, dim_y, self.batch)
         else:
             model = (ContextModel if self.kind == "context" else SlabsModel)(oracle, dim_x, dim_y)
-        model.viscous = self.viscous
+        model.viscous, model.records, model.opens = self.viscous, self.records, self.opens
         return model
 
     def library(self, sfl, case):
@@ -1122,15 +1684,20 @@ class Subject:
         if not self.solids:
             return own
         own = tuple(k for k in own if k not in SOLID_LEFT_OUT) + SOLID_WRITERS + SOLID_QUERIES
+        if self.opens:
+            return own + OPEN_WRITERS + OPEN_QUERIES
         if not self.viscous:
             return own
-        return own + (VISCOUS_WRITERS if self.kind == "context" else BATCH_VISCOUS_WRITERS) + VISCOUS_QUERIES
+        own += (VISCOUS_WRITERS if self.kind == "context" else BATCH_VISCOUS_WRITERS) + VISCOUS_QUERIES
+        return own + RECORD_WRITERS + RECORD_QUERIES if self.records else own
 
     def option_values(self):
         return {"context": OPTION_VALUES, "slabs": SLAB_OPTION_VALUES, "batch": {}}[self.kind]
 
 
 VISCOUS_LENGTH = {"context": 50, "batch": 48}     # ops of a sequence of the viscous subjects: the shortest the deck fits in
+RECORD_LENGTH = {"context": 69, "batch": 76}      # ... of the subjects with friction, torque and averages, found in the same way
+OPEN_LENGTH = {"context": 60, "batch": 67}       # ... and of the subjects with openings
 
 
 def _cases(dim_x, dim_y, seeds, base):
@@ -1156,6 +1723,17 @@ SUBJECTS = [
     # batch member smaller than a wavefront (slabs and large batches refuse viscosity)
     Subject("viscous-context", "context", _cases(130, 70, 3, 900) + _cases(61, 81, 2, 950), length=VISCOUS_LENGTH["context"], solids=True, viscous=True),
     Subject("viscous-batch", "batch", _cases(61, 81, 3, 1000) + _cases(7, 9, 2, 1050), batch=3, length=VISCOUS_LENGTH["batch"], solids=True, viscous=True),
+    # friction, torque and averages, on top of the viscous vocabulary and at its shapes: three more recorders with buffers, step
+    # counts and admission of their own beside the loads' and a history, pivots that follow the number of bodies, and averages
+    # that cut a batch's one-launch replay and a context's fused seams while every >= 1 and give them back when stopped
+    Subject("record-context", "context", _cases(130, 70, 3, 1100) + _cases(61, 81, 2, 1150), length=RECORD_LENGTH["context"], solids=True, viscous=True, records=True),
+    Subject("record-batch", "batch", _cases(61, 81, 3, 1200) + _cases(7, 9, 2, 1250), batch=3, length=RECORD_LENGTH["batch"], solids=True, viscous=True, records=True),
+    # openings, inflow profiles and the flux, on top of the solids' vocabulary and at its shapes (openings and a viscosity refuse
+    # each other): 130 x 70 is 3 x 3 ragged tiles of the masked solve, whose rim cells lie in the two-cell-wide last column and the
+    # six-deep last row; 61 x 81 one tile column; 7 x 9 a member smaller than a wavefront.  A map before and behind a mask, masks
+    # replaced and cleared behind a map, inflow cells that go solid and come back, profiles replaced, dropped and kept
+    Subject("open-context", "context", _cases(130, 70, 3, 1300) + _cases(61, 81, 2, 1350), length=OPEN_LENGTH["context"], solids=True, opens=True),
+    Subject("open-batch", "batch", _cases(61, 81, 3, 1400) + _cases(7, 9, 2, 1450), batch=3, length=OPEN_LENGTH["batch"], solids=True, opens=True),
 ]
 
 
@@ -1174,9 +1752,42 @@ class Gate:
         self.visc = None                                      # {"nu": [one per member, or one], "sweeps", "per_member"} while one is set
         self.labels, self.loads = None, None                  # the label kind while labels are set; [every, capacity, steps]
         self.two_launches = 0                                 # two-launch diffusions made so far: the third buffer has held a velocity
+        self.bodies, self.pivots = 1, None                    # the number of bodies; the set_body_pivots arguments while pivots are set
+        self.friction, self.torque = None, None               # [every, capacity, steps], as the loads recorder
+        self.ranges = {}                                      # a batch: recorder -> (first, count)
+        self.means = None                                     # {"what", "every", "first", "count", "steps", "samples"}
+        self.open, self.inflow, self.profile = None, None, None   # [map] or one per member; [(u, v)] likewise; the set_inflow_profile arguments
 
     def mixed(self):
         return self.masks is not None and any(mixed(m) for m in self.masks)
+
+    def maps_of(self, members):
+        """The map of every member named (a context: [0])."""
+        return [self.open[m if len(self.open) > 1 else 0] for m in members]
+
+    def mask_of(self, member):
+        return None if self.masks is None else self.masks[member if len(self.masks) > 1 else 0]
+
+    def live(self):
+        """(live inflow cells, live outflow cells) over all members, as `openings` reports them; (0, 0) without a map."""
+        if self.open is None:
+            return 0, 0
+        each = [live_cells(self.maps_of([m])[0], self.mask_of(m)) for m in range(max(self.batch, 1))]
+        return tuple(int(x) for x in np.sum(each, axis=0))
+
+    def profile_fits(self, a):
+        """Whether every record of a set_inflow_profile names an INFLOW cell of the map of every member it applies to."""
+        for k, cell in enumerate(a["cells"]):
+            members = range(max(self.batch, 1)) if a.get("members") is None else [a["members"][k]]
+            if any(inflow_rule.check_profile([(tuple(cell), None)], m) is not None for m in self.maps_of(members)):
+                return False
+        return True
+
+    def code(self, kind, a):
+        """The code of the refusal remedy() announces: SFL_ERR_INVALID for the three the library checks behind the state."""
+        if kind == "set_body_pivots" or (kind == "mean_sums" and self.means is not None) or (kind == "set_inflow_profile" and self.open is not None):
+            return ERR_INVALID
+        return ERR_STATE
 
     def remedy(self, kind, a):
         """None when the header takes the call, else the kind of a call to make in its place: the one that ends what it is
@@ -1191,20 +1802,42 @@ class Gate:
             if kind == "step_n_until" and self.visc is not None: return "step_n_each"      # "VISCOSITY": refused while one is set
         elif on and kind in ("view_scalar", "view_texels") and a["what"] == VIEW_DIVERGENCE:
             return "clear_solids"
+        if self.open is not None:                   # "OPENINGS": what is refused while a map is set ...
+            if self.batch:
+                if kind in ("step_n_until", "poisson_solve_until"): return kind.replace("until", "each")
+                if kind in ("history_start", "set_viscosity"): return "clear_openings"
+                if kind in ("record_view", "view_render_members") and a["what"] == VIEW_DIVERGENCE: return "clear_openings"
+            else:
+                if kind in ("view_scalar", "view_texels") and a["what"] == VIEW_DIVERGENCE: return "clear_openings"
+                if kind == "set_viscosity" and not (a["nu"] == 0 or a["sweeps"] == 0): return "clear_openings"
+            if kind == "set_inflow_profile" and a["cells"] and not self.profile_fits(a): return "inflow_profile"    # (SFL_ERR_INVALID; planted only)
+        else:                                       # ... and what is refused without one
+            if kind == "set_inflow" or (kind == "set_inflow_profile" and a["cells"]): return "set_openings"
+        if kind == "set_openings":                  # ... and what refuses the map
+            if self.batch and self.hist is not None: return "history_stop"
+            if self.batch and self.rec and self.view == VIEW_DIVERGENCE: return "record_stop"
+            if self.visc is not None: return "clear_viscosity"
         if kind in ("set_bodies", "clear_bodies") and self.loads is not None: return "loads_stop"   # "LOADS": the samples' layout
-        if self.hist is not None and kind in STEPS:
-            every, capacity, steps = self.hist
-            if (steps + a.get("n", 1)) // every - steps // every > capacity - steps // every: return "history_stop"
-        if self.loads is not None and kind in STEPS:
-            every, capacity, steps = self.loads
-            if (steps + a.get("n", 1)) // every - steps // every > capacity - steps // every: return "loads_stop"
+        if kind in ("set_bodies", "clear_bodies") and self.friction is not None: return "friction_stop"
+        if kind in ("set_bodies", "clear_bodies") and self.torque is not None: return "torque_stop"
+        for name, stop in (("hist", "history_stop"), ("loads", "loads_stop"), ("friction", "friction_stop"), ("torque", "torque_stop")):
+            recorder = getattr(self, name)          # the admission checks, in the library's order
+            if recorder is not None and kind in STEPS:
+                every, capacity, steps = recorder
+                if (steps + a.get("n", 1)) // every - steps // every > capacity - steps // every: return stop
+        if kind == "set_body_pivots" and a["pivot_kind"] is not None and a["bodies"] != self.bodies: return "body_pivots"    # (SFL_ERR_INVALID; planted only)
+        if kind == "mean_sums" and self.means is not None:                                               # (SFL_ERR_INVALID; planted only)
+            inside = self.means["first"] <= a.get("first", 0) and a.get("first", 0) + a.get("count", 1) <= self.means["first"] + self.means["count"]
+            if not (self.means["what"] & mean_rule.GROUP_OF[a["plane"]] and inside): return "mean_info"
         return None
 
     def missing(self, kind):
         """A query of something the handle does not hold now: the kind of the call that makes it."""
         need = {"history": (self.hist is not None, "history_start"), "trail": (self.trail or self.batch > 0, "trail_start"),
                 "frames": (self.rec, "record_start"), "record_view": (self.rec, "record_start"),
-                "loads_history": (self.loads is not None, "loads_start")}
+                "loads_history": (self.loads is not None, "loads_start"), "friction_history": (self.friction is not None, "friction_start"),
+                "torque_history": (self.torque is not None, "torque_start"), "mean_sums": (self.means is not None, "mean_start"),
+                "mean_sample": (self.means is not None, "mean_start")}
         if self.batch:
             need.update(residual=(self.norms, "step_n_each"), iterations=(self.iters, "step_n_until"))
         have, maker = need.get(kind, (True, None))
@@ -1234,6 +1867,31 @@ class Gate:
         if kind == "loads_start": self.loads = [a["every"], a["capacity"], 0]
         if kind == "loads_stop": self.loads = None
         if kind in STEPS and self.loads is not None: self.loads[2] += a.get("n", 1)
+        if kind in ("set_bodies", "clear_bodies"):
+            bodies = LABEL_KINDS[a["label_kind"]] if kind == "set_bodies" else 1
+            if bodies != self.bodies: self.bodies, self.pivots = bodies, None      # "TORQUE": another number of bodies: every pivot back to (0, 0)
+        if kind == "set_body_pivots": self.pivots = None if a["pivot_kind"] is None else dict(a)
+        if kind in ("loads_start", "friction_start", "torque_start", "mean_start"): self.ranges[kind[:-len("_start")]] = (a.get("first", 0), a.get("count", 1))
+        if kind == "friction_start": self.friction = [a["every"], a["capacity"], 0]
+        if kind == "friction_stop": self.friction = None
+        if kind == "torque_start": self.torque = [a["every"], a["capacity"], 0]
+        if kind == "torque_stop": self.torque = None
+        for recorder in (self.friction, self.torque):
+            if kind in STEPS and recorder is not None: recorder[2] += a.get("n", 1)
+        if kind == "mean_start": self.means = {"what": a["what"], "every": a["every"], "first": a.get("first", 0), "count": a.get("count", 1), "steps": 0, "samples": 0}
+        if kind == "mean_stop": self.means = None
+        if kind == "mean_sample": self.means["samples"] += 1
+        if kind in STEPS and self.means is not None and self.means["every"] >= 1:
+            m, n = self.means, a.get("n", 1)
+            m["samples"] += (m["steps"] + n) // m["every"] - m["steps"] // m["every"]
+            m["steps"] += n
+        if kind == "set_openings":
+            members = range(self.batch) if a.get("per_member") else [None]
+            self.open = [open_map(a["open_kind"], self.dim_x, self.dim_y, a["seed"], k) for k in members]
+            self.inflow, self.profile = [tuple(u) for u in a["inflow"]] if a.get("inflow_per_member") else [tuple(a["inflow"])], None
+        if kind == "clear_openings": self.open, self.inflow, self.profile = None, None, None
+        if kind == "set_inflow": self.inflow = [tuple(u) for u in a["inflow"]] if a.get("per_member") else [tuple(a["inflow"])]
+        if kind == "set_inflow_profile": self.profile = dict(a) if a["cells"] else None
         if self.batch:
             if kind in ("step_n", "poisson_solve") or (kind == "upload" and a["field"] in (FD, FP)): self.norms = self.iters = False
             if kind in ("step_n_each", "poisson_solve_each"): self.norms, self.iters = True, False
@@ -1296,6 +1954,12 @@ class _Draw:
         a.update(fixed)
         if kind == "set_bodies":
             a["bodies"] = LABEL_KINDS[a["label_kind"]]
+        if kind in ("set_openings", "set_inflow") and self.sub.kind == "batch":      # one (u, v), or one per member: as the flag says
+            each, nested = a["inflow_per_member" if kind == "set_openings" else "per_member"], isinstance(a["inflow"][0], list)
+            if each and not nested:
+                a["inflow"] = [list(INFLOWS[(INFLOWS.index(tuple(a["inflow"])) + k) % len(INFLOWS)]) for k in range(self.sub.batch)]
+            elif nested and not each:
+                a["inflow"] = a["inflow"][0]
         op = (kind, a)
         if self.shadow is not None:
             op = self._under_the_halo(op)
@@ -1314,7 +1978,7 @@ class _Draw:
             instead = self.gate.missing(kind) or (None if planted_refusal else self.gate.remedy(kind, a))
             if instead is None:
                 break
-            if a.get("what") == VIEW_DIVERGENCE and instead == "clear_solids":     # (another view will do)
+            if a.get("what") == VIEW_DIVERGENCE and instead in ("clear_solids", "clear_openings"):     # (another view will do)
                 op = (kind, dict(a, what=int(self.rng.integers(VIEW_DIVERGENCE))))
                 continue
             self.hints, planted_refusal = {}, False
@@ -1322,6 +1986,41 @@ class _Draw:
         if self.gate.remedy(*op) is None:
             self.gate.after(*op)
         return op
+
+    def pick_pair(self, values):
+        return values[int(self.rng.integers(len(values)))]
+
+    def profile_args(self, batch):
+        """The records of a set_inflow_profile on INFLOW cells of the map held -- of every member's map where a record goes to
+        all: three drawn cells, the first once more (of two records on one cell the later wins) and the second with the uniform
+        inflow as its velocity.  Hints: "_mask" (kind, seed): the first cell is one that this mask, set by a later link, makes
+        solid; "_off": one more record on an interior cell, whose byte is not INFLOW (refused with SFL_ERR_INVALID); "_clear":
+        n == 0; "_members": every record names its member.  A map without an inflow cell leaves n == 0."""
+        r, B, gate = self.rng, max(self.sub.batch, 1), self.gate
+        shared = {"members": None} if batch else {}
+        if gate.open is None:               # (without openings: refused where planted, else the call gives way to set_openings)
+            return dict({"cells": [[0, self.dim_y // 2]], "vels": [[1.0, 0.0]]}, **shared)
+        if self.hints.get("_clear"):
+            return dict({"cells": [], "vels": []}, **shared)
+        per_record = bool(batch and self.hints.get("_members", bool(r.integers(2))))
+        cells, vels, members = [], [], []
+        for at in range(3):
+            m = int(r.integers(B)) if per_record else None
+            inflow = np.all([held == opening_rule.INFLOW for held in gate.maps_of(range(B) if m is None else [m])], axis=0)
+            pool = np.argwhere(inflow)
+            if at == 0 and "_mask" in self.hints:
+                solid = np.argwhere(inflow & solid_mask(self.hints["_mask"][0], self.dim_x, self.dim_y, self.hints["_mask"][1]))
+                pool = solid if len(solid) else pool
+            if len(pool):
+                j, i = pool[int(r.integers(len(pool)))]
+                cells.append([int(i), int(j)]), vels.append(self.vels(1)[0]), members.append(m)
+        if cells:
+            if len(cells) >= 2:
+                vels[1] = [float(x) for x in gate.inflow[members[1] if members[1] is not None and len(gate.inflow) > 1 else 0]]
+            cells.append(list(cells[0])), vels.append(self.vels(1)[0]), members.append(members[0])
+        if self.hints.get("_off"):
+            cells.append([1, 1]), vels.append(self.vels(1)[0]), members.append(members[0] if members else (0 if per_record else None))
+        return dict({"cells": cells, "vels": vels}, **({"members": members if per_record else None} if batch else {}))
 
     def cells_on(self, masks, members):
         """One cell per entry of `members`, in turn a solid and a fluid cell of the member's mask (any cell where it has none)."""
@@ -1350,6 +2049,18 @@ class _Draw:
             if kind.endswith("until"):
                 a.update(tol=self.each(lambda: self.pick(TOLS)), every=self.each(lambda: self.pick(EVERYS)))
             return a
+        if kind == "queue_forces" and self.hints.get("_open"):
+            # under a map, by the hint: a record on an inflow cell, one on a profiled cell and one on an outflow cell (items 2 and 2a)
+            members, cells, held = [int(r.integers(B)) for _ in range(3)] if batch else [0] * 3, [], self.gate.profile
+            for at, m in enumerate(members):
+                byte = opening_rule.OUTFLOW if at == 2 else opening_rule.INFLOW
+                pool = [[i, j] for j, i in np.argwhere(self.gate.maps_of([m])[0] == byte)]
+                if at == 1 and held is not None:
+                    named = [c for k, c in enumerate(held["cells"]) if held.get("members") is None or held["members"][k] == m]
+                    pool = named or pool
+                cells.append([int(x) for x in pool[int(r.integers(len(pool)))]] if pool else self.cells(1)[0])
+            a = {"step": int(r.integers(0, 2)), "cells": cells, "vels": self.vels(3)}
+            return dict(a, members=members) if batch else a
         if kind == "queue_forces" and self.gate is not None and ("_mask" in self.hints or self.gate.masks is not None):
             # with a mask in force (or, by the hint, about to be set): records on solid cells and on fluid ones
             masks = [solid_mask(self.hints["_mask"][0], self.dim_x, self.dim_y, self.hints["_mask"][1])] if "_mask" in self.hints else self.gate.masks
@@ -1381,9 +2092,41 @@ class _Draw:
                 first = int(r.integers(B))
                 a.update(first=first, count=int(r.integers(1, B - first + 1)))
             return a
-        if kind == "loads" and batch:
+        if kind in ("loads", "friction", "torque", "openings_flux") and batch:
             first = int(r.integers(B))
             return {"first": first, "count": int(r.integers(1, B - first + 1))}
+        if kind in ("friction_start", "torque_start"):      # (room for every sample of a sequence: a full one is planted, with its stop)
+            a = {"every": self.pick((1, 2, 3)), "capacity": CAPACITY}
+            if batch:
+                first = int(r.integers(B))
+                a.update(first=first, count=int(r.integers(1, B - first + 1)))
+            return a
+        if kind == "set_body_pivots":       # `bodies` as the handle holds them ("_wrong": another number, refused with SFL_ERR_INVALID)
+            a = {"pivot_kind": self.pick(PIVOT_KINDS), "bodies": self.gate.bodies + (1 if self.hints.get("_wrong") else 0), "seed": int(r.integers(100))}
+            return dict(a, per_member=bool(r.integers(2))) if batch else a
+        if kind == "mean_start":
+            a = {"what": self.pick(MEAN_WHATS), "every": self.pick((0, 1, 2, 3))}
+            if batch:
+                first = int(r.integers(B))
+                a.update(first=first, count=int(r.integers(1, B - first + 1)))
+            return a
+        if kind == "mean_sums":             # a plane of the groups held ("_outside": of another group, refused with SFL_ERR_INVALID)
+            held = self.gate.means or {"what": mean_rule.ALL, "first": 0, "count": max(B, 1)}
+            planes = [k for k in range(mean_rule.PLANES) if bool(held["what"] & mean_rule.GROUP_OF[k]) != bool(self.hints.get("_outside"))]
+            a = {"plane": int(planes[int(r.integers(len(planes)))])}
+            if batch:                       # a range inside the recorded one
+                first = held["first"] + int(r.integers(held["count"]))
+                a.update(first=first, count=int(r.integers(1, held["first"] + held["count"] - first + 1)))
+            return a
+        if kind == "set_openings":
+            a = {"open_kind": self.pick(OPEN_KINDS), "seed": int(r.integers(100)), "inflow": list(self.pick_pair(INFLOWS))}
+            return dict(a, per_member=bool(r.integers(2)), inflow_per_member=bool(r.integers(2))) if batch else a
+        if kind == "set_inflow":
+            a = {"inflow": list(self.pick_pair(INFLOWS))}
+            return dict(a, per_member=bool(r.integers(2))) if batch else a
+        if kind == "set_inflow_profile":
+            return self.profile_args(batch)
+        if kind == "inflow_profile" and batch: return {"member": int(r.integers(B))}
         if kind == "queue_forces":
             n = int(r.integers(1, 4))
             a = {"step": int(r.integers(0, 4)), "cells": self.cells(n), "vels": self.vels(n)}
@@ -1522,7 +2265,7 @@ SOLID_HANDOVERS = {
 
 
 def handovers_of(subject):
-    if subject.viscous:
+    if subject.viscous or subject.opens:
         return viscous_handovers(subject)
     if subject.solids:
         return SOLID_HANDOVERS[subject.kind]
@@ -1545,7 +2288,7 @@ def planted(subject):
     """The items the generator plants whole (the ops of an item stay next to each other): the hand-overs, and every option
     value in front of a writer it affects, so that no value is only ever set."""
     kind = subject.kind
-    if subject.viscous:
+    if subject.viscous or subject.opens:
         return planted_viscous(subject)
     if subject.solids:
         return planted_solids(subject)
@@ -1763,14 +2506,253 @@ def viscous_items(subject):
     }
 
 
+def _fr(every, capacity=CAPACITY, **more): return ("friction_start", dict({"every": every, "capacity": capacity}, **more))
+def _tq(every, capacity=CAPACITY, **more): return ("torque_start", dict({"every": every, "capacity": capacity}, **more))
+def _mean(what, every, **more): return ("mean_start", dict({"what": what, "every": every}, **more))
+def _piv(pivot_kind, **more): return ("set_body_pivots", dict({"pivot_kind": pivot_kind}, **more))
+def _open(open_kind, **more): return ("set_openings", dict({"open_kind": open_kind}, **more))
+
+
+def record_items(subject):
+    """{what it walks: item} of the subjects with friction, torque and averages, hints as in planted_solids ("_wrong": pivots of
+    another number of bodies, "_outside": a plane outside `what`).  An item says itself what it needs ended in front of it; every
+    recorder of two samples is stopped inside the item that started it."""
+    clear, clear_nu, refused = ("clear_solids", {}), ("clear_viscosity", {}), {"_refused": True}
+    no_loads, no_fr, no_tq, no_hist, noise = ("loads_stop", {}), ("friction_stop", {}), ("torque_stop", {}), ("history_stop", {}), _up("noise")
+    stop3 = [no_loads, no_fr, no_tq]
+    reads = [("friction_history", {}), ("torque_history", {}), ("mean_info", {}), ("mean_sums", {})]
+    A, B = subject.cases[0][:2], subject.cases[-1][:2]
+    if subject.kind == "context":
+        step, step2, step3 = ("step", {}), ("step_n", {"n": 2}), ("step_n", {"n": 3})
+        solved = ("step", {"iters": 5})          # (a pressure that is not all zeros in front of a torque)
+        seam = [("forget_forces", {"_shape": A}), no_hist, ("set_tracers", {"follow": False}), clear, clear_nu, _opt("OPT_ADVECT_KERNEL", 2)]
+        return {
+            # five counters with five periods over 10 steps in four calls: samples 10, 5, 3, 2 and 2, remainders in every call
+            "a history, the loads, the friction, the torque and the averages on at once, each with its own every, behind viscous steps":
+                stop3 + [noise, ("history_start", {"every": 1, "capacity": CAPACITY}), _solid("disc"), _bodies("halves"), _piv("seeded"), _loads(2), _fr(3), _tq(4),
+                         _mean(15, 5), _visc(0.3, 3), solved, step2, step3, ("step_n", {"n": 4}), ("history", {}), ("loads_history", {})] + reads + [no_hist],
+            "a full friction recorder refuses the call whole while the others have room":
+                [("history_start", {"every": 1, "capacity": CAPACITY}), _loads(1), _tq(1), _mean(3, 1), _fr(1, 2), ("step_n", dict(n=3, **refused)), step2, ("history", {}),
+                 ("loads_history", {})] + reads + [no_fr, no_hist],
+            "a full torque recorder refuses the call whole while the others have room":
+                [("history_start", {"every": 1, "capacity": CAPACITY}), _loads(1), _fr(1), _mean(12, 1), _tq(1, 2), ("step_n", dict(n=3, **refused)), step2, ("history", {}),
+                 ("loads_history", {})] + reads + [no_tq, no_hist],
+            "the friction recorder across calls that leave remainders, restarted while on":
+                [_solid("isolated"), _loads(1), step, _fr(3), step2, solved, step2, ("friction_history", {}), _fr(2), step, step2, ("friction_history", {})],
+            "the torque recorder across calls that leave remainders, restarted while on":
+                [_solid("plate"), _tq(3), step2, solved, step2, ("torque_history", {}), _tq(2), step, step2, ("torque_history", {})],
+            "the averages restarted while on: the sums and the counts start from zero":
+                [_mean(3, 1), step2, ("mean_sample", {}), ("mean_info", {}), _mean(3, 2), step, step2, ("mean_info", {}), ("mean_sums", {})],
+            "set_bodies and clear_bodies, refused while the friction recorder is on":
+                [no_loads, no_tq, _fr(1), _bodies("halves", **refused), step, ("clear_bodies", dict(refused)), step, ("bodies", {}), no_fr],
+            "set_bodies and clear_bodies, refused while the torque recorder is on":
+                [no_loads, no_fr, _tq(1), _bodies("sixteen", **refused), step, ("clear_bodies", dict(refused)), step, ("bodies", {}), no_tq],
+            "the same number of bodies keeps the pivots, another puts them back to zero":
+                stop3 + [_solid("disc"), _bodies("with zeros", seed=1), _piv("seeded"), ("body_pivots", {}), _bodies("with zeros", seed=2), ("body_pivots", {}), solved,
+                         ("torque", {}), _bodies("sixteen"), ("body_pivots", {}), ("torque", {}), _bodies("with zeros", seed=3), ("body_pivots", {}), ("torque", {}), _piv("centre"),
+                         ("clear_bodies", {}), ("body_pivots", {})],
+            "pivots set while the torque recorder is on hold from the next sample":
+                [_solid("plate"), _tq(1), _piv("seeded", seed=1), solved, _piv("seeded", seed=2), step, ("torque_history", {}), _piv(None), step, ("torque_history", {})],
+            "set_body_pivots with another number of bodies, refused: the pivots stay":
+                [_piv("centre"), _piv("seeded", _wrong=True, **refused), step, ("body_pivots", {})],
+            "samples under a mask that is replaced and cleared while recording":
+                [_fr(1), _tq(1), _mean(15, 1), _solid("disc"), solved, _solid("seeded"), step, clear, step] + reads[:2] + reads[3:],
+            # the seam shape with every condition of the seam in front: with every >= 1 step_n runs without its fused boundaries,
+            # stopped it takes them again; with every == 0 it keeps them and mean_sample adds between the calls
+            "averages with every >= 1 on the seam shape, then stopped: the seams again":
+                seam + [_mean(7, 1), step2, ("mean_sums", {}), ("mean_stop", {}), step2, ("mean_info", {})],
+            "averages with every == 0 on the seam shape: mean_sample between fused calls":
+                seam + [_mean(9, 0), step2, ("mean_sample", {}), step3, ("mean_sample", {}), ("mean_info", {}), ("mean_sums", {})],
+            "a plane outside what, refused": [_mean(1, 1), step, ("mean_sums", dict(_outside=True, **refused)), step, ("mean_sums", {})],
+            # (the switches the seams depend on are only off inside their own items)
+            "the switches of the fused step off and on again":
+                [_opt("OPT_ADVECT_KERNEL", 1), _opt("OPT_FUSE_DIVERGENCE", 0), _opt("OPT_FUSE_PROJECTION", 0), step, _opt("OPT_FUSE_DIVERGENCE", 1), _opt("OPT_FUSE_PROJECTION", 1)],
+            "a step_n with the seams switched off": [_opt("OPT_STEP_SEAMS", 0), step2, _opt("OPT_STEP_SEAMS", 1)],
+            "the solver's options in front of a solve":
+                [_opt("OPT_SOR_KERNEL", 1), ("poisson_solve", {}), _opt("OPT_SOR_KERNEL", 2), _opt("OPT_SOR_FUSE", 2), ("poisson_continue", {}), _opt("OPT_SOR_FUSE", 16),
+                 ("poisson_solve_until", {})],
+        }
+    s1, s2, sn, each = ("step_n", {"n": 1}), ("step_n", {"n": 2}), ("step_n", {}), ("step_n_each", {})
+    solved, whole = ("step_n", {"n": 1, "iters": 5}), {"first": 0, "count": subject.batch}
+    replay = [clear, clear_nu, no_hist, ("record_stop", {}), ("set_tracers", {"follow": False}), ("forget_forces", {}), ("queue_forces", {"step": 1})]      # (frames would cut it too)
+    again = [("forget_forces", {}), ("queue_forces", {"step": 1})]
+    return {
+        # (a batch's history and its masks refuse each other: all five without a mask -- zero records but for pivot2 --, the four
+        # under one below); the ranges of the five differ
+        "a history, the loads, the friction, the torque and the averages on at once, each with its own every and its own range, behind viscous steps":
+            stop3 + [clear, noise, ("history_start", dict(every=1, capacity=CAPACITY, **whole)), _bodies("halves", per_member=True), _piv("seeded", per_member=True),
+                     _loads(2, **whole), _fr(3, first=1, count=2), _tq(4, first=0, count=1), _mean(15, 5, first=1, count=1), _visc([0.3, 0.0, 0.05], 3, per_member=True),
+                     solved, s2, ("step_n_each", {"n": 3}), ("step_n", {"n": 4}), ("history", {}), ("loads_history", {})] + reads + [no_hist],
+        "the four recorders under a per-member mask, labels, pivots and viscosity":
+            stop3 + [no_hist, _solid("disc", per_member=True), _bodies("halves", per_member=True), _piv("seeded", per_member=True), _loads(1, first=0, count=2),
+                     _fr(2, first=1, count=2), _tq(1, first=2, count=1), _mean(15, 2, first=0, count=2), _visc([0.3, 0.0, 0.05], 3, per_member=True), solved, s2,
+                     ("step_n_each", {"n": 3}), ("loads_history", {})] + reads,
+        "a full friction recorder refuses the call whole while the others have room":
+            [clear, ("record_start", {}), ("history_start", dict(every=1, capacity=CAPACITY, **whole)), _loads(1, **whole), _tq(1, **whole), _mean(3, 1, **whole), _fr(1, 2, **whole),
+             ("step_n", dict(n=3, **refused)), s2, ("history", {}), ("frames", {}), ("loads_history", {})] + reads + [no_fr, no_hist],
+        "a full torque recorder refuses the call whole while the others have room":
+            [clear, ("record_start", {}), ("history_start", dict(every=1, capacity=CAPACITY, **whole)), _loads(1, **whole), _fr(1, **whole), _mean(12, 1, **whole), _tq(1, 2, **whole),
+             ("step_n_each", dict(n=3, **refused)), s2, ("history", {}), ("frames", {}), ("loads_history", {})] + reads + [no_tq, no_hist],
+        "the friction recorder across calls that leave remainders, restarted while on":
+            [no_hist, _solid("isolated", per_member=False), _loads(1), s1, _fr(3), s2, solved, ("step_n_each", {"n": 2}), ("residual", {}), ("friction_history", {}), _fr(2), s1, s2,
+             ("friction_history", {})],
+        "the torque recorder across calls that leave remainders, restarted while on":
+            [no_hist, _solid("plate", per_member=True), _tq(3), s2, solved, ("step_n_each", {"n": 2}), ("torque_history", {}), _tq(2), s1, s2, ("torque_history", {})],
+        "the averages restarted while on: the sums and the counts start from zero":
+            [_mean(3, 1, **whole), s2, ("mean_sample", {}), ("mean_info", {}), _mean(3, 2, first=1, count=2), s1, s2, ("mean_info", {}), ("mean_sums", {})],
+        "set_bodies and clear_bodies, refused while the friction recorder is on":
+            [no_loads, no_tq, _fr(1), _bodies("halves", **refused), sn, ("clear_bodies", dict(refused)), sn, ("bodies", {}), no_fr],
+        "set_bodies and clear_bodies, refused while the torque recorder is on":
+            [no_loads, no_fr, _tq(1), _bodies("sixteen", **refused), sn, ("clear_bodies", dict(refused)), sn, ("bodies", {}), no_tq],
+        "the same number of bodies keeps the pivots, another puts them back to zero":
+            stop3 + [no_hist, _solid("disc", per_member=False), _bodies("with zeros", seed=1, per_member=False), _piv("seeded", per_member=True), ("body_pivots", {}),
+                     _bodies("with zeros", seed=2, per_member=True), ("body_pivots", {}), solved, ("torque", dict(whole)), _bodies("sixteen"), ("body_pivots", {}),
+                     ("torque", dict(whole)), _bodies("with zeros", seed=3, per_member=False), ("body_pivots", {}), ("torque", dict(whole)), _piv("centre", per_member=False),
+                     ("clear_bodies", {}), ("body_pivots", {})],
+        "pivots set while the torque recorder is on hold from the next sample":
+            [no_hist, _solid("plate", per_member=False), _tq(1, **whole), _piv("seeded", seed=1, per_member=False), solved, _piv("seeded", seed=2, per_member=True), s1,
+             ("torque_history", {}), _piv(None), s1, ("torque_history", {})],
+        "set_body_pivots with another number of bodies, refused: the pivots stay":
+            [_piv("centre", per_member=True), _piv("seeded", _wrong=True, **refused), sn, ("body_pivots", {})],
+        "samples under a mask that is replaced and cleared while recording":
+            [no_hist, _fr(1, **whole), _tq(1, **whole), _mean(15, 1, **whole), _solid("disc", per_member=False), solved, _solid("seeded", per_member=True), s1, clear, s1]
+            + reads[:2] + reads[3:],
+        # a record in a later step, no following set, no mask, no viscosity: the one-launch replay.  With every >= 1 it is cut where
+        # a sample is due inside the call, stopped it runs whole again; with every == 0 it stays whole and mean_sample adds
+        "averages with every >= 1 while a timeline is pending: the replay is cut; stopped: whole again":
+            replay + [_mean(7, 2, **whole), ("step_n", {"n": 3}), ("mean_info", {}), ("mean_sums", {})] + again + [("mean_stop", {}), ("step_n", {"n": 3}), ("mean_info", {})],
+        "averages with every == 0 while a timeline is pending: mean_sample between one-launch replays":
+            replay + [_mean(9, 0, first=1, count=2), ("step_n", {"n": 3}), ("mean_sample", {})] + again + [("step_n", {"n": 2}), ("mean_sample", {}), ("mean_info", {}),
+                                                                                                         ("mean_sums", {})],
+        "a plane outside what, refused": [_mean(1, 1), sn, ("mean_sums", dict(_outside=True, **refused)), sn, ("mean_sums", {})],
+        # (the calls to a tolerance need the mask and the viscosity gone: they stand in items that say so)
+        "cleared: a solve to a tolerance, then a viscosity again": [clear, clear_nu, ("poisson_solve_until", {}), ("iterations", {}), ("set_viscosity", {}), sn],
+        "cleared: a step to a tolerance, then a viscosity again": [clear, clear_nu, ("step_n_until", {}), ("iterations", {}), ("set_viscosity", {}), each, ("residual", {})],
+        "cleared: a solve to a tolerance": [clear, clear_nu, ("poisson_solve_until", {}), ("iterations", {}), sn],
+        "cleared: a step to a tolerance behind a step call": [clear, clear_nu, sn, ("step_n_until", {}), ("iterations", {}), ("residual", {})],
+        "cleared: the averages count through a step to a tolerance": [clear, clear_nu, _mean(12, 1), ("step_n_until", {}), ("iterations", {}), ("mean_info", {}), ("poisson_solve_until", {}), ("iterations", {})],
+    }
+
+
+def open_items(subject):
+    """{what it walks: item} of the subjects with openings, hints as in planted_solids ("_mask" on a profile: a cell the mask of a
+    later link makes solid, "_off": a record off the inflow cells, "_clear": n == 0, "_open" on queue_forces: records on an inflow,
+    a profiled and an outflow cell).  Every item that sets a map clears the viscosity first: the two refuse each other."""
+    clear, clear_nu, clear_open, refused = ("clear_solids", {}), ("clear_viscosity", {}), ("clear_openings", {}), {"_refused": True}
+    div, no_hist, profile, flux = dict(what=VIEW_DIVERGENCE, **refused), ("history_stop", {}), ("set_inflow_profile", {}), ("openings_flux", {})
+    A, B = subject.cases[0][:2], subject.cases[-1][:2]
+    if subject.kind == "context":
+        step, step2 = ("step", {}), ("step_n", {"n": 2})
+        return {
+            "a map set before the mask": [clear_nu, clear, _open("channel", inflow=[12.5, 0.0]), step2, _solid("disc"), step, ("openings", {}), flux],
+            "a mask set before the map": [clear_nu, clear_open, _solid("plate"), _open("every rim cell", inflow=[-3.0, 2.5]), step2, ("openings", {}), ("flow_stats", {}), clear_open, step],
+            "a mask replaced, and cleared, behind a map, a step right after each":
+                [clear_nu, _open("seeded", inflow=[12.5, 0.0]), _solid("disc"), step, _solid("seeded"), step, clear, step, flux],
+            "an inflow cell goes solid and comes back: the live counts move, a profile record on it is kept":
+                [clear_nu, clear, _open("channel", seed=3, inflow=[12.5, 0.0]), ("set_inflow_profile", {"_mask": ("seeded", 5)}), ("openings", {}), step, _solid("seeded", seed=5),
+                 ("openings", {}), step, flux, ("inflow_profile", {}), clear, ("openings", {}), step, flux],
+            "set_inflow without and with a profile held, a step after each":
+                [clear_nu, _open("channel", inflow=[12.5, 0.0]), ("set_inflow", {"inflow": [-3.0, 2.5]}), step, profile, ("set_inflow", {"inflow": [40.0, -7.25]}), step,
+                 ("inflow_profile", {}), ("openings", {})],
+            "a new map under a profile: the profile is gone": [clear_nu, _open("channel"), profile, step, _open("inflow only"), ("inflow_profile", {}), step],
+            "a profile replaced and a profile cleared":
+                [clear_nu, _open("every rim cell"), profile, step, profile, step, ("set_inflow_profile", {"_clear": True}), step, ("inflow_profile", {})],
+            "a queued force record on an inflow cell, on a profiled cell and on an outflow cell":
+                [clear_nu, ("forget_forces", {}), _open("channel"), profile, ("queue_forces", {"_open": True}), step2, ("forces_pending", {})],
+            "every operator and poisson_solve_until under a map":
+                [clear_nu, _open("seeded", inflow=[40.0, -7.25]), ("calculate_divergence", {}), ("poisson_solve", {}), ("poisson_continue", {}), ("subtract_gradient", {}),
+                 ("poisson_solve_until", {}), ("residual", {}), ("flow_stats", {})],
+            "a history, a trail and following tracers behind steps with openings":
+                [clear_nu, ("set_tracers", {"follow": True}), ("trail_start", {}), ("history_start", {"every": 1, "capacity": CAPACITY}), _open("channel", inflow=[12.5, 0.0]), step,
+                 step2, ("history", {}), ("trail", {}), ("tracers", {}), no_hist],
+            "a history's samples under a map and a mask":
+                [clear_nu, ("history_start", {"every": 2, "capacity": CAPACITY}), _open("every rim cell"), _solid("channel"), step2, ("history", {}), step, step, ("history", {}), no_hist],
+            # a cleared map gives every plain path back
+            "cleared at 130 x 70: the step seams":
+                [("forget_forces", {"_shape": A}), no_hist, ("set_tracers", {"follow": False}), clear, clear_nu, _opt("OPT_ADVECT_KERNEL", 2), _open("channel"), step2, clear_open,
+                 step2],
+            "cleared at 61 x 81: the one-launch step of a small grid":
+                [_opt("OPT_SOR_KERNEL", 0, _shape=B), _opt("OPT_SOR_FUSE", 0), _opt("OPT_ADVECT_KERNEL", 0), _opt("OPT_SMALL_GRID", 1), clear, clear_nu, _open("seeded"), step,
+                 clear_open, step, step2],
+            "cleared with the switches of the fused step off":
+                [clear_nu, clear, _opt("OPT_ADVECT_KERNEL", 1), _opt("OPT_FUSE_DIVERGENCE", 0), _opt("OPT_FUSE_PROJECTION", 0), _open("every rim cell"), step, clear_open, step, step2,
+                 _opt("OPT_FUSE_DIVERGENCE", 1), _opt("OPT_FUSE_PROJECTION", 1)],
+            "cleared with the seams switched off": [clear_nu, _opt("OPT_STEP_SEAMS", 0), _open("channel"), step2, clear_open, step2, _opt("OPT_STEP_SEAMS", 1)],
+            "the solver's options in front of a solve under a map":
+                [clear_nu, _open("channel"), _opt("OPT_SOR_KERNEL", 1), ("poisson_solve", {}), _opt("OPT_SOR_KERNEL", 2), _opt("OPT_SOR_FUSE", 2), ("poisson_continue", {}),
+                 _opt("OPT_SOR_FUSE", 16), ("poisson_solve_until", {})],
+            "outflow only": [clear_nu, _open("outflow only"), step, flux], "a single inflow cell": [clear_nu, _open("single inflow"), step, flux],
+            "a map with no opening": [clear_nu, _solid("disc"), _open("none"), step2, ("openings", {}), flux],
+            "inflow only: the incompatible Neumann problem": [clear_nu, _open("inflow only", inflow=[-3.0, 2.5]), step, ("residual", {})],
+            # the refusals, a step call behind each
+            "set_openings, refused while a viscosity is set": [clear_open, _visc(0.3, 3), _open("channel", **refused), step, clear_nu],
+            "the divergence view and set_viscosity with a nu, refused while openings are set":
+                [clear_nu, _open("channel"), ("view_scalar", dict(div)), step, ("view_texels", dict(div)), step, _visc(0.3, 3, **refused), step, _visc(0.0, 3), step],
+            "set_inflow and set_inflow_profile, refused without openings": [clear_open, ("set_inflow", dict(refused)), step, ("set_inflow_profile", dict(refused)), step],
+            "a profile with a record off the inflow cells, refused: the profile stays":
+                [clear_nu, _open("channel"), profile, ("set_inflow_profile", dict(_off=True, **refused)), step, ("inflow_profile", {})],
+        }
+    s1, s2, sn, each = ("step_n", {"n": 1}), ("step_n", {"n": 2}), ("step_n", {}), ("step_n_each", {})
+    whole = {"first": 0, "count": subject.batch}
+    flux = ("openings_flux", dict(whole))
+    fresh = [clear_nu, no_hist, ("record_start", {})]                  # what refuses a batch's map, ended (a fresh recorder draws the dye)
+    return {
+        "a map set before the mask": fresh + [clear, _open("channel", per_member=False, inflow=[12.5, 0.0], inflow_per_member=False), s2, _solid("disc", per_member=True), s1, ("openings", {}), flux],
+        "a mask set before the map": fresh + [clear_open, _solid("plate", per_member=False), _open("every rim cell", per_member=True, inflow=[-3.0, 2.5], inflow_per_member=False), s2, ("openings", {}), ("flow_stats", {}), clear_open, s1],
+        "a mask replaced, and cleared, behind a map, a step right after each":
+            fresh + [_open("seeded", per_member=True, inflow=[12.5, 0.0], inflow_per_member=False), _solid("disc", per_member=False), s1, _solid("seeded", per_member=True), s1, clear, s1, flux],
+        "an inflow cell goes solid and comes back: the live counts move, a profile record on it is kept":
+            fresh + [clear, _open("channel", seed=3, per_member=False, inflow=[12.5, 0.0], inflow_per_member=False), ("set_inflow_profile", {"_mask": ("seeded", 5)}), ("openings", {}), s1,
+                     _solid("seeded", seed=5, per_member=False), ("openings", {}), s1, flux, ("inflow_profile", {}), clear, ("openings", {}), s1, flux],
+        "set_inflow without and with a profile held, a step after each":
+            fresh + [_open("channel", per_member=False, inflow=[12.5, 0.0], inflow_per_member=False), ("set_inflow", {"per_member": True}), s1, profile, ("set_inflow", {"per_member": False, "inflow": [40.0, -7.25]}), s1, ("inflow_profile", {}),
+                     ("openings", {})],
+        "a new map under a profile: the profile is gone": fresh + [_open("channel", per_member=False), profile, s1, _open("inflow only", per_member=False), ("inflow_profile", {}), s1],
+        "a profile replaced and a profile cleared":
+            fresh + [_open("every rim cell", per_member=False), ("set_inflow_profile", {"_members": False}), s1, ("set_inflow_profile", {"_members": True}), s1,
+                     ("set_inflow_profile", {"_clear": True}), s1, ("inflow_profile", {})],
+        "a queued force record on an inflow cell, on a profiled cell and on an outflow cell":
+            fresh + [("forget_forces", {}), _open("channel", per_member=False), profile, ("queue_forces", {"_open": True}), s2, ("forces_pending", {})],
+        "step_n_each and poisson_solve_each under per-member maps and inflows":
+            fresh + [("set_tracers", {"follow": True}), _open("channel", per_member=True, inflow_per_member=True), each, ("tracers", {}), ("residual", {}), ("poisson_solve_each", {}), ("residual", {}), flux,
+                     ("poisson_solve", {}), sn],
+        # a cleared map gives every plain path back: the step to a tolerance, the one-launch replay of a timeline, a history
+        "cleared: step_n_until, the one-launch replay and history_start":
+            fresh + [clear, _open("channel"), s2, clear_open, ("poisson_solve_until", {}), ("iterations", {}), ("step_n_until", {}), ("iterations", {}), ("set_tracers", {"follow": False}), ("forget_forces", {}),
+                     ("queue_forces", {"step": 1}), ("step_n", {"n": 3}), ("history_start", dict(every=1, capacity=CAPACITY, **whole)), s1, ("history", {}), no_hist],
+        "cleared behind a step under a map: a step to a tolerance": fresh + [clear, _open("seeded"), sn, clear_open, ("step_n_until", {}), ("iterations", {}), ("poisson_solve_until", {}), ("iterations", {})],
+        "cleared: a viscosity between two maps": [clear_open, _visc([0.05, 0.0, 0.3], 1, per_member=True), sn, clear_nu, _open("channel"), sn],
+        "cleared: a history across two calls": fresh + [clear, clear_open, ("history_start", dict(every=1, capacity=CAPACITY, **whole)), s2, ("history", {}), sn, ("history", {}), no_hist],
+        "outflow only": fresh + [_open("outflow only", per_member=False), s1, flux], "a single inflow cell": fresh + [_open("single inflow", per_member=False), s1, flux],
+        "a map with no opening": fresh + [_solid("disc", per_member=False), _open("none", per_member=False), s2, ("openings", {}), flux],
+        "inflow only: the incompatible Neumann problem": fresh + [_open("inflow only", per_member=False, inflow=[-3.0, 2.5], inflow_per_member=False), each, ("residual", {})],
+        # the refusals, a step call behind each
+        "set_openings, refused while a history is on":
+            [clear, clear_open, clear_nu, ("history_start", dict(every=1, capacity=CAPACITY, **whole)), _open("channel", **refused), sn, no_hist],
+        "set_openings, refused while the recorder draws the divergence view":
+            [clear, clear_open, clear_nu, ("record_start", {}), ("record_view", {"what": VIEW_DIVERGENCE}), _open("channel", **refused), sn, ("record_view", {"what": None})],
+        "set_openings, refused while a viscosity is set": [clear_open, _visc(0.3, 3, per_member=False), _open("channel", **refused), sn, clear_nu],
+        "the calls to a tolerance, history_start, the divergence view and set_viscosity, refused while openings are set":
+            fresh + [clear, ("record_start", {}), _open("channel"), ("step_n_until", dict(refused)), sn, ("poisson_solve_until", dict(refused)), sn, ("history_start", dict(refused)), sn,
+                     ("record_view", dict(div)), sn, ("view_render_members", dict(div)), sn, _visc(0.3, 3, per_member=False, **refused), sn],
+        "set_inflow and set_inflow_profile, refused without openings": [clear_open, ("set_inflow", dict(refused)), sn, ("set_inflow_profile", dict(refused)), sn],
+        "a profile with a record off the inflow cells, refused: the profile stays":
+            fresh + [_open("channel", per_member=False), profile, ("set_inflow_profile", dict(_off=True, **refused)), sn, ("inflow_profile", {})],
+    }
+
+
+def items_of(subject):
+    return record_items(subject) if subject.records else open_items(subject) if subject.opens else viscous_items(subject)
+
+
 def planted_viscous(subject):
-    return list(viscous_items(subject).values())
+    return list(items_of(subject).values())
 
 
 def viscous_handovers(subject):
     """The items as chains for has_handover: the fixed arguments without the hints."""
     return {what: [_link(kind, **{k: v for k, v in fixed.items() if not k.startswith("_")}) for kind, fixed in item]
-            for what, item in viscous_items(subject).items()}
+            for what, item in items_of(subject).items()}
 
 
 def _prologue(subject, index):
@@ -1786,8 +2768,24 @@ def _epilogue(subject):
     """What every sequence of the viscous subjects ends with: a velocity that is not still, a mask with solid and fluid cells, a
     viscosity, a step that diffuses and solves, and the loads of the pressure it left -- so that no sequence compares only loads
     without a face or without a force, or steps without a diffusion that changes a bit."""
+    whole = {"first": 0, "count": subject.batch}
+    if subject.opens:
+        # ... of the subjects with openings: a channel with every rim cell live, a profile on it, a step that solves and the flux
+        # it leaves -- so that no sequence steps only under maps without a live cell, or compares only empty flux records
+        front = [("clear_viscosity", {}), _up("noise"), ("clear_solids", {})]
+        if subject.kind == "context":
+            return front + [_open("channel", inflow=[12.5, 0.0]), ("set_inflow_profile", {}), ("step", {"iters": 5}), ("openings_flux", {})]
+        return [("history_stop", {}), ("record_start", {})] + front + [_open("channel", inflow=[12.5, 0.0], per_member=False, inflow_per_member=False), ("set_inflow_profile", {}),
+                                                                        ("step_n", {"n": 1, "iters": 5}), ("openings_flux", dict(whole))]
     if not subject.viscous:
         return []
+    if subject.records:
+        # ... of the subjects with the three recorders: pivots away from (0, 0), averages of every group, two steps under a mask and
+        # a viscosity, and the friction, the torque and a plane of two samples they leave
+        if subject.kind == "context":
+            return [_up("noise"), ("set_solids", {}), _piv("seeded"), _mean(15, 1), _visc(0.3, 3), ("step_n", {"n": 2, "iters": 5}), ("friction", {}), ("torque", {}), ("mean_sums", {})]
+        return [("history_stop", {}), _up("noise"), ("set_solids", {}), _piv("seeded", per_member=True), _mean(15, 1, **whole), _visc([0.3, 0.0, 0.05], 3, per_member=True),
+                ("step_n", {"n": 2, "iters": 5}), ("friction", dict(whole)), ("torque", dict(whole)), ("mean_sums", {})]
     if subject.kind == "context":
         return [_up("noise"), ("set_solids", {}), _visc(0.3, 3), ("step", {"iters": 5}), ("loads", {})]
     return [("history_stop", {}), _up("noise"), ("set_solids", {}), _visc([0.3, 0.0, 0.05], 3, per_member=True), ("step_n", {"n": 1, "iters": 5}),
@@ -1884,8 +2882,8 @@ def plan(subject):
         dealt[k].append([(kind, dict(fixed)) for kind, fixed in items[at]])
         room[k] -= len(items[at])
     writers = [k for k in subject.kinds() if k not in QUERIES and k not in ("set_option", "forget_forces", "trail_stop", "record_stop", "clear_solids", "history_stop", "clear_viscosity",
-                                                                   "clear_bodies", "loads_stop") and
-               not (subject.still_solves and k == "set_tracers")]
+                                                                   "clear_bodies", "loads_stop", "friction_stop", "torque_stop", "mean_stop", "clear_openings") and
+               not (subject.still_solves and k == "set_tracers") and not (subject.opens and k == "set_viscosity")]      # (a viscosity would end the map)
     plans = []
     for k, mine in enumerate(dealt):
         mine += [[(writers[int(rng.integers(len(writers)))], {})] for _ in range(room[k])]
@@ -2275,6 +3273,176 @@ def fresh_handle_check(oracle, make_handle, dim_x=61, dim_y=81, seed=3):
            ("queue_forces", {"step": 4, "cells": [[7, 7]], "vels": [[1.0, 2.0]]}),
            ("step_n", {"n": 3, "dt": 1 / 30.0, "dx": 1.0, "iters": 5, "omega": 1.96}), ("forces_pending", {}),
            ("step", {"dt": 1 / 30.0, "dx": 1.0, "iters": 5, "omega": 1.96}), ("step", {"dt": 1 / 30.0, "dx": 1.0, "iters": 5, "omega": 1.96})]
+    model, handle = ContextModel(oracle, dim_x, dim_y), make_handle(dim_x, dim_y)
+    for op in ops:
+        want, got = model.apply(op), handle.apply(op)
+        if want is not None:
+            compare(got, want, f"a fresh handle, one order: {op[0]}")
+    compare(handle.snapshot(), model.snapshot(), "a fresh handle, one order")
+
+
+# ---- five for the state the friction, the torque and the averages add -----------------------------------------------------
+class PivotsSurviveAChangeOfTheBodies(ContextModel):
+    """set_bodies to another number of bodies keeps the pivots of the bodies both numbers have (no reset to (0, 0))."""
+
+    def do_set_bodies(self, label_kind, bodies, seed):
+        held = self.pivots
+        super().do_set_bodies(label_kind, bodies, seed)
+        if held is not None and self.pivots is None:
+            self.pivots = np.zeros((self.bodies, 2), np.int32)
+            self.pivots[:min(len(held), self.bodies)] = held[:self.bodies]
+
+
+class NewPivotsReachBack(ContextModel):
+    """set_body_pivots while the torque recorder is on writes the new pivots into the sample already taken."""
+
+    def do_set_body_pivots(self, pivot_kind, bodies, seed):
+        super().do_set_body_pivots(pivot_kind, bodies, seed)
+        if self.torque is not None and self.torque["records"]:
+            last = self.torque["records"][-1].copy()
+            last["pivot2"] = 0 if self.pivots is None else self.pivots
+            self.torque["records"][-1] = last
+
+
+class FrictionSharesTheLoadsCount(ContextModel):
+    """The friction recorder counts with the loads recorder's step counter while that one is on."""
+
+    def do_friction_start(self, every, capacity):
+        super().do_friction_start(every, capacity)
+        if self.loads is not None:
+            self.friction["steps"] = self.loads["steps"]
+
+
+class MeanCountStartsAgainEveryCall(ContextModel):
+    """The averages count the steps of one call, not across calls."""
+
+    def apply(self, op):
+        if op[0] in ("step", "step_n") and self.means is not None and self.means["every"] >= 1 and not self.refuses(*op):
+            self.means["steps"] = 0
+        return super().apply(op)
+
+
+class MeanRestartKeepsTheSums(ContextModel):
+    """mean_start while on zeroes the counts and keeps the sums of the planes both masks have."""
+
+    def do_mean_start(self, what, every):
+        held = self.means
+        super().do_mean_start(what, every)
+        if held is not None:
+            self.means["sums"].update({k: a for k, a in held["sums"].items() if k in self.means["sums"]})
+
+
+RECORD_STAND_INS = (PivotsSurviveAChangeOfTheBodies, NewPivotsReachBack, FrictionSharesTheLoadsCount, MeanCountStartsAgainEveryCall, MeanRestartKeepsTheSums)
+
+
+# ---- and five for the state the openings and the profiles add --------------------------------------------------------------
+class OldCodesBehindAMap(ContextModel):
+    """A change of the mask behind a map does not form the openings' codes again: while the map stays, every call that follows
+    the openings' rule, and the live counts, go by the mask that was held when the map was set."""
+    coded = None
+
+    def do_set_openings(self, open_kind, seed, inflow):
+        super().do_set_openings(open_kind, seed, inflow)
+        self.coded = self.mask
+
+    def apply(self, op):
+        stale = self.open is not None and op[0] in SOLVES + ("calculate_divergence", "subtract_gradient", "residual", "flow_stats", "openings", "openings_flux")
+        if not stale or self.refuses(*op):
+            return super().apply(op)
+        held, self.mask = self.mask, self.coded
+        try:
+            return super().apply(op)
+        finally:
+            self.mask = held
+
+
+class NewMapKeepsTheProfile(ContextModel):
+    """A new map keeps the records of the profile that still name an inflow cell."""
+
+    def do_set_openings(self, open_kind, seed, inflow):
+        held = self.profile
+        super().do_set_openings(open_kind, seed, inflow)
+        self.profile = [r for r in held or [] if self.open[r[0][1], r[0][0]] == opening_rule.INFLOW] or None
+
+
+class SetInflowDropsTheProfile(ContextModel):
+    """A new uniform inflow drops the profile."""
+
+    def do_set_inflow(self, inflow):
+        super().do_set_inflow(inflow)
+        self.profile = None
+
+
+class SolidInflowRecordIsForgotten(ContextModel):
+    """A record on an inflow cell that a new mask makes solid is forgotten, not kept for the day the cell is fluid again."""
+
+    def do_set_solids(self, mask_kind, seed):
+        super().do_set_solids(mask_kind, seed)
+        if self.profile:
+            self.profile = [r for r in self.profile if not self.mask[r[0][1], r[0][0]]] or None
+
+
+class ClearedOpeningsStillOpen(ContextModel):
+    """The first step after clear_openings still follows the map that was cleared where a mask is set (a stale hook)."""
+    stale = None
+
+    def do_clear_openings(self):
+        self.stale = (self.open, self.inflow, self.profile)
+        super().do_clear_openings()
+
+    def do_set_openings(self, open_kind, seed, inflow):
+        self.stale = None
+        super().do_set_openings(open_kind, seed, inflow)
+
+    def step_once(self, dt, dx, iters, omega, until=None):
+        if self.open is None and self.stale is not None and self.stale[0] is not None and self.mask is not None:
+            (self.open, self.inflow, self.profile), self.stale = self.stale, None
+            try:
+                return super().step_once(dt, dx, iters, omega, until)
+            finally:
+                self.open, self.inflow, self.profile = None, (0.0, 0.0), None
+        self.stale = None
+        return super().step_once(dt, dx, iters, omega, until)
+
+
+OPEN_STAND_INS = (OldCodesBehindAMap, NewMapKeepsTheProfile, SetInflowDropsTheProfile, SolidInflowRecordIsForgotten, ClearedOpeningsStillOpen)
+
+
+def later_stand_in_subject(cls):
+    return "record-context" if cls in RECORD_STAND_INS else "open-context"
+
+
+def record_fresh_handle_check(oracle, make_handle, dim_x=61, dim_y=81, seed=3):
+    """The kind of check the direct tests of the friction, the torque and the averages are: a fresh handle and every new call
+    once, in one fixed order -- mask, labels, pivots, the recorders and the averages started together, ONE step call, the reads,
+    the stops."""
+    up = lambda field: ("upload", {"field": field, "texture_kind": "noise", "seed": seed})
+    ops = [up(FV), up(FC), ("set_solids", {"mask_kind": "disc", "seed": 7}), ("set_bodies", {"label_kind": "halves", "bodies": 2, "seed": 1}),
+           ("set_body_pivots", {"pivot_kind": "seeded", "bodies": 2, "seed": 4}), ("body_pivots", {}), ("loads_start", {"every": 2, "capacity": 4}),
+           ("friction_start", {"every": 2, "capacity": 4}), ("torque_start", {"every": 1, "capacity": 4}), ("mean_start", {"what": 15, "every": 2}),
+           ("step_n", {"n": 4, "dt": 1 / 30.0, "dx": 0.5, "iters": 5, "omega": 1.5}), ("friction", {}), ("torque", {}), ("friction_history", {}), ("torque_history", {}),
+           ("mean_info", {})] + [("mean_sums", {"plane": k}) for k in range(mean_rule.PLANES)] + \
+          [("mean_sample", {}), ("mean_sums", {"plane": 4}), ("mean_stop", {}), ("friction_stop", {}), ("torque_stop", {}), ("loads_stop", {}),
+           ("set_body_pivots", {"pivot_kind": None, "bodies": 2, "seed": 0}), ("body_pivots", {}), ("torque", {})]
+    model, handle = ContextModel(oracle, dim_x, dim_y), make_handle(dim_x, dim_y)
+    for op in ops:
+        want, got = model.apply(op), handle.apply(op)
+        if want is not None:
+            compare(got, want, f"a fresh handle, one order: {op[0]}")
+    compare(handle.snapshot(), model.snapshot(), "a fresh handle, one order")
+
+
+def open_fresh_handle_check(oracle, make_handle, dim_x=61, dim_y=81, seed=3):
+    """The same for the openings: a mask, ONE map behind it, the inflow changed before the profile is set, one step call, the
+    reads, every operator once; cleared once with the mask cleared too, every field uploaded again, one step."""
+    up = lambda field: ("upload", {"field": field, "texture_kind": "noise", "seed": seed})
+    solve = {"dx": 0.5, "iters": 5, "omega": 1.5}
+    ops = [up(FV), up(FC), ("set_solids", {"mask_kind": "disc", "seed": 7}), ("set_openings", {"open_kind": "channel", "seed": 1, "inflow": [12.5, 0.0]}),
+           ("set_inflow", {"inflow": [-3.0, 2.5]}), ("set_inflow_profile", {"cells": [[0, 5], [0, 40], [0, 5]], "vels": [[1.0, 2.0], [-3.0, 2.5], [7.5, -1.0]]}),
+           ("openings", {}), ("inflow_profile", {}), ("step_n", dict({"n": 3, "dt": 1 / 30.0}, **solve)), ("openings_flux", {}), ("calculate_divergence", {"dx": 0.5}),
+           ("poisson_solve", solve), ("residual", {"dx": 0.5}), ("poisson_continue", dict(solve, iters=9)), ("subtract_gradient", {"dx": 0.5}), ("flow_stats", {"dx": 0.5}),
+           ("openings_flux", {}), ("clear_openings", {}), ("clear_solids", {}), ("openings", {}), ("inflow_profile", {}), up(FV), up(FC), up(FD), up(FP),
+           ("step", dict({"dt": 1 / 30.0}, **solve))]
     model, handle = ContextModel(oracle, dim_x, dim_y), make_handle(dim_x, dim_y)
     for op in ops:
         want, got = model.apply(op), handle.apply(op)

@@ -15,7 +15,13 @@ companions of a viscous step, a batch's coefficients staged call after call, the
 replaced and reset, a recorder across calls, restarted, sampling without a mask), the new refusals, planted and nowhere else --
 all read from the op lists -- and, evaluated on the model, that no sequence compares only empty loads or diffusions that change
 nothing.  Five more faulty models are caught by these sequences and missed by a fresh handle that makes each new call once.
-The op lists of solid-context and solid-batch are pinned as they were before this vocabulary."""
+The op lists of solid-context and solid-batch are pinned as they were before this vocabulary.
+
+Four more subjects walk the features that came after: record-context and record-batch the friction and the torque recorder, the
+pivots and the averages on top of the viscous vocabulary, open-context and open-batch the openings, the inflow profiles and the
+flux on top of the solids'.  Their census reads every planted chain and every refusal -- with its code -- from the op lists;
+the vacuity conditions are evaluated on the model; ten more faulty models are caught by these sequences and missed by a fresh
+handle.  The op lists of viscous-context and viscous-batch are pinned as they were before."""
 import copy
 import functools
 import hashlib
@@ -23,8 +29,13 @@ import hashlib
 import numpy as np
 import pytest
 
+import friction_rule
+import inflow_rule
 import load_rule
+import mean_rule
+import opening_rule
 import sequence_model as sm
+import torque_rule
 from oracle import loader
 
 IDS = [s.name for s in sm.SUBJECTS]
@@ -72,6 +83,18 @@ def test_the_sequences_from_before_viscosity_and_loads_have_not_moved(name):
     subject, seqs = sequences(name)
     assert subject.solids and not subject.viscous and subject.length == 36
     assert hashlib.sha256(repr([seqs[case] for case in subject.cases]).encode()).hexdigest() == PINNED_SOLIDS[name]
+
+
+# ... and the two with viscosity and loads, as they were before the openings', the friction's, the torque's and the averages'
+PINNED_VISCOUS = {"viscous-context": "93ef1888e616857f3e7ce146876eadc52db13c104f8db6b0bbe3bd47e27e4240",
+                  "viscous-batch": "b655f2643b07acfba0b73fd585cca85636d7c247fb786a68c862f208cd0722bf"}
+
+
+@pytest.mark.parametrize("name", sorted(PINNED_VISCOUS))
+def test_the_sequences_from_before_openings_and_recorders_have_not_moved(name):
+    subject, seqs = sequences(name)
+    assert subject.viscous and not subject.records and not subject.opens and subject.length == sm.VISCOUS_LENGTH[subject.kind]
+    assert hashlib.sha256(repr([seqs[case] for case in subject.cases]).encode()).hexdigest() == PINNED_VISCOUS[name]
 
 
 @pytest.mark.parametrize("name", IDS)
@@ -242,8 +265,10 @@ def test_a_failure_message_carries_what_replay_needs(oracle):
 
 
 # ---- solids and histories ------------------------------------------------------------------------------------------------
-SOLID_IDS = [s.name for s in sm.SUBJECTS if s.solids and not s.viscous]
-VISCOUS_IDS = [s.name for s in sm.SUBJECTS if s.viscous]
+SOLID_IDS = [s.name for s in sm.SUBJECTS if s.solids and not s.viscous and not s.opens]
+VISCOUS_IDS = [s.name for s in sm.SUBJECTS if s.viscous and not s.records]
+RECORD_IDS = [s.name for s in sm.SUBJECTS if s.records]
+OPEN_IDS = [s.name for s in sm.SUBJECTS if s.opens]
 HONOURED = {"context": ("step", "step_n", "calculate_divergence", "poisson_solve", "poisson_continue", "subtract_gradient", "residual",
                         "poisson_solve_until", "flow_stats"),
             "batch": ("step_n", "step_n_each", "poisson_solve", "poisson_solve_each", "flow_stats")}
@@ -258,7 +283,8 @@ def walks(name):
         walk = []
         for k, op, gate, refused in sm.gated(ops, subject, case):
             state = {"set": gate.masks is not None, "mixed": gate.mixed(), "masks": gate.masks, "per_member": gate.masks is not None and len(gate.masks) > 1,
-                     "hist": None if gate.hist is None else list(gate.hist), "rec": gate.rec, "view": gate.view}
+                     "hist": None if gate.hist is None else list(gate.hist), "rec": gate.rec, "view": gate.view,
+                     "code": gate.code(*op) if refused else None}
             walk.append((k, op, state, refused))
         out.append((case, walk))
     return subject, out
@@ -382,20 +408,20 @@ def test_census_a_queued_record_lies_on_a_solid_cell_and_one_on_a_fluid_cell_of_
     assert hits
 
 
-@pytest.mark.parametrize("name", SOLID_IDS + VISCOUS_IDS)
+@pytest.mark.parametrize("name", SOLID_IDS + VISCOUS_IDS + RECORD_IDS + OPEN_IDS)
 def test_the_model_refuses_what_the_census_says_is_refused(name, oracle):
-    """The models decide from the fields and counts they hold, the census from the op list: the same ops, and a refused op
-    changes nothing in the model."""
+    """The models decide from the fields and counts they hold, the census from the op list: the same ops, the same code, and a
+    refused op changes nothing in the model."""
     subject, cases = walks(name)
     seqs = sequences(name)[1]
     for case, walk in cases:
         model = subject.model(oracle, case)
-        for (k, op, _, refused) in walk:
+        for (k, op, st, refused) in walk:
             before = model.snapshot()
             got = model.apply(op)
             assert (isinstance(got, dict) and "refused" in got) == refused, (name, case, k, op)
             if refused:
-                assert got["refused"] == sm.ERR_STATE
+                assert got["refused"] == st["code"] and (st["code"] == sm.ERR_STATE or name in RECORD_IDS + OPEN_IDS)
                 sm.compare(model.snapshot(), before, "a refused op")
 
 
@@ -471,7 +497,10 @@ def test_the_two_viscous_subjects_and_their_shapes():
         assert s.solids and not s.large and 40 <= s.length <= 50
         assert set(sm.SOLID_WRITERS + sm.SOLID_QUERIES) <= set(s.kinds())
         assert new - set(s.kinds()) == (set() if s.kind == "context" else {"diffuse_velocity"})
-    assert not any(new & set(s.kinds()) for s in sm.SUBJECTS if not s.viscous), "no older subject's deck has a new kind"
+    assert not any(new & set(s.kinds()) for s in sm.SUBJECTS if not s.viscous and not s.opens), "no older subject's deck has a new kind"
+    for s in sm.SUBJECTS:       # (the subjects with openings, which came later, take the two calls that plant their refusals and no other)
+        if s.opens:
+            assert new & set(s.kinds()) == {"set_viscosity", "clear_viscosity"}
     assert set(sm.LABEL_KINDS) == {"all one", "halves", "with zeros", "sixteen"}
 
 
@@ -673,18 +702,35 @@ def test_census_the_new_refusals_are_the_planted_ones(name):
     assert sum(r for _, walk in cases for *_, r in walk) == len(VISCOUS_REFUSALS[name]), "only the planted refusals happen"
 
 
-@pytest.mark.parametrize("name", VISCOUS_IDS)
+def records_of(out, dtype):
+    """The records a query returned as raw bytes, as a flat array of the struct."""
+    return np.ascontiguousarray(out["records" if "records" in out else "record"]).reshape(-1).view(dtype)
+
+
+@pytest.mark.parametrize("name", VISCOUS_IDS + RECORD_IDS + OPEN_IDS)
 def test_no_sequence_passes_vacuously(name, oracle):
     """Evaluated on the model: in every sequence a compared load has faces and a force, and a viscous step changes the velocity's
-    bits against the same step with the viscosity taken away."""
+    bits against the same step with the viscosity taken away.  In every sequence with the three recorders a compared friction
+    record has a force, a compared torque record has both moments about a pivot that is not (0, 0), and a plane of at least two
+    samples is downloaded under a mask; in every sequence with openings a step runs under a map with a live inflow and a live
+    outflow cell, a compared flux record has both sums, and a step runs under a profile that differs from the uniform inflow on
+    a live cell.  (check_finite of the model's own run covers that the fields stay finite.)"""
     subject, seqs = sequences(name)
     for case, ops in seqs.items():
         model = subject.model(oracle, case)
         loaded = diffused = False
+        seen = set()
         for op in ops:
             kind = op[0]
             twin = None
             members = model.m if subject.kind == "batch" else [model]
+            if kind in sm.STEPS and not model.refuses(*op):
+                for m in members:
+                    if m.open is not None and all(sm.live_cells(m.open, m.mask)):
+                        seen.add("a step under a live inflow and a live outflow cell")
+                    fluid_inflow = opening_rule.inflow_cells(m.open, m.mask) if m.open is not None else None
+                    if m.profile and any(fluid_inflow[j, i] and tuple(np.float32(uv)) != tuple(np.float32(m.inflow)) for (i, j), uv in inflow_rule.unique(m.profile)):
+                        seen.add("a step under a profile that differs from the uniform inflow on a live cell")
             if kind in sm.STEPS and any(m.visc is not None and m.visc[0] > 0 and m.visc[1] > 0 for m in members) and not model.refuses(*op):
                 twin = copy.deepcopy(model, {id(oracle): oracle})
                 for m in (twin.m if subject.kind == "batch" else [twin]):
@@ -697,8 +743,26 @@ def test_no_sequence_passes_vacuously(name, oracle):
             if kind in ("loads", "loads_history") and "records" in out and out["records"].size:
                 rec = np.ascontiguousarray(out["records"]).view(load_rule.DTYPE).reshape(-1)
                 loaded |= bool(((rec["faces"].sum(axis=-1) > 0) & ((rec["fx"] != 0) | (rec["fy"] != 0))).any())
-        assert loaded, (name, case, "no compared load has faces and a force")
-        assert diffused, (name, case, "no viscous step changes the velocity")
+            if not isinstance(out, dict) or "refused" in out:
+                continue
+            if kind in ("friction", "friction_history") and out["records"].size:
+                rec = records_of(out, friction_rule.DTYPE)
+                seen |= {"a friction record with a force"} if ((rec["fx"] != 0) | (rec["fy"] != 0)).any() else set()
+            if kind in ("torque", "torque_history") and out["records"].size:
+                rec = records_of(out, torque_rule.DTYPE)
+                seen |= {"a torque record with both moments about a pivot"} if ((rec["mp"] != 0) & (rec["mf"] != 0) & (rec["pivot2"] != 0).any(axis=-1)).any() else set()
+            if kind == "mean_sums" and model.means["samples"] >= 2 and any(sm.mixed(m.mask) for m in members):
+                seen.add("a plane of two samples under a mask")
+            if kind == "openings_flux":
+                rec = records_of(out, inflow_rule.FLUX_DTYPE)
+                seen |= {"a flux record with both sums"} if ((rec["inflow"] != 0) & (rec["outflow"] != 0)).any() else set()
+        if name in VISCOUS_IDS:
+            assert loaded, (name, case, "no compared load has faces and a force")
+            assert diffused, (name, case, "no viscous step changes the velocity")
+        want = {"a friction record with a force", "a torque record with both moments about a pivot", "a plane of two samples under a mask"} if name in RECORD_IDS else \
+               {"a step under a live inflow and a live outflow cell", "a flux record with both sums",
+                "a step under a profile that differs from the uniform inflow on a live cell"} if name in OPEN_IDS else set()
+        assert want <= seen, (name, case, want - seen)
 
 
 def make_stand_in(cls, oracle):
@@ -724,3 +788,367 @@ def test_a_planted_viscosity_or_loads_bug_is_caught_by_the_sequences_and_missed_
         sm.viscous_fresh_handle_check(oracle, lambda dim_x, dim_y: cls(oracle, dim_x, dim_y))
         solid_fresh_handle_check(oracle, lambda dim_x, dim_y: cls(oracle, dim_x, dim_y))
         sm.fresh_handle_check(oracle, lambda dim_x, dim_y: cls(oracle, dim_x, dim_y))
+
+
+# ---- friction, torque and averages; openings, profiles and the flux ---------------------------------------------------------
+def later_walks(name):
+    """[(case, [(index, op, what the Gate knows while the op runs, the path state, refused)])] of the four later subjects."""
+    subject, seqs = sequences(name)
+    out = []
+    for case, ops in seqs.items():
+        walk = []
+        for (k, op, gate, refused), (_, _, path) in zip(sm.gated(ops, subject, case), sm.path_states(ops)):
+            st = {"set": gate.masks is not None, "mixed": gate.mixed(), "masks": gate.masks, "hist": None if gate.hist is None else list(gate.hist), "trail": gate.trail,
+                  "rec": gate.rec, "view": gate.view, "visc": None if gate.visc is None else dict(gate.visc), "labels": gate.labels,
+                  "loads": None if gate.loads is None else list(gate.loads), "friction": None if gate.friction is None else list(gate.friction),
+                  "torque": None if gate.torque is None else list(gate.torque), "means": None if gate.means is None else dict(gate.means),
+                  "ranges": dict(gate.ranges), "bodies": gate.bodies, "pivots": gate.pivots, "open": gate.open, "inflow": gate.inflow, "profile": gate.profile,
+                  "live": gate.live(), "code": gate.code(*op) if refused else None}
+            walk.append((k, op, st, path, refused))
+        out.append((case, walk))
+    return subject, out
+
+
+def has_room(recorder, op):
+    every, capacity, steps = recorder
+    return due(recorder, op) <= capacity - steps // every
+
+
+def fused(subject, case, op, st, path):
+    """The step call that runs fused when nothing cuts it: a context's step_n over its seams on the seam shape (every condition
+    set), a batch's one-launch replay of a timeline (a record in a later step of the call, no following set)."""
+    if st["set"] or st["visc"] is not None or st["hist"] is not None or st["open"] is not None:
+        return False
+    if subject.kind == "context":
+        return case[:2] == (130, 70) and sm.takes_the_seam(op, path) and path["options"]["OPT_ADVECT_KERNEL"] == 2
+    return op[0] == "step_n" and op[1]["n"] >= 2 and not path["follow"] and any(1 <= s < op[1]["n"] for s in path["pending"])
+
+
+def test_the_four_later_subjects_and_their_shapes():
+    by_name = {s.name: s for s in sm.SUBJECTS}
+    for new, old in (("record-context", "viscous-context"), ("record-batch", "viscous-batch"), ("open-context", "solid-context"), ("open-batch", "solid-batch")):
+        a, b = by_name[new], by_name[old]
+        assert [c[:2] for c in a.cases] == [c[:2] for c in b.cases] and a.batch == b.batch and a.kind == b.kind and not a.large
+        assert set(b.kinds()) <= set(a.kinds()), "on top of the older deck"
+    for name in RECORD_IDS:
+        assert set(by_name[name].kinds()) - set(by_name[name.replace("record", "viscous")].kinds()) == set(sm.RECORD_WRITERS + sm.RECORD_QUERIES)
+        assert by_name[name].length == sm.RECORD_LENGTH[by_name[name].kind]
+    for name in OPEN_IDS:
+        assert set(by_name[name].kinds()) - set(by_name[name.replace("open", "solid")].kinds()) == set(sm.OPEN_WRITERS + sm.OPEN_QUERIES)
+        assert by_name[name].length == sm.OPEN_LENGTH[by_name[name].kind]
+    new = set(sm.RECORD_WRITERS + sm.RECORD_QUERIES + sm.OPEN_WRITERS + sm.OPEN_QUERIES) - {"set_viscosity", "clear_viscosity"}
+    assert not any(new & set(s.kinds()) for s in sm.SUBJECTS if not (s.records or s.opens)), "no older subject's deck has a new kind"
+    for s in sm.SUBJECTS[-4:]:      # the shortest the deck fits in: one op less and the planner has no room
+        shorter = copy.copy(s)
+        shorter.length = s.length - 1
+        with pytest.raises(AssertionError, match="does not fit"):
+            sm.plan(shorter)
+
+
+def test_the_records_and_the_maps_of_the_model_are_the_packages(sfl):
+    assert friction_rule.DTYPE == sfl.BODY_FRICTION_DTYPE and friction_rule.DTYPE.itemsize == 48
+    assert torque_rule.DTYPE == sfl.BODY_TORQUE_DTYPE and torque_rule.DTYPE.itemsize == 64
+    assert inflow_rule.FLUX_DTYPE == sfl.OPEN_FLUX_DTYPE and sm.FLUX_BYTES == 40
+    assert sm.ERR_INVALID == sfl.capi.ERR_INVALID and sfl.capi.MEAN_ALL == mean_rule.ALL == 15
+    for kind in sm.OPEN_KINDS:
+        for member in (None, 0, 2):
+            for shape in ((130, 70), (61, 81), (7, 9)):
+                m = sm.open_map(kind, *shape, 3, member)
+                assert m.dtype == np.uint8 and m.shape == shape[::-1] and opening_rule.check_map(m) is None
+    count = lambda kind: sm.live_cells(sm.open_map(kind, 61, 81, 3), None)
+    assert count("channel") == (79, 79) and count("inflow only") == (79, 0) and count("outflow only") == (0, 79 + 59) and count("none") == (0, 0)
+    assert count("single inflow") == (1, 0) and sum(count("every rim cell")) == 2 * (79 + 59) and min(count("every rim cell")) > 0
+    assert all(min(sm.live_cells(sm.open_map(kind, 7, 9, seed, member), None)) > 0 for kind in sm.LIVE_OPEN_KINDS for seed in range(4) for member in (None,))
+    for kind in sm.PIVOT_KINDS:
+        p = sm.body_pivots_of(kind, 16, 61, 81, 5, member=1)
+        assert p.dtype == np.int32 and p.shape == (16, 2) and (p != 0).any(axis=1).all() and np.abs(p).max() <= torque_rule.MAX_PIVOT2
+
+
+def test_float64_planes_are_compared_as_their_bit_patterns():
+    a = np.array([[0.0, np.nan, 1.5]])
+    sm.compare({"plane": a.copy()}, {"plane": a}, "a NaN equals itself")
+    for other in (np.array([[-0.0, np.nan, 1.5]]), np.array([[0.0, -np.nan, 1.5]]), np.array([[0.0, np.nan, np.nextafter(1.5, 2)]])):
+        with pytest.raises(AssertionError, match="differ bitwise"):
+            sm.compare({"plane": other}, {"plane": a}, "+0.0 is not -0.0, a NaN of another sign is another NaN, one ulp is a difference")
+    with pytest.raises(AssertionError):
+        sm.compare({"plane": a.astype(np.float32)}, {"plane": a}, "no cast on either side")
+
+
+@pytest.mark.parametrize("name", RECORD_IDS)
+def test_census_the_recorders_the_pivots_and_the_averages_are_walked(name):
+    subject, cases = later_walks(name)
+    batch, seen, whats = subject.kind == "batch", set(), set()
+    for case, walk in cases:
+        five = 0                        # step calls in a row with all five counters on
+        sampled = None                  # the pivots under which the torque recorder that is on has taken a sample
+        zero_run = []                   # every == 0: fused call, mean_sample, fused call, mean_sample
+        for k, op, st, path, refused in walk:
+            kind, a = op
+            behind = walk[k + 1] if k + 1 < len(walk) else None
+            on = {n: st[n] for n in ("hist", "loads", "friction", "torque") if st[n] is not None}
+            averaging = st["means"] is not None and st["means"]["every"] >= 1
+            if kind == "mean_start" and not refused:
+                whats.add(a["what"])
+                if st["means"] is not None and st["means"]["samples"] > 0:
+                    seen.add("the averages restarted while on, behind a sample")
+            if kind in ("friction_start", "torque_start") and st[kind[:-len("_start")]] is not None and st[kind[:-len("_start")]][2] > 0:
+                seen.add(f"{kind}: a restart while on")
+            if kind in sm.STEPS and not refused:
+                if len(on) == 4 and averaging:
+                    everys = {r[0] for r in on.values()} | {st["means"]["every"]}
+                    five = five + 1 if len(everys) == 5 else 0
+                    if five >= 3 and any((r[2] + a.get("n", 1)) % r[0] for r in on.values()):
+                        seen.add("all five counters on, five periods, three calls, remainders")
+                    if batch and len({st["ranges"][n] for n in ("loads", "friction", "torque", "mean")}) == 4:
+                        seen.add("the ranges of the recorders differ")
+                else:
+                    five = 0
+                for n in ("friction", "torque"):
+                    if st[n] is not None:
+                        seen.add(f"{n}: counted through {kind}")
+                        if due(st[n], op) > 0 and in_force(st) and st["mixed"]:
+                            seen.add(f"{n}: a sample behind a viscous step under a mask")
+                if averaging:
+                    seen.add(f"averages: counted through {kind}")
+                    m, n = st["means"], a.get("n", 1)
+                    if fused(subject, case, op, st, path) and any((m["steps"] + j) % m["every"] == 0 for j in range(1, n)):
+                        seen.add("averages with every >= 1: a sample due inside a call that would run fused")
+                if st["torque"] is not None and due(st["torque"], op) > 0 and st["mixed"]:
+                    now = ("none", 0) if st["pivots"] is None else (st["pivots"]["pivot_kind"], st["pivots"]["seed"])
+                    if sampled is not None and sampled != now:
+                        seen.add("torque samples before and behind a change of the pivots while recording")
+                    sampled = sampled or now
+                if st["means"] is not None and st["means"]["every"] == 0 and fused(subject, case, op, st, path):
+                    zero_run = zero_run + ["fused"] if zero_run[-1:] != ["fused"] else zero_run
+            if kind in ("torque_start", "torque_stop"):
+                sampled = None
+            if kind == "mean_sample" and not refused and st["means"]["every"] == 0 and zero_run[-1:] == ["fused"]:
+                zero_run.append("sample")
+                if zero_run[-4:] == ["fused", "sample", "fused", "sample"]:
+                    seen.add("averages with every == 0: mean_sample between fused calls")
+            if kind in ("mean_start", "mean_stop"):
+                zero_run = []
+            if kind == "mean_stop" and averaging and behind is not None and fused(subject, case, behind[1], behind[2], behind[3]) and not behind[4]:
+                seen.add("mean_stop, then the fused path again")
+            if kind in ("set_solids", "clear_solids") and not refused and st["set"] and st["friction"] and st["torque"] and averaging and behind[1][0] in sm.STEPS:
+                seen.add(f"{kind} under a mask while the three record, a step behind it")
+            if kind == "set_bodies" and not refused and st["pivots"] is not None:
+                same = sm.LABEL_KINDS[a["label_kind"]] == st["bodies"]
+                asked = any(op2[0] == "body_pivots" for _, op2, *_ in walk[k + 1:k + 3])
+                seen |= {"set_bodies to the same number with pivots set" if same else "set_bodies to another number with pivots set"} if asked else set()
+            if kind == "set_bodies" and not refused and st["pivots"] is None and st["bodies"] != sm.LABEL_KINDS[a["label_kind"]] and \
+                    any(o2[0] == "set_body_pivots" and o2[1]["pivot_kind"] and o2[1]["bodies"] == sm.LABEL_KINDS[a["label_kind"]] and not r2 for _, o2, _, _, r2 in walk[:k]) and \
+                    walk[k + 1][1][0] == "body_pivots":
+                seen.add("set_bodies back to a number whose pivots were put back to zero, the pivots read behind it")
+            if kind == "clear_bodies" and not refused and st["pivots"] is not None and st["bodies"] != 1:
+                seen.add("clear_bodies with pivots set")
+            if kind == "set_body_pivots" and not refused and a["pivot_kind"] is None and st["pivots"] is not None:
+                seen.add("set_body_pivots(NULL) over pivots")
+            if refused:
+                assert behind[1][0] in sm.STEPS and not behind[4], (name, case, k, op, "a step call the header takes follows")
+                if kind in ("set_bodies", "clear_bodies"):
+                    assert st["loads"] is None and len(on) - (st["hist"] is not None) == 1
+                    seen.add(f"{kind}, refused under the {'friction' if st['friction'] else 'torque'} recorder alone")
+                elif kind in sm.STEPS:
+                    full = [n for n, r in on.items() if not has_room(r, op)]
+                    assert len(on) == 4 and averaging and len(full) == 1 and full[0] in ("friction", "torque"), (name, case, k, full)
+                    assert behind[1][1].get("n", 1) == 2, "the call behind it fits: two samples, the capacity"
+                    asked = {op2[0] for _, op2, *_ in walk[k + 2:k + 8]}
+                    assert {"history", "loads_history", "friction_history", "torque_history", "mean_info"} <= asked, "every count is read behind it"
+                    seen.add(f"a full {full[0]} recorder refuses the call whole while the others have room")
+                elif kind == "set_body_pivots":
+                    assert st["code"] == sm.ERR_INVALID and a["bodies"] != st["bodies"] and st["pivots"] is not None
+                    assert any(op2[0] == "body_pivots" for _, op2, *_ in walk[k + 2:k + 4])
+                    seen.add("set_body_pivots with another number of bodies, refused")
+                else:
+                    assert kind == "mean_sums" and st["code"] == sm.ERR_INVALID and not st["means"]["what"] & mean_rule.GROUP_OF[a["plane"]]
+                    seen.add("a plane outside what, refused")
+    want = {"the averages restarted while on, behind a sample", "friction_start: a restart while on", "torque_start: a restart while on",
+            "all five counters on, five periods, three calls, remainders", "friction: a sample behind a viscous step under a mask",
+            "torque: a sample behind a viscous step under a mask", "averages with every >= 1: a sample due inside a call that would run fused",
+            "torque samples before and behind a change of the pivots while recording", "averages with every == 0: mean_sample between fused calls",
+            "mean_stop, then the fused path again", "set_solids under a mask while the three record, a step behind it",
+            "clear_solids under a mask while the three record, a step behind it", "set_bodies to the same number with pivots set",
+            "set_bodies to another number with pivots set", "clear_bodies with pivots set",
+            "set_bodies back to a number whose pivots were put back to zero, the pivots read behind it", "set_body_pivots(NULL) over pivots",
+            "a full friction recorder refuses the call whole while the others have room", "a full torque recorder refuses the call whole while the others have room",
+            "set_body_pivots with another number of bodies, refused", "a plane outside what, refused"}
+    want |= {f"{kind}, refused under the {n} recorder alone" for kind in ("set_bodies", "clear_bodies") for n in ("friction", "torque")}
+    steps = ("step_n", "step_n_each") if batch else ("step", "step_n")
+    want |= {f"{n}: counted through {kind}" for n in ("friction", "torque", "averages") for kind in steps}
+    want |= {"the ranges of the recorders differ", "averages: counted through step_n_until"} if batch else set()
+    assert want <= seen, (name, want - seen)
+    assert sum(r for _, walk in cases for *_, r in walk) == 8, "only the planted refusals happen"
+    groups = lambda w: bin(w).count("1")
+    assert {min(groups(w), 2) for w in whats if w != 15} == {1, 2} and 15 in whats, ("what masks of one group, of several and of all", whats)
+
+
+LATER_STAND_INS = sm.RECORD_STAND_INS + sm.OPEN_STAND_INS
+
+
+@pytest.mark.parametrize("cls", LATER_STAND_INS, ids=[c.__name__ for c in LATER_STAND_INS])
+def test_a_planted_recorder_or_openings_bug_is_caught_by_the_sequences_and_missed_by_a_fresh_handle(cls, oracle):
+    subject, seqs = sequences(sm.later_stand_in_subject(cls))
+    hits = caught(subject, seqs, oracle, cls, ("lazy", "probing"))
+    print(cls.__name__, hits)
+    assert hits, f"{cls.__name__}: no sequence of {subject.name} saw the fault"
+    assert all("seed" in h[2] and "mode" in h[2] and "op " in h[2] for h in hits), "a failure names seed, mode and op"
+    make = lambda dim_x, dim_y: cls(oracle, dim_x, dim_y)       # every new call once on a fresh handle, one order: nothing seen
+    sm.record_fresh_handle_check(oracle, make)
+    sm.open_fresh_handle_check(oracle, make)
+    sm.viscous_fresh_handle_check(oracle, make)
+    solid_fresh_handle_check(oracle, make)
+    sm.fresh_handle_check(oracle, make)
+
+
+def test_a_map_with_no_opening_gives_the_solids_bits_and_with_no_solid_cell_the_plain_step(oracle):
+    """The anchor of "OPENINGS" on the model: the same ops with and without a map that has no opening, under a mask and without."""
+    up = lambda field: ("upload", {"field": field, "texture_kind": "noise", "seed": 5})
+    step = ("step_n", {"n": 2, "dt": 0.1, "dx": 0.5, "iters": 9, "omega": 1.96})
+    for mask in (("set_solids", {"mask_kind": "seeded", "seed": 2}), ("clear_solids", {})):
+        a, b = sm.ContextModel(oracle, 33, 18), sm.ContextModel(oracle, 33, 18)
+        for op in (up(sm.FV), up(sm.FC), mask):
+            a.apply(op), b.apply(op)
+        a.apply(("set_openings", {"open_kind": "none", "seed": 0, "inflow": [12.5, 0.0]}))
+        for op in (step, ("calculate_divergence", {"dx": 3.0}), ("poisson_solve", {"dx": 3.0, "iters": 5, "omega": 1.5}), ("subtract_gradient", {"dx": 3.0})):
+            a.apply(op), b.apply(op)
+            sm.compare(a.snapshot(), b.snapshot(), f"{mask[0]}, no opening: {op[0]}")
+        for q in (("residual", {"dx": 0.5}), ("flow_stats", {"dx": 0.5})):
+            sm.compare(a.apply(q), b.apply(q), f"{mask[0]}, no opening: {q[0]}")
+
+
+OPEN_REFUSALS = {
+    "open-context": {("set_openings", "viscosity"), ("view_scalar", "openings"), ("view_texels", "openings"), ("set_viscosity", "openings"),
+                     ("set_inflow", "no openings"), ("set_inflow_profile", "no openings"), ("set_inflow_profile", "off the inflow cells")},
+    "open-batch": {("set_openings", "history"), ("set_openings", "view"), ("set_openings", "viscosity"), ("step_n_until", "openings"),
+                   ("poisson_solve_until", "openings"), ("history_start", "openings"), ("record_view", "openings"), ("view_render_members", "openings"),
+                   ("set_viscosity", "openings"), ("set_inflow", "no openings"), ("set_inflow_profile", "no openings"),
+                   ("set_inflow_profile", "off the inflow cells")},
+}
+
+
+def applies_to(profile, member):
+    """The cells of a set_inflow_profile's records that go to `member`."""
+    return [tuple(c) for k, c in enumerate(profile["cells"]) if profile.get("members") is None or profile["members"][k] == member]
+
+
+@pytest.mark.parametrize("name", OPEN_IDS)
+def test_census_the_openings_the_profiles_and_the_refusals_are_walked(name):
+    subject, cases = later_walks(name)
+    batch, members, seen, causes, stepped_under = subject.kind == "batch", range(max(subject.batch, 1)), set(), set(), set()
+    for case, walk in cases:
+        first = None                    # which of the map and the mask, both held, was set first
+        under = None                    # the kind of the map in force, until a step call has run under it
+        gone = None                     # an inflow cell with a profile record that a mask made solid: what has been seen since, by phase
+        for k, op, st, path, refused in walk:
+            kind, a = op
+            behind = walk[k + 1] if k + 1 < len(walk) else None
+            is_open, live = st["open"] is not None, st["live"]
+            if refused:
+                assert behind[1][0] in sm.STEPS and not behind[4], (name, case, k, op, "a step call the header takes follows")
+                assert st["code"] == (sm.ERR_INVALID if kind == "set_inflow_profile" and is_open else sm.ERR_STATE)
+                if kind == "set_openings":
+                    why = [n for n, on in (("history", batch and st["hist"] is not None), ("view", batch and st["rec"] and st["view"] == sm.VIEW_DIVERGENCE),
+                                           ("viscosity", st["visc"] is not None)) if on]
+                    assert len(why) == 1
+                    causes.add((kind, why[0]))
+                elif kind in ("set_inflow", "set_inflow_profile") and not is_open:
+                    causes.add((kind, "no openings"))
+                elif kind == "set_inflow_profile":
+                    assert st["profile"] is not None and any(op2[0] == "inflow_profile" for _, op2, *_ in walk[k + 2:k + 4]), "the profile as it was is read behind it"
+                    causes.add((kind, "off the inflow cells"))
+                else:
+                    assert is_open and not st["set"] or kind in ("view_scalar", "view_texels", "record_view", "view_render_members", "set_viscosity") and is_open
+                    causes.add((kind, "openings"))
+                continue
+            if kind == "set_openings":
+                first = "mask" if st["set"] else "map"
+                under = a["open_kind"]
+                if st["profile"] is not None and behind[1][0] == "inflow_profile":
+                    seen.add("a new map under a profile, the profile read behind it")
+            if kind == "clear_openings":
+                first, under = ("mask" if st["set"] else None), None
+            if kind == "set_solids" and not st["set"]:
+                first = "map" if is_open else "mask"
+            if kind == "clear_solids":
+                first = "map" if is_open else None
+            if kind in sm.STEPS:
+                if is_open and st["set"] and first is not None:
+                    seen.add(f"a step under a map and a mask, the {first} set first")
+                if under is not None:
+                    stepped_under.add(under)
+                if is_open and batch:
+                    seen.add(f"{kind} under {'per-member' if len(st['open']) > 1 else 'shared'} maps and {'per-member' if len(st['inflow']) > 1 else 'shared'} inflows")
+                if is_open and min(live) > 0:
+                    seen |= {"a history's sample under a map"} if st["hist"] is not None and due(st["hist"], op) > 0 else set()
+                    seen |= {"a trail and a following set under a map"} if path["follow"] and st["trail"] else set()
+                    seen |= {"following tracers under a map"} if path["follow"] else set()
+            if kind in ("set_solids", "clear_solids") and is_open and st["set"] and behind[1][0] in sm.STEPS:
+                seen.add(f"{kind} over a mask behind a map, a step right after")
+            if kind == "set_inflow" and is_open and behind[1][0] in sm.STEPS and [tuple(u) for u in (a["inflow"] if a.get("per_member") else [a["inflow"]])] != st["inflow"]:
+                seen.add(f"set_inflow {'with' if st['profile'] is not None else 'without'} a profile held, a step after")
+            if kind == "set_inflow_profile" and is_open and behind[1][0] in sm.STEPS:
+                if st["profile"] is not None:
+                    seen.add("a profile replaced, a step after" if a["cells"] else "a profile cleared, a step after")
+                for m in members:
+                    cells = applies_to(a, m)
+                    vels = [tuple(u) for k2, u in enumerate(a["vels"]) if a.get("members") is None or a["members"][k2] == m]
+                    seen |= {"a profile with a duplicate cell"} if len(set(cells)) < len(cells) else set()
+                    seen |= {"a profile with a record equal to the uniform inflow"} if tuple(st["inflow"][m if len(st["inflow"]) > 1 else 0]) in vels else set()
+            if kind == "queue_forces" and is_open:
+                for m, (i, j) in zip(a.get("members", [0] * len(a["cells"])), a["cells"]):
+                    held = st["open"][m if len(st["open"]) > 1 else 0]
+                    if 0 <= i < case[0] and 0 <= j < case[1] and held[j, i]:
+                        on = "an outflow" if held[j, i] == opening_rule.OUTFLOW else "a profiled" if st["profile"] and (i, j) in applies_to(st["profile"], m) else "an inflow"
+                        seen.add(f"a queued force record on {on} cell")
+            if is_open and min(live) > 0 and kind in ("calculate_divergence", "poisson_solve", "poisson_continue", "subtract_gradient", "poisson_solve_until", "residual",
+                                                      "flow_stats", "poisson_solve_each"):
+                seen.add(f"{kind} under a map")
+            # an inflow cell with a profile record on it goes solid and comes back
+            if kind == "set_solids" and is_open and st["profile"] is not None:
+                solid = [sm.solid_mask(a["mask_kind"], case[0], case[1], a["seed"], m if a.get("per_member") else None) for m in members]
+                named = [c for m in members for c in applies_to(st["profile"], m) if solid[m][c[1], c[0]]]
+                gone = {"phase": "solid", "solid": set(), "back": set()} if named and behind[2]["live"][0] < live[0] else None
+            elif gone is not None and kind in ("set_openings", "clear_openings", "set_inflow_profile", "set_solids"):
+                gone = None
+            elif gone is not None and kind == "clear_solids" and gone["phase"] == "solid":
+                gone["phase"] = "back"
+                assert behind[2]["live"][0] > live[0], "the live count comes back"
+            elif gone is not None:
+                gone[gone["phase"]].add("step" if kind in sm.STEPS else kind)
+                if {"openings", "step", "openings_flux", "inflow_profile"} <= gone["solid"] and {"openings", "step", "openings_flux"} <= gone["back"]:
+                    seen.add("an inflow cell with a profile record goes solid and comes back, the counts, the flux and the profile read in both states")
+            # a cleared map gives the plain paths back: the step call right behind the clear
+            if kind == "clear_openings" and is_open and behind is not None and not behind[4]:
+                op2, st2, path2 = behind[1], behind[2], behind[3]
+                if not batch:
+                    seen |= {"cleared: the step seams"} if fused(subject, case, op2, st2, path2) else set()
+                    seen |= {"cleared: the one-launch step of a small grid"} if case[:2] == (61, 81) and op2[0] == "step" and not st2["set"] and sm.on_small_grid(path2) else set()
+                    seen |= {"cleared: the unfused step"} if op2[0] == "step" and not st2["set"] and path2["options"]["OPT_FUSE_PROJECTION"] == 0 else set()
+                    seen |= {"cleared: step_n with the seams switched off"} if op2[0] == "step_n" and path2["options"]["OPT_STEP_SEAMS"] == 0 else set()
+                    seen |= {"cleared with a mask still set"} if op2[0] in sm.STEPS and st2["mixed"] else set()
+                else:
+                    later = [(o[0], r) for _, o, _, _, r in walk[k + 1:k + 14]]
+                    seen |= {"cleared: step_n_until"} if ("step_n_until", False) in later else set()
+                    seen |= {"cleared: poisson_solve_until"} if ("poisson_solve_until", False) in later else set()
+                    seen |= {"cleared: history_start"} if ("history_start", False) in later else set()
+                    seen |= {"cleared: the one-launch replay"} if any(fused(subject, case, o, s, p) and not r for _, o, s, p, r in walk[k + 1:k + 14]) else set()
+                    seen |= {"cleared with a mask still set"} if op2[0] in sm.STEPS and st2["mixed"] else set()
+    want = {"a step under a map and a mask, the map set first", "a step under a map and a mask, the mask set first", "set_solids over a mask behind a map, a step right after",
+            "clear_solids over a mask behind a map, a step right after", "set_inflow with a profile held, a step after", "set_inflow without a profile held, a step after",
+            "a new map under a profile, the profile read behind it", "a profile replaced, a step after", "a profile cleared, a step after", "a profile with a duplicate cell",
+            "a profile with a record equal to the uniform inflow", "a queued force record on an inflow cell", "a queued force record on a profiled cell",
+            "a queued force record on an outflow cell", "an inflow cell with a profile record goes solid and comes back, the counts, the flux and the profile read in both states",
+            "cleared with a mask still set"}
+    if batch:
+        want |= {f"{kind} under {maps} maps and {inflows} inflows" for kind, maps, inflows in (("step_n", "shared", "shared"), ("step_n_each", "per-member", "per-member"))}
+        want |= {"poisson_solve_each under a map", "poisson_solve under a map", "flow_stats under a map", "cleared: step_n_until", "cleared: poisson_solve_until",
+                 "cleared: history_start", "cleared: the one-launch replay", "following tracers under a map"}
+    else:
+        want |= {f"{kind} under a map" for kind in ("calculate_divergence", "poisson_solve", "poisson_continue", "subtract_gradient", "poisson_solve_until", "residual", "flow_stats")}
+        want |= {"a history's sample under a map", "a trail and a following set under a map", "cleared: the step seams", "cleared: the one-launch step of a small grid",
+                 "cleared: the unfused step", "cleared: step_n with the seams switched off"}
+    assert want <= seen, (name, want - seen)
+    assert stepped_under == set(sm.OPEN_KINDS), (name, "every kind of map in front of a step call", set(sm.OPEN_KINDS) - stepped_under)
+    assert causes == OPEN_REFUSALS[name], (name, causes ^ OPEN_REFUSALS[name])
+    assert sum(r for _, walk in cases for *_, r in walk) == len(OPEN_REFUSALS[name]), "only the planted refusals happen"

@@ -20,6 +20,17 @@ set before the mask, masks replaced and cleared under labels, labels replaced an
 that leave remainders, is restarted while on, samples zeros where no mask is set -- inside a context's seam loop and a
 batch's one-launch replay -- and, full, refuses a step call whole behind a history and a trail that have room.
 
+Four more walk what came after, at the same shapes.  record-context and record-batch (69 and 76 ops, on the viscous vocabulary):
+a history, the loads, the friction, the torque and the averages on at once with five periods across calls that leave remainders;
+a full friction and a full torque recorder refusing a call whole; restarts while on; set_bodies refused under either recorder;
+pivots kept by the same number of bodies and put back by another, changed while recording, refused with SFL_ERR_INVALID for
+another `bodies`; averages that cut a batch's one-launch replay and a context's seams while every >= 1, keep them with
+every == 0 and give them back when stopped; float64 planes compared as their bit patterns.  open-context and open-batch (60 and
+67 ops, on the solids' vocabulary): a map before and behind a mask, masks replaced and cleared behind a map, inflow cells that go
+solid and come back with a profile record on them, set_inflow with and without a profile, a new map that drops the profile, force
+records on inflow, profiled and outflow cells, every operator under a map, every plain path behind a cleared map, and the
+refusals between openings, viscosity, a history, the divergence view and the calls to a tolerance.
+
 A failure prints the seed, the mode, the first op that disagreed and the op list up to there as a literal for
 sequence_model.replay.  There is no tolerance anywhere."""
 import functools
@@ -48,6 +59,7 @@ def test_a_sequence_on_a_live_handle(sfl, oracle, name, case, mode):
 
 LIVE = [(cls, "general") for cls in sm.STAND_INS] + [(cls, "solid-context") for cls in sm.SOLID_STAND_INS]
 LIVE += [(cls, sm.stand_in_subject(cls)) for cls in sm.VISCOUS_STAND_INS + sm.LOAD_STAND_INS]      # (viscous-context; viscous-batch for the batch's fault)
+LIVE += [(cls, sm.later_stand_in_subject(cls)) for cls in sm.RECORD_STAND_INS + sm.OPEN_STAND_INS]  # (record-context; open-context)
 
 
 @pytest.mark.gpu
@@ -55,14 +67,15 @@ LIVE += [(cls, sm.stand_in_subject(cls)) for cls in sm.VISCOUS_STAND_INS + sm.LO
 def test_the_comparisons_on_the_library_are_live(sfl, oracle, cls, name):
     """A model with a planted state fault, taken as the truth: the library does not have the fault, so some sequence of the
     subject (general; solid-context for the faults in the solids' state; viscous-context and viscous-batch for those in the
-    viscosity's and the loads') must disagree -- in lazy or probing mode, as
+    viscosity's and the loads'; record-context and open-context for those in the recorders', the pivots', the averages' and the
+    openings') must disagree -- in lazy or probing mode, as
     tests/test_sequences.py shows for models on both sides."""
     subject, seqs = sequences(name)
     hits = 0
     for case, ops in seqs.items():
         for mode in ("lazy", "probing"):
             model = cls(oracle, case[0], case[1], subject.batch) if subject.kind == "batch" else cls(oracle, case[0], case[1])
-            model.viscous, handle = subject.viscous, subject.library(sfl, case)
+            model.viscous, model.records, model.opens, handle = subject.viscous, subject.records, subject.opens, subject.library(sfl, case)
             try:
                 sm.replay(model, handle, ops, mode, seed=case[2])
             except AssertionError:
