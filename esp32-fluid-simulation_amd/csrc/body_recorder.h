@@ -3,8 +3,7 @@
 // "FRICTION") and the torque (torque.cpp; "TORQUE").  Host C++ only.  Generic over the holder H (sfl_context, sfl_batch) and
 // over the kind K, a struct of statics:
 //     Record                        the record type (48 bytes; the torque's 64)
-//     state(H *)                    the recorder's plain data on the holder (context.h Loads, Friction): on, every, first, count,
-//                                   capacity, written, steps, d_records, d_bytes
+//     state(H *)                    the recorder's plain data on the holder (context.h Recorder, as Loads, Friction or Torque)
 //     launch_sample(H *, first, count, Record *out)   the sampler's launches on the holder's stream (solids are set)
 //     set_hook(H *)                 sets the holder's step pointer from state(x).on
 //     zero_sample(H *, first, count, Record *out)     the records of a sample taken while no solids are set, on the stream, and
@@ -58,15 +57,14 @@ struct ZeroRecords {
 
 inline size_t scratch_records(const Holder &o) { return (size_t)o.members * o.bodies; }
 // sample `sample` of a recorder over `count` members: behind the records of one sample of every member
-template <class K, class S>
-typename K::Record *slot(const Holder &o, const S &l, int sample)
+template <class K>
+typename K::Record *slot(const Holder &o, const Recorder &l, int sample)
 {
     return static_cast<typename K::Record *>(l.d_records) + scratch_records(o) + (size_t)sample * l.count * o.bodies;
 }
 
 // d_records holds at least `bytes`: kept when it does, else drained (a sample may still write it) and made anew
-template <class S>
-int ensure_records(const Holder &o, S &l, size_t bytes, const char *call)
+inline int ensure_records(const Holder &o, Recorder &l, size_t bytes, const char *call)
 {
     if (l.d_records && l.d_bytes >= bytes) return SFL_OK;
     if (l.d_records) {
@@ -107,8 +105,7 @@ int step(H *x, int steps)
     return SFL_OK;
 }
 
-template <class S>
-void stop_recorder(S &l)
+inline void stop_recorder(Recorder &l)
 {
     l.on = false;
     l.every = l.first = l.count = l.capacity = l.written = 0;

@@ -259,88 +259,58 @@ inline int history_admit(const History &h, int64_t n)
 // how many of the next n steps may run in one launch before a sample is due (n without a history): record_run's rule
 inline int history_run(const History &h, int n) { return h.on ? (int)std::min<int64_t>(n, h.every - h.steps % h.every) : n; }
 
-// Loads (loads.cpp; include/sfl.h "LOADS"): what a context or a batch holds of its bodies' labels and of the loads
-// recorder.  Plain data, as History and for the same reason: the destroy paths free the two allocations and the step calls
-// admit without a symbol of loads.cpp; the sample is launched through the `loads_step` pointer of the two structs, which
-// loads.cpp sets while a recorder is on (null: the step calls launch what they launched before there were loads).
-struct Loads {
+// The recorder of one record per solid body (body_recorder.h), as the loads, the friction and the torque each hold one,
+// independent of each other.  Plain data, as History and for the same reason: the destroy paths free the records and the
+// step calls admit without a symbol of loads.cpp, friction.cpp or torque.cpp; the sample is launched through the `loads_step`,
+// `friction_step` and `torque_step` pointers of the two structs, which those units set while their recorder is on (null: the
+// step calls launch what they launched before there was such a recorder).
+struct Recorder {
+    bool on = false;
+    int every = 0, first = 0, count = 0, capacity = 0, written = 0;   // members [first, first + count) (a context: [0, 1))
+    int64_t steps = 0;            // counted since the recorder's start
+    // the records (48 bytes; the torque's 64): in front those of ONE sample of every member (what the synchronous call
+    // writes and copies out), behind them `capacity` samples of count * bodies, sample-major.  Kept by a restart that does
+    void *d_records = nullptr;    //   not need more, freed by the recorder's stop and the destroy paths
+    size_t d_bytes = 0;
+};
+
+// SFL_ERR_STATE if the n steps of a call would complete more samples than are free: history_admit's rule.  noun: "loads",
+// read_calls: "sfl_loads_read, sfl_batch_loads_read"
+inline int recorder_admit(const Recorder &r, int64_t n, const char *noun, const char *read_calls)
+{
+    if (!r.on) return SFL_OK;
+    const int64_t due = (r.steps + n) / r.every - r.steps / r.every, room = r.capacity - r.written;
+    if (due > room)
+        return fail(SFL_ERR_STATE, "the %s recorder has room for %lld more samples (%d of %d written) and %lld steps would complete %lld: "
+                    "nothing stepped; read the samples (%s) and start the recorder again to make room",
+                    noun, (long long)room, r.written, r.capacity, (long long)n, (long long)due, read_calls);
+    return SFL_OK;
+}
+
+// Loads (loads.cpp; include/sfl.h "LOADS"): the loads recorder and the bodies' labels, which every kind reads.
+struct Loads : Recorder {
     uint8_t *d_labels = nullptr;   // one label byte per cell (a batch: of every member when per_member); null: every solid is body 1
     size_t d_label_bytes = 0;
     bool per_member = false;
     int bodies = 1;
-    bool on = false;
-    int every = 0, first = 0, count = 0, capacity = 0, written = 0;   // members [first, first + count) (a context: [0, 1))
-    int64_t steps = 0;            // counted since loads_start
-    // the records of 48 bytes: in front those of ONE sample of every member (what the synchronous call writes and copies
-    // out), behind them `capacity` samples of count * bodies, sample-major.  Kept by a restart that does not need more,
-    void *d_records = nullptr;    //   freed by loads_stop and the destroy paths
-    size_t d_bytes = 0;
 };
+inline int loads_admit(const Loads &l, int64_t n) { return recorder_admit(l, n, "loads", "sfl_loads_read, sfl_batch_loads_read"); }
 
-// SFL_ERR_STATE if the n steps of a call would complete more samples than are free: history_admit's rule
-inline int loads_admit(const Loads &l, int64_t n)
-{
-    if (!l.on) return SFL_OK;
-    const int64_t due = (l.steps + n) / l.every - l.steps / l.every, room = l.capacity - l.written;
-    if (due > room)
-        return fail(SFL_ERR_STATE, "the loads recorder has room for %lld more samples (%d of %d written) and %lld steps would complete %lld: "
-                    "nothing stepped; read the samples (sfl_loads_read, sfl_batch_loads_read) and start the recorder again to make room",
-                    (long long)room, l.written, l.capacity, (long long)n, (long long)due);
-    return SFL_OK;
-}
+// Friction (friction.cpp; include/sfl.h "FRICTION"): the recorder alone; the labels and `bodies` are Loads'.
+struct Friction : Recorder {};
+inline int friction_admit(const Friction &f, int64_t n) { return recorder_admit(f, n, "friction", "sfl_friction_read, sfl_batch_friction_read"); }
 
-// Friction (friction.cpp; include/sfl.h "FRICTION"): the second recorder of 48-byte records per body, beside the loads' and
-// independent of it.  The labels and `bodies` are Loads'; this is the recorder alone, with the field names of Loads so
-// that body_recorder.h serves both.  Plain data for the same reason; the sample is launched through `friction_step`.
-struct Friction {
-    bool on = false;
-    int every = 0, first = 0, count = 0, capacity = 0, written = 0;   // members [first, first + count) (a context: [0, 1))
-    int64_t steps = 0;            // counted since friction_start
-    void *d_records = nullptr;    // laid out as Loads::d_records; freed by friction_stop and the destroy paths
-    size_t d_bytes = 0;
-};
-
-// SFL_ERR_STATE if the n steps of a call would complete more samples than are free: loads_admit's rule
-inline int friction_admit(const Friction &f, int64_t n)
-{
-    if (!f.on) return SFL_OK;
-    const int64_t due = (f.steps + n) / f.every - f.steps / f.every, room = f.capacity - f.written;
-    if (due > room)
-        return fail(SFL_ERR_STATE, "the friction recorder has room for %lld more samples (%d of %d written) and %lld steps would complete %lld: "
-                    "nothing stepped; read the samples (sfl_friction_read, sfl_batch_friction_read) and start the recorder again to make room",
-                    (long long)room, f.written, f.capacity, (long long)n, (long long)due);
-    return SFL_OK;
-}
-
-// Torque (torque.cpp; include/sfl.h "TORQUE"): the pivots of the bodies and the third recorder of records per body (64 bytes
-// each), beside the loads' and the friction's and independent of both.  The labels and `bodies` are Loads'; the recorder has
-// the field names of Loads so that body_recorder.h serves it too.  Plain data for the same reason; the sample is launched
-// through `torque_step`.  The pivots live twice: on the host, for the records that need no launch (no solids set) and for the
-// download, and in a small device table that the samplers read.
-struct Torque {
-    bool on = false;
-    int every = 0, first = 0, count = 0, capacity = 0, written = 0;   // members [first, first + count) (a context: [0, 1))
-    int64_t steps = 0;            // counted since torque_start
-    void *d_records = nullptr;    // laid out as Loads::d_records; freed by torque_stop and the destroy paths
-    size_t d_bytes = 0;
+// Torque (torque.cpp; include/sfl.h "TORQUE"): the recorder and the pivots of the bodies; the labels and `bodies` are Loads'.
+// The pivots live twice: on the host, for the records that need no launch (no solids set) and for the download, and in a
+// small device table that the samplers read.
+struct Torque : Recorder {
     // (x2, y2) per body, of every member when pivots_per_member; null / empty: every pivot is (0, 0)
     int32_t *d_pivot2 = nullptr;  //   freed by set_body_pivots(NULL), by a set_bodies that changes `bodies` and by the destroy paths
     size_t d_pivot_bytes = 0;
     bool pivots_per_member = false;
     std::vector<int32_t> h_pivot2;
 };
-
-// SFL_ERR_STATE if the n steps of a call would complete more samples than are free: loads_admit's rule
-inline int torque_admit(const Torque &t, int64_t n)
-{
-    if (!t.on) return SFL_OK;
-    const int64_t due = (t.steps + n) / t.every - t.steps / t.every, room = t.capacity - t.written;
-    if (due > room)
-        return fail(SFL_ERR_STATE, "the torque recorder has room for %lld more samples (%d of %d written) and %lld steps would complete %lld: "
-                    "nothing stepped; read the samples (sfl_torque_read, sfl_batch_torque_read) and start the recorder again to make room",
-                    (long long)room, t.written, t.capacity, (long long)n, (long long)due);
-    return SFL_OK;
-}
+inline int torque_admit(const Torque &t, int64_t n) { return recorder_admit(t, n, "torque", "sfl_torque_read, sfl_batch_torque_read"); }
 
 // Averages (means.cpp; include/sfl.h "AVERAGES"): the per-cell sums over time that a context or a batch holds.  Plain data,
 // as History and for the same reason: the destroy paths free the planes and batch.cpp finds the cut points of a replay

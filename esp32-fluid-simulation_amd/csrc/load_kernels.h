@@ -9,10 +9,6 @@
 
 namespace sfl {
 
-constexpr int kLoadThreads = 256;        // threads of a sampler's workgroup, batch and context
-constexpr int kLoadGroupCells = 16;      // code bytes a thread of the context's passes takes with one load
-constexpr int kLoadMaxBlocks = 2048;     // workgroups of a context's pass at most: they stride over the groups
-
 // One sample of a batch: the `bodies` records of members [first, first + count) into out, member-major.  One workgroup
 // per member.  codes / labels: the bytes of member m start at m * code_stride / m * label_stride (0: shared by all
 // members; the two independently); labels null: every solid cell is body 1.

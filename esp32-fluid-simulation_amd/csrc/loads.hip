@@ -2,198 +2,45 @@
 // exact integer sums fx and fy of the truncated face terms, the exponent they are scaled by, the largest |p| on a face,
 // the face counts and the count of faces with a pressure that is not finite.
 //
-// Both samplers read the code bytes of the solids (solids.cpp solid_codes: bit 0 W, 1 E, 2 S, 3 N neighbour present, bit
-// 4 the cell is fluid): a fluid cell with an absent neighbour that is INSIDE THE DOMAIN -- derived from the cell's
-// coordinates, not from the byte -- has a solid cell there, whose label (1 without labels) names the body of that wet face.
-//
-//   A batch     one workgroup per member, launched behind the step whose pressure it reads.  Pass 1: every thread keeps
-//               the maximum of the bit patterns of |p| per body in registers (sixteen words, indexed at compile time), the
-//               wave reduces the bodies in use by __shfl_xor and its lane 0 folds them into LDS.  Barrier.  Pass 2: the
-//               same walk; every face's term goes into the body's 64-bit LDS accumulator and counters.  Barrier.  Thread k
-//               stores the record of body k + 1 with ordinary stores: no global atomics, no memset in front.
-//   A context   a streaming pass over the code bytes taken as ONE flat array: a thread takes 16 cells with one 16-byte load
-//               (the array starts 16-byte aligned, so every group does whatever the width; the cells of the last, partial
-//               group -- and every group if the array is not aligned -- come by byte loads) and skips a word whose bytes are
-//               all 0 or all 0x1F: nothing wet, which is nearly all of a large grid.  Only a fluid cell with an absent
-//               neighbour divides its index into (i, j); only one with a face reads p and its solid neighbours' labels (a
-//               cell that merely touches the rim reads neither).  Two launches: the
-//               maxima, then the sums, which read the finished maxima.  Each folds its faces into LDS words per body and
-//               issues at most one integer atomic per workgroup and touched field of a body, on records the launcher
-//               zeroes on the stream in front (update_norm.hip's idiom).
-// The walk over the wet faces, the quantisation and the per-body accumulators are body_walk.h's, shared with friction.hip.
-// The term of a face is formed on the float's bits: the mantissa shifted by (its exponent - 23) - q, towards zero -- what
-// (int64_t)trunc(ldexp((double)p, -q)) gives, exactly.  Integer sums, maxima of bit patterns and counts do not depend on
-// the order of reduction: the two samplers write the same bytes for the same shape, mask, labels and pressure.
+// The scheme of a batch's and a context's sampler, the walks and the kernel bodies are body_walk.h's, shared with
+// friction.hip; here is what the loads are as a kind: a face takes the pressure of its fluid cell, whatever its direction,
+// into fx (the fluid cell W or E of the solid one: directions 0, 1) or fy (S or N: 2, 3), negated where the fluid cell lies
+// on the positive side (1, 3).
 // Compiler's figures (-Rpass-analysis=kernel-resource-usage): DESIGN.md 4.13; no scratch in any of the three kernels.
-#include <algorithm>
-
 #include "body_walk.h"
 #include "load_kernels.h"
 
 namespace sfl {
 namespace {
 
-constexpr int kT = kLoadThreads;
-static_assert(sizeof(struct sfl_body_load) == 48 && kT >= kB && kT % 64 == 0, "include/sfl.h: 48 bytes; a thread per body");
+struct LoadsKind {
+    typedef struct sfl_body_load Record;
+    template <class A>
+    static __device__ __forceinline__ const float *field(const A &a) { return a.p; }
+    static __device__ __forceinline__ unsigned bits(float p, int) { return __float_as_uint(p); }
+    static __device__ __forceinline__ void sum(Gathered &g, int body, int dir, long long t)
+    {
+        atomicAdd(dir < 2 ? &g.fx[body] : &g.fy[body], (u64)((dir & 1) ? -t : t));
+    }
+    static __device__ __forceinline__ float &maximum(Record &r) { return r.max_abs_p; }
+};
+static_assert(sizeof(struct sfl_body_load) == 48, "include/sfl.h: 48 bytes");
 
-// one face into the body's sums (g.max_bits holds the finished maxima)
-__device__ __forceinline__ void add_face(Gathered &g, int body, int dir, unsigned bits)
-{
-    atomicAdd(&g.faces[body][dir], 1u);
-    if ((bits & 0x7f800000u) == 0x7f800000u) {
-        atomicAdd(&g.nonfinite[body], 1u);
-        return;
-    }
-    const long long t = term_of(bits, exp2_of(g.max_bits[body]));
-    atomicAdd(dir < 2 ? &g.fx[body] : &g.fy[body], (u64)((dir & 1) ? -t : t));   // (two's complement: the sum of the signed terms)
-}
+__global__ void __launch_bounds__(kT) batch_loads_kernel(const BatchLoadSample a) { batch_sample<LoadsKind>(a); }
 
-__global__ void __launch_bounds__(kT) batch_loads_kernel(const BatchLoadSample a)
-{
-    __shared__ Gathered g;
-    const int member = a.first + (int)blockIdx.x, dim_x = a.dim_x, dim_y = a.dim_y, cells = dim_x * dim_y, bodies = a.bodies;
-    const float *p = a.p + (size_t)member * (size_t)cells;
-    const uint8_t *codes = a.codes + (size_t)member * a.code_stride;
-    const uint8_t *labels = a.labels ? a.labels + (size_t)member * a.label_stride : nullptr;
-    clear(g);
-    __syncthreads();
-    // ---- pass 1: the maxima, per thread in registers
-    unsigned m[kB];
-#pragma unroll
-    for (int k = 0; k < kB; ++k) m[k] = 0u;
-    for (int c = threadIdx.x; c < cells; c += kT) {
-        const unsigned code = codes[c];
-        if (!wet_candidate(code)) continue;
-        const unsigned faces = face_bits(code, c, dim_x, dim_y);
-        if (!faces) continue;                                         // (the rim alone: no load of p)
-        const unsigned bits = __float_as_uint(p[c]) & 0x7fffffffu;   // |p|
-        if (bits >= 0x7f800000u) continue;                            // (not finite: no part in the maximum)
-        wet_faces(faces, c, dim_x, labels, bodies, [&](int body, int) {
-#pragma unroll
-            for (int k = 0; k < kB; ++k) m[k] = (k == body && bits > m[k]) ? bits : m[k];
-        });
-    }
-#pragma unroll
-    for (int k = 0; k < kB; ++k)
-        if (k < bodies) {   // (uniform)
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const unsigned t = __shfl_xor(m[k], o);
-                m[k] = t > m[k] ? t : m[k];
-            }
-            if ((threadIdx.x & 63) == 0 && m[k]) atomicMax(&g.max_bits[k], m[k]);
-        }
-    __syncthreads();
-    // ---- pass 2: the terms, the face counts
-    for (int c = threadIdx.x; c < cells; c += kT) {
-        const unsigned code = codes[c];
-        if (!wet_candidate(code)) continue;
-        const unsigned faces = face_bits(code, c, dim_x, dim_y);
-        if (!faces) continue;
-        const unsigned bits = __float_as_uint(p[c]);
-        wet_faces(faces, c, dim_x, labels, bodies, [&](int body, int dir) { add_face(g, body, dir, bits); });
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < bodies) {
-        const int k = threadIdx.x;
-        struct sfl_body_load r;
-        r.fx = (int64_t)g.fx[k];
-        r.fy = (int64_t)g.fy[k];
-        r.exp2 = exp2_of(g.max_bits[k]);
-        r.max_abs_p = __uint_as_float(g.max_bits[k]);
-#pragma unroll
-        for (int d = 0; d < 4; ++d) r.faces[d] = g.faces[k][d];
-        r.nonfinite = g.nonfinite[k];
-        r.reserved = 0u;
-        a.out[(size_t)blockIdx.x * bodies + k] = r;
-    }
-}
-
-// SUMS false: the maxima into max_abs_p of the zeroed records; true: everything else, from the finished maxima
 template <bool SUMS>
 __global__ void __launch_bounds__(kT) context_loads_kernel(const ContextLoadSample a, int cells, int groups, bool aligned)
 {
-    __shared__ Gathered g;
-    const int dim_x = a.dim_x, dim_y = a.dim_y, bodies = a.bodies;
-    clear(g);
-    __syncthreads();
-    if (SUMS) {
-        if ((int)threadIdx.x < bodies) g.max_bits[threadIdx.x] = __float_as_uint(a.out[threadIdx.x].max_abs_p);
-        __syncthreads();
-    }
-    const auto cell = [&](int c, unsigned code) {
-        const unsigned faces = face_bits(code, c, dim_x, dim_y);
-        if (!faces) return;   // (the rim alone: no load of p)
-        const unsigned bits = __float_as_uint(a.p[c]);
-        if (!SUMS && (bits & 0x7f800000u) == 0x7f800000u) return;
-        wet_faces(faces, c, dim_x, a.labels, bodies, [&](int body, int dir) {
-            if (SUMS)
-                add_face(g, body, dir, bits);
-            else
-                atomicMax(&g.max_bits[body], bits & 0x7fffffffu);
-        });
-    };
-    for (int grp = blockIdx.x * kT + threadIdx.x; grp < groups; grp += gridDim.x * kT) {
-        const int base = grp * kLoadGroupCells;   // < 2^28
-        if (aligned && base + kLoadGroupCells <= cells) {
-            const uint4 w = *reinterpret_cast<const uint4 *>(a.codes + base);
-            const unsigned words[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (words[k] == 0u || words[k] == 0x1f1f1f1fu) continue;   // four solid cells, or four with every neighbour present
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const unsigned code = (words[k] >> (8 * q)) & 0xffu;
-                    if (wet_candidate(code)) cell(base + 4 * k + q, code);
-                }
-            }
-        } else {
-            const int end = min(base + kLoadGroupCells, cells);
-            for (int c = base; c < end; ++c) {
-                const unsigned code = a.codes[c];
-                if (wet_candidate(code)) cell(c, code);
-            }
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < bodies) {
-        const int k = threadIdx.x;
-        struct sfl_body_load *r = a.out + k;
-        if (!SUMS) {
-            if (g.max_bits[k]) atomicMax(reinterpret_cast<unsigned *>(&r->max_abs_p), g.max_bits[k]);
-        } else {
-            if (g.fx[k]) atomicAdd(reinterpret_cast<u64 *>(&r->fx), g.fx[k]);
-            if (g.fy[k]) atomicAdd(reinterpret_cast<u64 *>(&r->fy), g.fy[k]);
-#pragma unroll
-            for (int d = 0; d < 4; ++d)
-                if (g.faces[k][d]) atomicAdd(&r->faces[d], g.faces[k][d]);
-            if (g.nonfinite[k]) atomicAdd(&r->nonfinite, g.nonfinite[k]);
-            if (blockIdx.x == 0) r->exp2 = exp2_of(g.max_bits[k]);   // (a field no atomic touches)
-        }
-    }
+    context_sample<LoadsKind, SUMS>(a, cells, groups, aligned);
 }
 
 }  // namespace
 
-hipError_t launch_batch_loads(hipStream_t s, const BatchLoadSample &a)
-{
-    if (a.count < 1 || a.bodies < 1 || a.bodies > kB) return hipErrorInvalidValue;
-    batch_loads_kernel<<<a.count, kT, 0, s>>>(a);
-    return hipGetLastError();
-}
+hipError_t launch_batch_loads(hipStream_t s, const BatchLoadSample &a) { return launch_batch(s, a, batch_loads_kernel); }
 
 hipError_t launch_context_loads(hipStream_t s, const ContextLoadSample &a)
 {
-    if (a.bodies < 1 || a.bodies > kB) return hipErrorInvalidValue;
-    const hipError_t e = hipMemsetAsync(a.out, 0, (size_t)a.bodies * sizeof(struct sfl_body_load), s);
-    if (e != hipSuccess) return e;
-    const long long cells = (long long)a.dim_x * a.dim_y;   // <= 2^28
-    const int groups = (int)((cells + kLoadGroupCells - 1) / kLoadGroupCells);
-    const int blocks = std::min((groups + kT - 1) / kT, kLoadMaxBlocks);
-    const bool aligned = reinterpret_cast<uintptr_t>(a.codes) % 16 == 0;
-    context_loads_kernel<false><<<blocks, kT, 0, s>>>(a, (int)cells, groups, aligned);
-    context_loads_kernel<true><<<blocks, kT, 0, s>>>(a, (int)cells, groups, aligned);
-    return hipGetLastError();
+    return launch_context(s, a, context_loads_kernel<false>, context_loads_kernel<true>);
 }
 
 }  // namespace sfl

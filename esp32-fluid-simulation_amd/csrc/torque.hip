@@ -3,28 +3,16 @@
 // exponents they are scaled by, the two maxima, the number of faces, the longest doubled arm, the counts of faces whose
 // pressure / tangential component is not finite, and the pivot.
 //
-// The geometry is that of loads.hip and friction.hip, and the walk over the wet faces and the quantisation are the same code
-// (body_walk.h).  What differs: ONE walk reads BOTH fields -- the fluid cell's pressure and its velocity as a float2, once per
+// The scheme of a batch's and a context's sampler, the walks and the launchers are body_walk.h's, shared with loads.hip and
+// friction.hip.  What differs: ONE walk reads BOTH fields -- the fluid cell's pressure and its velocity as a float2, once per
 // cell -- and every term is multiplied by an arm about the body's pivot (torque_face.h, shared with the host driver of the
 // tests).  The exponents are raised by s = max(0, L(faces) + L(max_arm2) - 30), so that a sum of `faces` products stays
 // inside 64 bits: pass 1 therefore gathers faces and max_arm2 beside the two maxima, and the terms wait for all four.
-//
-//   A batch     one workgroup per member, launched behind the step whose fields it reads.  The pivots of the member go into
-//               LDS first (a workgroup-uniform address).  Pass 1: every face folds |p|, |v_t|, its longest arm and a count
-//               into the body's LDS words -- a maximum only where it beats the value read, so a body costs a handful of LDS
-//               atomics, not one per face.  Barrier; thread k forms body k's exponents; barrier.  Pass 2: the same walk;
-//               both products go into the body's 64-bit LDS accumulators.  Barrier.  Thread k stores the record of body
-//               k + 1 with ordinary stores: no global atomics, no memset in front.
-//   A context   the streaming pass of friction.hip over the code bytes taken as ONE flat array in groups of 16 (one 16-byte
-//               load; the last, partial group -- and every group if the array is not aligned -- by byte loads), skipping a
-//               word whose bytes are all 0 or all 0x1F.  Two launches behind a memset of the records: pass 1, then the sums,
-//               which read the finished pass 1.  Each folds its faces into LDS words per body and issues at most one integer
-//               atomic per workgroup and touched field of a body; the exponents and the pivot are stored by workgroup 0.
-// Integer sums, maxima and counts do not depend on the order of reduction: the two samplers write the same bytes for the
-// same shape, mask, labels, pivots and fields.  There is no float arithmetic: everything happens behind the float's bits.
+// In a batch the pivots of the member go into LDS first (a workgroup-uniform address); pass 1 folds |p|, |v_t|, the longest
+// arm and a count into the body's LDS words -- a maximum only where it beats the value read, so a body costs a handful of LDS
+// atomics, not one per face -- and thread k forms body k's exponents between the passes.  In a context the exponents and the
+// pivot are the fields that workgroup 0 stores.  There is no float arithmetic: everything happens behind the float's bits.
 // Compiler's figures (-Rpass-analysis=kernel-resource-usage): DESIGN.md 4.19; no scratch in any of the kernels.
-#include <algorithm>
-
 #include "body_walk.h"
 #include "torque_face.h"
 #include "torque_kernels.h"
@@ -34,8 +22,7 @@ namespace {
 
 using torque_face::Arms;
 
-constexpr int kT = kTorqueThreads;
-static_assert(sizeof(struct sfl_body_torque) == 64 && kT >= kB && kT % 64 == 0, "include/sfl.h: 64 bytes; a thread per body");
+static_assert(sizeof(struct sfl_body_torque) == 64, "include/sfl.h: 64 bytes");
 
 // what a workgroup gathers of its faces, per body
 struct TorqueGathered {
@@ -57,9 +44,6 @@ __device__ __forceinline__ void clear(TorqueGathered &g, const int32_t *pivot2, 
         g.py2[k] = set ? pivot2[2 * k + 1] : 0;
     }
 }
-
-// the bits of the tangential component of a face in direction dir
-__device__ __forceinline__ unsigned tangential(float2 v, int dir) { return __float_as_uint(dir < 2 ? v.y : v.x); }
 
 __device__ __forceinline__ void grow(unsigned *word, unsigned value)
 {
@@ -111,30 +95,22 @@ __global__ void __launch_bounds__(kT) batch_torque_kernel(const BatchTorqueSampl
     clear(g, a.pivot2 ? a.pivot2 + (size_t)member * a.pivot_stride : nullptr, bodies);
     __syncthreads();
     // ---- pass 1: the maxima of both fields, the faces, the longest arm
-    for (int c = threadIdx.x; c < cells; c += kT) {
-        const unsigned code = codes[c];
-        if (!wet_candidate(code)) continue;
-        const unsigned faces = face_bits(code, c, dim_x, dim_y);
-        if (!faces) continue;   // (the rim alone: no load of a field)
+    member_walk(codes, dim_x, dim_y, [&](int c, unsigned faces) {
         const unsigned p_bits = __float_as_uint(p[c]);
         const float2 u = v[c];
         const int j = c / dim_x, i = c - j * dim_x;
         wet_faces(faces, c, dim_x, labels, bodies, [&](int body, int dir) { see_face(g, body, dir, i, j, p_bits, tangential(u, dir)); });
-    }
+    });
     __syncthreads();
     exponents(g, bodies);
     __syncthreads();
     // ---- pass 2: the products
-    for (int c = threadIdx.x; c < cells; c += kT) {
-        const unsigned code = codes[c];
-        if (!wet_candidate(code)) continue;
-        const unsigned faces = face_bits(code, c, dim_x, dim_y);
-        if (!faces) continue;
+    member_walk(codes, dim_x, dim_y, [&](int c, unsigned faces) {
         const unsigned p_bits = __float_as_uint(p[c]);
         const float2 u = v[c];
         const int j = c / dim_x, i = c - j * dim_x;
         wet_faces(faces, c, dim_x, labels, bodies, [&](int body, int dir) { add_face(g, body, dir, i, j, p_bits, tangential(u, dir)); });
-    }
+    });
     __syncthreads();
     if ((int)threadIdx.x < bodies) {
         const int k = threadIdx.x;
@@ -174,9 +150,7 @@ __global__ void __launch_bounds__(kT) context_torque_kernel(const ContextTorqueS
         }
         __syncthreads();
     }
-    const auto cell = [&](int c, unsigned code) {
-        const unsigned faces = face_bits(code, c, dim_x, dim_y);
-        if (!faces) return;   // (the rim alone: no load of a field)
+    context_walk(a.codes, dim_x, dim_y, cells, groups, aligned, [&](int c, unsigned faces) {
         const unsigned p_bits = __float_as_uint(a.p[c]);
         const float2 u = a.v[c];
         const int j = c / dim_x, i = c - j * dim_x;
@@ -186,29 +160,7 @@ __global__ void __launch_bounds__(kT) context_torque_kernel(const ContextTorqueS
             else
                 see_face(g, body, dir, i, j, p_bits, tangential(u, dir));
         });
-    };
-    for (int grp = blockIdx.x * kT + threadIdx.x; grp < groups; grp += gridDim.x * kT) {
-        const int base = grp * kTorqueGroupCells;   // < 2^28
-        if (aligned && base + kTorqueGroupCells <= cells) {
-            const uint4 w = *reinterpret_cast<const uint4 *>(a.codes + base);
-            const unsigned words[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (words[k] == 0u || words[k] == 0x1f1f1f1fu) continue;   // four solid cells, or four with every neighbour present
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const unsigned code = (words[k] >> (8 * q)) & 0xffu;
-                    if (wet_candidate(code)) cell(base + 4 * k + q, code);
-                }
-            }
-        } else {
-            const int end = min(base + kTorqueGroupCells, cells);
-            for (int c = base; c < end; ++c) {
-                const unsigned code = a.codes[c];
-                if (wet_candidate(code)) cell(c, code);
-            }
-        }
-    }
+    });
     __syncthreads();
     if ((int)threadIdx.x < bodies) {
         const int k = threadIdx.x;
@@ -248,25 +200,11 @@ __global__ void __launch_bounds__(kT) torque_empty_kernel(struct sfl_body_torque
 
 }  // namespace
 
-hipError_t launch_batch_torque(hipStream_t s, const BatchTorqueSample &a)
-{
-    if (a.count < 1 || a.bodies < 1 || a.bodies > kB) return hipErrorInvalidValue;
-    batch_torque_kernel<<<a.count, kT, 0, s>>>(a);
-    return hipGetLastError();
-}
+hipError_t launch_batch_torque(hipStream_t s, const BatchTorqueSample &a) { return launch_batch(s, a, batch_torque_kernel); }
 
 hipError_t launch_context_torque(hipStream_t s, const ContextTorqueSample &a)
 {
-    if (a.bodies < 1 || a.bodies > kB) return hipErrorInvalidValue;
-    const hipError_t e = hipMemsetAsync(a.out, 0, (size_t)a.bodies * sizeof(struct sfl_body_torque), s);
-    if (e != hipSuccess) return e;
-    const long long cells = (long long)a.dim_x * a.dim_y;   // <= 2^28
-    const int groups = (int)((cells + kTorqueGroupCells - 1) / kTorqueGroupCells);
-    const int blocks = std::min((groups + kT - 1) / kT, kTorqueMaxBlocks);
-    const bool aligned = reinterpret_cast<uintptr_t>(a.codes) % 16 == 0;
-    context_torque_kernel<false><<<blocks, kT, 0, s>>>(a, (int)cells, groups, aligned);
-    context_torque_kernel<true><<<blocks, kT, 0, s>>>(a, (int)cells, groups, aligned);
-    return hipGetLastError();
+    return launch_context(s, a, context_torque_kernel<false>, context_torque_kernel<true>);
 }
 
 hipError_t launch_torque_empty(hipStream_t s, struct sfl_body_torque *out, const int32_t *pivot2, size_t pivot_stride, int first, int count, int bodies)

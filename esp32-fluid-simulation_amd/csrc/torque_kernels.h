@@ -9,10 +9,6 @@
 
 namespace sfl {
 
-constexpr int kTorqueThreads = 256;      // threads of a sampler's workgroup, batch and context
-constexpr int kTorqueGroupCells = 16;    // code bytes a thread of the context's passes takes with one load
-constexpr int kTorqueMaxBlocks = 2048;   // workgroups of a context's pass at most: they stride over the groups
-
 // One sample of a batch: the `bodies` records of members [first, first + count) into out, member-major.  One workgroup
 // per member.  p: the pressure, v: the velocity (x, y) per cell, both member-major.  codes / labels: the bytes of member m
 // start at m * code_stride / m * label_stride (0: shared by all members; the two independently); labels null: every solid

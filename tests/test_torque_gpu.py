@@ -2,9 +2,10 @@
 tests/torque_rule.py -- the header's rule in numpy, whose own sanity tests/test_torque.py checks.  Every comparison is bit for
 bit, on the bytes of the 64-byte records: there is no tolerance anywhere.
 
-Shapes: a batch of 7 x 5 with one solid cell (a member smaller than a wavefront); 61 x 81 x 3 with a disc, a seeded mask and an
+Shapes: a batch of 7 x 5 with one solid cell (a member smaller than a wavefront) and 2 x 2 with all 16 masks; 61 x 81 x 3 with a disc, a seeded mask and an
 empty member, labels and pivots per member, 16 bodies, one of them without a face; a large-member batch 96 x 96 x 2 (no solids
-there: zeros and the pivots); contexts 67 x 35 and 130 x 70, whose flat arrays end in a partial group of 16; 9 x 9 with a
+there: zeros and the pivots); contexts 67 x 35 and 130 x 70, whose flat arrays end in a partial group of 16, and 515 x 260 (several workgroups; most words skipped; channel walls
+labelled 0); 9 x 9 with a
 checkerboard and a pivot 2^23 cells away, where s > 0.  Fields: what three steps with forces left; magnitudes 1e-44..1e37 with
 both signs and -0.0f; NaN and +-Inf planted in p and in ONE velocity component of a third of the wet cells; denormals only; all
 zeros.  Pivots: seeded half-integers, negative ones and ones outside the grid included."""
@@ -92,6 +93,20 @@ def test_a_member_smaller_than_a_wavefront_with_one_solid_cell(sfl):
                 assert_records_equal(b.torque(), want, f"7x5 {name}")
                 assert (want["faces"] == 4).all()
         assert (b.body_pivots() == [[[4.5, 2.5]]] * 2).all()
+    # ... and the smallest member there is: 2 x 2 with all 16 masks as one batch of 16, pivots per member
+    masks = sg.masks_of(2, 2)
+    pivot2 = pivots_of((16, 1), 2, 2, 44)
+    with sfl.BatchSolver(2, 2, 16) as b:
+        b.set_solids(masks)
+        some_face = False
+        for name, (p, v) in field_cases(masks, 45).items():
+            set_fields(sfl, b, p, v)
+            for piv in (None, pivot2):
+                set_pivots(b, piv)
+                want = want_of(p, v, masks, None, 1, piv)
+                assert_records_equal(b.torque(), want, f"2x2 {name}")
+                some_face |= bool(want["mp"].any() and want["mf"].any())
+        assert some_face and want["faces"].max() == 4 and not want[0]["faces"].any() and not want[15]["faces"].any()
 
 
 def test_a_batch_with_masks_labels_and_pivots_per_member_and_16_bodies(sfl):
@@ -163,11 +178,17 @@ def test_a_large_member_batch_reports_zeros_and_the_pivots(sfl):
 
 
 # ---- contexts --------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dim_x,dim_y", [(67, 35), (130, 70)], ids=["67x35", "130x70"])
+@pytest.mark.parametrize("dim_x,dim_y", [(67, 35), (130, 70), (515, 260)], ids=["67x35", "130x70", "515x260"])
 def test_a_contexts_torque_is_the_rules_and_a_batch_members(sfl, dim_x, dim_y):
     cap = sfl.capi
     assert (dim_x * dim_y) % 16 != 0, "the flat array ends in a partial group"
-    solid = sg.mask_of("seeded", dim_x, dim_y) | sg.mask_of("disc", dim_x, dim_y)
+    channel = (dim_x, dim_y) == (515, 260)   # several workgroups, most words skipped: the loads' channel walls, labelled 0, and two discs
+    if channel:
+        solid, walls = lg.channel_with_disc(dim_x, dim_y)
+        labellings = [(None, 1), (walls, 2), (walls, 16)]
+    else:
+        solid = sg.mask_of("seeded", dim_x, dim_y) | sg.mask_of("disc", dim_x, dim_y)
+        labellings = [(None if bodies == 1 else labels_of("shared", bodies, 1, dim_x, dim_y), bodies) for bodies in (1, 3, 16)]
     fits_a_batch = dim_x * dim_y <= 6144
     with sfl.Solver(dim_x, dim_y) as c:
         v0, col = random_fields(dim_x, dim_y, 300, vamp=40.0)[:2]
@@ -185,8 +206,7 @@ def test_a_contexts_torque_is_the_rules_and_a_batch_members(sfl, dim_x, dim_y):
             set_fields(sfl, c, p[0], v[0])
             if batch:
                 set_fields(sfl, batch, p, v)
-            for bodies in (1, 3, 16):
-                labels = None if bodies == 1 else labels_of("shared", bodies, 1, dim_x, dim_y)
+            for labels, bodies in labellings:
                 c.set_bodies(labels, bodies)
                 if batch:
                     batch.set_bodies(labels, bodies)
@@ -198,7 +218,7 @@ def test_a_contexts_torque_is_the_rules_and_a_batch_members(sfl, dim_x, dim_y):
                     if batch:
                         set_pivots(batch, piv)
                         assert batch.torque().tobytes() == got.tobytes(), "a batch member of the same shape, mask, labels, pivots and fields"
-            assert want["faces"].all()
+            assert want[0, :2]["faces"].all() and not want[0, 2:]["faces"].any() if channel else want["faces"].all()
             assert_bit_equal(c.download(cap.FIELD_VELOCITY), v[0], "the velocity held")
             assert_bit_equal(c.download(cap.FIELD_PRESSURE), p[0], "the pressure held")
         if batch:

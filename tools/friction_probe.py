@@ -21,7 +21,8 @@ With --parent PATH (the library of the parent commit, built from a scratch workt
 alternating in the same rounds through the same raw ctypes calls, on --objects batches (contexts) of each made in turn: where
 an object's fields lie moves a step by more than the rounds of one object differ.  The ONE condition: (a) on this library
 agrees with (a) on the parent's inside the spread the probe itself reports for the PARENT's rounds and objects, max - min.
-Everything else is written down as measured.
+Then (b), (c) and (d) are run on both libraries too (loads_probe.py samples_against_parent): what a sample costs on this one
+against what it costs on the parent's.  Everything else is written down as measured.
 
 usage: python3 tools/friction_probe.py [--parent libsfl_parent.so] [--objects K] [--reps R] [--steps N] [--out profiles/friction.txt]"""
 import argparse
@@ -37,6 +38,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sfl = importlib.import_module("esp32-fluid-simulation_amd")
 capi = sfl.capi
+from loads_probe import samples_against_parent   # noqa: E402  (beside this file)
 
 OUT = []
 DT, DX, OMEGA = 0.05, 1.0, 1.9
@@ -140,6 +142,9 @@ def workload(a, batch, dim_x, dim_y, members, iters, radius):
         say("  the parent's library: not measured (no --parent)")
     for _, _, r in raws:
         r.close()
+    if a.parent:
+        samples_against_parent(a, say, batch, dim_x, dim_y, members, iters, mask,
+                               {"(b) step, a friction sample": ("friction",), "(c) step, a loads sample": ("loads",), "(d) step, both samples": ("loads", "friction")})
     # ---- the recorders and the sampler alone
     def make():
         s = sfl.BatchSolver(dim_x, dim_y, members) if batch else sfl.Solver(dim_x, dim_y)

@@ -18,7 +18,9 @@ and for each
 With --parent PATH (the library of the parent commit, built from a scratch worktree) (a) is also run on that library, the two
 alternating in the same rounds through the same raw ctypes calls, on --objects batches (contexts) of each made in turn: where
 an object's fields lie moves a step by more than the rounds of one object differ.  The agreement is judged inside the spread
-the probe itself reports for (a) on this library: max - min over the rounds and the objects.
+the probe itself reports for (a) on this library: max - min over the rounds and the objects.  Then (b) is run on both
+libraries too (samples_against_parent): what a sample costs on this one against what it costs on the parent's.  The synchronous
+configurations (c) and (d) are measured on this library alone.
 
 usage: python3 tools/loads_probe.py [--parent libsfl_parent.so] [--objects K] [--reps R] [--steps N] [--out profiles/loads.txt]"""
 import argparse
@@ -61,22 +63,29 @@ def disc(dim_x, dim_y, r):
 class Raw:
     """The few calls of the C ABI the comparison with the parent's library needs, on either library, through the same code."""
 
-    def __init__(self, path, batch, dim_x, dim_y, members, mask):
+    def __init__(self, path, batch, dim_x, dim_y, members, mask, velocity=None, pivot=None):
         self.lib = C.CDLL(path)
         for name, (res, args) in capi.SIGNATURES.items():
             if hasattr(self.lib, name):
                 fn = getattr(self.lib, name)
                 fn.restype, fn.argtypes = res, args
-        self.batch, self.h = batch, C.c_void_p()
+        self.batch, self.members, self.h = batch, members, C.c_void_p()
         ptr = mask.ctypes.data_as(C.POINTER(C.c_uint8))
         if batch:
             self.ok(self.lib.sfl_batch_create(C.byref(self.h), 0, dim_x, dim_y, members))
             self.ok(self.lib.sfl_batch_setup_sketch_fields(self.h))
-            self.ok(self.lib.sfl_batch_set_solids(self.h, ptr, 0))
         else:
             self.ok(self.lib.sfl_create(C.byref(self.h), 0, dim_x, dim_y))
             self.ok(self.lib.sfl_setup_sketch_fields(self.h))
-            self.ok(self.lib.sfl_set_solids(self.h, ptr))
+        if velocity is not None:   # (x, y) in every cell instead of the sketch's fluid at rest
+            v = np.empty((members if batch else 1, dim_y, dim_x, 2), np.float32)
+            v[...] = velocity
+            head = (self.h, capi.FIELD_VELOCITY) + ((0, members) if batch else ())
+            self.ok((self.lib.sfl_batch_upload if batch else self.lib.sfl_upload)(*head, v.ctypes.data, v.nbytes))
+        self.ok(self.lib.sfl_batch_set_solids(self.h, ptr, 0) if batch else self.lib.sfl_set_solids(self.h, ptr))
+        if pivot is not None:   # of the one body, in cells
+            p2 = (C.c_int32 * 2)(2 * pivot[0], 2 * pivot[1])
+            self.ok(self.lib.sfl_batch_set_body_pivots(self.h, p2, 0, 1) if batch else self.lib.sfl_set_body_pivots(self.h, p2, 1))
 
     def ok(self, rc):
         if rc != capi.OK:
@@ -88,8 +97,60 @@ class Raw:
     def synchronize(self):
         self.ok((self.lib.sfl_batch_synchronize if self.batch else self.lib.sfl_synchronize)(self.h))
 
+    def start(self, kind, capacity):
+        """The recorder of `kind` ("loads", "friction", "torque"), every = 1, all members."""
+        if self.batch:
+            self.ok(getattr(self.lib, f"sfl_batch_{kind}_start")(self.h, 1, 0, self.members, capacity))
+        else:
+            self.ok(getattr(self.lib, f"sfl_{kind}_start")(self.h, 1, capacity))
+
+    def stop(self, kind):
+        self.ok(getattr(self.lib, f"sfl_batch_{kind}_stop" if self.batch else f"sfl_{kind}_stop")(self.h))
+
     def close(self):
         (self.lib.sfl_batch_destroy if self.batch else self.lib.sfl_destroy)(self.h)
+
+
+def samples_against_parent(a, say, batch, dim_x, dim_y, members, iters, mask, configs, **fields):
+    """With --parent: what a sample costs on this library and on the parent's (also for friction_probe.py and torque_probe.py).
+    configs: {label: the recorders that are on}.  --objects batches (contexts) of each library, made in turn, all in the same
+    rounds, either end first in turn, as (a) runs.  In a round EVERY object runs step_n(n) without a recorder and then once per
+    configuration, the recorders started in front of the timed call and stopped behind it: the cost of a sample is (the
+    configuration's step) - (the step without a recorder) of the SAME object in the same round -- where an object's fields lie
+    moves its step by more than a sample's cost differs between the libraries, and an object of its own per configuration
+    measures that.  The condition: this library's median cost is no more than the parent's median plus the parent's own
+    max - min over its rounds and objects."""
+    n = a.steps
+    libs = {"this": capi.LIB_PATH, "parent": os.path.abspath(a.parent)}
+    raws = [(name, Raw(path, batch, dim_x, dim_y, members, mask, **fields)) for _ in range(a.objects) for name, path in libs.items()]
+    for _, r in raws:
+        r.step_n(2, iters)
+    step = {(name, label): [] for name in libs for label in configs}
+    cost = {(name, label): [] for name in libs for label in configs}
+    for rnd in range(a.warmup + a.reps):
+        for name, r in (raws if rnd % 2 == 0 else raws[::-1]):
+            t0 = timed(lambda: r.step_n(n, iters), r.synchronize)
+            for label, kinds in configs.items():
+                for kind in kinds:
+                    r.start(kind, n)
+                t = timed(lambda: r.step_n(n, iters), r.synchronize)
+                for kind in kinds:
+                    r.stop(kind)
+                if rnd >= a.warmup:
+                    step[(name, label)].append(t / n)
+                    cost[(name, label)].append((t - t0) / n)
+    say(f"  with recorders, {a.objects} objects of this library and of the parent's in the same rounds, us per step:")
+    for label in configs:
+        med = {name: statistics.median(cost[(name, label)]) for name in libs}
+        for name in libs:
+            c = cost[(name, label)]
+            say(f"    {label:<30} {name:<7} step median {statistics.median(step[(name, label)]):9.2f}   a sample, step - (no recorder): "
+                f"median {med[name]:+7.2f}   min {min(c):+7.2f}   max {max(c):+7.2f}")
+        spread = max(cost[("parent", label)]) - min(cost[("parent", label)])
+        verdict = "no more than" if med["this"] <= med["parent"] + spread else "MORE THAN"
+        say(f"    {label:<30} this - parent = {med['this'] - med['parent']:+.2f}: {verdict} the parent's median plus its max - min of {spread:.2f}")
+    for _, r in raws:
+        r.close()
 
 
 def report(us, n, base):
@@ -140,6 +201,8 @@ def workload(a, batch, dim_x, dim_y, members, iters, radius):
         say("  the parent's library: not measured (no --parent)")
     for _, _, r in raws:
         r.close()
+    if a.parent:
+        samples_against_parent(a, say, batch, dim_x, dim_y, members, iters, mask, {"(b) step, a sample a step": ("loads",)})
     # ---- the recorder, the sampler alone, the synchronous loop
     def make():
         s = sfl.BatchSolver(dim_x, dim_y, members) if batch else sfl.Solver(dim_x, dim_y)

@@ -24,7 +24,9 @@ With --parent PATH (the library of the parent commit, built from a scratch workt
 alternating in the same rounds through the same raw ctypes calls, on --objects batches (contexts) of each made in turn: where
 an object's fields lie moves a step by more than the rounds of one object differ.  The conditions: (a) on this library agrees
 with (a) on the parent's inside the spread the probe itself reports for the PARENT's rounds and objects, max - min; and
-(b) - (a) is no more than (e) - (a) beyond the spread of (e)'s rounds.  Everything is written down as measured either way.
+(b) - (a) is no more than (e) - (a) beyond the spread of (e)'s rounds.  Then (b) to (e) are run on both libraries too
+(loads_probe.py samples_against_parent): what a sample costs on this one against what it costs on the parent's.  Everything is
+written down as measured either way.
 
 usage: python3 tools/torque_probe.py [--parent libsfl_parent.so] [--objects K] [--reps R] [--steps N] [--out profiles/torque.txt]"""
 import argparse
@@ -40,6 +42,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sfl = importlib.import_module("esp32-fluid-simulation_amd")
 capi = sfl.capi
+from loads_probe import samples_against_parent   # noqa: E402  (beside this file)
 
 OUT = []
 DT, DX, OMEGA = 0.05, 1.0, 1.9
@@ -143,6 +146,10 @@ def workload(a, batch, dim_x, dim_y, members, iters, radius):
         say("  the parent's library: not measured (no --parent)")
     for _, _, r in raws:
         r.close()
+    if a.parent:   # (in the stream of (20, 3), as the recorders below)
+        samples_against_parent(a, say, batch, dim_x, dim_y, members, iters, mask,
+                               {"(b) step, a torque sample": ("torque",), "(c) step, a loads sample": ("loads",), "(d) step, a friction sample": ("friction",),
+                                "(e) step, loads and friction": ("loads", "friction")}, velocity=(20.0, 3.0), pivot=(dim_x // 2, dim_y // 2))
     # ---- the recorders and the sampler alone
     def make():
         s = sfl.BatchSolver(dim_x, dim_y, members) if batch else sfl.Solver(dim_x, dim_y)
