@@ -279,6 +279,21 @@ __device__ __forceinline__ int open_neighbour_count(int code)
     return __builtin_popcount(code & kSolidAll) + ((code & kOpenOutflow) ? 1 : 0);
 }
 
+// The stencils by the TYPE of a member's codes, for the bodies that serve both (small_grid_core.h, batch_member.h): a
+// uint8_t is a code byte and takes the solids' functions, a uint16_t an open code.
+template <class Code>
+__device__ __forceinline__ float divergence_sum_coded(const float2 *q, int stride, int code)
+{
+    if constexpr (sizeof(Code) == 1) return divergence_sum_solid(q, stride, code);
+    else return divergence_sum_open(q, stride, code);
+}
+template <class Code>
+__device__ __forceinline__ float2 project_cell_coded(float2 u, const float *q, int stride, int code, float two_dx_inv)
+{
+    if constexpr (sizeof(Code) == 1) return project_cell_solid(u, q, stride, code, two_dx_inv);
+    else return project_cell_open(u, q, stride, code, two_dx_inv);
+}
+
 struct uq3 {
     uint32_t x, y, z;
 };

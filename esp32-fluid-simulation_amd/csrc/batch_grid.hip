@@ -37,51 +37,12 @@
 //
 // Numerics contract: -ffp-contract=off, every operation individually rounded in the
 // reference's order.  Reference citations are file:line under /root/reference/ESP32-fluid-simulation/.
-#include "batch.h"
-#include "small_grid_core.h"
-
-#ifndef SFL_BATCH_THREADS
-#define SFL_BATCH_THREADS 1024
-#endif
-#ifndef SFL_BATCH_WAVES_PER_EU
-#define SFL_BATCH_WAVES_PER_EU 8
-#endif
-#if SFL_BATCH_WAVES_PER_EU > 0
-#define SFL_BATCH_BOUNDS __launch_bounds__(SFL_BATCH_THREADS) __attribute__((amdgpu_waves_per_eu(SFL_BATCH_WAVES_PER_EU)))
-#else
-#define SFL_BATCH_BOUNDS __launch_bounds__(SFL_BATCH_THREADS)
-#endif
+#include "batch_member.h"
 
 namespace sfl {
 namespace {
 
-using namespace small_core;
-
-constexpr int kThreads = SFL_BATCH_THREADS;
-// every workgroup size must own the same cells of one colour in total as small_grid.hip's 1024 threads: the batch
-// accepts exactly the shapes small_grid_fits accepts
-static_assert(cells_per_colour<kThreads>() * kThreads == kSmallGridMaxCells / 2, "SFL_BATCH_THREADS must divide 3072");
-
-// the step of one member: every pointer at that member's first cell, its force records
-__device__ __forceinline__ SmallStep member_step(const BatchStep &b, size_t member)
-{
-    const size_t base = member * (size_t)b.step.dim_x * (size_t)b.step.dim_y;   // 64-bit: cells before this member
-    SmallStep a = b.step;
-    a.v_in += 2 * base;
-    a.v_out += 2 * base;
-    a.col_in += 3 * base;
-    a.col_out += 3 * base;
-    a.div += base;
-    a.p += base;
-    a.n_forces = 0;
-    if (b.force_offsets) {   // this member's records, in queue order
-        const int f0 = b.force_offsets[member], f1 = b.force_offsets[member + 1];
-        a.force_cells += 2 * (size_t)f0;
-        a.force_vel += 2 * (size_t)f0;
-        a.n_forces = f1 - f0;
-    }
-    return a;
-}
+using namespace batch_member;   // (the workgroup's shape, member_step, apply_member, launch_members)
 
 // ---- one whole step of member blockIdx.x, ino:252-287 ---------------------------------------------
 __global__ void SFL_BATCH_BOUNDS
@@ -112,10 +73,7 @@ batch_step_each_kernel(BatchStep b, const BatchMember *__restrict__ members, flo
     const BatchMember q = members[blockIdx.x];   // workgroup-uniform: scalar loads
     const size_t member = (size_t)q.member;      // (the host hands out long members first)
     SmallStep a = member_step(b, member);
-    a.dt = q.dt;
-    a.two_dx_inv = q.two_dx_inv;
-    a.iters = q.iters;
-    a.prm = q.prm;
+    apply_member(a, q);
 #include "small_step_body.inc"
     // (the body's last loop only reads l.p and l.v; l.p and l.d are final since the solve's last barrier)
     update_norm_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, a.prm.dx, report + member);
@@ -156,10 +114,7 @@ batch_step_until_kernel(BatchStep b, const BatchMember *__restrict__ members, co
     const BatchStop stop = stops[blockIdx.x];
     const size_t member = (size_t)q.member;
     SmallStep a = member_step(b, member);
-    a.dt = q.dt;
-    a.two_dx_inv = q.two_dx_inv;
-    a.iters = q.iters;
-    a.prm = q.prm;
+    apply_member(a, q);
 #define SFL_STEP_SOLVE const UntilResult r = sor_until_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, a.iters, a.prm, stop.tol, stop.every)
 #include "small_step_body.inc"
 #undef SFL_STEP_SOLVE
@@ -181,18 +136,6 @@ batch_solve_until_kernel(float *__restrict__ p_out, const float *__restrict__ d_
     const UntilResult r = sor_until_in_lds<kThreads>(l.p, l.d, dim_x, dim_y, q.iters, q.prm, stop.tol, stop.every);
     for (int c = threadIdx.x; c < cells; c += kThreads) p_out[base + c] = l.p[c];
     leave_until(r, (size_t)q.member, report, counts, 0);
-}
-
-// every launch of this file: one workgroup per member, 16 B of LDS per cell, which a kernel is granted once per device
-template <auto KERNEL, class... A>
-hipError_t launch_members(hipStream_t s, int dim_x, int dim_y, int batch, A... args)
-{
-    static bool granted[64];
-    const size_t lds = (size_t)dim_x * dim_y * 16;
-    hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(KERNEL), granted);
-    if (e != hipSuccess) return e;
-    KERNEL<<<batch, kThreads, lds, s>>>(args...);
-    return hipGetLastError();
 }
 
 }  // namespace

@@ -15,33 +15,15 @@
 //
 // Addressing: a member's base offset (member x cells x element) is computed in 64-bit; offsets inside a member are
 // 32-bit ints.  Numerics contract: -ffp-contract=off, no denormal flushing.
+#include "batch_member.h"
 #include "large_member_core.h"
 
 namespace sfl {
 namespace {
 
 using namespace large_core;
-
-// the step of one member: every pointer at that member's first cell, its force records
-__device__ __forceinline__ SmallStep member_step(const BatchStep &b, size_t member)
-{
-    const size_t base = member * (size_t)b.step.dim_x * (size_t)b.step.dim_y;   // 64-bit: cells before this member
-    SmallStep a = b.step;
-    a.v_in += 2 * base;
-    a.v_out += 2 * base;
-    a.col_in += 3 * base;
-    a.col_out += 3 * base;
-    a.div += base;
-    a.p += base;
-    a.n_forces = 0;
-    if (b.force_offsets) {   // this member's records, in queue order
-        const int f0 = b.force_offsets[member], f1 = b.force_offsets[member + 1];
-        a.force_cells += 2 * (size_t)f0;
-        a.force_vel += 2 * (size_t)f0;
-        a.n_forces = f1 - f0;
-    }
-    return a;
-}
+using batch_member::apply_member;   // (the two that do not depend on the bytes of LDS per cell)
+using batch_member::member_step;
 
 // what a member leaves besides its fields: report[m] = the update norm of its final pressure (kEach, kUntil) and
 // counts[2 m], counts[2 m + 1] = the iterations of this solve and their sum over the launches of one call (kUntil; `add`
@@ -78,10 +60,7 @@ large_step_kernel(BatchStep b, const BatchMember *__restrict__ members, const Ba
         const BatchMember q = members[blockIdx.x];   // workgroup-uniform: scalar loads
         member = (size_t)q.member;                   // (the host hands out long members first)
         a = member_step(b, member);
-        a.dt = q.dt;
-        a.two_dx_inv = q.two_dx_inv;
-        a.iters = q.iters;
-        a.prm = q.prm;
+        apply_member(a, q);
         if (kMode == kUntil) {
             const BatchStop stop = stops[blockIdx.x];
             tol = stop.tol;

@@ -33,28 +33,12 @@
 // stencil written once: every field ends up bit for bit where `steps` launches of batch_step[_each]_kernel leave it.
 //
 // Numerics contract: -ffp-contract=off, every operation individually rounded in the reference's order.
-#include "batch.h"
-#include "small_grid_core.h"
-
-#ifndef SFL_BATCH_THREADS
-#define SFL_BATCH_THREADS 1024
-#endif
-#ifndef SFL_BATCH_WAVES_PER_EU
-#define SFL_BATCH_WAVES_PER_EU 8
-#endif
-#if SFL_BATCH_WAVES_PER_EU > 0
-#define SFL_BATCH_BOUNDS __launch_bounds__(SFL_BATCH_THREADS) __attribute__((amdgpu_waves_per_eu(SFL_BATCH_WAVES_PER_EU)))
-#else
-#define SFL_BATCH_BOUNDS __launch_bounds__(SFL_BATCH_THREADS)
-#endif
+#include "batch_member.h"
 
 namespace sfl {
 namespace {
 
-using namespace small_core;
-
-constexpr int kThreads = SFL_BATCH_THREADS;
-static_assert(cells_per_colour<kThreads>() * kThreads == kSmallGridMaxCells / 2, "SFL_BATCH_THREADS must divide 3072");
+using namespace batch_member;   // (the workgroup's shape, apply_member)
 
 __global__ void SFL_BATCH_BOUNDS
 batch_play_kernel(BatchPlay b, int batch, const BatchMember *__restrict__ members, float *__restrict__ report)
@@ -65,10 +49,7 @@ batch_play_kernel(BatchPlay b, int batch, const BatchMember *__restrict__ member
     if (members) {   // workgroup-uniform: scalar loads
         const BatchMember q = members[blockIdx.x];
         member = (size_t)q.member;
-        a.dt = q.dt;
-        a.two_dx_inv = q.two_dx_inv;
-        a.iters = q.iters;
-        a.prm = q.prm;
+        apply_member(a, q);
     }
     const size_t base = member * (size_t)a.dim_x * (size_t)a.dim_y;   // 64-bit: cells before this member
     float2 *const lds_v = reinterpret_cast<float2 *>(lds_raw);   // region A at cell 0, region B at cell `cells`

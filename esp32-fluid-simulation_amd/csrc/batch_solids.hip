@@ -1,166 +1,51 @@
 // batch_solids.hip -- batch members with solid cells inside their grids (gfx950 / MI355X; include/sfl.h "SOLIDS"): the
 // step, the pressure solve and the velocity statistics of batch_grid.hip and flow_stats.hip for a batch whose members
-// carry a mask of solid cells.  Kernels of their own, written a second time as sor_until_in_lds was: the kernels of
-// batch_grid.hip, small_step_body.inc and sor_in_lds keep their text and their instructions, and a batch without solids
-// launches exactly what it launched before.
+// carry a mask of solid cells.  The kernels and launchers alone: their bodies are batch_member.h's (step_in_lds,
+// coded_solve_in_lds, velocity_stats_of) and small_grid_core.h's (sor_coded_in_lds, update_norm_coded_in_lds), shared with
+// batch_openings.hip and batch_viscous.hip and instantiated here on bytes.  Kernels of their own beside batch_grid.hip's,
+// whose text is small_step_body.inc and keeps its instructions: a batch without solids launches exactly what it did.
 //
 // One CODE BYTE per cell, formed on the host (solids.cpp) and read from memory: bits 0..3 = W, E, S, N neighbour present
 // (inside the domain and fluid), bit 4 = the cell is fluid, a solid cell's byte 0 (advect_math.h).  The bytes stay out of
 // LDS -- two members of 61 x 81 share a CU with 2 x 79 056 of its 163 840 bytes, and a byte per cell in LDS would cost the
 // second member -- and a mask shared by all members (member stride 0) stays in L2.  The solve's set-up reads the byte of
-// every owned cell once, into the registers sor_iteration already keeps (sor_cells_init_solid); its loop is the
+// every owned cell once, into the registers sor_iteration already keeps (sor_cells_init_coded); its loop is the
 // existing one.  The three per-cell passes of a step read it once per cell.
 //
 // The step, in the order of small_step_body.inc (the rule of include/sfl.h, items 1 - 7):
 //   * advection of the velocity as it stands, on every cell; what is stored for a solid cell is (0, 0);
 //   * forces in queue order, a record on a solid cell skipped: together the same as zeroing the solids after the forces,
 //     without a pass and a barrier of its own;
-//   * divergence (divergence_sum_solid), solve (sor_solid_in_lds), gradient (project_cell_solid), dye as ever.
+//   * divergence (divergence_sum_solid), solve (sor_coded_in_lds), gradient (project_cell_solid), dye as ever.
 //
 // Workgroup shape and occupancy: those of batch_grid.hip (1024 threads, 8 waves per SIMD, 16 B of dynamic LDS per cell).
-//
-// Numerics contract: -ffp-contract=off, every operation individually rounded in the reference's order.
-#include "batch.h"
-#include "small_grid_core.h"
-#include "stats_kernels.h"
-
-#ifndef SFL_BATCH_THREADS
-#define SFL_BATCH_THREADS 1024
-#endif
-#ifndef SFL_BATCH_WAVES_PER_EU
-#define SFL_BATCH_WAVES_PER_EU 8
-#endif
-#if SFL_BATCH_WAVES_PER_EU > 0
-#define SFL_BATCH_BOUNDS __launch_bounds__(SFL_BATCH_THREADS) __attribute__((amdgpu_waves_per_eu(SFL_BATCH_WAVES_PER_EU)))
-#else
-#define SFL_BATCH_BOUNDS __launch_bounds__(SFL_BATCH_THREADS)
-#endif
+#include "batch_member.h"
 
 namespace sfl {
 namespace {
 
-using namespace small_core;
-
-constexpr int kThreads = SFL_BATCH_THREADS;
-static_assert(cells_per_colour<kThreads>() * kThreads == kSmallGridMaxCells / 2, "SFL_BATCH_THREADS must divide 3072");
-
-// the step of one member: every pointer at that member's first cell, its force records (batch_grid.hip member_step)
-__device__ __forceinline__ SmallStep member_step(const BatchStep &b, size_t member)
-{
-    const size_t base = member * (size_t)b.step.dim_x * (size_t)b.step.dim_y;   // 64-bit: cells before this member
-    SmallStep a = b.step;
-    a.v_in += 2 * base;
-    a.v_out += 2 * base;
-    a.col_in += 3 * base;
-    a.col_out += 3 * base;
-    a.div += base;
-    a.p += base;
-    a.n_forces = 0;
-    if (b.force_offsets) {   // this member's records, in queue order
-        const int f0 = b.force_offsets[member], f1 = b.force_offsets[member + 1];
-        a.force_cells += 2 * (size_t)f0;
-        a.force_vel += 2 * (size_t)f0;
-        a.n_forces = f1 - f0;
-    }
-    return a;
-}
-
-// the code bytes of one member: stride 0 = one mask for all members
-__device__ __forceinline__ const uint8_t *member_codes(const BatchSolids &s, size_t member) { return s.codes + member * s.member_stride; }
-
-// One whole step of the grid `a` describes, its code bytes at `codes`; returns the carved LDS (p and d final, for the
-// update norm of the *_each kernel).
-__device__ __forceinline__ Lds solid_step(const SmallStep &a, const uint8_t *__restrict__ codes, char *lds_raw)
-{
-    const int dim_x = a.dim_x, dim_y = a.dim_y, cells = dim_x * dim_y;
-    const Lds l = carve(lds_raw, cells);
-    const Slab g{dim_x, dim_y, 0, dim_y};
-    const float2 *v_in = reinterpret_cast<const float2 *>(a.v_in);
-    float2 *v_out = reinterpret_cast<float2 *>(a.v_out);
-
-    // advect(v_next, v, v, dt, no_slip) on every cell (item 1); a solid cell keeps (0, 0) (item 3)
-    for (int c = threadIdx.x; c < cells; c += kThreads) {
-        const int gj = c / dim_x, i = c - gj * dim_x;
-        const float2 u = v_in[c];
-        const float si = (float)i - u.x * a.dt;
-        const float sj = (float)gj - u.y * a.dt;
-        const SrcPos s = classify(si, sj, dim_x, dim_y);
-        const float2 r = sample_global_vec2f<true>(v_in, g, s, si, sj);
-        l.v[c] = (codes[c] & kSolidFluid) ? r : make_float2(0.0f, 0.0f);
-    }
-    __syncthreads();
-    // drag forces, in queue order: later entries win; a record on a solid cell has no effect (items 2 and 3)
-    if (a.n_forces > 0) {
-        if (threadIdx.x == 0)
-            for (int k = 0; k < a.n_forces; ++k) {
-                const int i = a.force_cells[2 * k], gj = a.force_cells[2 * k + 1];
-                if (i < 0 || i >= dim_x || gj < 0 || gj >= dim_y) continue;
-                if (!(codes[gj * dim_x + i] & kSolidFluid)) continue;
-                l.v[gj * dim_x + i] = make_float2(a.force_vel[2 * k], a.force_vel[2 * k + 1]);
-            }
-        __syncthreads();
-    }
-    // the divergence of a fluid cell; 0.0f in a solid one (item 4)
-    for (int c = threadIdx.x; c < cells; c += kThreads) {
-        const int code = codes[c];
-        const float sum = divergence_sum_solid(l.v + c, dim_x, code);
-        const float dv = (code & kSolidFluid) ? sum * a.two_dx_inv : 0.0f;
-        l.d[c] = dv;
-        a.div[c] = dv;
-    }
-    // the pressure (item 5; the barrier inside also orders the divergence writes above)
-    sor_solid_in_lds<kThreads>(l.p, l.d, codes, dim_x, dim_y, a.iters, a.prm);
-    // the gradient (item 6), then the dye back-trace with the projected velocity of the cell itself (item 7)
-    const uint32_t *col_in = a.col_in;
-    for (int c = threadIdx.x; c < cells; c += kThreads) {
-        const int gj = c / dim_x, i = c - gj * dim_x;
-        const float pc = l.p[c];
-        const float2 u = project_cell_solid(l.v[c], l.p + c, dim_x, codes[c], a.two_dx_inv);
-        v_out[c] = u;
-        a.p[c] = pc;
-        const float si = (float)i - u.x * a.dt;
-        const float sj = (float)gj - u.y * a.dt;
-        const SrcPos s = classify(si, sj, dim_x, dim_y);
-        store_uq3(a.col_out, (size_t)c, sample_global_uq3<false>(col_in, g, s, si, sj));
-    }
-    return l;
-}
-
-// poisson_solve of ONE grid with solid cells: d_in -> p_out (solve_in_lds)
-__device__ __forceinline__ Lds solid_solve(char *lds_raw, float *p_out, const float *d_in, const uint8_t *__restrict__ codes, int dim_x,
-                                           int dim_y, int iters, SorParams prm)
-{
-    const int cells = dim_x * dim_y;
-    const Lds l = carve(lds_raw, cells);
-    for (int c = threadIdx.x; c < cells; c += kThreads) l.d[c] = d_in[c];
-    sor_solid_in_lds<kThreads>(l.p, l.d, codes, dim_x, dim_y, iters, prm);   // (its first barrier also covers the copy of d)
-    for (int c = threadIdx.x; c < cells; c += kThreads) p_out[c] = l.p[c];
-    return l;
-}
+using namespace batch_member;
 
 __global__ void SFL_BATCH_BOUNDS
 batch_solid_step_kernel(BatchStep b, BatchSolids solids)
 {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     const SmallStep a = member_step(b, blockIdx.x);
-    solid_step(a, member_codes(solids, blockIdx.x), lds_raw);
+    step_in_lds(a, member_codes(solids, blockIdx.x), lds_raw);
 }
 
 __global__ void SFL_BATCH_BOUNDS
 batch_solid_step_each_kernel(BatchStep b, BatchSolids solids, const BatchMember *__restrict__ members, float *__restrict__ report)
 {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-    const BatchMember q = members[blockIdx.x];   // workgroup-uniform: scalar loads
-    const size_t member = (size_t)q.member;      // (the host hands out long members first)
+    const BatchMember q = members[blockIdx.x];
+    const size_t member = (size_t)q.member;
     SmallStep a = member_step(b, member);
-    a.dt = q.dt;
-    a.two_dx_inv = q.two_dx_inv;
-    a.iters = q.iters;
-    a.prm = q.prm;
+    apply_member(a, q);
     const uint8_t *codes = member_codes(solids, member);
-    const Lds l = solid_step(a, codes, lds_raw);
+    const Lds l = step_in_lds(a, codes, lds_raw);
     // (the step's last loop only reads l.p and l.v; l.p and l.d are final since the solve's last barrier)
-    update_norm_solid_in_lds<kThreads>(l.p, l.d, codes, a.dim_x, a.dim_y, a.prm.dx, report + member);
+    update_norm_coded_in_lds<kThreads>(l.p, l.d, codes, a.dim_x, a.dim_y, a.prm.dx, report + member);
 }
 
 __global__ void SFL_BATCH_BOUNDS
@@ -169,7 +54,7 @@ batch_solid_solve_kernel(float *__restrict__ p_out, const float *__restrict__ d_
 {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     const size_t base = (size_t)blockIdx.x * (size_t)dim_x * (size_t)dim_y;
-    solid_solve(lds_raw, p_out + base, d_in + base, member_codes(solids, blockIdx.x), dim_x, dim_y, iters, prm);
+    coded_solve_in_lds(lds_raw, p_out + base, d_in + base, member_codes(solids, blockIdx.x), dim_x, dim_y, iters, prm);
 }
 
 __global__ void SFL_BATCH_BOUNDS
@@ -180,62 +65,15 @@ batch_solid_solve_each_kernel(float *__restrict__ p_out, const float *__restrict
     const BatchMember q = members[blockIdx.x];
     const size_t base = (size_t)q.member * (size_t)dim_x * (size_t)dim_y;
     const uint8_t *codes = member_codes(solids, (size_t)q.member);
-    const Lds l = solid_solve(lds_raw, p_out + base, d_in + base, codes, dim_x, dim_y, q.iters, q.prm);
-    update_norm_solid_in_lds<kThreads>(l.p, l.d, codes, dim_x, dim_y, q.prm.dx, report + q.member);
+    const Lds l = coded_solve_in_lds(lds_raw, p_out + base, d_in + base, codes, dim_x, dim_y, q.iters, q.prm);
+    update_norm_coded_in_lds<kThreads>(l.p, l.d, codes, dim_x, dim_y, q.prm.dx, report + q.member);
 }
-
-// ---- the velocity statistics of members with solid cells ----------------------------------------------------------
-// max |v.x|, max |v.y| over all cells and max |divergence| by item 4 of the rule over all cells (0.0f in a solid one), as
-// bit patterns into records zeroed in front (flow_stats.hip's reduction: a maximum does not depend on the order).  A
-// member is at most 6144 cells: blockIdx.y is the member, the workgroups of blockIdx.x share its cells, a thread a cell
-// at a time with its neighbours read from memory -- L2 at this size.
-constexpr int kStatsThreads = 256;
 
 __global__ void __launch_bounds__(kStatsThreads)
 solid_velocity_stats_kernel(const float *__restrict__ v, BatchSolids solids, int dim_x, int dim_y, float two_dx_inv,
                             const float *__restrict__ member_two_dx_inv, FlowStatsRecord *__restrict__ out)
 {
-    const size_t member = blockIdx.y;
-    const int cells = dim_x * dim_y;
-    const float2 *q = reinterpret_cast<const float2 *>(v) + member * (size_t)cells;
-    const uint8_t *codes = member_codes(solids, member);
-    const float scale = member_two_dx_inv ? member_two_dx_inv[member] : two_dx_inv;
-    unsigned m[3] = {0u, 0u, 0u};
-    for (int c = blockIdx.x * kStatsThreads + threadIdx.x; c < cells; c += gridDim.x * kStatsThreads) {
-        const int code = codes[c];
-        const float2 own = q[c];
-        const float sum = divergence_sum_solid(q + c, dim_x, code);
-        const float dv = (code & kSolidFluid) ? sum * scale : 0.0f;
-        const unsigned bx = __float_as_uint(own.x) & 0x7fffffffu, by = __float_as_uint(own.y) & 0x7fffffffu;
-        const unsigned bd = __float_as_uint(dv) & 0x7fffffffu;
-        m[0] = bx > m[0] ? bx : m[0];
-        m[1] = by > m[1] ? by : m[1];
-        m[2] = bd > m[2] ? bd : m[2];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int o = 32; o > 0; o >>= 1) {   // the wave's maximum
-            const unsigned t = __shfl_xor(m[k], o);
-            m[k] = t > m[k] ? t : m[k];
-        }
-    if ((threadIdx.x & 63) == 0) {
-        FlowStatsRecord *rec = out + member;
-        atomicMax(&rec->max_abs_vx, m[0]);
-        atomicMax(&rec->max_abs_vy, m[1]);
-        atomicMax(&rec->max_abs_div, m[2]);
-    }
-}
-
-// every step or solve launch of this file: one workgroup per member, 16 B of LDS per cell, granted once per device
-template <auto KERNEL, class... A>
-hipError_t launch_members(hipStream_t s, int dim_x, int dim_y, int batch, A... args)
-{
-    static bool granted[64];
-    const size_t lds = (size_t)dim_x * dim_y * 16;
-    hipError_t e = allow_small_grid_lds(reinterpret_cast<const void *>(KERNEL), granted);
-    if (e != hipSuccess) return e;
-    KERNEL<<<batch, kThreads, lds, s>>>(args...);
-    return hipGetLastError();
+    velocity_stats_of(v, solids, dim_x, dim_y, two_dx_inv, member_two_dx_inv, out);
 }
 
 }  // namespace
@@ -266,20 +104,8 @@ hipError_t launch_batch_solid_solve_each(hipStream_t s, float *p, const float *d
 hipError_t launch_solid_velocity_stats(hipStream_t s, FlowStatsRecord *out, const float *v, const BatchSolids &solids, int dim_x,
                                        int dim_y, int members, float two_dx_inv, const float *member_two_dx_inv)
 {
-    if (members <= 0) return hipSuccess;
-    const int cells = dim_x * dim_y;
-    const int per_member = (cells + 4 * kStatsThreads - 1) / (4 * kStatsThreads);   // four cells per thread, at most six workgroups
-    for (int first = 0; first < members; first += 65535) {   // (gridDim.y is a 16-bit number)
-        const int count = members - first < 65535 ? members - first : 65535;
-        BatchSolids part = solids;
-        part.codes += (size_t)first * solids.member_stride;
-        solid_velocity_stats_kernel<<<dim3(per_member, count), kStatsThreads, 0, s>>>(
-            v + 2 * (size_t)first * cells, part, dim_x, dim_y, two_dx_inv, member_two_dx_inv ? member_two_dx_inv + first : nullptr,
-            out + first);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_coded_velocity_stats<solid_velocity_stats_kernel>(s, out, v, solids, dim_x, dim_y, members, two_dx_inv,
+                                                                    member_two_dx_inv);
 }
 
 }  // namespace sfl

@@ -1,7 +1,7 @@
 // inflow.hip -- inflow profiles and the flux through the openings (gfx950 / MI355X; include/sfl.h "INFLOW PROFILES AND
 // FLUX"): item 2a of a context with a profile, and the flux record of a batch member and of a context.  New kernels;
-// every other unit keeps its text.  (The step of a batch with a profile is the second instantiation of
-// batch_openings.hip's open_step.)
+// every other unit keeps its text.  (The step of a batch with a profile is the kProfile instantiation of
+// batch_member.h's step_in_lds, in batch_openings.hip.)
 //
 //   open_inflow_profile_kernel   v[cells[k]] = values[k] over the compact list of the fluid inflow cells: the host
 //                                (context_openings.cpp) forms `values` beside the list -- a record's velocity where the

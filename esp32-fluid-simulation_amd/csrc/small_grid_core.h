@@ -308,17 +308,29 @@ __device__ __forceinline__ void update_norm_in_lds(const float *p, const float *
     if (threadIdx.x == 0) *out = __uint_as_float(worst);
 }
 
-// ---- solid cells inside the grid (include/sfl.h "SOLIDS"; batch_solids.hip) ------------------------------------------
-// sor_cells_init with the boundary facts read from the member's code bytes (advect_math.h: bits 0..3 neighbour present,
-// bit 4 the cell is fluid, a solid cell's byte 0) instead of derived from (i, j): a solid neighbour is one more reason for
-// a neighbour to be absent.  The byte of a fluid cell IS the (m | 16) that sor_cells_init packs into cm; a solid cell
-// gets cm = 0 like a position without a cell -- its existence bit is clear, so sor_iteration never stores it and p keeps
-// the zero of the fill; no fluid cell has a neighbour bit that points at it, so it is never read either.  Beyond the
-// reference's table: k = -1.0f for one present neighbour, 0.0f for none (a fluid cell walled in on all sides).
+// ---- members whose cells carry CODES: solid cells inside the grid, openings on its rim -------------------------------
+// (include/sfl.h "SOLIDS" and "OPENINGS"; batch_member.h has the kernels' bodies)
+// ONE text for both kinds of code, over the element type (advect_math.h): a uint8_t is the solids' code byte -- bits 0..3
+// neighbour present, bit 4 the cell is fluid, a solid cell's byte 0 -- and a uint16_t an open code, that byte with the
+// opening in bits 8..12.  Read as a byte, bits 8..12 are known to be clear, and what asks for them folds away: the byte
+// instantiation is the solids' rule and nothing more.
+//
+// The k of item 5 from n = the neighbours that count (open_neighbour_count: the present ones, plus one for an outflow's
+// ghost pressure of zero).  Beyond the reference's table: -1.0f for one, 0.0f for none (a fluid cell walled in on all sides).
+__device__ __forceinline__ float coded_k_factor(int n)
+{
+    return (n == 4) ? -0.25f : (n == 3) ? (float)(-1.0 / 3.0) : (n == 2) ? (float)(-1.0 / 2.0) : (n == 1) ? -1.0f : 0.0f;
+}
+
+// sor_cells_init with the boundary facts read from the member's codes instead of derived from (i, j): a solid or an open
+// neighbour is one more reason for a neighbour to be absent -- the loop reads -0.0f for it and z is +0.0f, as for a wall.
+// The low byte of a fluid cell's code IS the (m | 16) that sor_cells_init packs into cm; a solid cell gets cm = 0 like a
+// position without a cell -- its existence bit is clear, so sor_iteration never stores it and p keeps the zero of the
+// fill; no fluid cell has a neighbour bit that points at it, so it is never read either.
 // `codes` is memory (one load per owned cell, here and nowhere in the loop): sor_iteration runs as it stands.
-template <int kThreads>
-__device__ __forceinline__ void sor_cells_init_solid(SorCells<kThreads> &t, const float *d, const uint8_t *codes, int dim_x,
-                                                     int dim_y, float dx)
+template <int kThreads, class Code>
+__device__ __forceinline__ void sor_cells_init_coded(SorCells<kThreads> &t, const float *d, const Code *codes, int dim_x, int dim_y,
+                                                     float dx)
 {
     constexpr int kCellsPerColour = SorCells<kThreads>::kCellsPerColour;
     const int half = (dim_x + 1) / 2;
@@ -336,35 +348,32 @@ __device__ __forceinline__ void sor_cells_init_solid(SorCells<kThreads> &t, cons
             const int code = have ? (int)codes[c] : 0;
             const bool fluid = (code & kSolidFluid) != 0;
             const int present = __builtin_popcount(code & kSolidAll);
-            t.cm[colour][k] = fluid ? (c | (code << 16)) : 0;
+            t.cm[colour][k] = fluid ? (c | ((code & 0xff) << 16)) : 0;
             t.own[colour][k] = 0.0f;
             t.rhs[colour][k] = fluid ? dx * d[c] : 0.0f;
-            t.kf[colour][k] = (present == 4)   ? -0.25f
-                              : (present == 3) ? (float)(-1.0 / 3.0)
-                              : (present == 2) ? (float)(-1.0 / 2.0)
-                              : (present == 1) ? -1.0f
-                                               : 0.0f;
+            t.kf[colour][k] = coded_k_factor(open_neighbour_count(code));
             t.z[colour][k] = (present == 4) ? -0.0f : 0.0f;
         }
 }
 
-// sor_in_lds over a member with solid cells: the zero fill, the masked set-up, the iterations of sor_iteration
-template <int kThreads>
-__device__ __forceinline__ void sor_solid_in_lds(float *p, const float *d, const uint8_t *codes, int dim_x, int dim_y, int iters,
+// sor_in_lds over a member with codes: the zero fill, the set-up above, the iterations of sor_iteration
+template <int kThreads, class Code>
+__device__ __forceinline__ void sor_coded_in_lds(float *p, const float *d, const Code *codes, int dim_x, int dim_y, int iters,
                                                  SorParams prm)
 {
     const int cells = dim_x * dim_y;
     for (int c = threadIdx.x; c < cells; c += kThreads) p[c] = 0.0f;
     __syncthreads();   // (also: d is complete)
     SorCells<kThreads> t;
-    sor_cells_init_solid(t, d, codes, dim_x, dim_y, prm.dx);
+    sor_cells_init_coded(t, d, codes, dim_x, dim_y, prm.dx);
     for (int it = 0; it < iters; ++it) sor_iteration(t, p, dim_x, prm);
 }
 
-// update_norm_in_lds over the FLUID cells of a member: `present`, and which neighbours are read, come from the code byte;
-// a solid cell has no say, and a member without a fluid cell reports 0.0f.  The same reduction, the same barriers.
-template <int kT>
-__device__ __forceinline__ void update_norm_solid_in_lds(const float *p, const float *d, const uint8_t *codes, int dim_x, int dim_y,
+// update_norm_in_lds over the FLUID cells of a member with codes: `present`, which neighbours are read and k -- the
+// solve's -- come from the code; a solid cell has no say, and a member without a fluid cell reports 0.0f.  The same
+// reduction, the same barriers.
+template <int kT, class Code>
+__device__ __forceinline__ void update_norm_coded_in_lds(const float *p, const float *d, const Code *codes, int dim_x, int dim_y,
                                                          float dx, float *out)
 {
     __shared__ unsigned worst;
@@ -379,94 +388,7 @@ __device__ __forceinline__ void update_norm_solid_in_lds(const float *p, const f
         const float s = (code & kSolidS) ? p[c - dim_x] : -0.0f;
         const float n = (code & kSolidN) ? p[c + dim_x] : -0.0f;
         const float z = (present == 4) ? -0.0f : 0.0f;
-        const float kf = (present == 4)   ? -0.25f
-                         : (present == 3) ? (float)(-1.0 / 3.0)
-                         : (present == 2) ? (float)(-1.0 / 2.0)
-                         : (present == 1) ? -1.0f
-                                          : 0.0f;
-        const float sum = (((z + w) + e) + s) + n;
-        const float p_gs = kf * (dx * d[c] - sum);
-        const unsigned bits = __float_as_uint(p_gs - p[c]) & 0x7fffffffu;   // |p_gs - p|
-        if (code & kSolidFluid) m = bits > m ? bits : m;
-    }
-    for (int o = 32; o > 0; o >>= 1) {   // the wave's maximum
-        const unsigned t = __shfl_xor(m, o);
-        m = t > m ? t : m;
-    }
-    __syncthreads();   // worst = 0 is visible
-    if ((threadIdx.x & 63) == 0) atomicMax(&worst, m);
-    __syncthreads();
-    if (threadIdx.x == 0) *out = __uint_as_float(worst);
-}
-
-// ---- openings on the rim of the grid (include/sfl.h "OPENINGS"; batch_openings.hip) ----------------------------------
-// The k of item 5 from n = the present neighbours, plus one for an outflow's ghost pressure of zero: the solids' table.
-__device__ __forceinline__ float open_k_factor(int n)
-{
-    return (n == 4) ? -0.25f : (n == 3) ? (float)(-1.0 / 3.0) : (n == 2) ? (float)(-1.0 / 2.0) : (n == 1) ? -1.0f : 0.0f;
-}
-
-// sor_cells_init_solid with the member's OPEN CODES (advect_math.h: the code byte below, the opening above it): only kf
-// differs.  The open neighbour is absent in bits 0..3, so the loop reads -0.0f for it and z is +0.0f, as for a wall.
-template <int kThreads>
-__device__ __forceinline__ void sor_cells_init_open(SorCells<kThreads> &t, const float *d, const uint16_t *codes, int dim_x,
-                                                    int dim_y, float dx)
-{
-    constexpr int kCellsPerColour = SorCells<kThreads>::kCellsPerColour;
-    const int half = (dim_x + 1) / 2;
-    const int per_colour = dim_y * half;
-    t.kmax = (per_colour + kThreads - 1) / kThreads;
-#pragma unroll
-    for (int colour = 0; colour < 2; ++colour)
-#pragma unroll
-        for (int k = 0; k < kCellsPerColour; ++k) {
-            const int q = threadIdx.x + k * kThreads;
-            const int gj = q / half, ii = q - gj * half;
-            const int i = 2 * ii + ((gj + colour) & 1);
-            const bool have = k < t.kmax && gj < dim_y && i < dim_x;
-            const int c = have ? gj * dim_x + i : 0;
-            const int code = have ? (int)codes[c] : 0;
-            const bool fluid = (code & kSolidFluid) != 0;
-            const int present = __builtin_popcount(code & kSolidAll);
-            t.cm[colour][k] = fluid ? (c | ((code & 0xff) << 16)) : 0;
-            t.own[colour][k] = 0.0f;
-            t.rhs[colour][k] = fluid ? dx * d[c] : 0.0f;
-            t.kf[colour][k] = open_k_factor(open_neighbour_count(code));
-            t.z[colour][k] = (present == 4) ? -0.0f : 0.0f;
-        }
-}
-
-// sor_solid_in_lds over a member with openings: the zero fill, the set-up above, the iterations of sor_iteration
-template <int kThreads>
-__device__ __forceinline__ void sor_open_in_lds(float *p, const float *d, const uint16_t *codes, int dim_x, int dim_y, int iters,
-                                                SorParams prm)
-{
-    const int cells = dim_x * dim_y;
-    for (int c = threadIdx.x; c < cells; c += kThreads) p[c] = 0.0f;
-    __syncthreads();   // (also: d is complete)
-    SorCells<kThreads> t;
-    sor_cells_init_open(t, d, codes, dim_x, dim_y, prm.dx);
-    for (int it = 0; it < iters; ++it) sor_iteration(t, p, dim_x, prm);
-}
-
-// update_norm_solid_in_lds with open codes: the same k as the solve's
-template <int kT>
-__device__ __forceinline__ void update_norm_open_in_lds(const float *p, const float *d, const uint16_t *codes, int dim_x, int dim_y,
-                                                        float dx, float *out)
-{
-    __shared__ unsigned worst;
-    if (threadIdx.x == 0) worst = 0u;
-    const int cells = dim_x * dim_y;
-    unsigned m = 0u;
-    for (int c = threadIdx.x; c < cells; c += kT) {
-        const int code = codes[c];
-        const int present = __builtin_popcount(code & kSolidAll);
-        const float w = (code & kSolidW) ? p[c - 1] : -0.0f;
-        const float e = (code & kSolidE) ? p[c + 1] : -0.0f;
-        const float s = (code & kSolidS) ? p[c - dim_x] : -0.0f;
-        const float n = (code & kSolidN) ? p[c + dim_x] : -0.0f;
-        const float z = (present == 4) ? -0.0f : 0.0f;
-        const float kf = open_k_factor(open_neighbour_count(code));
+        const float kf = coded_k_factor(open_neighbour_count(code));
         const float sum = (((z + w) + e) + s) + n;
         const float p_gs = kf * (dx * d[c] - sum);
         const unsigned bits = __float_as_uint(p_gs - p[c]) & 0x7fffffffu;   // |p_gs - p|

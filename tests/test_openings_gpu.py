@@ -2,7 +2,9 @@
 tests/opening_rule.py -- the header's rule in numpy float32, itself anchored on tests/solid_rule.py by tests/test_openings.py.
 Every comparison is bit for bit.
 
-Shapes: 7 x 5 (one owned cell per thread and colour), 61 x 81 (the sketch's grid, up to three) and 64 x 96 (the 6144-cell limit).
+Shapes: 7 x 5 (one owned cell per thread and colour), 61 x 81 (the sketch's grid, up to three) and 64 x 96 (the 6144-cell limit);
+3 x 3, the smallest grid that holds an opening (a rim cell that is no corner), with members of its own (set "c") at 0, 1 and 3
+iterations.
 Batches of four and five members with a DIFFERENT map and mask each.  The maps: west in / east out, south in / north out, all
 four sides, outflow only, inflow only (run with 3 iterations: its Neumann problem is incompatible and the solve drifts), a slot
 of one side, openings on solid rim cells (ignored) and none.  The masks: none, a disc, a channel (solid top and bottom rows,
@@ -57,7 +59,10 @@ def solid_of(kind, dim_x, dim_y):
 SETS = {"a": [("west_east", "none", (3.5, 0.0)), ("four", "disc", (2.0, 1.5)), ("slot", "seeded", (-0.0, 0.0)),
               ("on_solid", "walls", (1.25, -0.5)), ("empty", "channel", (9.0, 9.0))],
         "b": [("south_north", "none", (0.0, 2.5)), ("out_only", "seeded", (7.0, 7.0)), ("in_only", "disc", (1.5, 0.0)),
-              ("empty", "none", (4.0, 4.0))]}
+              ("empty", "none", (4.0, 4.0))],
+        # 3 x 3: every opening is ONE cell between two corners; "one" makes the centre solid, "walls" leaves a channel of 3 x 1
+        "c": [("west_east", "none", (3.5, 0.0)), ("south_north", "none", (0.0, 2.5)), ("four", "none", (2.0, 1.5)),
+              ("four", "one", (1.25, -0.5)), ("west_east", "walls", (-0.0, 0.75))]}
 
 
 @functools.lru_cache(maxsize=None)
@@ -81,6 +86,10 @@ def test_the_members_hold_the_cases_they_are_there_for():
         assert 0 < slot.sum() < dim_y - 2
         maps, masks, _ = members_of("b", dim_x, dim_y)
         assert not (maps[2] == OUT).any() and not (maps[1] == IN).any() and not maps[3].any() and not masks[3].any()
+    maps, masks, _ = members_of("c", 3, 3)
+    for m in range(len(maps)):   # at least one inflow and one outflow cell that counts in every member, and a fluid cell without one
+        assert rule.inflow_cells(maps[m], masks[m]).any() and rule.sides(maps[m], masks[m])[1].any() and (~masks[m] & (maps[m] == 0)).any()
+    assert masks[3][1, 1] and masks[3].sum() == 1 and (~masks[4]).sum() == 3 and not maps[4][0].any() and not maps[4][-1].any()
     n = solid_rule.count_present(mask_of("seeded", 61, 81))
     assert all((n[:, 0] == k).any() or (n[:, -1] == k).any() for k in (1, 2, 3)), "rim cells of every present count carry an opening"
 
@@ -157,7 +166,8 @@ def bits(a):
 
 
 # ---- 1. step_n against the rule ------------------------------------------------------------------------------------------
-CASES = [(7, 5, "a", it) for it in (0, 1, 7, 8, 9, 19)] + [(7, 5, "b", 3), (61, 81, "a", 8), (61, 81, "b", 3), (64, 96, "a", 19), (64, 96, "b", 9)]
+CASES = [(3, 3, "c", it) for it in (0, 1, 3)] + [(7, 5, "a", it) for it in (0, 1, 7, 8, 9, 19)] + \
+    [(7, 5, "b", 3), (61, 81, "a", 8), (61, 81, "b", 3), (64, 96, "a", 19), (64, 96, "b", 9)]
 
 
 @pytest.mark.parametrize("dim_x,dim_y,name,iters", CASES, ids=[f"{x}x{y}-{n}-i{it}" for x, y, n, it in CASES])
@@ -253,8 +263,9 @@ def test_step_n_each_with_per_member_inflow_equals_one_batch_per_member(sfl, ora
 
 
 # ---- 4. the operators one by one -----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dim_x,dim_y,name,iters", [(7, 5, "a", 9), (7, 5, "b", 3), (61, 81, "a", 19), (61, 81, "b", 1), (64, 96, "a", 7), (64, 96, "b", 8)],
-                         ids=["7x5-a", "7x5-b", "61x81-a", "61x81-b", "64x96-a", "64x96-b"])
+@pytest.mark.parametrize("dim_x,dim_y,name,iters", [(3, 3, "c", 0), (3, 3, "c", 1), (3, 3, "c", 3), (7, 5, "a", 9), (7, 5, "b", 3), (61, 81, "a", 19),
+                                                    (61, 81, "b", 1), (64, 96, "a", 7), (64, 96, "b", 8)],
+                         ids=["3x3-i0", "3x3-i1", "3x3-i3", "7x5-a", "7x5-b", "61x81-a", "61x81-b", "64x96-a", "64x96-b"])
 def test_the_solves_and_the_statistics_follow_the_rule(sfl, dim_x, dim_y, name, iters):
     cap = sfl.capi
     maps, masks, inflow = members_of(name, dim_x, dim_y)

@@ -15,6 +15,8 @@ Which test launches which kernel file on a denormal-bearing texture (the quiesce
                                                            test_stopped_steps_of_a_batch[96x96]
   batch_solids.hip                                         test_batches_with_solids_and_viscosity[*-solids], [*-both]
   batch_viscous.hip                                        test_batches_with_solids_and_viscosity[*-viscous], [*-both]
+  batch_member.h                                           the step body of the two files above: their tests (member_step and
+                                                           apply_member: every batch test here)
   context_solids.hip, sor_solid_tile.h                     test_contexts_step_by_the_oracle[masked-*],
                                                            test_the_operators_one_by_one[disc], test_a_context_stops_...[masked]
   context_viscous.hip, diffuse_tile.h                      test_contexts_step_by_the_oracle[viscous-*], test_diffuse_velocity
