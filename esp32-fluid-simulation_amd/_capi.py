@@ -361,6 +361,12 @@ SIGNATURES = {
     "sfl_batch_mean_sample": (_i, [_ctx]),
     "sfl_batch_mean_info": (_i, [_ctx, _pi, _pi, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sfl_batch_mean_download": (_i, [_ctx, _i, _i, _i, C.c_void_p, _sz]),
+    "sfl_set_wall_velocity": (_i, [_ctx, _pi, _pf, _i]),
+    "sfl_wall_velocity_info": (_i, [_ctx, _pi]),
+    "sfl_wall_velocity_download": (_i, [_ctx, _pi, _pf, _i]),
+    "sfl_batch_set_wall_velocity": (_i, [_ctx, _pi, _pi, _pf, _i]),
+    "sfl_batch_wall_velocity_info": (_i, [_ctx, _pi, C.POINTER(C.c_int64)]),
+    "sfl_batch_wall_velocity_download": (_i, [_ctx, _i, _pi, _pf, _i, _pi]),
     "sfl_batch_synchronize": (_i, [_ctx]),
 }
 

@@ -22,7 +22,7 @@ void release(sfl_batch *b)
                     (void *)b->tracers.d_xy, (void *)b->tracers.d_trail, (void *)b->views.d_palette, b->views.d_out,
                     (void *)b->d_rec_palette, b->history.d_records, (void *)b->solids.d_codes,
                     (void *)b->loads.d_labels, b->loads.d_records, b->friction.d_records, b->torque.d_records, (void *)b->torque.d_pivot2, b->means.d_planes, b->viscosity.d_table, (void *)b->openings.d_codes,
-                    (void *)b->openings.d_inflow, b->openings.d_profile, b->openings.d_flux})
+                    (void *)b->openings.d_inflow, b->openings.d_profile, b->openings.d_flux, b->walls.d_table})
         if (m) (void)hipFree(m);
     if (b->h_stats) (void)hipHostFree(b->h_stats);
     if (b->h_dist) (void)hipHostFree(b->h_dist);
@@ -254,7 +254,9 @@ int run_steps(sfl_batch *b, int n, StepKind kind, sfl::BatchStep a)
         a.step.v_out = b->vel_tmp;
         a.step.col_in = b->col;
         a.step.col_out = b->col_tmp;
-        if (b->viscosity.set)   // (never kUntil, never large: refused at the call and at sfl_batch_set_viscosity)
+        if (b->walls.step)   // (a wall table is held: never without solids, so never kUntil, never large; walls.cpp picks the kernel)
+            SFL_TRY(b->walls.step(b, kind == kEach, a));
+        else if (b->viscosity.set)   // (never kUntil, never large: refused at the call and at sfl_batch_set_viscosity)
             SFL_TRY(b->viscosity.step(b, kind == kEach, a));
         else if (b->openings.set)   // (never kUntil, never large, never with viscosity: refused at the calls; its codes hold the solids')
             SFL_TRY(b->openings.step(b, kind == kEach, a));

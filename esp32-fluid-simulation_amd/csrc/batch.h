@@ -163,6 +163,25 @@ hipError_t launch_batch_open_profile_step_each(hipStream_t s, const BatchStep &a
 hipError_t launch_batch_open_flux(hipStream_t s, struct sfl_open_flux *out, const float *v, const BatchOpenings &open, int dim_x, int dim_y,
                                   int first, int count);
 
+// ---- members whose solid cells move (batch_walls.hip; include/sfl.h "WALL VELOCITIES") -------------------------------
+// The wall table is a BatchProfile: member m's records are [offsets[m], offsets[m + 1]), record k the cell index cells[k]
+// -- a SOLID cell of that member, unique within the row, in cell order -- and its velocity.  Formed by the host
+// (walls.cpp, wall_table.h) once per sfl_batch_set_wall_velocity.  Two pairs of kernels:
+//   * on the solids' bytes: launch_batch_viscous_solid_step[_each] with the row; visc == nullptr = no member has item 3a
+//     (launch_batch_solid_step[_each] with the row);
+//   * on open codes: launch_batch_open_profile_step[_each] with the row; profile.offsets == nullptr = no profile
+//     (launch_batch_open_step[_each] with the row).
+// With empty rows, or rows of +0.0f, the same results bit for bit as those launches.
+struct BatchViscous;   // viscous_kernels.h
+hipError_t launch_batch_wall_step(hipStream_t s, const BatchStep &a, const BatchSolids &solids, const BatchViscous *visc,
+                                  const BatchProfile &walls, int batch);
+hipError_t launch_batch_wall_step_each(hipStream_t s, const BatchStep &a, const BatchSolids &solids, const BatchViscous *visc,
+                                       const BatchProfile &walls, int batch, const BatchMember *members, float *report);
+hipError_t launch_batch_open_wall_step(hipStream_t s, const BatchStep &a, const BatchOpenings &open, const BatchProfile &profile,
+                                       const BatchProfile &walls, int batch);
+hipError_t launch_batch_open_wall_step_each(hipStream_t s, const BatchStep &a, const BatchOpenings &open, const BatchProfile &profile,
+                                            const BatchProfile &walls, int batch, const BatchMember *members, float *report);
+
 // ---- the draw task of many members in one launch (batch_render.hip) -----------------------------------------------
 // Image k of `images` (k in [0, count), member-major: image k starts at pixel k * H * W, H = scaling * (dim_x - 1) rows of
 // W = scaling * (dim_y - 1) uint16) = launch_render_rgb565 of the dye at colour_of_first_member + 3 * k * dim_x * dim_y,

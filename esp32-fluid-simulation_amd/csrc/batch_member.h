@@ -174,14 +174,21 @@ __device__ __forceinline__ float2 no_inflow() { return make_float2(0.0f, 0.0f); 
 //   kProfile  the records of `row` -- unique fluid inflow cells, which the force loop never writes -- go into l.v by all
 //             threads behind the advection's barrier, beside the forces, and ONE barrier that every workgroup reaches
 //             stands in front of the divergence instead of the forces' own.
+//   kWalls    the records of `walls` (include/sfl.h "WALL VELOCITIES") -- unique SOLID cells, which neither the force loop
+//             nor the profile writes -- go into l.v beside the profile's, behind the same barriers (the extended item 3:
+//             only item 3a ever reads them), and into v_out behind the projection's stores with a barrier between
+//             (item 8: item 6 has just stored (0, 0) there, by whichever thread owns the cell).
 // Imposing the inflow and zeroing the solids happen where a cell's velocity is stored and where a force record is
 // skipped: together the same as doing both after the forces, without a pass and a barrier of their own.
-template <class Code, bool kViscous = false, bool kProfile = false>
+template <class Code, bool kViscous = false, bool kProfile = false, bool kWalls = false>
 __device__ __forceinline__ Lds step_in_lds(const SmallStep &a, const Code *__restrict__ codes, char *lds_raw, float2 inflow = no_inflow(),
-                                           BatchViscous visc = kNoViscosity, ProfileRow row = ProfileRow{nullptr, nullptr, 0})
+                                           BatchViscous visc = kNoViscosity, ProfileRow row = ProfileRow{nullptr, nullptr, 0},
+                                           ProfileRow walls = ProfileRow{nullptr, nullptr, 0})
 {
     constexpr bool kCoded = !std::is_void_v<Code>;
+    constexpr bool kRows = kProfile || kWalls;   // a table's rows stand beside the forces: one barrier for both
     static_assert(!kProfile || kCoded, "a profile's cells are inflow cells");
+    static_assert(!kWalls || kCoded, "a wall's cells are solid cells");
     const int dim_x = a.dim_x, dim_y = a.dim_y, cells = dim_x * dim_y;
     const Lds l = carve(lds_raw, cells);
     const Slab g{dim_x, dim_y, 0, dim_y};
@@ -207,6 +214,8 @@ __device__ __forceinline__ Lds step_in_lds(const SmallStep &a, const Code *__res
     __syncthreads();
     if constexpr (kProfile)   // the profile's part of item 2a
         for (int k = threadIdx.x; k < row.n; k += kThreads) l.v[row.cells[k]] = row.vel[k];
+    if constexpr (kWalls)     // the walls' part of item 3
+        for (int k = threadIdx.x; k < walls.n; k += kThreads) l.v[walls.cells[k]] = walls.vel[k];
     // drag forces, in queue order: later entries win; a record on a solid or an inflow cell has no effect (items 2, 2a, 3)
     if (a.n_forces > 0) {
         if (threadIdx.x == 0)
@@ -219,9 +228,9 @@ __device__ __forceinline__ Lds step_in_lds(const SmallStep &a, const Code *__res
                 }
                 l.v[gj * dim_x + i] = make_float2(a.force_vel[2 * k], a.force_vel[2 * k + 1]);
             }
-        if constexpr (!kProfile) __syncthreads();
+        if constexpr (!kRows) __syncthreads();
     }
-    if constexpr (kProfile) __syncthreads();   // the records and the forces are visible to the divergence
+    if constexpr (kRows) __syncthreads();   // the records and the forces are visible to the diffusion and the divergence
     // the diffusion (item 3a); skipped whole by a member without one
     if constexpr (kViscous)
         if (visc.sweeps > 0) diffuse_in_lds(l, codes, dim_x, dim_y, visc);
@@ -263,6 +272,10 @@ __device__ __forceinline__ Lds step_in_lds(const SmallStep &a, const Code *__res
         const float sj = (float)gj - u.y * a.dt;
         const SrcPos s = classify(si, sj, dim_x, dim_y);
         store_uq3(a.col_out, (size_t)c, sample_global_uq3<false>(col_in, g, s, si, sj));
+    }
+    if constexpr (kWalls) {   // item 8: the walls hold their velocity again, behind every thread's (0, 0) of item 6
+        __syncthreads();
+        for (int k = threadIdx.x; k < walls.n; k += kThreads) v_out[walls.cells[k]] = walls.vel[k];
     }
     return l;
 }

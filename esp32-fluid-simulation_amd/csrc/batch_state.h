@@ -192,6 +192,21 @@ struct sfl_batch {
         int (*profile_step)(sfl_batch *b, bool each, const sfl::BatchStep &a) = nullptr;
         int (*profile_restage)(sfl_batch *b, const uint16_t *codes, size_t member_stride) = nullptr;
     } openings;
+    // wall velocities (walls.cpp; include/sfl.h "WALL VELOCITIES"): the rows as given, duplicates removed and in cell order
+    // (wall_table.h: one row for all members or one per member), and ONE CSR table on the device (batch.h BatchProfile),
+    // freed by the destroy path.  Plain data, as the solids are and for the same reason; while a table is held every step of
+    // batch.cpp launches through `step`, in front of the viscosity's, the openings' and the solids', and every successful
+    // sfl_batch_set_solids calls `drop` (the stream is idle there), which frees the table and clears both.  walls.cpp sets
+    // both with `on`; null, a batch launches exactly what it launched before there were walls.
+    struct Walls {
+        bool on = false;
+        sfl::walls::Rows rows;
+        void *d_table = nullptr;
+        size_t d_bytes = 0;
+        sfl::BatchProfile table{nullptr, nullptr, nullptr};
+        int (*step)(sfl_batch *b, bool each, const sfl::BatchStep &a) = nullptr;
+        void (*drop)(sfl_batch *b) = nullptr;
+    } walls;
 };
 
 namespace sfl {

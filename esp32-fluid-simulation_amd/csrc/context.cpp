@@ -337,7 +337,7 @@ int sfl_destroy(sfl_context *c)
                     (void *)c->tracers.d_trail, (void *)c->views.d_palette, c->views.d_out, c->history.d_records,
                     (void *)c->solids.d_codes, (void *)c->loads.d_labels, c->loads.d_records, c->friction.d_records, c->torque.d_records, (void *)c->torque.d_pivot2, c->means.d_planes, (void *)c->viscosity.d_third,
                     (void *)c->openings.d_codes, (void *)c->openings.d_open, (void *)c->openings.d_inflow_cells,
-                    (void *)c->openings.d_inflow_values, c->openings.d_flux})
+                    (void *)c->openings.d_inflow_values, c->openings.d_flux, c->walls.d_list})
         if (m) (void)hipFree(m);
     for (auto &st : c->force_stage) {
         if (st.cells) (void)hipHostFree(st.cells);

@@ -45,6 +45,7 @@
 #include "../../include/sfl.h"
 #include "kernels.h"
 #include "slab_plan.h"
+#include "wall_table.h"
 
 namespace sfl {
 namespace host {
@@ -407,6 +408,23 @@ struct ContextViscosity {
     int (*step)(sfl_context *c, float dt, float dx, int iters, float omega) = nullptr;
 };
 
+// Wall velocities of a whole-domain context (context_walls.cpp; include/sfl.h "WALL VELOCITIES"): the records as given,
+// duplicates removed and in cell order (wall_table.h), and the same as a compact list on the device -- `records` cell
+// indices, behind them one (u, v) each, in ONE allocation that sfl_destroy frees.  Plain data, as ContextSolids and for
+// the same reason: while a table is held the step reaches the sequence with the walls' launches through `step`, in front
+// of the viscosity's and the solids', and every successful sfl_set_solids calls `drop` (the stream is idle there), which
+// frees the list and clears both.  Null, every call launches exactly what it launched before there were walls.
+struct ContextWalls {
+    bool on = false;
+    std::vector<sfl::walls::Record> row;
+    void *d_list = nullptr;
+    size_t d_bytes = 0;
+    const uint32_t *d_cells = nullptr;
+    const float *d_vel = nullptr;
+    int (*step)(sfl_context *c, float dt, float dx, int iters, float omega) = nullptr;
+    void (*drop)(sfl_context *c) = nullptr;
+};
+
 }  // namespace host
 }  // namespace sfl
 
@@ -542,6 +560,7 @@ struct sfl_context {
     int (*mean_step)(sfl_context *c) = nullptr;
     sfl::host::ContextViscosity viscosity;  // item 3a of a step (context_viscous.cpp)
     sfl::host::ContextOpenings openings;     // inflow and outflow cells on the rim (context_openings.cpp)
+    sfl::host::ContextWalls walls;           // solid cells that hold a velocity (context_walls.cpp)
 
     sfl::host::Options opt;  // what sfl_set_option stores (kOptions above: one row per option)
 

@@ -134,6 +134,7 @@ int sfl_set_solids(sfl_context *c, const uint8_t *mask)
             (void)hipFree(s.d_codes);
         }
         s = ContextSolids{};
+        if (c->walls.drop) c->walls.drop(c);   // (a wall is a solid cell: the table goes with the mask)
         if (c->openings.restage) SFL_TRY(c->openings.restage(c));   // (the openings' bytes and pointers: every cell is fluid again)
         return SFL_OK;
     }
@@ -161,6 +162,7 @@ int sfl_set_solids(sfl_context *c, const uint8_t *mask)
     s.set = true;
     s.solid_cells = solid;
     set_hooks(c);
+    if (c->walls.drop) c->walls.drop(c);   // (the table was checked against the mask this call replaced: it goes)
     if (c->openings.restage) SFL_TRY(c->openings.restage(c));   // (an opening counts only where the cell is fluid)
     return SFL_OK;
 }

@@ -69,6 +69,8 @@ int diffuse(sfl_context *c, float nu, float dt, float dx, int sweeps, bool zero_
 // forces, the diffusion (with solids: its first launch also zeroes the solid cells' velocity, item 3), then the
 // divergence, the solve, the gradient and the dye advection as the calls of their own run them, by the solids' rule
 // where a mask is set.  No seam, no fused kernel, no small-grid one-launch step.
+// (context_walls.cpp's step restates this sequence with one launch of its own in front of the diffusion, which it then calls
+// without the zeroing: a change of the order here is a change there.)
 int step(sfl_context *c, float dt, float dx, int iters, float omega)
 {
     SFL_TRY(sfl_advect_velocity(c, dt, 1));                                              // item 1

@@ -294,6 +294,7 @@ static int step_seam(sfl_context *c, float dt, float dx)
 // sfl_step behind its checks: the step that takes the records of step 0 of the timeline
 static int step_of_timeline(sfl_context *ctx, float dt, float dx, int iters, float omega)
 {
+    if (ctx->walls.step) return ctx->walls.step(ctx, dt, dx, iters, omega);   // a wall table is held (never without solids): the sequence below with items 3 and 8 extended
     if (ctx->viscosity.step) return ctx->viscosity.step(ctx, dt, dx, iters, omega);   // viscosity set: the unfused sequence with item 3a
     if (ctx->solids.step) return ctx->solids.step(ctx, dt, dx, iters, omega);   // solid cells set: the unfused sequence of their rule
     if (small_grid(ctx)) return small_grid_step(ctx, dt, dx, iters, omega);

@@ -107,6 +107,7 @@ int sfl_batch_set_solids(sfl_batch *b, const uint8_t *mask, int per_member)
             (void)hipFree(s.d_codes);
         }
         s = sfl_batch::Solids{};
+        if (b->walls.drop) b->walls.drop(b);   // (a wall is a solid cell: the table goes with the mask)
         if (b->openings.restage) SFL_TRY(b->openings.restage(b));   // (the openings' codes: every cell is fluid again)
         return SFL_OK;
     }
@@ -133,6 +134,7 @@ int sfl_batch_set_solids(sfl_batch *b, const uint8_t *mask, int per_member)
     s.set = true;
     s.per_member = per_member != 0;
     set_hooks(b);
+    if (b->walls.drop) b->walls.drop(b);   // (the table was checked against the mask this call replaced: it goes)
     if (b->openings.restage) SFL_TRY(b->openings.restage(b));   // (an opening counts only where the cell is fluid)
     return SFL_OK;
 }

@@ -514,12 +514,29 @@ class _Friction:
             raise ValueError(f"friction: nu of shape {a.shape}, want a number or {(count,)}")
         return a[:, None, None]
 
-    def friction_xy(self, nu=None, first: int = 0, count=None) -> np.ndarray:
+    def friction_xy(self, nu=None, first: int = 0, count=None, relative: bool = False) -> np.ndarray:
         """:meth:`friction` as float64 ``(count, bodies, 2)``: nu * fx * 2^exp2, nu * fy * 2^exp2 -- the force per unit
         depth and density, with NO factor dx.  `nu`: a number, one value per member, or None for the viscosity that is
-        set (zeros when none is)."""
+        set (zeros when none is).  `relative`: the wall's share (:func:`wall_shares`, from the wall table that is set) is
+        subtracted in front of nu: the friction of the fluid's velocity RELATIVE to a moving wall.  The records keep
+        their definition, the wall at rest."""
         rec = self.friction(first, count)
-        return self._friction_nu(nu, first, rec.shape[0]) * _Loads._xy(rec)
+        xy = _Loads._xy(rec)
+        if relative:
+            xy = xy - self._wall_shares(first, rec.shape[0])[0]
+        return self._friction_nu(nu, first, rec.shape[0]) * xy
+
+    def _wall_shares(self, first, count):
+        """(friction share float64 (count, bodies, 2), torque share float64 (count, bodies)) of members [first, first +
+        count) -- a context: count = 1 -- from the mask, the labels, the pivots and the wall table that are set."""
+        n_bodies = self.bodies_info()[0]
+        if self._loads_batch:
+            masks, labels, pivots = self.solids(first, count), self.bodies(first, count), self.body_pivots(first, count)
+            tables = [self.wall_velocity(first + k) for k in range(count)]
+        else:
+            masks, labels, pivots, tables = self.solids()[None], self.bodies()[None], self.body_pivots()[None], [self.wall_velocity()]
+        shares = [wall_shares(masks[k], labels[k], n_bodies, np.round(pivots[k] * 2.0).astype(np.int64), *tables[k]) for k in range(count)]
+        return np.stack([f for f, _ in shares]), np.stack([t for _, t in shares])
 
     def friction_start(self, every: int, capacity: int, first: int = 0, count=None):
         """Start the friction recorder, by the rules of :meth:`loads_start` and independent of it: after every
@@ -709,10 +726,17 @@ class _Torque:
         mf = rec["mf"].astype(np.float64) * np.ldexp(1.0, rec["exp2_f"].astype(np.int64) - 1) * nu * (float(rho) * float(dx))
         return np.stack([mp, mf], axis=-1)
 
-    def torque_xy(self, dx: float = 1.0, rho: float = 1.0, first: int = 0, count=None) -> np.ndarray:
+    def torque_xy(self, dx: float = 1.0, rho: float = 1.0, first: int = 0, count=None, relative: bool = False) -> np.ndarray:
         """:meth:`torque` as float64 ``(count, bodies, 2)``: [..., 0] the pressure torque in pressure x length^2, [..., 1] the
-        friction torque per unit depth, with the viscosity that is set (zeros when none is).  Counter-clockwise positive."""
-        return self._torque_xy(self.torque(first, count), first, dx, rho)
+        friction torque per unit depth, with the viscosity that is set (zeros when none is).  Counter-clockwise positive.
+        `relative`: the wall's share of the friction torque (:func:`wall_shares`) is subtracted, as in :meth:`friction_xy`."""
+        rec = self.torque(first, count)
+        out = self._torque_xy(rec, first, dx, rho)
+        if relative:
+            nu = self._friction_nu(None, first, rec.shape[-2])
+            nu = nu if nu.ndim == 0 else nu[:, :, 0]
+            out[..., 1] -= self._wall_shares(first, rec.shape[-2])[1] * nu * (float(rho) * float(dx))
+        return out
 
     def torque_start(self, every: int, capacity: int, first: int = 0, count=None):
         """Start the torque recorder, by the rules of :meth:`loads_start` and independent of the other recorders; behind a
@@ -1060,6 +1084,27 @@ class Solver(_Tracers, _History, _Loads, _Friction, _Torque, _Means):
         c, v = np.zeros((n.value, 2), np.int32), np.zeros((n.value, 2), np.float32)
         capi.check(self._lib.sfl_inflow_profile_download(self._h, c.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data_as(C.POINTER(C.c_float)), n.value))
         return c, v
+
+    def set_wall_velocity(self, cells, vel):
+        """Wall velocities (include/sfl.h "WALL VELOCITIES"): `cells` integers ``(n, 2)``, (i, j) per record, each a SOLID
+        cell of the mask that is set; `vel` float32 ``(n, 2)``.  In step and step_n those cells hold their record's velocity
+        where item 3a and the next step's advection read them; the pressure still sees a wall at rest.  Of two records on
+        one cell the later wins; n == 0 (or None) clears the table; every set_solids drops it."""
+        c, v = _profile_records([] if cells is None else cells, [] if vel is None else vel, "wall velocity")
+        capi.check(self._lib.sfl_set_wall_velocity(self._h, c.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data_as(C.POINTER(C.c_float)), len(c)))
+
+    def wall_velocity(self):
+        """(cells int32[n, 2], vel float32[n, 2]): the records held, in cell-index order; empty without a table."""
+        n = self.wall_velocity_info()
+        c, v = np.zeros((n, 2), np.int32), np.zeros((n, 2), np.float32)
+        capi.check(self._lib.sfl_wall_velocity_download(self._h, c.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return c, v
+
+    def wall_velocity_info(self) -> int:
+        """The number of unique cells the wall table holds (0 without one).  Never waits."""
+        n = C.c_int(0)
+        capi.check(self._lib.sfl_wall_velocity_info(self._h, C.byref(n)))
+        return n.value
 
     def openings_flux(self) -> np.ndarray:
         """The flux through the live open cells from the velocity held: one OPEN_FLUX_DTYPE record (shape ``()``); exact
@@ -1592,20 +1637,105 @@ class BatchSolver(_Tracers, _History, _Loads, _Friction, _Torque, _Means):
         capi.check(self._lib.sfl_batch_openings_flux(self._h, first, count, out.ctypes.data_as(C.POINTER(capi.OpenFlux)), out.nbytes))
         return out
 
+    def set_wall_velocity(self, cells, vel, members=None):
+        """Wall velocities (include/sfl.h "WALL VELOCITIES"): `cells` integers ``(n, 2)``, (i, j) per record; `vel` float32
+        ``(n, 2)``; `members` None -- every record to every member -- or ``n`` member numbers, record k to member
+        members[k] (one batch is then a sweep over the wall's speed).  Each record names a cell that is SOLID in the mask
+        of every member it applies to.  Of two records on one cell of one member the later wins; n == 0 (or None) clears
+        the table; every set_solids drops it."""
+        c, v = _profile_records([] if cells is None else cells, [] if vel is None else vel, "wall velocity")
+        who = None
+        if members is not None and len(c):
+            w = np.asarray(members)
+            if w.shape != (len(c),) or not np.issubdtype(w.dtype, np.integer):
+                raise ValueError(f"wall velocity: members of shape {w.shape} and dtype {w.dtype}, want {(len(c),)} integers")
+            w = np.ascontiguousarray(w, np.int32)
+            who = w.ctypes.data_as(C.POINTER(C.c_int))
+        capi.check(self._lib.sfl_batch_set_wall_velocity(self._h, who, c.ctypes.data_as(C.POINTER(C.c_int)),
+                                                         v.ctypes.data_as(C.POINTER(C.c_float)), len(c)))
+
+    def wall_velocity(self, member: int = 0):
+        """(cells int32[n, 2], vel float32[n, 2]): the records of one member, in cell-index order; empty without a table."""
+        n = C.c_int(0)
+        capi.check(self._lib.sfl_batch_wall_velocity_download(self._h, member, None, None, 0, C.byref(n)))   # (no arrays: the count alone)
+        c, v = np.zeros((n.value, 2), np.int32), np.zeros((n.value, 2), np.float32)
+        capi.check(self._lib.sfl_batch_wall_velocity_download(self._h, member, c.ctypes.data_as(C.POINTER(C.c_int)),
+                                                              v.ctypes.data_as(C.POINTER(C.c_float)), n.value, None))
+        return c, v
+
+    def wall_velocity_info(self):
+        """(set, unique cells held over all members, a shared table counted once per member).  Never waits."""
+        s, n = C.c_int(0), C.c_int64(0)
+        capi.check(self._lib.sfl_batch_wall_velocity_info(self._h, C.byref(s), C.byref(n)))
+        return bool(s.value), n.value
+
     def synchronize(self):
         capi.check(self._lib.sfl_batch_synchronize(self._h))
 
 
-def _profile_records(cells, vel):
-    """(cells int32[n, 2], vel float32[n, 2]) of an inflow profile, checked for shape before the library sees them."""
+def rigid_wall_velocity(labels, body: int, u=0.0, v=0.0, omega=0.0, pivot2=(0, 0)):
+    """(cells int32[n, 2], vel float32[n, 2]) for set_wall_velocity: every cell of `labels` (integers ``(dim_y, dim_x)``,
+    the bodies' labels) that carries `body` moves as one rigid body -- translation (u, v) plus rotation `omega` (radians per
+    unit time, counter-clockwise) about the pivot, given in HALF CELLS as the torque's pivots are.  Per cell (i, j), every
+    operation one float32 rounding: rx = 0.5f * (2 i - px2), ry = 0.5f * (2 j - py2), wu = u - omega * ry, wv = v + omega * rx.
+    Cells in cell-index order."""
+    lab = np.asarray(labels)
+    if lab.ndim != 2 or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"rigid wall velocity: labels of shape {lab.shape} and dtype {lab.dtype}, want integers (dim_y, dim_x)")
+    F = np.float32
+    j, i = np.nonzero(lab == body)
+    rx = F(0.5) * (2 * i.astype(np.int64) - int(pivot2[0])).astype(F)
+    ry = F(0.5) * (2 * j.astype(np.int64) - int(pivot2[1])).astype(F)
+    wu = (F(u) - (F(omega) * ry).astype(F)).astype(F)
+    wv = (F(v) + (F(omega) * rx).astype(F)).astype(F)
+    return np.stack([i, j], axis=1).astype(np.int32), np.stack([wu, wv], axis=1).astype(F)
+
+
+def wall_shares(solid, labels, bodies: int, pivot2, cells, vel):
+    """The wall's share of the friction and of the friction torque of every body, in float64, from a mask (bool ``(dim_y,
+    dim_x)``), the labels (integers, same shape; a label counts only where the cell is solid), the pivots in HALF cells
+    (integers ``(bodies, 2)``) and a wall table (`cells` ``(n, 2)``, `vel` ``(n, 2)``, unique cells): over the wet faces of a
+    body -- a solid cell of it and a fluid neighbour W, E, S or N of it -- the sum of the SOLID cell's tangential wall velocity
+    (v across a W or E face, u across an S or N face; 0 for a cell no record names), for the torque times the face's arm:
+    +rx * v across W and E, -ry * u across S and N, (rx, ry) = (i - px2 / 2, j - py2 / 2) of the solid cell.  Returns
+    (float64 ``(bodies, 2)``: x from the S and N faces, y from the W and E faces; float64 ``(bodies,)``) -- what
+    fx * 2^exp2, fy * 2^exp2 and mf * 2^(exp2_f - 1) of "FRICTION" and "TORQUE" would be if the fluid moved with the wall."""
+    solid = np.asarray(solid, bool)
+    lab = np.where(solid, np.asarray(labels).astype(np.int64), 0)
+    wall = np.zeros(solid.shape + (2,), np.float64)
+    c = np.asarray(cells, np.int64).reshape(-1, 2)
+    wall[c[:, 1], c[:, 0]] = np.asarray(vel, np.float64).reshape(-1, 2)
+    piv = np.asarray(pivot2, np.float64).reshape(bodies, 2)
+    j, i = np.mgrid[0:solid.shape[0], 0:solid.shape[1]]
+    fluid = ~solid
+    # the fluid neighbour W, E, S, N of every cell is inside the domain and fluid
+    wet = [np.zeros_like(solid) for _ in range(4)]
+    wet[0][:, 1:], wet[1][:, :-1], wet[2][1:, :], wet[3][:-1, :] = fluid[:, :-1], fluid[:, 1:], fluid[:-1, :], fluid[1:, :]
+    friction, torque = np.zeros((bodies, 2), np.float64), np.zeros(bodies, np.float64)
+    for b in range(1, bodies + 1):
+        mine = lab == b
+        rx, ry = i - piv[b - 1, 0] / 2.0, j - piv[b - 1, 1] / 2.0
+        for d in range(4):
+            face = mine & wet[d]
+            if d < 2:   # W, E: the fluid slides along y
+                friction[b - 1, 1] += wall[face, 1].sum()
+                torque[b - 1] += (rx[face] * wall[face, 1]).sum()
+            else:       # S, N: along x
+                friction[b - 1, 0] += wall[face, 0].sum()
+                torque[b - 1] -= (ry[face] * wall[face, 0]).sum()
+    return friction, torque
+
+
+def _profile_records(cells, vel, what="inflow profile"):
+    """(cells int32[n, 2], vel float32[n, 2]) of an inflow profile or a wall table, checked for shape before the library sees them."""
     c = np.asarray(cells)
     v = np.asarray(vel, dtype=np.float32)
     if c.size == 0 and v.size == 0:
         return np.zeros((0, 2), np.int32), np.zeros((0, 2), np.float32)
     if c.ndim != 2 or c.shape[1] != 2 or not np.issubdtype(c.dtype, np.integer):
-        raise ValueError(f"inflow profile: cells of shape {c.shape} and dtype {c.dtype}, want integers (n, 2): (i, j) per record")
+        raise ValueError(f"{what}: cells of shape {c.shape} and dtype {c.dtype}, want integers (n, 2): (i, j) per record")
     if v.shape != c.shape:
-        raise ValueError(f"inflow profile: vel of shape {v.shape}, want {c.shape}: (u, v) per record")
+        raise ValueError(f"{what}: vel of shape {v.shape}, want {c.shape}: (u, v) per record")
     return np.ascontiguousarray(c, np.int32), np.ascontiguousarray(v)
 
 

@@ -1637,6 +1637,65 @@ SFL_API int sfl_torque_start(sfl_context *ctx, int every, int capacity);
 SFL_API int sfl_torque_stop(sfl_context *ctx);
 SFL_API int sfl_torque_info(sfl_context *ctx, int *samples, int *capacity, int64_t *steps, int *bodies);
 SFL_API int sfl_torque_read(sfl_context *ctx, int first_sample, int samples, struct sfl_body_torque *host, size_t bytes);
+
+/* --- WALL VELOCITIES: solid cells that move -- the lid of a cavity, a belt under a body, a spinning disc.  The geometry stays
+ *     where it is; only what the wall cells HOLD changes.  Extends "SOLIDS" and "SOLIDS OF A CONTEXT" by calls of their own;
+ *     with no table set every call launches exactly what it launched before.
+ *   A WALL TABLE is a set of records (cell (i, j), velocity (u, v)), in grid units as every velocity here.  It extends the
+ * solids' step by two statements and changes no other item:
+ *     - ITEM 3, EXTENDED: after the forces, every solid cell holds (0, 0), except a solid cell named by a record: that cell
+ *       holds the record's velocity, both components, bits as given -- a -0.0f or a denormal is stored as it stands.
+ *     - ITEM 8, NEW, behind item 7: every solid cell named by a record holds its record's velocity again (item 6 has just
+ *       zeroed it).
+ *     - Items 4 to 7 are unchanged: the pressure sees an impermeable wall at rest, and a solid cell's dye is traced back with
+ *       (0, 0).
+ *   The wall acts on the flow through two things only: item 3a ("VISCOSITY"), whose sweeps read a solid neighbour as it is,
+ * and item 1, whose samples interpolate the stored field, wall cells included.  A velocity component NORMAL to a wet face is
+ * accepted and acts through those two items only: it drives nothing through the wall, which stays impermeable.  Consequence:
+ * from rest and without viscosity a wall moves nothing; with nu > 0 a lid drags the row beside it.
+ *     - A record must name a cell that is solid in the mask that is set -- in a batch with per-member masks, in the mask of
+ *       every member the record applies to.  Otherwise the call returns SFL_ERR_INVALID and the message names the first
+ *       offending record, and the member where there is one.  The velocity must be finite.
+ *     - Of two records on one cell of one member the later wins.  The host removes the duplicates: the device sees unique
+ *       cells in cell order, and the result does not depend on the order of execution.
+ *     - A call replaces the table that was set; n == 0 clears it.  Every successful sfl_batch_set_solids / sfl_set_solids, a
+ *       clear included, DROPS the table: it was checked against the mask that call replaced.  Nothing is staged again.
+ *     - The table acts in step calls only: sfl_step, sfl_step_n, sfl_batch_step_n, sfl_batch_step_n_each.  Operators called on
+ *       their own and sfl_diffuse_velocity are unchanged.
+ *     - It works with and without viscosity and with and without openings and inflow profiles: walls are solid cells, inflow
+ *       cells are fluid cells, and the two tables never meet.  Whatever the solids refuse stays refused.
+ *     - THE RECORDS OF "FRICTION" AND "TORQUE" KEEP THEIR DEFINITION: the fluid's tangential velocity with the wall AT REST.
+ *       No byte of them moves; the wall's share is the caller's to subtract from what the table says.
+ *     - ANCHORS: a table whose velocities are all +0.0f gives the bits of no table; a context holds what a batch member of
+ *       its shape holds; n steps of one call equal n calls of one step.
+ *   A batch keeps the table as one CSR table on the device with a row per member (a shared table counts once per member),
+ * staged once per call, never per step, and steps through kernels of its own, one launch per step.  A context keeps a compact
+ * list; a step is the step that would have run with ONE launch over the list behind it (item 8: a thread per record), and,
+ * where item 3a runs, ONE launch over the code bytes in front of the diffusion that stores (0, 0) or the record's velocity into
+ * every solid cell.  Where item 3a does not run the extended item 3 cannot be observed and is not launched.
+ *   Admission as everywhere.  A call's own argument checks come first, SFL_ERR_INVALID and answered on a machine without a GPU
+ * where they need no handle: n < 0, NULL arrays with n > 0, a non-finite velocity (the message names the record), a NULL
+ * handle, a member outside the batch.  The state refusal comes next: no solids set gives SFL_ERR_STATE -- so everything that
+ * sfl_[batch_]set_solids refuses stays refused.  Then the records against the mask.  A refused call stages and launches
+ * nothing and leaves the table as it was.                                                                                   */
+/* Set the wall table of a context: record k is cell (cells_ij[2 k], cells_ij[2 k + 1]) with velocity (vel_xy[2 k],
+ * vel_xy[2 k + 1]); both arrays are read during the call only.  n == 0 clears the table (the arrays may then be NULL).
+ * Synchronous.                                                                                                             */
+SFL_API int sfl_set_wall_velocity(sfl_context *ctx, const int *cells_ij, const float *vel_xy, int n);
+/* The number of unique cells the table holds (0 without one).  Never waits.                                                */
+SFL_API int sfl_wall_velocity_info(sfl_context *ctx, int *records);
+/* The records held, in cell-index order (dim_x * j + i ascending); capacity counts records, and capacity < records returns
+ * SFL_ERR_INVALID.  Never waits.                                                                                           */
+SFL_API int sfl_wall_velocity_download(sfl_context *ctx, int *cells_ij, float *vel_xy, int capacity);
+/* The same for a batch.  members NULL: every record goes to every member; else record k goes to member members[k] alone, and
+ * a member that no record names has no moving wall.  Synchronous.                                                          */
+SFL_API int sfl_batch_set_wall_velocity(sfl_batch *b, const int *members, const int *cells_ij, const float *vel_xy, int n);
+/* set: a table is held; records: the unique cells over all members, a shared table counted once per member.  Never waits.  */
+SFL_API int sfl_batch_wall_velocity_info(sfl_batch *b, int *set, int64_t *records);
+/* The records of one member, in cell-index order; *records (may be NULL) receives their number whatever the capacity, and
+ * capacity < that number returns SFL_ERR_INVALID -- except capacity 0 with both arrays NULL, which asks for the number alone and
+ * succeeds.  Never waits.                                                                                                  */
+SFL_API int sfl_batch_wall_velocity_download(sfl_batch *b, int member, int *cells_ij, float *vel_xy, int capacity, int *records);
 /* A batch is used from one thread at a time, as a context is.                                    */
 SFL_API int sfl_batch_synchronize(sfl_batch *b);
 
